@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the NeighborRetr similarity / loss head on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One STEP = one pass of the hot path over one synthetic batch already resident in HBM:
     [N>1: RCCL all-gather of the per-rank feature/mask shards]  ->  token clustering (global
@@ -23,13 +23,18 @@ every step.  Three forms of the job:
   --replicated_loss   the reference's semantics (modeling.py:274-298): every rank evaluates every loss.
 A step that contains collectives is replayed as ONE graph with the RCCL collectives inside, or as the graphs of its rank-local
 segments with the collectives eager between them, or eagerly -- the ranks decide together (comm.CollectiveCapture); the line says
-which (`config.step_form`).  The JSON line also carries:
+which (`config.step_form`).  A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the
+last timed step's `losses`); `--dump-outputs DIR` also writes those losses to DIR/losses.npy.  The inputs, the parameters and the
+noise stream are seeded, so two runs with the same arguments compute the same outputs.  With `--full` the line also carries:
+  ms_per_step_min / _median / _max   the same K-step loop repeated, for its spread;
   roofline     the fused local_level kernel (the dominant kernel): algorithmic flops per launch
                (F_sim / 3 launches) / its average duration, timed live
                with HIP events on the launch stream, against the dense bf16 MFMA peak;
   cpu_baseline the CPU oracle (a port of the reference algorithm, oracle/nr_oracle.py) timed on this
                host's cores on the same workload (N=1, rank 0 only; bounded sample);
   parity       one un-timed step against the reference fixture of this workload;
+  exchange_step_ms, sync_step   (N>1) the exchange step alone, and the synchronous sharded step timed in the same job.
+With or without `--full`, `--backward`, `--e2e` and `--emulate_world` add their own fields:
   rank_local   (--emulate_world) what one rank of a W-rank job does, emulated on this GPU.
 """
 import argparse
@@ -128,6 +133,13 @@ def parse():
                     help="also time BASELINE configs[4] on this GPU: ViT-B/32 towers + temporal transformer (stock PyTorch-ROCm, "
                          "random init, bf16 autocast) feeding the HIP head from synthetic pixels, forward and forward+backward "
                          "(extra field `e2e`; never the headline value)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the spread of the timed loop over repeats, the "
+                         "roofline (live, and N=1: two child runs under rocprofv3), the parity gate against the reference fixture, "
+                         "the CPU baseline; N>1: the exchange step alone and the synchronous sharded step (`sync_step`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned -- its five losses (total, centrality, "
+                         "uniform, neighbor, kl) -- to DIR/losses.npy (float32)")
     args = ap.parse_args()
     CFG.update(CFGS[args.config])
     if args.unroll <= 0:
@@ -463,7 +475,7 @@ def kernel_profiles(args):
         finally:
             shutil.rmtree(d, ignore_errors=True)
     me = os.path.abspath(__file__)
-    child = [me, "--_child", "--no-cpu-baseline", "--no_kernel_profile", "--steps", str(args.steps), "--warmup", str(args.warmup),
+    child = [me, "--_child", "--full", "--no-cpu-baseline", "--no_kernel_profile", "--steps", str(args.steps), "--warmup", str(args.warmup),
              "--config", str(args.config), "--precision", args.precision, "--unroll", str(args.unroll)]
     child += ["--no-graph"] if args.no_graph else []
     child += ["--no-pipeline"] if args.no_pipeline else []
@@ -499,7 +511,7 @@ def main():
     if args.gpus > 1 and world == 1:
         raise SystemExit(launch_ranks(args.gpus))
     prof = None
-    if world == 1 and not args._child and not args.no_kernel_profile:
+    if world == 1 and args.full and not args._child and not args.no_kernel_profile:
         prof = kernel_profiles(args)          # (children; this process has not touched the GPU yet)
     import torch.distributed as dist
     t_start = time.perf_counter()
@@ -545,6 +557,8 @@ def main():
     if c["B"] % world:
         raise SystemExit(f"global batch {c['B']} must divide over the ranks")
     b = c["B"] // world
+    # the model's noise stream is seeded from torch's seed (modeling._rng_state_on), which is random per process unless set
+    torch.manual_seed(20240607)
     model = build_model(args.precision, dev)
     model.config.world_size, model.config.local_rank = world, rank
     # N > 1, three forms of the job.  DEFAULT: step-interleaved (model.interleave_steps): every rank gathers every step's batch
@@ -940,7 +954,9 @@ def main():
     # Clock ramp: the first ~0.1 s of back-to-back steps after an idle period run 10 % slower than the steady state (measured:
     # 0.361 ms/step for the first 200 steps after a 20-step warm-up, 0.324 for every later 200) -- the chip has to leave its
     # idle power state.  Part of the untimed set-up, like the capture warm-ups above: >= 0.4 s of steps before the contract's
-    # W warm-up steps, so that the timed K steps measure the steady state whatever W is.
+    # W warm-up steps, so that the timed K steps measure the steady state whatever W is.  A FIXED number of steps (2000 ~ 0.5 s at
+    # configs[1]), not a clock-bounded loop: every step advances the noise stream's counter, and the last timed step's outputs
+    # (--dump-outputs) must not depend on how many steps the clock allowed; N > 1: the same count on every rank.
     def run_steps(n):
         """EXACTLY n steps: replays that cover several steps (--unroll) only while that many are still wanted."""
         budget[0] = n
@@ -953,14 +969,8 @@ def main():
     gc.collect()
     torch.cuda.synchronize()
     gc.disable()
-    t_ramp = time.perf_counter()
-    if world == 1:
-        while time.perf_counter() - t_ramp < 0.4:
-            run_steps(48)
-            torch.cuda.synchronize()
-    else:                                   # the SAME number of steps on every rank: a clock-bounded loop would let the ranks disagree
-        run_steps(1200)
-        torch.cuda.synchronize()
+    run_steps(2000 if world == 1 else 1200)
+    torch.cuda.synchronize()
     progress(f"form: {step_form}; clock ramp done; timing {args.steps} steps")
     run_steps(args.warmup)
     if interleaved:                         # the timed steps start at a round's start on every rank
@@ -975,11 +985,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     losses = result["losses"].cpu().numpy().tolist()
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "losses.npy"), result["losses"].float().cpu().numpy())
     # Spread of the timed loop (extra fields; `value` / `steps` / `ms_per_step` above keep the contract's meaning): the same
     # K-step loop repeated, each repeat bracketed like the timed region.  At the driver's --steps 20 the region is ~7 ms, so
     # one number says little about its own noise.
     rep_ms = []
-    for _ in range(max(5, min(25, int(200 / max(args.steps, 1))))):
+    for _ in range(max(5, min(25, int(200 / max(args.steps, 1)))) if args.full else 0):
         sync()
         t1 = time.perf_counter()
         run_steps(args.steps)
@@ -1056,7 +1069,7 @@ def main():
             model.use_side_streams = True
             step_form, n_segments, run, graph = primary["step_form"], primary["n_segments"], primary["run"], primary["graph"]
 
-    if world > 1:
+    if world > 1 and args.full:
         # the exchange step alone (pack, packed all-gather, unpack; eager), so that a rehearsal on gloo ranks -- whose collectives
         # go through the host -- shows how much of a step is the collective's own data path
         from neighborretr_amd.dist import packed_allgather as _pg
@@ -1137,7 +1150,7 @@ def main():
 
     # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream ------------
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         f_sim, f_mlp = algorithmic_flops(c["B"], c["Nt"], c["Nv"], c["M"])
         from neighborretr_amd import head
         p_bb, p_mlp, p_bank = head.precision_plan(model._prec())
@@ -1338,20 +1351,20 @@ def main():
                        "form_probes": (probes or None) if world > 1 and not args.replicated_loss and not args.no_graph else None,
                        "memory_bank": "ring (device head) + persistent prepared bf16 shadow, extended by the batch rows at every push"},
             "losses": [round(float(x), 5) for x in losses],
-            "ms_per_step_min": round(min(rep_ms), 4), "ms_per_step_median": round(float(np.median(rep_ms)), 4),
-            "ms_per_step_max": round(max(rep_ms), 4), "ms_per_step_repeats": len(rep_ms),
-            "roofline": roofline,
         }
         line.update(extra)
-        ws_, sl_ = model.config.world_size, model.shard_loss
-        model.config.world_size, model.shard_loss = 1, False       # rank 0 alone: the gate is a single-rank evaluation
-        try:
-            line["parity"] = parity_gates(model, dev)
-        finally:
-            model.config.world_size, model.shard_loss = ws_, sl_
-        if world == 1 and not args.no_cpu_baseline and args.config == 1:
-            line["cpu_baseline"] = cpu_baseline()
-    if world > 1 and interleaved and not args.no_sync_probe and not args.no_graph:
+        if args.full:
+            line.update({"ms_per_step_min": round(min(rep_ms), 4), "ms_per_step_median": round(float(np.median(rep_ms)), 4),
+                         "ms_per_step_max": round(max(rep_ms), 4), "ms_per_step_repeats": len(rep_ms), "roofline": roofline})
+            ws_, sl_ = model.config.world_size, model.shard_loss
+            model.config.world_size, model.shard_loss = 1, False       # rank 0 alone: the gate is a single-rank evaluation
+            try:
+                line["parity"] = parity_gates(model, dev)
+            finally:
+                model.config.world_size, model.shard_loss = ws_, sl_
+            if world == 1 and not args.no_cpu_baseline and args.config == 1:
+                line["cpu_baseline"] = cpu_baseline()
+    if world > 1 and interleaved and args.full and not args.no_sync_probe and not args.no_graph:
         # The second field is built LAST, behind a timer of its own: should its collectives hang on some box, rank 0 still prints
         # the line it has (with the reason in `sync_step`) and every rank leaves with status 0 -- the headline never depends on it.
         import threading

@@ -168,7 +168,8 @@ def test_round4_entry_points_refuse_bad_arguments_before_any_launch():
     assert k8 == 0 and m8.dtype == torch.uint8
     import neighborretr_amd.interleave  # noqa: F401  (importable without a GPU)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and all(f in r.stdout for f in ("--no_overlap", "--overlap_tries", "--sync_step", "--unroll"))
+    assert r.returncode == 0 and all(f in r.stdout for f in ("--no_overlap", "--overlap_tries", "--sync_step", "--unroll", "--full",
+                                                             "--dump-outputs"))
 
 
 def test_k_slicing_of_a_weight_gradient():

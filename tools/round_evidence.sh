@@ -5,12 +5,12 @@
 tag="${1:-rNN}"; part="${2:-AB}"; repo="$(pwd)"; out="$repo/gpurun_out/$tag"; mkdir -p "$out"
 q() { grep -v "amdgpu.ids" ; }
 if [[ "$part" == *A* ]]; then
-python bench.py --steps 200 --backward 2> "$out/bench.err" > "$out/bench_final.json"
-python bench.py --steps 20 --warmup 5 2>/dev/null > "$out/bench_20steps.json"
-python bench.py --steps 200 --no-cpu-baseline --unroll 1 2>/dev/null > "$out/bench_unroll1.json"
-python bench.py --steps 200 --no-cpu-baseline --no-pipeline 2>/dev/null > "$out/bench_sequential_unroll.json"
-python bench.py --config 2 --steps 50 --warmup 10 2>/dev/null > "$out/bench_c2.json"
-python bench.py --config 3 --steps 50 --warmup 10 2>/dev/null > "$out/bench_c3.json"
+python bench.py --full --steps 200 --backward 2> "$out/bench.err" > "$out/bench_final.json"
+python bench.py --full --steps 20 --warmup 5 2>/dev/null > "$out/bench_20steps.json"
+python bench.py --full --steps 200 --no-cpu-baseline --unroll 1 2>/dev/null > "$out/bench_unroll1.json"
+python bench.py --full --steps 200 --no-cpu-baseline --no-pipeline 2>/dev/null > "$out/bench_sequential_unroll.json"
+python bench.py --full --config 2 --steps 50 --warmup 10 2>/dev/null > "$out/bench_c2.json"
+python bench.py --full --config 3 --steps 50 --warmup 10 2>/dev/null > "$out/bench_c3.json"
 python tools/rank_local_times.py --worlds 2 4 8 --train --eval --out "gpurun_out/$tag/rank_local.txt" > "$out/rank_local.log" 2>&1
 python tools/rank_local_times.py --worlds 8 --only_train --B 1024 --out "gpurun_out/$tag/rank_local_b1024.txt" > "$out/rank_local_b1024.log" 2>&1
 python tools/capture_sequence.py 2>&1 | q | grep -v "Warning\|warn\|^  " > "$out/capture_sequence.txt"
@@ -34,5 +34,5 @@ python tools/sinkhorn_large_times.py 2>&1 | q > "$out/sinkhorn_large.txt"
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$out/roof" -o r -- python3 "$repo/tools/roofline_launches.py" > "$out/roofline_launches.txt" 2>&1 )
 cp "$(find "$out/roof" -name '*kernel_stats.csv' | head -1)" "$out/roofline_kernel_stats.csv" 2>/dev/null; rm -rf "$out/roof"
 bash tools/pmc_passes.sh "$out/pmc" && python tools/pmc_to_json.py "$out/pmc" > "$out/pmc_sim.json"; rm -rf "$out/pmc" "$out"/pmc.*.log
-python bench.py --steps 50 --no-cpu-baseline --e2e 2>/dev/null > "$out/bench_e2e.json"
+python bench.py --full --steps 50 --no-cpu-baseline --e2e 2>/dev/null > "$out/bench_e2e.json"
 ls -la "$out"
