@@ -16,8 +16,6 @@ It is differentiable: `HeadLossFn` is a torch.autograd.Function whose backward r
 backward kernels (row losses, arg-max-routed similarity gradient, normalisation) and library
 GEMMs for the scorer MLP.  Nothing here falls back to eager PyTorch for the forward math.
 """
-import os
-
 import torch
 
 from . import hip, ops
@@ -119,52 +117,20 @@ def precision_plan(prec):
     return prec, prec, prec
 
 
-# The step's two bank products as chained tile pairs (one launch, nr_sim_pair_kernel).  OFF: measured alone the pair is
-# 1.9 us shorter than two launches (33.8 -> 31.9 us), but the step with it is 2.5 % SLOWER (0.3308 vs 0.3227 ms, six A/B
-# pairs of 1000 steps in one session): the first bank product can no longer start before the second chain's scorer has
-# finished, and one 32 us launch that owns every CU's LDS holds the clustering kernels up longer than two 16 us ones.
-# NR_PAIR_BANK=1 turns it on (developer A/B switch, tools/).
-PAIR_BANK_PRODUCTS = os.environ.get("NR_PAIR_BANK", "0") == "1"
-# Pipelined steps: the next step's bank chains wait for this step's row losses (see after_previous_push).  NR_TAIL_EDGE=0 turns
-# the edge off (developer A/B switch, tools/ab_tail.sh).
-TAIL_BEFORE_NEXT_BANK_READS = os.environ.get("NR_TAIL_EDGE", "1") == "1"
-# NR_TAIL_EDGE=2 (A/B hook): the edge goes to the next step's bank PUSH instead (the row losses then only have to end before
-# the next push, beside the next step's bank chain instead of in front of it)
-TAIL_BEFORE_NEXT_PUSH = os.environ.get("NR_TAIL_EDGE", "1") == "2"
-# Pipelined steps: the batch half of the local branch forked from the origin stream IN FRONT of the step's prologue
-# (StepPipeline.early_fork), i.e. beside the previous step's bank chain instead of behind its push.  OFF: bit-identical, and
-# 36 % SLOWER (0.354 vs 0.260 ms per step, two A/B pairs in one session, tools/ab_early_fork.sh) -- the same figure round 4 got
-# from --decouple_push: whenever a step's chip-filling launches are released ahead of the previous step's push, the replayed
-# graph runs slower, whatever the edges say.  NR_EARLY_FORK=1 turns it on (developer A/B switch).
-EARLY_LOCAL_FORK = os.environ.get("NR_EARLY_FORK", "0") == "1"
-# Loss-only split tail: the centrality weights computed inside the final row-loss launch (same arithmetic, same bits).
-# NR_FUSE_CW=0: their own launch in front of it (developer A/B switch).
-FUSE_CENTRALITY_WEIGHTS = os.environ.get("NR_FUSE_CW", "1") == "1"
-# The token means on the second bank stream instead of the local branch: measured SLOWER (3773-3789 vs 3844-3861 steps/s,
-# tools/ab_tail_fuse.sh; with the centrality weights fused: 3828-3839 vs 3873-3894) -- off; NR_COLSUM_OFF=1 turns it on (A/B switch)
-COLSUM_OFF_CHAIN = os.environ.get("NR_COLSUM_OFF", "0") == "1"
-# Loss-only split tail: the step's four token sets scored by ONE launch (nr_token_weights_fwd_group).  Alone that launch takes
-# 51 us against 68 for the four (tools/microbench.py mlp) -- and the STEP is slower with it: 3773-3806 vs 3871-3888 steps/s at
-# configs[1], 521 vs 562 at configs[3] (tools/ab_group_scorers.sh, two A/B pairs each): its 8-wave 192 x 256 workgroups (165
-# registers a lane) leave no room on a CU for the clustering's workgroups, which then queue behind a 59 us launch (front kernel
-# 40 us instead of 13 in the trace).  OFF; NR_GROUP_SCORERS=1 turns it on (developer A/B switch)
-GROUP_SCORERS = os.environ.get("NR_GROUP_SCORERS", "0") == "1"
-# Pipelined steps: the global logits on the tail stream (in front of the Sinkhorn solve) instead of closing the origin's part of
-# the step.  OFF: bit-identical and 3.5 % SLOWER (3672-3689 vs 3807-3814 steps/s, three A/B pairs, tools/ab_logits_tail.sh) -- one
-# more case of a shorter chain and a slower graph.  NR_LOGITS_TAIL=1 turns it on (developer A/B switch)
-LOGITS_ON_TAIL = os.environ.get("NR_LOGITS_TAIL", "0") == "1"
-# Loss-only step: the batch's text and video scorers as one launch (nr_token_weights_fwd_pair).  NR_PAIR_SCORERS=0: two launches (A/B).
-PAIR_BATCH_SCORERS = os.environ.get("NR_PAIR_SCORERS", "1") == "1"
-# ... from this many tokens in the smaller set on (a few workgroups per CU): configs[3] 517 -> 530 steps/s, configs[2] 424 -> 427;
-# at configs[1] (3072 + 1536 tokens: one workgroup per CU) the two launches one after the other are faster, 3725 vs 3605
-PAIR_BATCH_SCORERS_FROM = int(os.environ.get("NR_PAIR_SCORERS_FROM", "8192"))
+# The step issues the two bank products as two launches (nr_sim_pair_kernel, one launch for both, makes the step slower:
+# docs/LAB_NOTEBOOK.md); bench.py's roofline reads this name.
+PAIR_BANK_PRODUCTS = False
+# Loss-only step: the batch's text and video scorers as one launch (nr_token_weights_fwd_pair) from this many tokens in the smaller
+# set on (a few workgroups per CU): configs[3] 517 -> 530 steps/s, configs[2] 424 -> 427; at configs[1] (3072 + 1536 tokens: one
+# workgroup per CU) the two launches one after the other are faster, 3725 vs 3605
+PAIR_BATCH_SCORERS_FROM = 8192
 
 
 def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
                  gt, gv, sw_t, sw_v, hp, logit_scale, prec=hip.PREC_BF16, keep=False, sw_t1=None, sw_v1=None, join=None,
                  bank_streams=None, local_stream=None, bank_early=0,
-                 capture_order=((7, 5), (7, 1 << 30)), bank_prepared=None, prepared_out=None, bank_push=None, bb_late=False, slot=0,
-                 pipeline=None, local_masks=None):
+                 capture_order=((7, 5), (7, 1 << 30)), bank_prepared=None, prepared_out=None, bank_push=None, slot=0,
+                 pipeline=None):
     """Forward of the head.  Returns (losses[5] device tensor, saved-state dict or None).
 
     `join`: optional callable run right before the first use of gt / gv.  Either the caller produces the
@@ -184,7 +150,7 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
     at work when this function returns -- solve, row losses, bank push -- are appended to `pipeline.pending`, to be joined
     into the capture's origin stream by whoever captures the steps (every join of a capture goes into its origin:
     capture_guard).  This stream is then free for the next step's prologue and clustering while this step's tail runs."""
-    B, Nt, d = text_feat.shape
+    B, Nt, _ = text_feat.shape
     Nv = video_feat.shape[1]
     M = mb_feat_v.shape[0]
     K = int(hp["num_neighbors"])
@@ -206,99 +172,42 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
     # them up itself: two reduction launches less per step)
     split_tail = (not keep) and bank_streams is not None and local_stream is not None and B <= 128 and B % 4 == 0
 
-    # split tail: the two bank products as ONE launch of chained tile pairs (nr_local_level_group -> nr_sim_pair_kernel:
-    # every workgroup computes a tile of the first and then a tile of the second product through one K loop) when both
-    # run the 192 x 384 bf16 blocks on equally many tiles
-    pair_bank = (split_tail and bank_early in (0, 2) and PAIR_BANK_PRODUCTS
-                 and hip.local_level_group_kind(B, Nt, M, Nv, d, p_bank) == 0
-                 and hip.local_level_group_kind(M, Nt, B, Nv, d, p_bank) == 0)
-
     # The local branch, one kernel launch per step (a generator, so that it can be interleaved launch by launch
     # with the clustering -- see below); its results land in `L`.
     L = {}
     early = [None, None]
-    # Pipelined steps with an early fork (modeling.StepPipeline.early_fork): the local branch starts from a point of the origin
-    # stream that lies BEFORE this step's prologue, so it converts its own copy of the caller's masks instead of reading the
-    # prologue's (the same values: 0 / 1 as fp32)
-    early_fork = (pipeline.early_fork if (pipeline is not None and EARLY_LOCAL_FORK and local_masks is not None and local_stream is not None
-                                          and all(m is not None for m in local_masks)) else None)
-
-    def fork_local():
-        if early_fork is not None:
-            wait_event(local_stream, early_fork)
-        else:
-            wait_stream(local_stream, cur)
 
     def local_steps():
-        tm_l, vm_l = text_mask, video_mask
-        if early_fork is not None:
-            tm_l, vm_l = (m if m.dtype == torch.float32 else m.float() for m in local_masks)
-            L["masks"] = (tm_l, vm_l)
-        L["pt"], L["pv"] = pt_, pv_ = ops.prepare_tokens_pair(text_feat, tm_l, video_feat, vm_l, want_lo=lo_b, want_colsum=True)
+        L["pt"], L["pv"] = pt_, pv_ = ops.prepare_tokens_pair(text_feat, text_mask, video_feat, video_mask, want_lo=lo_b,
+                                                              want_colsum=True)
         yield
-        grouped = None
-        if (GROUP_SCORERS and split_tail and bank_prepared is not None and bank_early > 1 and local_stream is not None
-                and p_mlp == hip.PREC_BF16X3 and pt_.lo is not None):
-            # ALL four token sets of the step in one scorer launch (nr_token_weights_fwd_group): the bank's sets read its prepared
-            # shadow, so the launch waits for the previous step's push (as the step's prologue already did); the edge to the
-            # previous step's row losses moves to the first bank product (bank_video_steps / bank_text_steps)
-            if pipeline is not None and pipeline.prev_push_done is not None:
-                wait_event(torch.cuda.current_stream(), pipeline.prev_push_done)
-            pbt_, pbv_ = bank_prepared
-            grouped = ops.token_weights_group(
-                [(pt_, sw_t.w1_hi, sw_t.w1_lo, sw_t.b1, sw_t.w2, sw_t.b2, tm_l, B, Nt),
-                 (pv_, sw_v.w1_hi, sw_v.w1_lo, sw_v.b1, sw_v.w2, sw_v.b2, vm_l, B, Nv),
-                 (pbv_, sw_v.w1_hi, sw_v.w1_lo, sw_v.b1, sw_v.w2, sw_v.b2, mb_mask_v, M, Nv),
-                 (pbt_, sw_t.w1_hi, sw_t.w1_lo, sw_t.b1, sw_t.w2, sw_t.b2, mb_mask_t, M, Nt)],
-                [p_mlp, p_mlp, p_bank, p_bank])
-        if grouped is not None:
-            (L["w_t"], L["lg_t"]), (L["w_v"], L["lg_v"]), (L["w_bv"], _), (L["w_bt"], _) = grouped
-            yield
-        elif PAIR_BATCH_SCORERS and not keep and B * min(Nt, Nv) >= PAIR_BATCH_SCORERS_FROM:
+        if not keep and B * min(Nt, Nv) >= PAIR_BATCH_SCORERS_FROM:
             # the text and the video scorer in one grid; bit-identical to the two launches
             (L["w_t"], L["lg_t"]), (L["w_v"], L["lg_v"]) = ops.token_weights_pair(
-                [(pt_, sw_t.w1_hi, sw_t.w1_lo, sw_t.b1, sw_t.w2, sw_t.b2, tm_l, B, Nt),
-                 (pv_, sw_v.w1_hi, sw_v.w1_lo, sw_v.b1, sw_v.w2, sw_v.b2, vm_l, B, Nv)], p_mlp)
+                [(pt_, sw_t.w1_hi, sw_t.w1_lo, sw_t.b1, sw_t.w2, sw_t.b2, text_mask, B, Nt),
+                 (pv_, sw_v.w1_hi, sw_v.w1_lo, sw_v.b1, sw_v.w2, sw_v.b2, video_mask, B, Nv)], p_mlp)
             yield
         else:
-            L["w_t"], L["lg_t"] = token_weights(pt_, tm_l, sw_t, B, Nt, p_mlp, keep)
+            L["w_t"], L["lg_t"] = token_weights(pt_, text_mask, sw_t, B, Nt, p_mlp, keep)
             yield
-            L["w_v"], L["lg_v"] = token_weights(pv_, vm_l, sw_v, B, Nv, p_mlp, keep)
+            L["w_v"], L["lg_v"] = token_weights(pv_, video_mask, sw_v, B, Nv, p_mlp, keep)
             yield
-        if not (bb_late and split_tail):
-            L["S"], L["aux0"] = ops.local_level(pt_, pv_, L["w_t"], L["w_v"], B, Nt, B, Nv, p_bb, hip.OUT_FULL, keep)
-            yield
-        # mean of the (unmasked) normalised tokens for the centrality weights, both in one launch.  Only the tail reads it: in the
-        # split tail it runs on the second bank stream (idle until then), off the chain prepare -> scorers -> products -> push
-        # that paces the pipelined steps; else here on the local branch
-        if COLSUM_OFF_CHAIN and split_tail and bank_early > 1:
-            side2_ = bank_streams[1]
-            wait_stream(side2_, torch.cuda.current_stream())
-            with torch.cuda.stream(side2_):
-                L["mean_t"], L["mean_v"] = ops.colsum_pair(pt_.colsum, 1.0 / pt_.n_tok, pv_.colsum, 1.0 / pv_.n_tok)
-            for t_ in (pt_.colsum, pv_.colsum):
-                t_.record_stream(side2_)
-        else:
-            L["mean_t"], L["mean_v"] = ops.colsum_pair(pt_.colsum, 1.0 / pt_.n_tok, pv_.colsum, 1.0 / pv_.n_tok)
-            yield
+        L["S"], L["aux0"] = ops.local_level(pt_, pv_, L["w_t"], L["w_v"], B, Nt, B, Nv, p_bb, hip.OUT_FULL, keep)
+        yield
+        # mean of the (unmasked) normalised tokens for the centrality weights, both in one launch
+        L["mean_t"], L["mean_v"] = ops.colsum_pair(pt_.colsum, 1.0 / pt_.n_tok, pv_.colsum, 1.0 / pv_.n_tok)
+        yield
         # `bank_early` chains (0..2) run right behind the batch products, i.e. beside the clustering; the rest is
         # forked after the join (beside the Sinkhorn solve)
-        if local_stream is not None and bank_early > 0:
-            early[0] = yield from bank_video_steps()
-            if bank_early > 1:
-                early[1] = yield from bank_text_steps()
-                if pair_bank:                         # both chains stopped in front of their product: one launch for the two
-                    (pbv_, w_bv_, lg_bv_, _, _), (pbt_, w_bt_, lg_bt_, _, _) = early
-                    c1_, c0_ = ops.local_level_group([(L["pt"], pbv_, L["w_t"], w_bv_, B, Nt, M, Nv, p_bank, hip.OUT_ROWSUM),
-                                                      (pbt_, L["pv"], w_bt_, L["w_v"], M, Nt, B, Nv, p_bank, hip.OUT_COLSUM)])
-                    yield
-                    early[0], early[1] = (pbv_, w_bv_, lg_bv_, None, c1_), (pbt_, w_bt_, lg_bt_, None, c0_)
+        if local_stream is not None:
+            for i in range(min(bank_early, 2)):
+                early[i] = yield from bank_steps(*chains[i])
 
     def after_previous_push():
         """Pipelined steps: whatever reads the memory bank waits for the PREVIOUS step's push (on the stream it runs on)."""
         if pipeline is not None and pipeline.prev_push_done is not None:
             wait_event(torch.cuda.current_stream(), pipeline.prev_push_done)
-        if pipeline is not None and pipeline.prev_tail_done is not None and TAIL_BEFORE_NEXT_BANK_READS:
+        if pipeline is not None and pipeline.prev_tail_done is not None:
             # ... and for the previous step's ROW LOSSES.  No data flows along this edge.  It is there because of how the ROCm 7.2
             # runtime orders a graph's nodes: a node nothing depends on (the row-loss launch is the last of its step) is put at the
             # END of the graph's hardware queues -- the row losses of all ten steps of a pipelined graph ran one after the other
@@ -308,51 +217,33 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
             wait_event(torch.cuda.current_stream(), pipeline.prev_tail_done)
             pipeline.prev_tail_done = None
 
-    def bank_video_steps():
-        # text x bank-video, row mean  -> centrality of text j  (used by the v2t neighbour loss)
+    def bank_steps(feat, mask, prepared, sw, n_tok, out):
+        """One memory-bank chain: prepare (unless the bank's prepared shadow is given), scorer, the product with the batch and,
+        outside the split tail, the mean over the M entries.  Returns (prepared, weights, logits, aux, centrality)."""
         after_previous_push()
-        if bank_prepared is not None:
-            pbv = bank_prepared[1]
-        else:
-            pbv = ops.prepare_tokens(mb_feat_v, mb_mask_v, want_lo=lo_k)
+        pb = prepared
+        if pb is None:
+            pb = ops.prepare_tokens(feat, mask, want_lo=lo_k)
             yield
-        if "w_bv" in L:                                   # (scored by the step's grouped scorer launch)
-            w_bv, lg_bv = L["w_bv"], None
+        w_b, lg_b = token_weights(pb, mask, sw, M, n_tok, p_bank, keep)
+        yield
+        if out == hip.OUT_ROWSUM:
+            part, aux = ops.local_level(L["pt"], pb, L["w_t"], w_b, B, Nt, M, Nv, p_bank, out, keep)
         else:
-            w_bv, lg_bv = token_weights(pbv, mb_mask_v, sw_v, M, Nv, p_bank, keep)
-            yield
-        if pair_bank:
-            return pbv, w_bv, lg_bv, None, None          # the product itself: one launch with the other chain's (below)
-        p1, aux1 = ops.local_level(L["pt"], pbv, L["w_t"], w_bv, B, Nt, M, Nv, p_bank, hip.OUT_ROWSUM, keep)
+            part, aux = ops.local_level(pb, L["pv"], w_b, L["w_v"], M, Nt, B, Nv, p_bank, out, keep)
         yield
         if split_tail:
-            return pbv, w_bv, lg_bv, aux1, p1
-        c1 = ops.reduce_parts(p1, 1.0 / M)
+            return pb, w_b, lg_b, aux, part
+        c = ops.reduce_parts(part, 1.0 / M)
         yield
-        return pbv, w_bv, lg_bv, aux1, c1
+        return pb, w_b, lg_b, aux, c
 
-    def bank_text_steps():
-        # bank-text x video, column mean -> centrality of video j (used by the t2v neighbour loss)
-        after_previous_push()
-        if bank_prepared is not None:
-            pbt = bank_prepared[0]
-        else:
-            pbt = ops.prepare_tokens(mb_feat_t, mb_mask_t, want_lo=lo_k)
-            yield
-        if "w_bt" in L:
-            w_bt, lg_bt = L["w_bt"], None
-        else:
-            w_bt, lg_bt = token_weights(pbt, mb_mask_t, sw_t, M, Nt, p_bank, keep)
-            yield
-        if pair_bank:
-            return pbt, w_bt, lg_bt, None, None
-        p0, aux2 = ops.local_level(pbt, L["pv"], w_bt, L["w_v"], M, Nt, B, Nv, p_bank, hip.OUT_COLSUM, keep)
-        yield
-        if split_tail:
-            return pbt, w_bt, lg_bt, aux2, p0
-        c0 = ops.reduce_parts(p0, 1.0 / M)
-        yield
-        return pbt, w_bt, lg_bt, aux2, c0
+    # The two bank chains, in the order they start early:
+    #   text x bank-video, row mean     -> centrality of text j  (used by the v2t neighbour loss)
+    #   bank-text x video, column mean  -> centrality of video j (used by the t2v neighbour loss)
+    pb_t, pb_v = bank_prepared if bank_prepared is not None else (None, None)
+    chains = ((mb_feat_v, mb_mask_v, pb_v, sw_v, Nv, hip.OUT_ROWSUM),
+              (mb_feat_t, mb_mask_t, pb_t, sw_t, Nt, hip.OUT_COLSUM))
 
     def exhaust(gen):
         """Runs a step generator to its end; returns its return value."""
@@ -362,8 +253,9 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
             except StopIteration as stop:
                 return stop.value
 
-    bank_video = lambda: exhaust(bank_video_steps())     # noqa: E731
-    bank_text = lambda: exhaust(bank_text_steps())       # noqa: E731
+    def bank_chain(i):
+        """Chain i, unless it already ran early on the local stream."""
+        return early[i] or exhaust(bank_steps(*chains[i]))
 
     stepwise_join = join is not None and hasattr(join, "__next__")
     if local_stream is not None and stepwise_join:
@@ -371,7 +263,7 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
         # the nodes captured ahead of it have started (profiled step: a branch captured after 7 clustering nodes
         # began 120 us late and ended up the critical path).  So the two branches are captured interleaved:
         # `capture_order` = [(clustering launches, local launches), ...] per turn, the last pair repeating.
-        fork_local()
+        wait_stream(local_stream, cur)
         loc = local_steps()
         loc_alive, clu_alive = True, True
         produced = None
@@ -399,7 +291,7 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
     else:
         # `join`: one callable run right before gt / gv are needed (may return them); generators are run through
         if local_stream is not None:
-            fork_local()
+            wait_stream(local_stream, cur)
             if join is not None:
                 produced = exhaust(join) if stepwise_join else join()
                 if produced is not None:
@@ -418,7 +310,7 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
     pt, pv, w_t, w_v, lg_t, lg_v = L["pt"], L["pv"], L["w_t"], L["w_v"], L["lg_t"], L["lg_v"]
     if prepared_out is not None:
         prepared_out["pt"], prepared_out["pv"] = pt, pv
-    S, aux0, mean_t, mean_v = L.get("S"), L.get("aux0"), L["mean_t"], L["mean_v"]
+    S, aux0, mean_t, mean_v = L["S"], L["aux0"], L["mean_t"], L["mean_v"]
     _check_global_tokens(gt, gv, hp)
     gt2 = gt.float().contiguous()                  # [B, G, d]: G = 1 at the MSR-VTT token counts
     gv2 = gv.float().contiguous()
@@ -431,18 +323,8 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
     # is prologue -> clustering -> logits -> Sinkhorn, with neither a finalize launch nor the push behind it.
     if split_tail:
         tail = pipeline.tail_stream if pipeline is not None else None
-        if tail is not None and LOGITS_ON_TAIL:
-            # pipelined steps: the global logits (one small launch) open the TAIL stream instead of closing this one -- the next
-            # step's prologue follows the clustering's last launch directly
-            wait_stream(tail, cur)
-            with torch.cuda.stream(tail):
-                G = global_logits(gt, gv, sw_t1, sw_v1)
-                g_ready = record_event(tail)
-            for t_ in (gt, gv):
-                t_.record_stream(tail)
-        else:
-            G = global_logits(gt, gv, sw_t1, sw_v1)
-            g_ready = record_event(cur)
+        G = global_logits(gt, gv, sw_t1, sw_v1)
+        g_ready = record_event(cur)
         rowloss = torch.empty((2, 4, B), dtype=torch.float32, device=G.device)
         losses = torch.empty((5,), dtype=torch.float32, device=G.device)
         counter = ops.split_tail_counter(G.device, slot)
@@ -465,19 +347,10 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
             wait_stream(side, local_stream)
             wait_stream(side2, local_stream)
             with torch.cuda.stream(side2):
-                pbt, w_bt, lg_bt, aux2, c0 = early[1] or bank_text()
+                pbt, w_bt, lg_bt, aux2, c0 = bank_chain(1)
             with torch.cuda.stream(side):
-                if S is None:
-                    # `bb_late`: the batch x batch product runs HERE, beside the Sinkhorn solve (only the row losses read S)
-                    # -- one chip-filling launch less beside the clustering
-                    S, aux0 = ops.local_level(pt, pv, w_t, w_v, B, Nt, B, Nv, p_bb, hip.OUT_FULL, keep)
-                pbv, w_bv, lg_bv, aux1, c1 = early[0] or bank_video()
+                pbv, w_bv, lg_bv, aux1, c1 = bank_chain(0)
                 wait_stream(side, side2)
-                if pair_bank and early[0] is None:
-                    for t_ in (pbt.hi, w_bt):
-                        t_.record_stream(side)
-                    c1, c0 = ops.local_level_group([(L["pt"], pbv, L["w_t"], w_bv, B, Nt, M, Nv, p_bank, hip.OUT_ROWSUM),
-                                                    (pbt, L["pv"], w_bt, L["w_v"], M, Nt, B, Nv, p_bank, hip.OUT_COLSUM)])
                 if bank_push is not None:
                     # both bank products have read the bank (and its prepared shadow): the batch may take the oldest rows'
                     # place -- on a stream of its own, beside the centrality weights and the row losses.  (A stream that
@@ -489,15 +362,10 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
                     with torch.cuda.stream(pst):
                         for t_ in (pt.hi, pt.norm, pv.hi, pv.norm) + ((pt.lo, pv.lo) if pt.lo is not None else ()):
                             t_.record_stream(pst)
-                        if early_fork is not None and pipeline.prologue_done is not None:
-                            wait_event(pst, pipeline.prologue_done)      # the push writes at the ring head this step's prologue has moved
-                        if pipeline is not None and pipeline.prev_tail_done is not None and TAIL_BEFORE_NEXT_PUSH:
-                            wait_event(pst, pipeline.prev_tail_done)
-                            pipeline.prev_tail_done = None
                         with torch.no_grad():
                             bank_push()
                 wait_event(side, g_ready)
-                if FUSE_CENTRALITY_WEIGHTS and gt2.shape[1] == 1 and gv2.shape[1] == 1 and gt2.shape[0] == B and gv2.shape[0] == B:
+                if gt2.shape[1] == 1 and gv2.shape[1] == 1 and gt2.shape[0] == B and gv2.shape[0] == B:
                     # one global token per sample: the row-loss launch computes the centrality weights itself (one launch less
                     # on the chain that the next step's bank reads wait for)
                     wc_t = wc_v = cw_aux = None
@@ -563,17 +431,17 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
                 if local_stream is not None:
                     wait_stream(st_, local_stream)       # (their launches read the local branch's tokens / weights / means)
             with torch.cuda.stream(bank_streams[1]):
-                pbt, w_bt, lg_bt, aux2, c0 = early[1] or bank_text()
+                pbt, w_bt, lg_bt, aux2, c0 = bank_chain(1)
             with torch.cuda.stream(bank_streams[0]):
-                pbv, w_bv, lg_bv, aux1, c1 = early[0] or bank_video()
+                pbv, w_bv, lg_bv, aux1, c1 = bank_chain(0)
                 wc_t, wc_v, cw_aux = ops.centrality_weights_pair(gt2, gv2, mean_t, mean_v, hp["centrality_scale"], keep)
             for st_ in bank_streams:
                 wait_stream(cur, st_)
             for t_ in (c0, c1, wc_t, wc_v) + ((pbt.hi, pbv.hi, w_bt, w_bv) if keep else ()):
                 t_.record_stream(cur)
         else:
-            pbv, w_bv, lg_bv, aux1, c1 = early[0] or bank_video()
-            pbt, w_bt, lg_bt, aux2, c0 = early[1] or bank_text()
+            pbv, w_bv, lg_bv, aux1, c1 = bank_chain(0)
+            pbt, w_bt, lg_bt, aux2, c0 = bank_chain(1)
             wc_t, wc_v, cw_aux = ops.centrality_weights_pair(gt2, gv2, mean_t, mean_v, hp["centrality_scale"], keep)
         rowloss, losses = ops.row_losses_final(S, G, tgt_r, tgt_c, c0, c1, wc_t, wc_v, ls, K, hp["temperature"],
                                                hp["uniform_weight"], hp["neighbor_weight"], hp["kl_weight"])

@@ -214,6 +214,22 @@ def test_product_never_imports_oracle():
                 assert "nr_oracle" not in src and "import oracle" not in src, f
 
 
+def test_package_reads_only_the_listed_environment_variables():
+    """The shipped step must not change with a stray variable in the shell: every os.environ / getenv read of the package is
+    one of these (library path, build flags, the queue count that turns side streams off, the capture guard's trace)."""
+    allowed = {("build.py", "HIPCC"), ("build.py", "NR_EXTRA_FLAGS"), ("capture_guard.py", "NR_GUARD_TRACE"),
+               ("hip.py", "NR_HIP_LIB"), ("modeling.py", "GPU_MAX_HW_QUEUES")}
+    pkg = os.path.join(ROOT, "neighborretr_amd")
+    reads = set()
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            src = open(os.path.join(pkg, f)).read()
+            for m in re.finditer(r"environ|getenv", src):
+                name = re.match(r"(?:environ\.get\(|environ\[|getenv\()\s*[\"']([A-Za-z0-9_]+)[\"']", src[m.start():])
+                reads.add((f, name.group(1) if name else src[m.start():src.find("\n", m.start())]))
+    assert reads == allowed
+
+
 def test_multi_sentence_metrics_against_counting():
     """utils/metrics.py:82-148 semantics by brute force: sim[i, s, j] = sentence s of video i vs video j."""
     from neighborretr_amd.metrics import RetrievalMetrics

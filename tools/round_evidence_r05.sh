@@ -20,7 +20,6 @@ if [[ "$part" == B ]]; then
   bash tools/bench_profile.sh r05/step --unroll 1 > /dev/null 2>&1
   NR_PROF_TIMELINE_STEPS=3 bash tools/bench_profile.sh r05/pipe > /dev/null 2>&1
   python tools/sinkhorn_large_times.py 2>&1 | q > "$out/sinkhorn_large.txt"
-  bash tools/ab_tail_edge.sh > "$out/ab_tail_edge.txt" 2>&1
 fi
 if [[ "$part" == C ]]; then
   python tools/rank_local_times.py --worlds 2 4 8 --out "gpurun_out/r05/rank_local.txt" > "$out/rank_local.log" 2>&1
