@@ -739,6 +739,30 @@ int nr_slab_ranks(const float* S_slab, int n_rows, int N, int row0, const float*
 int nr_group_slab_ranks(const float* S_slab, int n_rows, int V, int row0, const int32_t* group_end, int G,
                         int32_t* greater_rows, int32_t* equal_before_rows, float* group_max, void* stream);
 
+/* Top-k lists for hubness evaluation (k-occurrence, NeighborRetr's project page "Hubness Observation"; the reference has no
+ * code for it).  Order of a line: score descending, equal scores by index ascending, -0.0 == +0.0, NaN never selected; a
+ * line with fewer than k selectable entries is padded with index -1 / value -inf.  Values are the exact bits of S.
+ * 1 <= k <= 128 (else NR_EINVAL before any launch).  Radix select in LDS, no sort; bitwise reproducible.
+ *   nr_slab_topk_rows: idx_out / val_out [n_rows, k], one list per row of S_slab [n_rows, N] (indices: columns).
+ *   nr_slab_topk_cols: idx_out / val_out [N, k], one list per column over this slab's rows only, indices row0 + i: the
+ *     partial lists that nr_topk_merge combines over the ranks. */
+int nr_slab_topk_rows(const float* S_slab, int n_rows, int N, int k, int32_t* idx_out, float* val_out, void* stream);
+int nr_slab_topk_cols(const float* S_slab, int n_rows, int N, int row0, int k, int32_t* idx_out, float* val_out, void* stream);
+
+/* Merge of n_lists partial lists per item: idx / val [n_lists, n_items, k], each list in the order above with its absent
+ * entries (index < 0 or NaN value) last, as the two functions above write them -> idx_out / val_out [n_items, k] in the
+ * same order.  Combines column lists of row slabs, or lists of a gallery scored in chunks.  An index found in several lists
+ * with equal keys is kept once per list, ordered by list number. */
+int nr_topk_merge(int n_lists, const int32_t* idx, const float* val, int n_items, int k, int32_t* idx_out, float* val_out,
+                  void* stream);
+
+/* k-occurrence counts of n_q lists idx [n_q, k] over a gallery of n_gallery items: occ[j] = #{q : j in list q},
+ * good[j] = #{q : j in list q and gt_begin[q] <= j < gt_end[q]} (int32, zeroed here first).  gt_begin / gt_end [n_q]:
+ * query q's ground-truth range (single-sentence sets: [q, q+1); multi-sentence: the group's video, or the video's
+ * sentences).  Absent slots (-1) and indices outside the gallery are not counted.  n_q = 0: the zeroed counts. */
+int nr_topk_occurrences(const int32_t* idx, int n_q, int k, int n_gallery, const int32_t* gt_begin, const int32_t* gt_end,
+                        int32_t* occ, int32_t* good, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

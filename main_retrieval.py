@@ -89,6 +89,9 @@ def get_args():
                    help="1: BASELINE configs[4] -- ViT-B/32 image tower, text tower and temporal transformer (stock "
                         "PyTorch-ROCm modules, random init unless --init_model) in front of the HIP head; --synthetic then "
                         "feeds random pixels [b, frames, 3, 224, 224] and token ids instead of token features")
+    p.add_argument("--hubness_k", type=int, default=0,
+                   help="k > 0 (at most 128): the evaluation also reports hubness of the top-k lists in both directions "
+                        "(k-occurrence skewness, hubs, anti-hubs, bad hubs; DESIGN.md); 0 = off")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -444,7 +447,8 @@ def eval_epoch(args, model, test):
     they are the inputs), one packed all-gather + index scatter restores dataset order (evaluator.py:173-189), rank r
     computes rows [r N/W, (r+1) N/W) of the N x N similarity and the rank counts of its slab on the GPU, three small
     collectives complete them."""
-    from neighborretr_amd.evaluator import gather_eval_features, rank_sample_indices, sharded_metrics
+    from neighborretr_amd.evaluator import gather_eval_features, rank_sample_indices, sharded_metrics, sharded_metrics_with_hubness
+    hubness_k = int(getattr(args, "hubness_k", 0) or 0)
     model.eval()
     dev = args.device
     mine = rank_sample_indices(test.n, args.world_size, args.rank)     # equal counts on every rank (padded like DistributedSampler)
@@ -455,9 +459,16 @@ def eval_epoch(args, model, test):
         t, tm, v, vm = (torch.cat([p[k] for p in parts], 0) for k in range(4))
     if args.world_size > 1:
         t, v, tm, vm = gather_eval_features(t, v, mine.to(dev), tm, vm, args)
-    t2v, v2t = sharded_metrics(model, t, v, tm.float(), vm.float(), args)
+    if hubness_k:
+        t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k)
+    else:
+        t2v, v2t = sharded_metrics(model, t, v, tm.float(), vm.float(), args)
     log(args, f"text->video R@1 {t2v['R1']:.1f} R@5 {t2v['R5']:.1f} R@10 {t2v['R10']:.1f} MedR {t2v['MR']:.1f} | "
               f"video->text R@1 {v2t['R1']:.1f} R@5 {v2t['R5']:.1f} R@10 {v2t['R10']:.1f} MedR {v2t['MR']:.1f}")
+    if hubness_k:
+        from neighborretr_amd.metrics import RetrievalMetrics
+        log(args, RetrievalMetrics.format_hubness(t2v["hubness"], prefix="text->video "))
+        log(args, RetrievalMetrics.format_hubness(v2t["hubness"], prefix="video->text "))
     return t2v, v2t
 
 

@@ -93,8 +93,14 @@ def sharded_retrieval_ranks(model, text_feat, video_feat, text_mask, video_mask,
     if video_feat.shape[0] != N:
         raise ValueError("single-sentence retrieval: one text per video expected")
     r0, r1 = slab_bounds(N, W, rank)
-    dev = text_feat.device
     S_slab = _slab_similarity(model, text_feat, video_feat, text_mask, video_mask, r0, r1, chunk)
+    return _ranks_from_slab(S_slab, N, W, rank)
+
+
+def _ranks_from_slab(S_slab, N, W, rank):
+    """sharded_retrieval_ranks from this rank's slab S[r0:r1, :] (three collectives)."""
+    r0, r1 = slab_bounds(N, W, rank)
+    dev = S_slab.device
     n = r1 - r0
     # the diagonal of the whole matrix: this slab's part, gathered (slabs differ by at most one row: padded to the largest)
     width = -(-N // W)
@@ -149,14 +155,18 @@ def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, vide
     W = _world(args)
     rank = comm.get_rank() if W > 1 else 0
     Ns, V = text_feat.shape[0], video_feat.shape[0]
-    ends = np.asarray(cut_off_points, dtype=np.int64) + 1
-    if len(ends) != V or (np.diff(ends) <= 0).any() or ends[0] <= 0 or ends[-1] != Ns:
-        raise ValueError(f"cut_off_points must give {V} non-empty, increasing sentence groups ending at {Ns - 1}")
-    dev = text_feat.device
+    ends = _group_ends(cut_off_points, Ns, V)
+    r0, r1 = slab_bounds(Ns, W, rank)
+    S_slab = _slab_similarity(model, text_feat, video_feat, text_mask, video_mask, r0, r1, chunk)
+    return _multi_sentence_from_slab(S_slab, ends, Ns, V, W, rank)
+
+
+def _multi_sentence_from_slab(S_slab, ends, Ns, V, W, rank):
+    """sharded_multi_sentence_metrics from this rank's slab of sentence rows (two collectives)."""
+    dev = S_slab.device
     group_end = torch.from_numpy(ends.astype(np.int32)).to(dev)
     r0, r1 = slab_bounds(Ns, W, rank)
     n = r1 - r0
-    S_slab = _slab_similarity(model, text_feat, video_feat, text_mask, video_mask, r0, r1, chunk)
     width = -(-Ns // W)
     mine = torch.zeros((width,), dtype=torch.int32, device=dev)
     if n:
@@ -173,4 +183,136 @@ def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, vide
         ranks = mine[:n]
     t2v = RetrievalMetrics.multi_sentence_metrics_from_ranks(ranks[ranks >= 0])      # < 0: own score NaN / inf, not ranked
     v2t = RetrievalMetrics.compute_metrics(gmax.T.contiguous())          # [video, caption group], metrics.py:146-148
+    return t2v, v2t
+
+
+# ---- top-k lists and hubness (DESIGN.md "Top-k lists and hubness") ------------------------------------------------------
+# Rank r scores only its slab of rows, as above.  Text->video (row) lists are complete on the rank that owns the row;
+# video->text (column) lists are partial per slab: one all-gather of every rank's [N, k] partial lists and nr_topk_merge
+# give every rank the same complete lists.  k-occurrences of the rows: each rank counts its own rows, one int32 all-reduce
+# sums them.  Only integers and the selected scores cross the ranks; the N x N matrix never leaves its slabs.
+
+def _group_ends(cut_off_points, Ns, V):
+    ends = np.asarray(cut_off_points, dtype=np.int64) + 1
+    if len(ends) != V or (np.diff(ends) <= 0).any() or ends[0] <= 0 or ends[-1] != Ns:
+        raise ValueError(f"cut_off_points must give {V} non-empty, increasing sentence groups ending at {Ns - 1}")
+    return ends
+
+
+def _ground_truth(n_rows, n_cols, ends, dev):
+    """(row_begin, row_end [n_rows], col_begin, col_end [n_cols]) int32 on `dev`: the ground-truth range of every row query
+    (over the columns) and of every column query (over the rows).  ends = None: item i's ground truth is item i; otherwise
+    ends[g] = one past the last sentence (row) of video (column) g."""
+    if ends is None:
+        r, c = np.arange(n_rows), np.arange(n_cols)
+        rb, re_, cb, ce = r, r + 1, c, c + 1
+    else:
+        rb = np.searchsorted(ends, np.arange(n_rows), side="right")          # the group of sentence s
+        re_ = rb + 1
+        cb, ce = np.concatenate(([0], ends[:-1])), ends
+    return tuple(torch.from_numpy(np.asarray(a, dtype=np.int32)).to(dev) for a in (rb, re_, cb, ce))
+
+
+def _slab_row_lists(S_slab, k, n_cols):
+    if S_slab.shape[0]:
+        return ops.slab_topk_rows(S_slab, k)
+    dev = S_slab.device
+    return torch.empty((0, k), dtype=torch.int32, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev)
+
+
+def _column_lists(S_slab, n_rows, n_cols, k, W, rank):
+    """Complete column lists [n_cols, k] on every rank: this slab's partial lists, one all-gather, nr_topk_merge."""
+    r0, r1 = slab_bounds(n_rows, W, rank)
+    dev = S_slab.device
+    if r1 > r0:
+        ci, cv = ops.slab_topk_cols(S_slab, r0, k)
+    else:
+        ci = torch.full((n_cols, k), -1, dtype=torch.int32, device=dev)
+        cv = torch.full((n_cols, k), float("-inf"), dtype=torch.float32, device=dev)
+    if W == 1:
+        return ci, cv
+    part = torch.stack((ci, cv.view(torch.int32)))                   # scores travel as their int32 bits
+    allp = torch.empty((W, 2, n_cols, k), dtype=torch.int32, device=dev)
+    comm.all_gather_into_tensor(allp.view(-1), part.view(-1))
+    return ops.topk_merge(allp[:, 0].contiguous(), allp[:, 1].contiguous().view(torch.float32))
+
+
+def _topk_from_slab(S_slab, n_rows, n_cols, k, W, rank):
+    r0, r1 = slab_bounds(n_rows, W, rank)
+    dev = S_slab.device
+    ri, rv = _slab_row_lists(S_slab, k, n_cols)
+    if W > 1:
+        width = -(-n_rows // W)
+        mine = torch.zeros((width, 2, k), dtype=torch.int32, device=dev)
+        mine[:r1 - r0, 0], mine[:r1 - r0, 1] = ri, rv.view(torch.int32)
+        allr = torch.empty((W, width, 2, k), dtype=torch.int32, device=dev)
+        comm.all_gather_into_tensor(allr.view(-1), mine.view(-1))
+        rows = torch.cat([allr[r, :slab_bounds(n_rows, W, r)[1] - slab_bounds(n_rows, W, r)[0]] for r in range(W)])
+        ri, rv = rows[:, 0].contiguous(), rows[:, 1].contiguous().view(torch.float32)
+    ci, cv = _column_lists(S_slab, n_rows, n_cols, k, W, rank)
+    return ri, rv, ci, cv
+
+
+def _hubness_from_slab(S_slab, n_rows, n_cols, k, W, rank, ends):
+    r0, r1 = slab_bounds(n_rows, W, rank)
+    rb, re_, cb, ce = _ground_truth(n_rows, n_cols, ends, S_slab.device)
+    ri, _ = _slab_row_lists(S_slab, k, n_cols)
+    occ_t = torch.stack(ops.topk_occurrences(ri, n_cols, rb[r0:r1], re_[r0:r1]))
+    if W > 1:
+        comm.all_reduce(occ_t)                                        # the ranks' row counts -> the whole matrix's
+    ci, _ = _column_lists(S_slab, n_rows, n_cols, k, W, rank)
+    occ_v = torch.stack(ops.topk_occurrences(ci, n_rows, cb, ce))
+    occ_t, occ_v = occ_t.cpu().numpy(), occ_v.cpu().numpy()
+    return (RetrievalMetrics.hubness_from_occurrences(occ_t[0], occ_t[1], k, n_rows),
+            RetrievalMetrics.hubness_from_occurrences(occ_v[0], occ_v[1], k, n_cols))
+
+
+def _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk):
+    """(S_slab, n_rows, n_cols, W, rank, ends) of this rank: its rows of the text (sentence) x video similarity."""
+    W = _world(args)
+    rank = comm.get_rank() if W > 1 else 0
+    n_rows, n_cols = text_feat.shape[0], video_feat.shape[0]
+    if cut_off_points is None:
+        if n_cols != n_rows:
+            raise ValueError("single-sentence retrieval: one text per video expected")
+        ends = None
+    else:
+        ends = _group_ends(cut_off_points, n_rows, n_cols)
+    r0, r1 = slab_bounds(n_rows, W, rank)
+    S_slab = _slab_similarity(model, text_feat, video_feat, text_mask, video_mask, r0, r1, chunk)
+    return S_slab, n_rows, n_cols, W, rank, ends
+
+
+def sharded_topk(model, text_feat, video_feat, text_mask, video_mask, k, args, cut_off_points=None, chunk=256):
+    """-> (t2v_idx [Nt,k] int32, t2v_val [Nt,k] fp32, v2t_idx [V,k], v2t_val [V,k]) on the device, identical on every rank:
+    the top-k videos of every text (sentence) and the top-k texts of every video, scores descending, ties by lower index,
+    NaN never selected, padded with -1 / -inf; values are the exact bits of the rank-exact similarity."""
+    S_slab, n_rows, n_cols, W, rank, _ = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    ops._check_k(k)
+    return _topk_from_slab(S_slab, n_rows, n_cols, int(k), W, rank)
+
+
+def sharded_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k=15, cut_off_points=None, chunk=256):
+    """-> (t2v_hub, v2t_hub): RetrievalMetrics.hubness_from_occurrences of the text->video and video->text top-k lists,
+    identical on every rank.  Multi-sentence sets (cut_off_points as in sharded_multi_sentence_metrics): a sentence's ground
+    truth is its video, a video's every sentence of its group."""
+    S_slab, n_rows, n_cols, W, rank, ends = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points,
+                                                       chunk)
+    ops._check_k(k)
+    return _hubness_from_slab(S_slab, n_rows, n_cols, int(k), W, rank, ends)
+
+
+def sharded_metrics_with_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k, cut_off_points=None, chunk=256):
+    """sharded_metrics (cut_off_points None) or sharded_multi_sentence_metrics, plus a "hubness" entry in each dictionary
+    (sharded_hubness), from ONE scoring of this rank's slab."""
+    S_slab, n_rows, n_cols, W, rank, ends = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points,
+                                                       chunk)
+    ops._check_k(k)
+    if ends is None:
+        gt, et, gv, ev = _ranks_from_slab(S_slab, n_rows, W, rank)
+        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
+        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
+    else:
+        t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
+    t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, int(k), W, rank, ends)
     return t2v, v2t

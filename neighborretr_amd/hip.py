@@ -219,7 +219,12 @@ _SIGNATURES = {
     "nr_diag_ranks": ([_P, _I, _P, _P, _P], _I),
     "nr_slab_ranks": ([_P, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "nr_group_slab_ranks": ([_P, _I, _I, _I, _P, _I, _P, _P, _P, _P], _I),
+    "nr_slab_topk_rows": ([_P, _I, _I, _I, _P, _P, _P], _I),
+    "nr_slab_topk_cols": ([_P, _I, _I, _I, _I, _P, _P, _P], _I),
+    "nr_topk_merge": ([_I, _P, _P, _I, _I, _P, _P, _P], _I),
+    "nr_topk_occurrences": ([_P, _I, _I, _I, _P, _P, _P, _P, _P], _I),
 }
+TOPK_MAX = 128                               # largest k of the top-k entry points
 
 
 class NrHipError(RuntimeError):

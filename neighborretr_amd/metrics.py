@@ -94,6 +94,51 @@ class RetrievalMetrics:
         sim = torch.as_tensor(sim_tensor)
         return torch.nan_to_num(sim, nan=float("-inf"), posinf=float("inf"), neginf=float("-inf")).amax(dim=1).T
 
+    @staticmethod
+    def hubness_from_occurrences(occ, good, k, n_queries):
+        """Hubness summary of one direction from its k-occurrence counts (DESIGN.md "Top-k lists and hubness"): occ[j] = N_k
+        of gallery item j (queries whose top-k list holds j), good[j] = GN_k (those for which j is a ground truth).  Hubs are
+        the items with N_k > 2 mu; percentages follow the R@K convention (count * 100 / n)."""
+        occ = np.asarray(occ, dtype=np.int64).reshape(-1)
+        good = np.asarray(good, dtype=np.int64).reshape(-1)
+        if occ.shape != good.shape or occ.size == 0:
+            raise ValueError("occ and good must be non-empty and of one length")
+        n = occ.size
+        total = int(occ.sum())
+        mu = total / n
+        dev = occ.astype(np.float64) - mu
+        std = float(np.sqrt(np.mean(dev ** 2)))
+        skew = float(np.mean(dev ** 3) / std ** 3) if std > 0 else 0.0
+        hubs = occ > 2 * mu
+        bad = occ - good
+        return {
+            "k": int(k),
+            "n_queries": int(n_queries),
+            "n_gallery": int(n),
+            "mu": float(mu),
+            "skewness": skew,
+            "anti_hub_pct": float(np.sum(occ == 0)) * 100 / n,
+            "hub_pct": float(np.sum(hubs)) * 100 / n,
+            "hub_occurrence_pct": float(np.sum(occ[hubs])) * 100 / total if total else 0.0,
+            "bad_hub_pct": float(np.sum(hubs & (bad > good))) * 100 / n,
+            "good_occurrence_pct": float(np.sum(good)) * 100 / total if total else 0.0,
+            "max_occurrence": int(occ.max()),
+            "occurrence": occ,
+            "good_occurrence": good,
+        }
+
+    @staticmethod
+    def format_hubness(hub, prefix=""):
+        return (f"{prefix}Hubness@{hub['k']}: skew {hub['skewness']:.2f} - hubs {hub['hub_pct']:.1f}% - "
+               f"hub occurrence {hub['hub_occurrence_pct']:.1f}% - bad hubs {hub['bad_hub_pct']:.1f}% - "
+               f"anti-hubs {hub['anti_hub_pct']:.1f}% - good occurrence {hub['good_occurrence_pct']:.1f}% - "
+               f"max N_k {hub['max_occurrence']}")
+
+    def log_hubness(self, hub, prefix=""):
+        """One line per direction, in the style of print_metrics (silent without a logger)."""
+        if self.logger is not None:
+            self.logger.info(self.format_hubness(hub, prefix))
+
     def print_metrics(self, metrics, prefix=""):
         msg = (f"{prefix}R@1: {metrics['R1']:.1f} - R@5: {metrics['R5']:.1f} - R@10: {metrics['R10']:.1f} - "
                f"R@50: {metrics.get('R50', 0.0):.1f} - Median R: {metrics['MR']:.1f} - Mean R: {metrics['MeanR']:.1f}")

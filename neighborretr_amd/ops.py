@@ -891,6 +891,73 @@ def group_slab_ranks(S_slab, row0, group_end):
     return gr, eb, gmax
 
 
+def _check_k(k):
+    k = int(k)
+    if not 1 <= k <= hip.TOPK_MAX:
+        raise ValueError(f"k must lie in [1, {hip.TOPK_MAX}], got {k}")
+    return k
+
+
+def slab_topk_rows(S_slab, k):
+    """(idx [n,k] int32, val [n,k] fp32): the top-k list of every row of S_slab [n,N] (nr_slab_topk_rows): score descending,
+    ties by lower column, NaN never selected, padded with -1 / -inf."""
+    k = _check_k(k)
+    S_slab = _f32(S_slab).contiguous()
+    if S_slab.dim() != 2:
+        raise ValueError("S_slab must be 2-D")
+    n, N = S_slab.shape
+    idx = torch.empty((n, k), dtype=torch.int32, device=S_slab.device)
+    val = torch.empty((n, k), dtype=torch.float32, device=S_slab.device)
+    hip.call("nr_slab_topk_rows", hip.ptr(S_slab), n, N, k, hip.ptr(idx), hip.ptr(val), hip.stream_ptr())
+    return idx, val
+
+
+def slab_topk_cols(S_slab, row0, k):
+    """(idx [N,k] int32, val [N,k] fp32): every column's top-k list over this slab's rows only, indices row0 + i
+    (nr_slab_topk_cols) -- the partial lists topk_merge combines."""
+    k = _check_k(k)
+    S_slab = _f32(S_slab).contiguous()
+    if S_slab.dim() != 2:
+        raise ValueError("S_slab must be 2-D")
+    n, N = S_slab.shape
+    idx = torch.empty((N, k), dtype=torch.int32, device=S_slab.device)
+    val = torch.empty((N, k), dtype=torch.float32, device=S_slab.device)
+    hip.call("nr_slab_topk_cols", hip.ptr(S_slab), n, N, int(row0), k, hip.ptr(idx), hip.ptr(val), hip.stream_ptr())
+    return idx, val
+
+
+def topk_merge(idx, val):
+    """idx [W,n,k] int32, val [W,n,k] fp32 (W partial lists per item, each in the top-k order) -> the merged (idx, val)
+    [n,k] (nr_topk_merge)."""
+    if idx.dim() != 3 or idx.shape != val.shape:
+        raise ValueError("idx and val must both be [n_lists, n_items, k]")
+    W, n, k = idx.shape
+    k = _check_k(k)
+    idx, val = idx.contiguous(), val.contiguous()
+    out_i = torch.empty((n, k), dtype=torch.int32, device=idx.device)
+    out_v = torch.empty((n, k), dtype=torch.float32, device=idx.device)
+    hip.call("nr_topk_merge", W, hip.ptr(idx, torch.int32), hip.ptr(val, torch.float32), n, k, hip.ptr(out_i), hip.ptr(out_v),
+             hip.stream_ptr())
+    return out_i, out_v
+
+
+def topk_occurrences(idx, n_gallery, gt_begin, gt_end):
+    """(occ, good) [n_gallery] int32 k-occurrence counts of the lists idx [n_q,k] int32 (nr_topk_occurrences); query q's
+    ground truth is the gallery range [gt_begin[q], gt_end[q]) (int32 [n_q] on the device)."""
+    if idx.dim() != 2:
+        raise ValueError("idx must be [n_queries, k]")
+    n_q, k = idx.shape
+    k = _check_k(k)
+    if gt_begin.shape != (n_q,) or gt_end.shape != (n_q,):
+        raise ValueError("gt_begin / gt_end must have one entry per query")
+    idx = idx.contiguous()
+    occ = torch.empty((n_gallery,), dtype=torch.int32, device=idx.device)
+    good = torch.empty((n_gallery,), dtype=torch.int32, device=idx.device)
+    hip.call("nr_topk_occurrences", hip.ptr(idx, torch.int32), n_q, k, int(n_gallery), hip.ptr(gt_begin.contiguous(), torch.int32),
+             hip.ptr(gt_end.contiguous(), torch.int32), hip.ptr(occ), hip.ptr(good), hip.stream_ptr())
+    return occ, good
+
+
 def linear_x3(x, w, bias=None, residual=None):
     """Y = X W^T (+ bias) (+ residual) on the split-bf16 MFMA tile engine (nr_linear_x3): x [M,K], w [N,K] fp32, K padded to
     a multiple of 64 with zeros.  ~fp32-grade products (3 bf16 passes); used for the clustering GEMMs and for the

@@ -157,7 +157,9 @@ def eval_epoch(args, model, test_dataloader, device):
     (rank r: rows [r N/W, (r+1) N/W)).  Multi-sentence sets (`dataset.multi_sentence_per_video`): every rank walks the whole
     loader, as in the reference (:114-131), keeps the video of each group's last sentence (:137-149), and the
     sentence x video matrix is again scored in row slabs (evaluator.sharded_multi_sentence_metrics)."""
-    from .evaluator import dataset_order, gather_eval_features, sharded_metrics, sharded_multi_sentence_metrics
+    from .evaluator import (dataset_order, gather_eval_features, sharded_metrics, sharded_metrics_with_hubness,
+                            sharded_multi_sentence_metrics)
+    hubness_k = int(getattr(args, "hubness_k", 0) or 0)
     logger = getattr(args, "logger", None)
     tracker = RetrievalMetrics(logger=logger)
     model = _unwrap(model).to(device)
@@ -174,7 +176,10 @@ def eval_epoch(args, model, test_dataloader, device):
             keep = torch.isin(ind, torch.tensor(cut_off_points, device=ind.device))      # evaluator.py:137-149
             vf, vm = vf[keep], vm[keep]
             toc1 = time.time()
-            t2v, v2t = sharded_multi_sentence_metrics(model, tf, vf, tm.float(), vm.float(), cut_off_points, args)
+            if hubness_k:
+                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, cut_off_points)
+            else:
+                t2v, v2t = sharded_multi_sentence_metrics(model, tf, vf, tm.float(), vm.float(), cut_off_points, args)
         else:
             ind, tf, tm, vf, vm = _cache_features(model, test_dataloader, device, separate=False)
             if int(getattr(args, "world_size", 1)) > 1 and dist.is_initialized():
@@ -182,7 +187,10 @@ def eval_epoch(args, model, test_dataloader, device):
             else:
                 tf, vf, tm, vm = dataset_order(tf, vf, ind, tm, vm)
             toc1 = time.time()
-            t2v, v2t = sharded_metrics(model, tf, vf, tm.float(), vm.float(), args)
+            if hubness_k:
+                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k)
+            else:
+                t2v, v2t = sharded_metrics(model, tf, vf, tm.float(), vm.float(), args)
     toc2 = time.time()
     if is_main_process() and logger is not None:
         logger.info("Evaluation timing breakdown:")
@@ -192,6 +200,9 @@ def eval_epoch(args, model, test_dataloader, device):
         logger.info("EVALUATION RESULTS")
         logger.info("=" * 80)
         tracker.log_current_metrics(t2v, v2t, (t2v["R1"] + v2t["R1"]) / 2)
+        if hubness_k:
+            tracker.log_hubness(t2v["hubness"], prefix="Text-to-Video ")
+            tracker.log_hubness(v2t["hubness"], prefix="Video-to-Text ")
     return t2v, v2t
 
 
