@@ -763,6 +763,33 @@ int nr_topk_merge(int n_lists, const int32_t* idx, const float* val, int n_items
 int nr_topk_occurrences(const int32_t* idx, int n_q, int k, int n_gallery, const int32_t* gt_begin, const int32_t* gt_end,
                         int32_t* occ, int32_t* good, void* stream);
 
+/* Test-time hubness reduction (IS, DSL, QB-Norm; DESIGN.md "Test-time hubness reduction"; the reference has no code for it,
+ * its README and project page compare against it).  Statistics of a line of beta * S, beta finite and > 0 (the product
+ * rounded to fp32): (max, sum) with sum = sum of exp(beta x - max) over the non-NaN entries, an entry equal to the max adding
+ * exactly 1; lse = max + log(sum), -inf for a line with no entry.  Fixed reduction orders, no float atomics: bitwise
+ * reproducible.  n = 0 or L = 0 is allowed; a negative extent, a null pointer, a bad beta or mode: NR_EINVAL before any launch.
+ *   nr_hubnorm_row_lse: lse [n] of the rows of S [n, L] (one wave per row).
+ *   nr_hubnorm_col_stats: stats [2, L] = (max [L], sum [L]) of the columns of S [n, L]: partial pairs of 64-row blocks in
+ *     `workspace` (nr_hubnorm_col_workspace(n, L) bytes, 16-B aligned for the vector path; may be null when n = 0), then
+ *     nr_hubnorm_combine in block order.  n = 0: every column (-inf, 0). */
+#define NR_HUBNORM_IS 0  /* inverted softmax, in log form: fl(fl(beta s) - c)                                   */
+#define NR_HUBNORM_DSL 1 /* dual softmax: s * exp(beta s - c)                                                   */
+int nr_hubnorm_row_lse(const float* S, int n, int L, float beta, float* lse, void* stream);
+size_t nr_hubnorm_col_workspace(int n, int L);
+int nr_hubnorm_col_stats(const float* S, int n, int L, float beta, void* workspace, float* stats, void* stream);
+
+/* Merge of P (max, sum) pairs per item, parts [P, 2, L] (pair p of item c: parts[2p L + c], parts[(2p + 1) L + c]), in
+ * index order p = 0, 1, ... -> stats [2, L] and / or lse [L] (either may be null, not both).  Used by nr_hubnorm_col_stats
+ * and by the cross-rank merge of gathered column statistics: every rank combines the same bits in rank order. */
+int nr_hubnorm_combine(int P, const float* parts, int L, float* stats, float* lse, void* stream);
+
+/* One read of S [n, L] -> T and / or V [n, L] (either may be null, not both).  mode NR_HUBNORM_IS or NR_HUBNORM_DSL.
+ *   T[i,j] = f(S[i,j], col_norm[j]) where row_gate[i] != 0, else S[i,j]   (row_gate null: every row; col_norm [L])
+ *   V[i,j] = f(S[i,j], row_norm[i]) where col_gate[j] != 0, else S[i,j]   (col_gate null: every column; row_norm [n])
+ * is: fl(fl(beta s) - c) without fused multiply-add; dsl: s * expf(beta s - c), the exponent carried to about one rounding. */
+int nr_hubnorm_apply(const float* S, int n, int L, float beta, int mode, const float* col_norm, const int32_t* row_gate,
+                     float* T, const float* row_norm, const int32_t* col_gate, float* V, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,12 @@ def get_args():
     p.add_argument("--hubness_k", type=int, default=0,
                    help="k > 0 (at most 128): the evaluation also reports hubness of the top-k lists in both directions "
                         "(k-occurrence skewness, hubs, anti-hubs, bad hubs; DESIGN.md); 0 = off")
+    p.add_argument("--test_norm", default="none", choices=["none", "is", "dsl", "qbnorm"],
+                   help="test-time hubness reduction, reported next to the raw metrics: is (inverted softmax), dsl (dual "
+                        "softmax), qbnorm (QB-Norm with the memory bank as querybank; DESIGN.md); none = off")
+    p.add_argument("--test_norm_beta", type=float, default=20.0, help="inverse temperature beta of --test_norm")
+    p.add_argument("--qb_k", type=int, default=1,
+                   help="--test_norm qbnorm: a gallery item is active when it is in the top-qb_k list of some querybank item")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -447,8 +453,10 @@ def eval_epoch(args, model, test):
     they are the inputs), one packed all-gather + index scatter restores dataset order (evaluator.py:173-189), rank r
     computes rows [r N/W, (r+1) N/W) of the N x N similarity and the rank counts of its slab on the GPU, three small
     collectives complete them."""
-    from neighborretr_amd.evaluator import gather_eval_features, rank_sample_indices, sharded_metrics, sharded_metrics_with_hubness
+    from neighborretr_amd.evaluator import (gather_eval_features, rank_sample_indices, sharded_metrics, sharded_metrics_with_hubness,
+                                            sharded_metrics_with_test_norm, test_norm_label)
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
+    test_norm = getattr(args, "test_norm", None) or "none"
     model.eval()
     dev = args.device
     mine = rank_sample_indices(test.n, args.world_size, args.rank)     # equal counts on every rank (padded like DistributedSampler)
@@ -459,7 +467,10 @@ def eval_epoch(args, model, test):
         t, tm, v, vm = (torch.cat([p[k] for p in parts], 0) for k in range(4))
     if args.world_size > 1:
         t, v, tm, vm = gather_eval_features(t, v, mine.to(dev), tm, vm, args)
-    if hubness_k:
+    if test_norm != "none":
+        t2v, v2t = sharded_metrics_with_test_norm(model, t, v, tm.float(), vm.float(), args, test_norm, args.test_norm_beta,
+                                                  qb_k=args.qb_k, hubness_k=hubness_k)
+    elif hubness_k:
         t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k)
     else:
         t2v, v2t = sharded_metrics(model, t, v, tm.float(), vm.float(), args)
@@ -469,6 +480,15 @@ def eval_epoch(args, model, test):
         from neighborretr_amd.metrics import RetrievalMetrics
         log(args, RetrievalMetrics.format_hubness(t2v["hubness"], prefix="text->video "))
         log(args, RetrievalMetrics.format_hubness(v2t["hubness"], prefix="video->text "))
+    if test_norm != "none":
+        from neighborretr_amd.metrics import RetrievalMetrics
+        nt, nv = t2v["test_norm"], v2t["test_norm"]
+        tag = test_norm_label(test_norm, nt["beta"])
+        log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
+                  f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
+        if hubness_k:
+            log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
+            log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
     return t2v, v2t
 
 
@@ -508,7 +528,11 @@ def main():
                 torch.save(model.state_dict(), os.path.join(args.output_dir, f"pytorch_model.bin.{epoch}"))
             clear_memory_bank(model)
     elif args.do_eval:
+        if args.test_norm == "qbnorm":                      # QB-Norm's querybank: the memory bank of the training set
+            load_memory_bank(args, model, train)
         eval_epoch(args, model, test)
+        if args.test_norm == "qbnorm":
+            clear_memory_bank(model)
     if args.world_size > 1:
         dist.destroy_process_group()
 

@@ -253,18 +253,29 @@ def _topk_from_slab(S_slab, n_rows, n_cols, k, W, rank):
     return ri, rv, ci, cv
 
 
-def _hubness_from_slab(S_slab, n_rows, n_cols, k, W, rank, ends):
+def _row_hubness(S_slab, n_rows, n_cols, k, W, rank, ends):
+    """Hubness of the row (text -> video) lists: each rank counts its rows, one int32 all-reduce."""
     r0, r1 = slab_bounds(n_rows, W, rank)
-    rb, re_, cb, ce = _ground_truth(n_rows, n_cols, ends, S_slab.device)
+    rb, re_, _, _ = _ground_truth(n_rows, n_cols, ends, S_slab.device)
     ri, _ = _slab_row_lists(S_slab, k, n_cols)
     occ_t = torch.stack(ops.topk_occurrences(ri, n_cols, rb[r0:r1], re_[r0:r1]))
     if W > 1:
         comm.all_reduce(occ_t)                                        # the ranks' row counts -> the whole matrix's
+    occ_t = occ_t.cpu().numpy()
+    return RetrievalMetrics.hubness_from_occurrences(occ_t[0], occ_t[1], k, n_rows)
+
+
+def _col_hubness(S_slab, n_rows, n_cols, k, W, rank, ends):
+    """Hubness of the column (video -> text) lists: partial lists, one all-gather, merge (_column_lists)."""
+    _, _, cb, ce = _ground_truth(n_rows, n_cols, ends, S_slab.device)
     ci, _ = _column_lists(S_slab, n_rows, n_cols, k, W, rank)
-    occ_v = torch.stack(ops.topk_occurrences(ci, n_rows, cb, ce))
-    occ_t, occ_v = occ_t.cpu().numpy(), occ_v.cpu().numpy()
-    return (RetrievalMetrics.hubness_from_occurrences(occ_t[0], occ_t[1], k, n_rows),
-            RetrievalMetrics.hubness_from_occurrences(occ_v[0], occ_v[1], k, n_cols))
+    occ_v = torch.stack(ops.topk_occurrences(ci, n_rows, cb, ce)).cpu().numpy()
+    return RetrievalMetrics.hubness_from_occurrences(occ_v[0], occ_v[1], k, n_cols)
+
+
+def _hubness_from_slab(S_slab, n_rows, n_cols, k, W, rank, ends):
+    return (_row_hubness(S_slab, n_rows, n_cols, k, W, rank, ends),
+            _col_hubness(S_slab, n_rows, n_cols, k, W, rank, ends))
 
 
 def _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk):
@@ -315,4 +326,192 @@ def sharded_metrics_with_hubness(model, text_feat, video_feat, text_mask, video_
     else:
         t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
     t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, int(k), W, rank, ends)
+    return t2v, v2t
+
+
+# ---- test-time hubness reduction: IS, DSL, QB-Norm (DESIGN.md "Test-time hubness reduction") -------------------------------
+# T (text -> video, rows are the queries) and V (video -> text, columns are the queries) are normalised copies of this rank's
+# slab of S.  The column normalisers of T come from the ranks' partial (max, sum) pairs: one all-gather of [W, 2, N] fp32 and a
+# combine in rank order, so every rank holds the same bits.  V's row normalisers are rank-local.  QB-Norm replaces the test
+# queries by a querybank (the memory bank) and normalises only the queries whose top-1 lies in the bank's activation set.
+
+TEST_NORM_MODES = ("is", "dsl", "qbnorm")
+TEST_NORM_LABELS = {"is": "IS", "dsl": "DSL", "qbnorm": "QB-Norm"}
+
+
+def test_norm_label(mode, beta):
+    """The tag of the log lines of the normalised metrics, e.g. "[IS b=20]"."""
+    return f"[{TEST_NORM_LABELS[mode]} b={beta:g}]"
+
+
+def _check_test_norm(mode, beta, qb_k, hubness_k):
+    if mode not in TEST_NORM_MODES:
+        raise ValueError(f"test_norm mode must be one of {TEST_NORM_MODES}, got {mode!r}")
+    beta = ops._check_beta(beta)
+    qb_k = ops._check_k(qb_k)
+    hubness_k = int(hubness_k or 0)
+    if hubness_k:
+        ops._check_k(hubness_k)
+    return beta, qb_k, hubness_k
+
+
+def _querybank(model, querybank, dev):
+    """(text_feat, text_mask, video_feat, video_mask) of the querybank on `dev`: `querybank` as such a tuple, or None for the
+    model's memory bank (mb_feat_t / mb_mask_t / mb_feat_v / mb_mask_v)."""
+    if querybank is None:
+        bank = (model.mb_feat_t, model.mb_mask_t, model.mb_feat_v, model.mb_mask_v)
+    else:
+        bank = tuple(querybank)
+        if len(bank) != 4:
+            raise ValueError("querybank must be (text_feat, text_mask, video_feat, video_mask)")
+    if bank[0].dim() != 3 or bank[2].dim() != 3 or bank[0].shape[0] == 0 or bank[2].shape[0] == 0:
+        raise ValueError("qbnorm needs a querybank and the model's memory bank is empty: call load_memory_bank(...) before "
+                         "evaluating, or pass querybank=(text_feat, text_mask, video_feat, video_mask)")
+    tf, tm, vf, vm = bank
+    return tf.to(dev).float(), tm.to(dev).float(), vf.to(dev).float(), vm.to(dev).float()
+
+
+def _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, bank, W, rank, chunk=256):
+    """(Qt_slab, Qv_slab) of this rank: bank texts slab_bounds(M, W, rank) x every test video, and this rank's test texts x every
+    bank video, on the rank-exact path of S."""
+    btf, btm, bvf, bvm = bank
+    q0, q1 = slab_bounds(btf.shape[0], W, rank)
+    r0, r1 = slab_bounds(text_feat.shape[0], W, rank)
+    Qt = _slab_similarity(model, btf, video_feat, btm, video_mask, q0, q1, chunk)
+    Qv = _slab_similarity(model, text_feat, bvf, text_mask, bvm, r0, r1, chunk)
+    return Qt, Qv
+
+
+def _gathered_lse(stats, W):
+    """This rank's column pairs [2, L] -> lse [L] over every rank's rows: one all-gather, combine in rank order."""
+    if W > 1:
+        allp = torch.empty((W,) + tuple(stats.shape), dtype=torch.float32, device=stats.device)
+        comm.all_gather_into_tensor(allp.view(-1), stats.reshape(-1))
+    else:
+        allp = stats[None]
+    return ops.hubnorm_combine(allp)
+
+
+def _activated(idx, n_gallery):
+    """bool [n_gallery]: the items that appear in some list of idx [n_q, k] (absent slots -1 ignored), as int32 counts."""
+    dev = idx.device
+    none = torch.zeros((idx.shape[0],), dtype=torch.int32, device=dev)
+    occ, _ = ops.topk_occurrences(idx, n_gallery, none, none)
+    return occ
+
+
+def _gate(top1, active):
+    """int32 [n_q]: 1 where the query's top-1 (idx [n_q, 1], -1 = none) is an active item."""
+    i = top1[:, 0].long()
+    return ((i >= 0) & active[i.clamp(min=0)]).to(torch.int32)
+
+
+def _normalised_from_slab(S_slab, n_rows, n_cols, W, rank, mode, beta, bank_slabs=None, qb_k=1):
+    """(T_slab, V_slab) of this rank's slab S[r0:r1] (rows: texts / sentences, columns: videos).  qbnorm: bank_slabs =
+    (Qt_slab, Qv_slab) as _bank_slabs scores them."""
+    if mode in ("is", "dsl"):
+        c_v = _gathered_lse(ops.hubnorm_col_stats(S_slab, beta), W)
+        c_t = ops.hubnorm_row_lse(S_slab, beta)
+        return ops.hubnorm_apply(S_slab, beta, mode, col_norm=c_v, row_norm=c_t)
+    Qt, Qv = bank_slabs
+    n_bank_v = Qv.shape[1]
+    c_v = _gathered_lse(ops.hubnorm_col_stats(Qt, beta), W)
+    c_t = ops.hubnorm_row_lse(Qv, beta)
+    # A_v: videos in the top-qb_k list of some bank text (this rank's bank rows, one int32 all-reduce)
+    occ_v = _activated(_slab_row_lists(Qt, qb_k, n_cols)[0], n_cols)
+    if W > 1:
+        comm.all_reduce(occ_v)
+    # A_t: test texts in the top-qb_k list of some bank video (partial column lists of Qv, merged)
+    occ_t = _activated(_column_lists(Qv, n_rows, n_bank_v, qb_k, W, rank)[0], n_rows)
+    row_gate = _gate(_slab_row_lists(S_slab, 1, n_cols)[0], occ_v > 0)
+    col_gate = _gate(_column_lists(S_slab, n_rows, n_cols, 1, W, rank)[0], occ_t > 0)
+    return ops.hubnorm_apply(S_slab, beta, "is", col_norm=c_v, row_gate=row_gate, row_norm=c_t, col_gate=col_gate)
+
+
+def _metrics_from_normalised(T_slab, V_slab, n_rows, n_cols, W, rank, ends, hubness_k):
+    """(t2v, v2t): text->video ranks from the rows of T, video->text from the columns of V (multi-sentence sets: the group
+    ranks of T, the group max of V), and with hubness_k the hubness of T's row lists and V's column lists."""
+    if ends is None:
+        gt, et, _, _ = _ranks_from_slab(T_slab, n_rows, W, rank)
+        _, _, gv, ev = _ranks_from_slab(V_slab, n_rows, W, rank)
+        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
+        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
+    else:
+        t2v, _ = _multi_sentence_from_slab(T_slab, ends, n_rows, n_cols, W, rank)
+        _, v2t = _multi_sentence_from_slab(V_slab, ends, n_rows, n_cols, W, rank)
+    if hubness_k:
+        t2v["hubness"] = _row_hubness(T_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+        v2t["hubness"] = _col_hubness(V_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    return t2v, v2t
+
+
+def _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k, chunk):
+    S_slab, n_rows, n_cols, W, rank, _ = slab
+    bank_slabs = None
+    if mode == "qbnorm":
+        bank = _querybank(model, querybank, S_slab.device)
+        bank_slabs = _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, bank, W, rank, chunk)
+    return _normalised_from_slab(S_slab, n_rows, n_cols, W, rank, mode, beta, bank_slabs, qb_k)
+
+
+def sharded_normalised_slabs(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None, qb_k=1,
+                             cut_off_points=None, chunk=256):
+    """-> (T_slab, V_slab) fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the text->video
+    scores (rows are the queries) and the video->text scores (columns are the queries) after the test-time correction `mode`
+    ("is" | "dsl" | "qbnorm", DESIGN.md "Test-time hubness reduction").  querybank: (text_feat, text_mask, video_feat,
+    video_mask) of the qbnorm querybank; None: the model's memory bank (load_memory_bank)."""
+    beta, qb_k, _ = _check_test_norm(mode, beta, qb_k, 0)
+    if mode == "qbnorm":
+        _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    return _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
+                                      chunk)
+
+
+def _test_norm_entry(metrics, mode, beta, qb_k):
+    metrics.update(mode=mode, beta=beta)
+    if mode == "qbnorm":
+        metrics["qb_k"] = qb_k
+    return metrics
+
+
+def sharded_normalised_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None, qb_k=1,
+                               hubness_k=0, cut_off_points=None, chunk=256):
+    """(text->video, video->text) metric dictionaries of the normalised scores (sharded_normalised_slabs), identical on every
+    rank, each with "mode" and "beta" (and "qb_k" for qbnorm) and, with hubness_k, a "hubness" entry (sharded_hubness's
+    summary of T's row lists / V's column lists)."""
+    beta, qb_k, hubness_k = _check_test_norm(mode, beta, qb_k, hubness_k)
+    if mode == "qbnorm":
+        _querybank(model, querybank, text_feat.device)
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    T, V = _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
+                                      chunk)
+    _, n_rows, n_cols, W, rank, ends = slab
+    t2v, v2t = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k)
+    return _test_norm_entry(t2v, mode, beta, qb_k), _test_norm_entry(v2t, mode, beta, qb_k)
+
+
+def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None,
+                                   qb_k=1, hubness_k=0, cut_off_points=None, chunk=256):
+    """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
+    each with one more entry "test_norm" = sharded_normalised_metrics, from ONE scoring of this rank's slab."""
+    beta, qb_k, hubness_k = _check_test_norm(mode, beta, qb_k, hubness_k)
+    if mode == "qbnorm":
+        _querybank(model, querybank, text_feat.device)
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    S_slab, n_rows, n_cols, W, rank, ends = slab
+    if ends is None:
+        gt, et, gv, ev = _ranks_from_slab(S_slab, n_rows, W, rank)
+        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
+        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
+    else:
+        t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
+    if hubness_k:
+        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    T, V = _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
+                                      chunk)
+    del S_slab, slab
+    nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k)
+    t2v["test_norm"] = _test_norm_entry(nt, mode, beta, qb_k)
+    v2t["test_norm"] = _test_norm_entry(nv, mode, beta, qb_k)
     return t2v, v2t

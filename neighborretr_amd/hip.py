@@ -223,8 +223,14 @@ _SIGNATURES = {
     "nr_slab_topk_cols": ([_P, _I, _I, _I, _I, _P, _P, _P], _I),
     "nr_topk_merge": ([_I, _P, _P, _I, _I, _P, _P, _P], _I),
     "nr_topk_occurrences": ([_P, _I, _I, _I, _P, _P, _P, _P, _P], _I),
+    "nr_hubnorm_row_lse": ([_P, _I, _I, _F, _P, _P], _I),
+    "nr_hubnorm_col_workspace": ([_I, _I], _Z),
+    "nr_hubnorm_col_stats": ([_P, _I, _I, _F, _P, _P, _P], _I),
+    "nr_hubnorm_combine": ([_I, _P, _I, _P, _P, _P], _I),
+    "nr_hubnorm_apply": ([_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P], _I),
 }
 TOPK_MAX = 128                               # largest k of the top-k entry points
+HUBNORM_IS, HUBNORM_DSL = 0, 1               # nr_hubnorm_apply modes
 
 
 class NrHipError(RuntimeError):

@@ -3,6 +3,7 @@
 Each function allocates its outputs with torch (device memory plumbing only), enqueues the HIP
 kernel on torch's current stream and returns without synchronising.
 """
+import math
 from collections import namedtuple
 
 import torch
@@ -956,6 +957,95 @@ def topk_occurrences(idx, n_gallery, gt_begin, gt_end):
     hip.call("nr_topk_occurrences", hip.ptr(idx, torch.int32), n_q, k, int(n_gallery), hip.ptr(gt_begin.contiguous(), torch.int32),
              hip.ptr(gt_end.contiguous(), torch.int32), hip.ptr(occ), hip.ptr(good), hip.stream_ptr())
     return occ, good
+
+
+HUBNORM_MODES = {"is": hip.HUBNORM_IS, "dsl": hip.HUBNORM_DSL}
+
+
+def _check_beta(beta):
+    beta = float(beta)
+    if not (beta > 0 and math.isfinite(beta)):
+        raise ValueError(f"beta must be finite and > 0, got {beta}")
+    return beta
+
+
+def _slab_2d(S):
+    S = _f32(S).contiguous()
+    if S.dim() != 2:
+        raise ValueError("S must be 2-D")
+    return S
+
+
+def hubnorm_row_lse(S, beta):
+    """lse [n] fp32: log-sum-exp of every row of beta * S [n, L] over its non-NaN entries, -inf for a row with none
+    (nr_hubnorm_row_lse)."""
+    beta = _check_beta(beta)
+    S = _slab_2d(S)
+    n, L = S.shape
+    lse = torch.empty((n,), dtype=torch.float32, device=S.device)
+    if n:
+        hip.call("nr_hubnorm_row_lse", hip.ptr(S), n, L, beta, hip.ptr(lse), hip.stream_ptr())
+    return lse
+
+
+def hubnorm_col_stats(S, beta):
+    """stats [2, L] fp32 = (max, sum of exp(beta x - max)) of every column of beta * S [n, L] (nr_hubnorm_col_stats): the
+    partial pairs a row slab contributes, merged over the slabs by hubnorm_combine."""
+    beta = _check_beta(beta)
+    S = _slab_2d(S)
+    n, L = S.shape
+    ws = torch.empty((int(hip.lib().nr_hubnorm_col_workspace(n, L)),), dtype=torch.uint8, device=S.device)
+    stats = torch.empty((2, L), dtype=torch.float32, device=S.device)
+    hip.call("nr_hubnorm_col_stats", hip.ptr(S), n, L, beta, hip.ptr(ws), hip.ptr(stats), hip.stream_ptr())
+    return stats
+
+
+def hubnorm_combine(parts, want_stats=False):
+    """parts [P, 2, L] fp32 (max, sum) pairs -> lse [L], merged in index order (nr_hubnorm_combine); want_stats: (stats [2, L],
+    lse)."""
+    parts = _f32(parts).contiguous()
+    if parts.dim() != 3 or parts.shape[1] != 2:
+        raise ValueError("parts must be [P, 2, L]")
+    P, _, L = parts.shape
+    lse = torch.empty((L,), dtype=torch.float32, device=parts.device)
+    stats = torch.empty((2, L), dtype=torch.float32, device=parts.device) if want_stats else None
+    hip.call("nr_hubnorm_combine", P, hip.ptr(parts), L, hip.ptr(stats, allow_none=True), hip.ptr(lse), hip.stream_ptr())
+    return (stats, lse) if want_stats else lse
+
+
+def hubnorm_apply(S, beta, mode, col_norm=None, row_gate=None, row_norm=None, col_gate=None, want_t=True, want_v=True):
+    """(T, V) [n, L] fp32 from one read of S [n, L] (nr_hubnorm_apply); mode "is" | "dsl".  T uses the column normaliser
+    col_norm [L] on the rows where row_gate [n] (int32, None: every row) is non-zero and keeps S elsewhere; V uses the row
+    normaliser row_norm [n] on the columns where col_gate [L] is non-zero.  An output not wanted is None."""
+    beta = _check_beta(beta)
+    if mode not in HUBNORM_MODES:
+        raise ValueError(f"mode must be one of {sorted(HUBNORM_MODES)}, got {mode!r}")
+    if not (want_t or want_v):
+        raise ValueError("nothing to compute")
+    S = _slab_2d(S)
+    n, L = S.shape
+    dev = S.device
+
+    def vec(x, size, dtype, what):
+        if x is None:
+            return None
+        x = x.to(device=dev, dtype=dtype).contiguous()
+        if x.shape != (size,):
+            raise ValueError(f"{what} must have shape ({size},), got {tuple(x.shape)}")
+        return x
+
+    col_norm, row_norm = vec(col_norm, L, torch.float32, "col_norm"), vec(row_norm, n, torch.float32, "row_norm")
+    row_gate, col_gate = vec(row_gate, n, torch.int32, "row_gate"), vec(col_gate, L, torch.int32, "col_gate")
+    if (want_t and col_norm is None) or (want_v and row_norm is None):
+        raise ValueError("T needs col_norm, V needs row_norm")
+    T = torch.empty_like(S) if want_t else None
+    V = torch.empty_like(S) if want_v else None
+    if n == 0 or L == 0:
+        return T, V
+    p = lambda x: hip.ptr(x, allow_none=True)                  # noqa: E731
+    hip.call("nr_hubnorm_apply", hip.ptr(S), n, L, beta, HUBNORM_MODES[mode], p(col_norm), p(row_gate), p(T), p(row_norm),
+             p(col_gate), p(V), hip.stream_ptr())
+    return T, V
 
 
 def linear_x3(x, w, bias=None, residual=None):

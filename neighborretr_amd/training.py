@@ -157,12 +157,19 @@ def eval_epoch(args, model, test_dataloader, device):
     (rank r: rows [r N/W, (r+1) N/W)).  Multi-sentence sets (`dataset.multi_sentence_per_video`): every rank walks the whole
     loader, as in the reference (:114-131), keeps the video of each group's last sentence (:137-149), and the
     sentence x video matrix is again scored in row slabs (evaluator.sharded_multi_sentence_metrics)."""
-    from .evaluator import (dataset_order, gather_eval_features, sharded_metrics, sharded_metrics_with_hubness,
-                            sharded_multi_sentence_metrics)
+    from .evaluator import (_check_test_norm, _querybank, dataset_order, gather_eval_features, sharded_metrics,
+                            sharded_metrics_with_hubness, sharded_metrics_with_test_norm, sharded_multi_sentence_metrics,
+                            test_norm_label)
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
+    test_norm = getattr(args, "test_norm", None) or "none"
     logger = getattr(args, "logger", None)
     tracker = RetrievalMetrics(logger=logger)
     model = _unwrap(model).to(device)
+    if test_norm != "none":          # the test-time correction (DESIGN.md "Test-time hubness reduction"): checked before any work
+        beta, qb_k, _ = _check_test_norm(test_norm, getattr(args, "test_norm_beta", 20.0), getattr(args, "qb_k", 1), hubness_k)
+        if test_norm == "qbnorm":
+            _querybank(model, None, device)
+        norm = dict(mode=test_norm, beta=beta, qb_k=qb_k, hubness_k=hubness_k)
     dataset = getattr(test_dataloader, "dataset", None)
     multi = bool(getattr(dataset, "multi_sentence_per_video", False))
     model.eval()
@@ -176,7 +183,10 @@ def eval_epoch(args, model, test_dataloader, device):
             keep = torch.isin(ind, torch.tensor(cut_off_points, device=ind.device))      # evaluator.py:137-149
             vf, vm = vf[keep], vm[keep]
             toc1 = time.time()
-            if hubness_k:
+            if test_norm != "none":
+                t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args,
+                                                          cut_off_points=cut_off_points, **norm)
+            elif hubness_k:
                 t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, cut_off_points)
             else:
                 t2v, v2t = sharded_multi_sentence_metrics(model, tf, vf, tm.float(), vm.float(), cut_off_points, args)
@@ -187,7 +197,9 @@ def eval_epoch(args, model, test_dataloader, device):
             else:
                 tf, vf, tm, vm = dataset_order(tf, vf, ind, tm, vm)
             toc1 = time.time()
-            if hubness_k:
+            if test_norm != "none":
+                t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args, **norm)
+            elif hubness_k:
                 t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k)
             else:
                 t2v, v2t = sharded_metrics(model, tf, vf, tm.float(), vm.float(), args)
@@ -203,6 +215,13 @@ def eval_epoch(args, model, test_dataloader, device):
         if hubness_k:
             tracker.log_hubness(t2v["hubness"], prefix="Text-to-Video ")
             tracker.log_hubness(v2t["hubness"], prefix="Video-to-Text ")
+        if test_norm != "none":
+            tag = test_norm_label(test_norm, t2v["test_norm"]["beta"])
+            tracker.print_metrics(t2v["test_norm"], prefix=f"Text-to-Video {tag}: ")
+            tracker.print_metrics(v2t["test_norm"], prefix=f"Video-to-Text {tag}: ")
+            if hubness_k:
+                tracker.log_hubness(t2v["test_norm"]["hubness"], prefix=f"Text-to-Video {tag} ")
+                tracker.log_hubness(v2t["test_norm"]["hubness"], prefix=f"Video-to-Text {tag} ")
     return t2v, v2t
 
 
