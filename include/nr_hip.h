@@ -790,6 +790,50 @@ int nr_hubnorm_combine(int P, const float* parts, int L, float* stats, float* ls
 int nr_hubnorm_apply(const float* S, int n, int L, float beta, int mode, const float* col_norm, const int32_t* row_gate,
                      float* T, const float* row_norm, const int32_t* col_gate, float* V, void* stream);
 
+/* Multi-tensor BertAdam step (models/optimization.py:76-211 with the trainer's clip and clamp around it, trainer.py:104-119;
+ * DESIGN.md "BertAdam in the captured step").  fp32 tensors only.  Per step, for every table entry t with group q:
+ *   c    = min(1, global_max_norm / (sqrt(sum_t ||g_t||^2) + 1e-6))             (global_max_norm <= 0: c = 1)
+ *   c_t  = min(1, q.max_grad_norm / (c ||g_t|| + 1e-6))                          (q.max_grad_norm <= 0: c_t = 1)
+ *   gh   = g c c_t;  m = b1 m + (1 - b1) gh;  v = b2 v + (1 - b2) gh^2;  u = m / (sqrt(v) + e) [+ weight_decay p if > 0]
+ *   lr_t = q.lr * schedule(*step / t_total, warmup), *step read BEFORE its increment (q.t_total == -1: lr_t = q.lr),
+ *          evaluated in double and rounded to fp32 once
+ *   p   -= lr_t u;  p = min(p, clamp_max) where has_clamp;  *step += 1.          No bias correction; g is never written.
+ * Three launches whatever T is (chunk sums of g^2; one workgroup of scalars; the update), every reduction in a fixed order, no
+ * float atomics: same inputs, same bits, launched eagerly or replayed from a graph.  Non-finite gradients propagate as the
+ * formulas give.  `table` and `groups` are DEVICE arrays; nothing the launches read comes from the host after the call. */
+#define NR_SCHEDULE_WARMUP_COSINE 0   /* x / warmup if x < warmup else 0.5 (1 + cos(pi x))                  */
+#define NR_SCHEDULE_WARMUP_CONSTANT 1 /* ... else 1                                                         */
+#define NR_SCHEDULE_WARMUP_LINEAR 2   /* ... else max((x - 1) / (warmup - 1), 0)                            */
+typedef struct {
+    float* p;          /* parameter, n elements, 4-byte aligned (16-byte aligned p, g, m, v take the vector path)     */
+    const float* g;    /* gradient                                                                                     */
+    float* m;          /* first moment  (next_m)                                                                       */
+    float* v;          /* second moment (next_v)                                                                       */
+    int32_t* step;     /* the tensor's step counter (device)                                                           */
+    int64_t n;
+    int32_t group;     /* index into groups                                                                            */
+    int32_t chunk0;    /* first chunk of this tensor: written by nr_bertadam_plan                                      */
+    int32_t has_clamp; /* != 0: p = min(p, clamp_max) after the update                                                 */
+    float clamp_max;
+} NrOptimTensor; /* 64 bytes */
+typedef struct {
+    double lr, weight_decay, b1, b2, e, max_grad_norm, warmup;
+    int64_t t_total;   /* -1: constant learning rate                                                                   */
+    int32_t schedule;  /* NR_SCHEDULE_*                                                                                */
+    int32_t pad_;
+} NrOptimGroup; /* 72 bytes */
+
+/* Host-only: validates the HOST copies of the table and the groups before they are uploaded (null pointers, misaligned
+ * pointers, negative counts, group indices out of range, bad schedule ids, t_total 0 or < -1: NR_EINVAL), writes every
+ * entry's chunk0 and returns the number of chunks in *n_chunks. */
+int nr_bertadam_plan(NrOptimTensor* entries, int T, const NrOptimGroup* groups, int G, int* n_chunks);
+size_t nr_bertadam_workspace_bytes(int T, int n_chunks);
+/* The three launches.  table [T] / groups [G]: device copies of what nr_bertadam_plan checked; workspace:
+ * nr_bertadam_workspace_bytes(T, n_chunks) bytes, 8-byte aligned.  NR_EINVAL before any launch for null pointers, negative
+ * counts, a NaN global_max_norm. */
+int nr_bertadam_step(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, int G, float global_max_norm,
+                     void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,11 @@ def get_args():
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
                         "average -- as one graph with the RCCL collectives inside, or (when that is refused / fails its validation, "
                         "and on gloo) the rank-local segments between the collectives as graphs; the ranks decide together")
+    p.add_argument("--optimizer", default="adamw", choices=["adamw", "bertadam"],
+                   help="adamw: torch.optim.AdamW at --lr on every tensor.  bertadam: the reference's optimizer and grouping "
+                        "(training/optimizer.py: `clip.` names at lr * coef_lr, no decay on bias / LayerNorm, warm-up + cosine "
+                        "over len(train) * epochs steps) as multi-tensor HIP kernels, with the trainer's global clip and "
+                        "logit-scale clamp inside; under --hip_graph 1 on one rank the update is part of the replayed graph")
     args = p.parse_args()
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
         raise ValueError("--batch_size must divide over the ranks (args_parser.py:149-165)")
@@ -220,7 +225,15 @@ def clear_memory_bank(model):
 
 class GraphedStep:
     """Forward + backward of one training step as a captured HIP graph with static input buffers: run() leaves the losses in
-    .losses and the gradients in the parameters' .grad (the optimizer step stays eager).
+    .losses and the gradients in the parameters' .grad.  Without `optimizer` the optimizer step stays eager and with the caller.
+
+    optimizer (a neighborretr_amd.optim.BertAdam): the update belongs to the step.  One rank: its three launches are captured
+    behind the backward, so one replay = forward + backward + update (the table of pointers the kernels read is filled by a
+    copy node from a pinned host buffer the optimizer keeps: the static gradients only come into being inside the capture).
+    Several ranks: the same launches follow the step's replay, after the gradient average, outside the forms that
+    CollectiveCapture validates.  Warm-up passes and re-captures apply no update; a batch of another shape takes an eager step
+    that ends in optimizer.step().  Either way run() returns with the update issued, and the optimizer's step count is the
+    number of run() calls.
 
     world_size > 1: the step that is replayed is the WHOLE data-parallel step -- exchange step, loss, backward with the
     reductions of its differentiable collectives, and the gradient average over the ranks (one all-reduce of a flat buffer that
@@ -229,10 +242,16 @@ class GraphedStep:
     inside; else the rank-local segments between the collectives as graphs (comm.SegmentedStep); else eager launches.  Each
     form is validated against the eager step on every rank before it is used."""
 
-    def __init__(self, model, example, params, args=None):
+    def __init__(self, model, example, params, args=None, optimizer=None):
         self.static = [t.clone() for t in example]
         self.params = params
         self.model = model
+        self.optimizer = optimizer
+        if optimizer is not None:
+            from neighborretr_amd.optim import BertAdam
+            if not isinstance(optimizer, BertAdam):
+                raise TypeError("GraphedStep(optimizer=...) takes a neighborretr_amd.optim.BertAdam: its step is three capturable "
+                                f"launches; got {type(optimizer).__name__}")
         self.world = int(getattr(args, "world_size", 1)) if args is not None else 1
         self.rank = int(getattr(args, "rank", 0)) if args is not None else 0
         self.backend = getattr(args, "dist_backend", "nccl") if args is not None else "nccl"
@@ -272,6 +291,8 @@ class GraphedStep:
         self._warm_up(fwd_bwd)
         # the device-resident ring head must exist before the capture (creating it is a host-to-device copy)
         model._ring_ready(B)
+        if self.optimizer is not None:
+            self.optimizer.prepare(params, owner=self)   # moments, counters, workspace: allocated (and zeroed) outside the capture
         torch.cuda.synchronize()
         for p in params:
             p.grad = None
@@ -288,6 +309,10 @@ class GraphedStep:
         with torch.cuda.graph(self.graph):
             losses = model(*self.static, 0)
             grads = torch.autograd.grad(losses[0], params, allow_unused=True)
+            if self.optimizer is not None:
+                for p, g in zip(params, grads):
+                    p.grad = g
+                self._updated = self.optimizer.issue()           # captured, not executed: advance() follows every replay
         self.losses = tuple(l.detach() for l in losses)          # the loss VALUES only (no autograd graph kept alive)
         del losses
         self.grads = list(grads)                     # static gradient buffers of the graph (None: the step does not reach it)
@@ -397,6 +422,8 @@ class GraphedStep:
         grads = torch.autograd.grad(losses[0], self.params, allow_unused=True)
         for p, g in zip(self.params, grads):
             p.grad = g
+        if self.optimizer is not None:
+            self.optimizer.step()
         return tuple(l.detach() for l in losses)
 
     def run(self, batch):
@@ -410,9 +437,13 @@ class GraphedStep:
         if self.world > 1:
             for p, g in zip(self._used, self._views):    # optimizer.zero_grad(set_to_none=True) drops them: put them back
                 p.grad = g
+            if self.optimizer is not None:
+                self.optimizer.step()                    # the same table every step: the views never move
             return tuple(self._out["losses"].unbind(0))
         for p, g in zip(self.params, self.grads):    # optimizer.zero_grad(set_to_none=True) drops them: put them back
             p.grad = g
+        if self.optimizer is not None:
+            self.optimizer.advance(self._updated)        # the replay has applied the update: versions and the step mirror
         return self.losses
 
 
@@ -421,13 +452,15 @@ def train_epoch(args, model, ddp, data, optimizer, epoch, global_step):
     model.train()
     t0 = time.time()
     graphed = getattr(args, "_graphed_step", None)
+    fused = args.optimizer == "bertadam"             # global clip, update and logit-scale clamp in the optimizer's kernels
     for i in range(len(data)):
         global_step += 1
         text, text_mask, video, video_mask, idx = data.batch(i, args.device)
         if args.hip_graph:
             if graphed is None:
                 graphed = args._graphed_step = GraphedStep(model, (text, text_mask, video, video_mask, idx),
-                                                           [p for p in model.parameters() if p.requires_grad], args)
+                                                           [p for p in model.parameters() if p.requires_grad], args,
+                                                           optimizer=optimizer if fused else None)
                 log(args, f"training step replayed as: {graphed.form}")
             losses = graphed.run((text, text_mask, video, video_mask, idx))
             loss = None
@@ -435,14 +468,20 @@ def train_epoch(args, model, ddp, data, optimizer, epoch, global_step):
             losses = ddp(text, text_mask, video, video_mask, idx, global_step)
             loss = losses[0]
             loss.backward()
-        torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
-        optimizer.step()
-        optimizer.zero_grad(set_to_none=True)
-        torch.clamp_(model.clip.logit_scale.data, max=float(np.log(100)))        # trainer.py:114-119
+        if fused:
+            if not args.hip_graph:                   # (a graphed step has issued the update itself)
+                optimizer.step()
+            optimizer.zero_grad(set_to_none=True)
+        else:
+            torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
+            optimizer.step()
+            optimizer.zero_grad(set_to_none=True)
+            torch.clamp_(model.clip.logit_scale.data, max=float(np.log(100)))    # trainer.py:114-119
         if global_step % args.n_display == 0 or i == len(data) - 1:
             red = reduce_losses(losses, args).tolist()                            # one reduce instead of five
+            lr = f" lr {optimizer.group_lr(applied=True)[1]:.3e}" if fused else ""     # the head's (decayed, non-CLIP) group, this step
             log(args, f"epoch {epoch} step {i + 1}/{len(data)} loss {red[0]:.4f} centrality {red[1]:.4f} "
-                      f"uniform {red[2]:.4f} neighbor {red[3]:.4f} kl {red[4]:.4f} "
+                      f"uniform {red[2]:.4f} neighbor {red[3]:.4f} kl {red[4]:.4f}{lr} "
                       f"({(time.time() - t0) / (i + 1) * 1e3:.1f} ms/step)")
     return global_step
 
@@ -516,7 +555,13 @@ def main():
     Data = SyntheticClips if args.encoders else SyntheticFeatures
     train = Data(args, args.synthetic_train, "train", args.seed)
     test = Data(args, args.synthetic_test, "test", args.seed + 1)
-    optimizer = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    if args.optimizer == "bertadam":
+        from neighborretr_amd.optim import prep_optimizer
+        # (wrap=False: the model is wrapped above, or not at all under --hip_graph 1)
+        optimizer = prep_optimizer(args, model, len(train) * args.epochs, args.device_index, global_max_norm=1.0,
+                                   clamp_logit_scale=True, wrap=False)[0]
+    else:
+        optimizer = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
     os.makedirs(args.output_dir, exist_ok=True)
     global_step = 0
     if args.do_train:

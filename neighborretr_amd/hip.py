@@ -114,7 +114,19 @@ class TokenWeightsProblem(ctypes.Structure):
                 + [(n, ctypes.c_int32) for n in ("n_samples", "N", "d", "H", "n_counters", "reserved")])
 
 
-STRUCTS = {"NrTokenWeightsProblem": TokenWeightsProblem, "NrBankAbsorbDesc": BankAbsorbDesc, "NrCtmStageDesc": CtmStageDesc, "NrLocalLevelProblem": LocalLevelProblem, "NrSplitItem": SplitItem,
+class OptimTensor(ctypes.Structure):
+    """NrOptimTensor of include/nr_hip.h."""
+    _fields_ = ([(n, _P) for n in ("p", "g", "m", "v", "step")] + [("n", ctypes.c_int64)]
+                + [(n, ctypes.c_int32) for n in ("group", "chunk0", "has_clamp")] + [("clamp_max", _F)])
+
+
+class OptimGroup(ctypes.Structure):
+    """NrOptimGroup of include/nr_hip.h."""
+    _fields_ = ([(n, ctypes.c_double) for n in ("lr", "weight_decay", "b1", "b2", "e", "max_grad_norm", "warmup")]
+                + [("t_total", ctypes.c_int64), ("schedule", ctypes.c_int32), ("pad_", ctypes.c_int32)])
+
+
+STRUCTS = {"NrOptimTensor": OptimTensor, "NrOptimGroup": OptimGroup, "NrTokenWeightsProblem": TokenWeightsProblem, "NrBankAbsorbDesc": BankAbsorbDesc, "NrCtmStageDesc": CtmStageDesc, "NrLocalLevelProblem": LocalLevelProblem, "NrSplitItem": SplitItem,
            "NrColsumItem": ColsumItem, "NrLinearProblem": LinearProblem, "NrCtmAttnBwdDesc": CtmAttnBwdDesc,
            "NrCtmMidBwdDesc": CtmMidBwdDesc, "NrSimBwdItem": SimBwdItem, "NrSimBwdOperand": SimBwdOperand, "NrSlabSum": SlabSum,
            "NrPoolWSrc": PoolWSrc, "NrPoolWJob": PoolWJob}
@@ -228,9 +240,13 @@ _SIGNATURES = {
     "nr_hubnorm_col_stats": ([_P, _I, _I, _F, _P, _P, _P], _I),
     "nr_hubnorm_combine": ([_I, _P, _I, _P, _P, _P], _I),
     "nr_hubnorm_apply": ([_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P], _I),
+    "nr_bertadam_plan": ([ctypes.POINTER(OptimTensor), _I, ctypes.POINTER(OptimGroup), _I, ctypes.POINTER(_I)], _I),
+    "nr_bertadam_workspace_bytes": ([_I, _I], _Z),
+    "nr_bertadam_step": ([_P, _I, _I, _P, _I, _F, _P, _P], _I),
 }
 TOPK_MAX = 128                               # largest k of the top-k entry points
 HUBNORM_IS, HUBNORM_DSL = 0, 1               # nr_hubnorm_apply modes
+SCHEDULE_IDS = {"warmup_cosine": 0, "warmup_constant": 1, "warmup_linear": 2}      # NR_SCHEDULE_*
 
 
 class NrHipError(RuntimeError):

@@ -1070,3 +1070,30 @@ def linear_x3(x, w, bias=None, residual=None):
     hip.call("nr_linear_x3", hip.ptr(xh), hip.ptr(xl), hip.ptr(wh), hip.ptr(wl), hip.ptr(b, allow_none=True), hip.ptr(r, allow_none=True),
              M, N, K, hip.ptr(out), hip.stream_ptr())
     return out
+
+
+def bertadam_plan(entries, groups):
+    """Host-only check of a BertAdam table before its upload (nr_bertadam_plan): `entries` a ctypes array of hip.OptimTensor,
+    `groups` one of hip.OptimGroup.  Writes every entry's chunk0 -> the number of chunks; raises on a null / misaligned pointer,
+    a negative count, a group index out of range or a bad schedule id."""
+    import ctypes
+    n_chunks = ctypes.c_int(0)
+    hip._check("nr_bertadam_plan", hip.lib().nr_bertadam_plan(entries, len(entries), groups, len(groups), ctypes.byref(n_chunks)))
+    return int(n_chunks.value)
+
+
+def bertadam_workspace_bytes(n_tensors, n_chunks):
+    return int(hip.lib().nr_bertadam_workspace_bytes(int(n_tensors), int(n_chunks)))
+
+
+def bertadam_step(groups_dev, n_groups, table_dev, n_tensors, n_chunks, workspace, global_max_norm=None, table_offset=0):
+    """The three launches of the multi-tensor BertAdam update (nr_bertadam_step) on the current stream.  groups_dev / table_dev:
+    uint8 device tensors holding the uploaded hip.OptimGroup / hip.OptimTensor arrays that bertadam_plan checked (the table
+    starts `table_offset` bytes into table_dev); workspace: uint8, bertadam_workspace_bytes(n_tensors, n_chunks) or more."""
+    import ctypes
+    if workspace.numel() < bertadam_workspace_bytes(n_tensors, n_chunks):
+        raise hip.NrHipError("bertadam_step: workspace too small")
+    gmn = -1.0 if global_max_norm is None else float(global_max_norm)
+    hip.call("nr_bertadam_step", ctypes.c_void_p(hip.ptr(table_dev, torch.uint8).value + int(table_offset)), int(n_tensors),
+             int(n_chunks), hip.ptr(groups_dev, torch.uint8), int(n_groups), ctypes.c_float(gmn), hip.ptr(workspace, torch.uint8),
+             hip.stream_ptr())

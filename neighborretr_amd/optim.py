@@ -1,0 +1,351 @@
+"""BertAdam and prep_optimizer with the reference's interfaces (models/optimization.py:76-211, training/optimizer.py:12-86),
+the update itself done by the multi-tensor HIP kernels of csrc/nr_optim.hip (DESIGN.md "BertAdam in the captured step").
+
+What a step computes, in this order (trainer.py:104-119 around BertAdam.step):
+
+  1. optional global clip (`global_max_norm`, the trainer's 1.0):  c = min(1, global_max_norm / (sqrt(sum_t ||g_t||^2) + 1e-6));
+  2. per tensor, if the group's max_grad_norm > 0:                 c_t = min(1, max_grad_norm / (c ||g_t|| + 1e-6));
+     the gradient that enters the moments is g c c_t -- the gradient tensors themselves are never written;
+  3. m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  u = m / (sqrt(v) + e) (+ weight_decay * p when > 0); no bias correction;
+  4. lr_t = lr * schedule(step / t_total, warmup) with the tensor's step counter BEFORE this step (lr when t_total == -1);
+  5. p -= lr_t u;  p = min(p, clamp_max[p]) where given (`clip.logit_scale`: ln 100);  step += 1.
+
+`step()` issues three launches on the current stream and nothing else -- no `.item()`, no device synchronisation, no allocation
+once the moments exist (the one host wait it can take: a table upload finding all four staging buffers still unread by the device)
+-- so it can be captured into a HIP graph; the step counters and the schedule live on the device.  The table of
+pointers the kernels read is uploaded again only when one of its pointers (or a group's hyper-parameter) has changed.  There is
+no CPU or eager path behind it: parameters that are not on the GPU raise.
+"""
+import ctypes
+import math
+
+import torch
+from torch.optim import Optimizer
+
+from . import hip, ops
+
+
+# What a schedule returns once the warm-up ramp (x / warmup while x < warmup) is over; x = step / t_total.
+_PAST_WARMUP = {
+    "warmup_cosine": lambda x, warmup: (1.0 + math.cos(math.pi * x)) / 2.0,
+    "warmup_constant": lambda x, warmup: 1.0,
+    "warmup_linear": lambda x, warmup: max((x - 1.0) / (warmup - 1.0), 0.0),
+}
+
+
+def _make_schedule(name):
+    past = _PAST_WARMUP[name]
+
+    def schedule(x, warmup=0.002):
+        return x / warmup if x < warmup else past(x, warmup)
+    schedule.__name__ = schedule.__qualname__ = name
+    schedule.__doc__ = f"Learning-rate multiplier of `{name}` at x = step / t_total (DESIGN.md 6.3)."
+    return schedule
+
+
+SCHEDULES = {name: _make_schedule(name) for name in _PAST_WARMUP}
+warmup_cosine, warmup_constant, warmup_linear = (SCHEDULES[k] for k in ("warmup_cosine", "warmup_constant", "warmup_linear"))
+_REQUIRED = object()
+_RING = 4                     # pinned staging buffers of the eager path (a buffer is reused only after its copy has completed)
+_ENTRY = ctypes.sizeof(hip.OptimTensor)
+_GROUP = ctypes.sizeof(hip.OptimGroup)
+
+
+class BertAdam(Optimizer):
+    """Adam without bias correction, with decoupled weight decay, a per-tensor gradient clip and a built-in warm-up schedule.
+
+    The reference's constructor and argument checks, plus
+      global_max_norm  None / <= 0: off; else the trainer's clip_grad_norm_(parameters, global_max_norm) fused into the step;
+      clamp_max        {parameter: upper bound} applied after the update (the trainer's logit-scale clamp).
+    `state[p] = {'step', 'next_m', 'next_v'}` as in the reference, so state dicts move between the two implementations; 'step'
+    is the host's mirror of the device counter."""
+
+    def __init__(self, params, lr=_REQUIRED, warmup=-1, t_total=-1, schedule="warmup_linear", b1=0.9, b2=0.999, e=1e-6,
+                 weight_decay=0.01, max_grad_norm=1.0, global_max_norm=None, clamp_max=None):
+        if lr is _REQUIRED:
+            raise ValueError("BertAdam needs a learning rate")
+        unit = lambda x: 0.0 <= x < 1.0                                           # noqa: E731
+        for name, value, ok, wanted in (("lr", lr, lambda x: x >= 0.0, "a number >= 0"),
+                                        ("schedule", schedule, lambda x: x in SCHEDULES, "one of " + ", ".join(SCHEDULES)),
+                                        ("warmup", warmup, lambda x: x == -1 or unit(x), "-1 (none) or a fraction in [0, 1)"),
+                                        ("b1", b1, unit, "in [0, 1)"), ("b2", b2, unit, "in [0, 1)"),
+                                        ("e", e, lambda x: x >= 0.0, "a number >= 0"),
+                                        ("global_max_norm", global_max_norm, lambda x: x is None or float(x) == float(x),
+                                         "None or a number")):
+            if not ok(value):
+                raise ValueError(f"BertAdam: {name} = {value!r} is not accepted, it must be {wanted}")
+        defaults = dict(lr=lr, schedule=schedule, warmup=warmup, t_total=t_total, b1=b1, b2=b2, e=e, weight_decay=weight_decay,
+                        max_grad_norm=max_grad_norm)
+        super().__init__(params, defaults)
+        self.global_max_norm = None if global_max_norm is None else float(global_max_norm)
+        self.clamp_max = {}
+        known = {id(p) for g in self.param_groups for p in g["params"]}
+        for p, bound in (clamp_max or {}).items():
+            if id(p) not in known:
+                raise ValueError("clamp_max names a tensor that is not one of the optimizer's parameters")
+            self.clamp_max[id(p)] = float(bound)
+        self._dev = None          # device-side state: created by the first step() / prepare()
+        self._key = None          # what the device table currently holds
+        self._held = {}           # tables of captured steps, per owner: alive (and untouched) as long as that capture is in use
+
+    # ---- the reference's interface --------------------------------------------------------------------------------------
+    def get_lr(self):
+        """The scheduled learning rate of every parameter that has a gradient, from the host's mirror of the step counters
+        ([0] before the first step, as in the reference)."""
+        live = [(group, self.state[p]) for group in self.param_groups for p in group["params"] if p.grad is not None]
+        if any(len(state) == 0 for _, state in live):
+            return [0]
+        return [_scheduled(group, state["step"]) for group, state in live]
+
+    def group_lr(self, applied=False):
+        """One scheduled learning rate per parameter group, read at its most advanced tensor: the rate the NEXT step will use
+        (what get_lr() reports), or with `applied=True` the rate the last step used (0 steps: the first step's)."""
+        out = []
+        for group in self.param_groups:
+            steps = [self.state[p]["step"] for p in group["params"] if len(self.state[p])]
+            step = max(steps) if steps else 0
+            out.append(_scheduled(group, max(step - 1, 0) if applied else step))
+        return out
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.advance(self.issue())
+        return loss
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """Moments that already exist keep their storage and take the loaded values (a captured step has their addresses in its
+        table); the device counters are set from the loaded step counts."""
+        mine = {p: (st["next_m"], st["next_v"]) for p, st in self.state.items() if "next_m" in st}
+        super().load_state_dict(state_dict)
+        for p, (m, v) in mine.items():
+            st = self.state[p]
+            if "next_m" in st and st["next_m"].shape == m.shape and st["next_v"].shape == v.shape:
+                m.copy_(st["next_m"])
+                v.copy_(st["next_v"])
+            else:                                    # the loaded state has nothing for this tensor: it starts over
+                m.zero_()
+                v.zero_()
+                st.setdefault("step", 0)
+            st["next_m"], st["next_v"] = m, v
+        self._key = None
+        if self._dev is not None:
+            self._upload_steps()
+
+    # ---- the two halves of step(), for a caller that captures the launches into a graph ----------------------------------
+    @torch.no_grad()
+    def prepare(self, params=None, owner=None):
+        """Ahead of ONE graph capture of issue(): allocates the moments (for `params`, default: every parameter), the counters,
+        the workspace, and the pair of buffers -- pinned host, device -- the captured table copy will use.  Nothing is
+        allocated inside the capture.  `owner`: whoever holds the graph; the pair of its previous capture, which that graph
+        replaces, is dropped (a step that is re-captured every epoch keeps one pair, not one per epoch)."""
+        dev = self._device_state()
+        for p in (params if params is not None else self._all):
+            self._moments(p)
+        if owner is not None:
+            self._held.pop(id(owner), None)
+        dev["spare"] = (owner, torch.empty(dev["bytes"], dtype=torch.uint8, pin_memory=True),
+                        torch.empty(dev["bytes"], dtype=torch.uint8, device=dev["device"]))
+
+    @torch.no_grad()
+    def issue(self):
+        """The three launches for the parameters that have a gradient now -> those parameters.  Host state (the step mirror,
+        the tensors' version counters) is NOT touched: advance() does that, once per execution of the launches."""
+        dev = self._device_state()
+        live = [p for p in self._all if p.grad is not None]
+        if not live:
+            return live
+        capturing = torch.cuda.is_current_stream_capturing()
+        key = self._table_key(live)
+        if capturing or key != self._key:
+            if capturing and (dev["spare"] is None or any(len(self.state[p]) == 0 for p in live)):
+                raise RuntimeError("BertAdam.issue() inside a graph capture: call prepare() before the capture begins (moments "
+                                   "and the table's buffers must not be allocated inside it)")
+            table, n_chunks = self._build(live)
+            if capturing:
+                # the copy below becomes a memcpy node that reads the pinned buffer on every replay: both buffers belong to
+                # this capture alone and stay alive, untouched, as long as the optimizer
+                owner, pinned, buf = dev["spare"]
+                dev["spare"] = None
+                self._held[id(owner) if owner is not None else id(pinned)] = (pinned, buf)
+            else:
+                slot = dev["ring"][dev["next"]]
+                dev["next"] = (dev["next"] + 1) % _RING
+                pinned, event = slot
+                # the copy that last read this buffer: done long ago as a rule; a host wait only when the host has run _RING
+                # table uploads ahead of the device
+                event.synchronize()
+                buf = dev["table"]
+            ctypes.memmove(pinned.data_ptr(), table, len(table))
+            buf.copy_(pinned, non_blocking=True)
+            if capturing:
+                launch = (buf, len(live), n_chunks)
+            else:
+                event.record()
+                self._key, dev["launch"] = key, (buf, len(live), n_chunks)
+                launch = dev["launch"]
+        else:
+            launch = dev["launch"]
+        buf, T, n_chunks = launch
+        ops.bertadam_step(buf, len(self.param_groups), buf, T, n_chunks, dev["workspace"], self.global_max_norm,
+                          table_offset=dev["table_off"])
+        return live
+
+    def advance(self, live):
+        """After one execution of issue()'s launches: the parameters have changed outside autograd, so their version counters
+        move (modeling.scorer_weights / cluster_fused.build_stage_weights key their bf16 splits on them), and so does the
+        host's mirror of the step counters."""
+        if not live:
+            return
+        torch.autograd.graph.increment_version(live)
+        for p in live:
+            self.state[p]["step"] += 1
+
+    # ---- internals ----------------------------------------------------------------------------------------------------------
+    def _device_state(self):
+        if self._dev is not None:
+            return self._dev
+        self._all = [p for g in self.param_groups for p in g["params"]]
+        if not self._all:
+            raise ValueError("BertAdam has no parameters")
+        for p in self._all:
+            if not p.is_cuda:
+                raise hip.NrHipError(f"BertAdam: a parameter of shape {tuple(p.shape)} lives on '{p.device}', not on a GPU; the "
+                                     "update runs in HIP kernels and has no CPU fallback (move the model to the device before "
+                                     "building the optimizer)")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise hip.NrHipError(f"BertAdam: parameters must be contiguous float32 tensors, got {p.dtype} "
+                                     f"{'contiguous' if p.is_contiguous() else 'non-contiguous'} of shape {tuple(p.shape)}")
+        device = self._all[0].device
+        if any(p.device != device for p in self._all):
+            raise hip.NrHipError("BertAdam: all parameters must live on one device")
+        hip.lib()
+        N, G = len(self._all), len(self.param_groups)
+        self._index = {id(p): i for i, p in enumerate(self._all)}
+        self._group_of = [gi for gi, g in enumerate(self.param_groups) for _ in g["params"]]
+        table_off = (G * _GROUP + 63) // 64 * 64
+        nbytes = table_off + N * _ENTRY
+        max_chunks = sum((p.numel() + 4095) // 4096 for p in self._all)
+        ws = ops.bertadam_workspace_bytes(N, max_chunks)
+        with torch.cuda.device(device):
+            self._dev = dict(
+                device=device, bytes=nbytes, table_off=table_off,
+                steps=torch.zeros(N, dtype=torch.int32, device=device),
+                table=torch.empty(nbytes, dtype=torch.uint8, device=device),
+                workspace=torch.empty(max(ws, 256), dtype=torch.uint8, device=device),
+                ring=[(torch.empty(nbytes, dtype=torch.uint8, pin_memory=True), torch.cuda.Event()) for _ in range(_RING)],
+                next=0, launch=None, spare=None)
+        self._upload_steps()
+        return self._dev
+
+    def _upload_steps(self):
+        host = torch.tensor([int(self.state[p]["step"]) if len(self.state[p]) else 0 for p in self._all], dtype=torch.int32)
+        self._dev["steps"].copy_(host)
+
+    def _moments(self, p):
+        state = self.state[p]
+        if len(state) == 0:
+            state["step"] = 0
+            state["next_m"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            state["next_v"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return state
+
+    def _group_values(self):
+        return tuple((float(g["lr"]), float(g["weight_decay"]), float(g["b1"]), float(g["b2"]), float(g["e"]),
+                      float(g["max_grad_norm"]), float(g["warmup"]), int(g["t_total"]), g["schedule"])
+                     for g in self.param_groups)
+
+    def _table_key(self, live):
+        return (tuple((id(p), p.data_ptr(), p.grad.data_ptr()) for p in live), self._group_values(), self.global_max_norm)
+
+    def _build(self, live):
+        """Host image of [groups | table] for the tensors in `live`, checked and chunked by nr_bertadam_plan."""
+        dev = self._dev
+        G = len(self.param_groups)
+        groups = (hip.OptimGroup * G)()
+        for q, vals in zip(groups, self._group_values()):
+            q.lr, q.weight_decay, q.b1, q.b2, q.e, q.max_grad_norm, q.warmup, q.t_total = vals[:8]
+            if vals[8] not in hip.SCHEDULE_IDS:
+                raise ValueError("Invalid schedule parameter: {}".format(vals[8]))
+            q.schedule = hip.SCHEDULE_IDS[vals[8]]
+        entries = (hip.OptimTensor * len(live))()
+        steps = dev["steps"].data_ptr()
+        for ent, p in zip(entries, live):
+            g = p.grad
+            if g.is_sparse:
+                raise RuntimeError("BertAdam does not support sparse gradients")
+            if g.device != p.device or g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != p.numel():
+                raise hip.NrHipError(f"BertAdam: the gradient of a parameter of shape {tuple(p.shape)} must be a contiguous float32 "
+                                     f"tensor of that size on {p.device} (got {g.dtype}, {tuple(g.shape)}, {g.device})")
+            state = self._moments(p)
+            m, v = state["next_m"], state["next_v"]
+            if (m.device != p.device or v.device != p.device or m.dtype != torch.float32 or v.dtype != torch.float32
+                    or not m.is_contiguous() or not v.is_contiguous() or m.numel() != p.numel() or v.numel() != p.numel()):
+                raise hip.NrHipError("BertAdam: next_m / next_v must be contiguous float32 tensors of the parameter's size on its device")
+            i = self._index[id(p)]
+            ent.p, ent.g, ent.m, ent.v = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+            ent.step = steps + 4 * i
+            ent.n = p.numel()
+            ent.group = self._group_of[i]
+            bound = self.clamp_max.get(id(p))
+            ent.has_clamp = int(bound is not None)
+            ent.clamp_max = bound if bound is not None else 0.0
+        n_chunks = ops.bertadam_plan(entries, groups)
+        image = bytearray(dev["bytes"])
+        image[:G * _GROUP] = bytes(groups)
+        image[dev["table_off"]:dev["table_off"] + len(live) * _ENTRY] = bytes(entries)
+        return (ctypes.c_char * len(image)).from_buffer(image), n_chunks
+
+
+def _scheduled(group, step):
+    if group["t_total"] != -1:
+        return group["lr"] * SCHEDULES[group["schedule"]](step / group["t_total"], group["warmup"])
+    return group["lr"]
+
+
+_UNDECAYED = ("bias", "LayerNorm.bias", "LayerNorm.weight")     # substrings of parameter names that take no weight decay
+
+
+def _group_index(name):
+    """0: CLIP, decayed; 1: head, decayed; 2: CLIP, no decay; 3: head, no decay (the order of the reference's four groups)."""
+    return (0 if "clip." in name else 1) + (2 if any(mark in name for mark in _UNDECAYED) else 0)
+
+
+def prep_optimizer(args, model, num_train_optimization_steps, local_rank, global_max_norm=None, clamp_logit_scale=False,
+                   wrap=True):
+    """training/optimizer.py:12-86 -> (optimizer, None, model).  Four groups: names with `clip.` train at lr * coef_lr, names
+    containing `bias`, `LayerNorm.bias` or `LayerNorm.weight` take no weight decay; warmup_cosine over
+    `num_train_optimization_steps`, b1 0.9, b2 0.98, e 1e-6, per-tensor max_grad_norm 1.0.
+
+    By default the trainer's global clip and logit-scale clamp stay with the caller (training.train_epoch does both around
+    step(), like the reference's trainer); `global_max_norm=1.0` / `clamp_logit_scale=True` move them into the step.  The model
+    comes back wrapped in DistributedDataParallel when a process group is up (the reference wraps whenever CUDA is there, which
+    needs one; `wrap=False`: never), else as it came."""
+    if hasattr(model, "module"):
+        model = model.module
+    named = list(model.named_parameters())
+    members = [[], [], [], []]
+    for name, p in named:
+        members[_group_index(name)].append(p)
+    clip_lr = args.lr * args.coef_lr
+    groups = [dict(params=members[0], weight_decay=args.weight_decay, lr=clip_lr),
+              dict(params=members[1], weight_decay=args.weight_decay),
+              dict(params=members[2], weight_decay=0.0, lr=clip_lr),
+              dict(params=members[3], weight_decay=0.0)]
+    clamp = {}
+    if clamp_logit_scale:
+        clamp = {p: math.log(100.0) for n, p in named if n.endswith("clip.logit_scale") or n == "logit_scale"}
+        if not clamp:
+            raise ValueError("clamp_logit_scale: the model has no clip.logit_scale parameter")
+    optimizer = BertAdam(groups, lr=args.lr, warmup=args.warmup_proportion, schedule="warmup_cosine", b1=0.9, b2=0.98, e=1e-6,
+                         t_total=num_train_optimization_steps, weight_decay=args.weight_decay, max_grad_norm=1.0,
+                         global_max_norm=global_max_norm, clamp_max=clamp)
+    import torch.distributed as dist
+    if wrap and torch.cuda.is_available() and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local_rank], output_device=local_rank,
+                                                          find_unused_parameters=True)
+    return optimizer, None, model

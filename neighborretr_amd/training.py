@@ -15,8 +15,10 @@ DataLoader-like iterable of `(text_ids, text_mask, video, video_mask, inds, idx)
   * the five logged losses are reduced with one collective instead of five;
   * the memory bank handed to the model is adopted by its ring + bf16 shadow (modeling._bank_set), not re-read per step.
 
-Datasets, tokenizer, BertAdam and checkpoints stay the reference's own (out of scope): any torch optimizer with
-`step()/zero_grad()` works here; `get_lr()` is used for the log line when the optimizer has it.
+Datasets, tokenizer and checkpoints stay the reference's own (out of scope).  Any torch optimizer with
+`step()/zero_grad()` works here, `get_lr()` is used for the log line when the optimizer has it; the reference's BertAdam and
+prep_optimizer are neighborretr_amd.optim's (multi-tensor HIP kernels), built WITHOUT the fused global clip / clamp for this
+loop, which clips and clamps around step() like the reference's trainer.
 """
 import logging
 import time
@@ -297,7 +299,10 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
                           neighbor_loss=red[3], kl_loss=red[4])
         if logging_now and is_main_process() and logger is not None:
             eta = str(timedelta(seconds=int(_meter_value(meters, "time", "global_avg") * (max_steps - global_step))))
-            lr = optimizer.get_lr()[0] if hasattr(optimizer, "get_lr") else optimizer.param_groups[0]["lr"]
+            # (get_lr() lists the tensors that hold a gradient: none after zero_grad(set_to_none=True) -- optim.BertAdam then
+            # reports its first group's scheduled rate)
+            lrs = optimizer.get_lr() if hasattr(optimizer, "get_lr") else []
+            lr = lrs[0] if lrs else (optimizer.group_lr()[0] if hasattr(optimizer, "group_lr") else optimizer.param_groups[0]["lr"])
             logger.info(" | ".join([
                 f"Epoch: {epoch}/{args.epochs}", f"Iter: {global_step}/{max_steps}",
                 f"Loss: {_meter_value(meters, 'loss', 'median'):.4f}",
