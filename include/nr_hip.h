@@ -790,6 +790,33 @@ int nr_hubnorm_combine(int P, const float* parts, int L, float* stats, float* ls
 int nr_hubnorm_apply(const float* S, int n, int L, float beta, int mode, const float* col_norm, const int32_t* row_gate,
                      float* T, const float* row_norm, const int32_t* col_gate, float* V, void* stream);
 
+/* Test-time Sinkhorn normalisation (DESIGN.md "Test-time Sinkhorn normalisation"): the log-domain iteration of the reference's
+ * uniform regularisation (until_module.py:223-266; :248-250 is the order of the two half-steps) on a test similarity slab
+ * S [n, L] instead of the batch's logits.  a[i,j] = fl(beta S[i,j]), beta finite and > 0; log_mu [n], log_nu [L]: the log
+ * marginals, as vectors; u [n], v [L]: the potentials (start: 0).  Statistics are the (max, sum) pairs of nr_hubnorm_*: NaN
+ * entries are skipped, an entry equal to the max adds exactly 1, fixed reduction orders, no float atomics: bitwise reproducible.
+ * A line whose LSE is not finite (no entry, only -inf, a +inf entry) gets potential 0.  n = 0 or L = 0 is allowed; a negative
+ * extent, a null pointer or a bad beta: NR_EINVAL before any launch.  Each entry point is one launch unless said.
+ *   nr_sinknorm_row (until_module.py:249): u[i] = log_mu[i] - LSE_j(fl(a[i,j] + v[j])), one wave per row.
+ *   nr_sinknorm_col_stats (until_module.py:250, first part): (max, sum) pairs of fl(a[i,j] + u[i]) down the columns, per block
+ *     of 64 rows, into `workspace` (nr_hubnorm_col_workspace(n, L) bytes: [ceil(n / 64), 2, L] floats, 16-B aligned for the
+ *     vector path; may be null when n = 0).  stats non-null: a second launch merges them in block order into stats [2, L]
+ *     (what a rank contributes to the cross-rank gather; n = 0: every column (-inf, 0)).  stats null: the pairs stay in the
+ *     workspace for nr_sinknorm_finish_cols (one rank: no launch in between).
+ *   nr_sinknorm_finish_cols (until_module.py:250, second part): v[j] = log_nu[j] - lse of P pairs per column, parts [P, 2, L],
+ *     merged in index order (the workspace's blocks, or the gathered ranks' stats in rank order).
+ *   nr_sinknorm_apply (until_module.py:253-257, in the log domain): T[i,j] = fl(fl(a[i,j] + u[i]) + v[j]), no fused
+ *     multiply-add; one read of S, one write of T.  NaN stays NaN.
+ *   nr_sinknorm_row_err: err[i] = |exp(LSE_j(T[i,j]) - log_mu[i]) - 1| with T as nr_sinknorm_apply gives it (not stored), 0 for
+ *     a row whose LSE is not finite: how far the rows are from their marginal after the last column half-step. */
+int nr_sinknorm_row(const float* S, int n, int L, float beta, const float* v, const float* log_mu, float* u, void* stream);
+int nr_sinknorm_col_stats(const float* S, int n, int L, float beta, const float* u, void* workspace, float* stats,
+                          void* stream);
+int nr_sinknorm_finish_cols(int P, const float* parts, int L, const float* log_nu, float* v, void* stream);
+int nr_sinknorm_apply(const float* S, int n, int L, float beta, const float* u, const float* v, float* T, void* stream);
+int nr_sinknorm_row_err(const float* S, int n, int L, float beta, const float* u, const float* v, const float* log_mu,
+                        float* err, void* stream);
+
 /* Multi-tensor BertAdam step (models/optimization.py:76-211 with the trainer's clip and clamp around it, trainer.py:104-119;
  * DESIGN.md "BertAdam in the captured step").  fp32 tensors only.  Per step, for every table entry t with group q:
  *   c    = min(1, global_max_norm / (sqrt(sum_t ||g_t||^2) + 1e-6))             (global_max_norm <= 0: c = 1)

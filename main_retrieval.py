@@ -92,10 +92,13 @@ def get_args():
     p.add_argument("--hubness_k", type=int, default=0,
                    help="k > 0 (at most 128): the evaluation also reports hubness of the top-k lists in both directions "
                         "(k-occurrence skewness, hubs, anti-hubs, bad hubs; DESIGN.md); 0 = off")
-    p.add_argument("--test_norm", default="none", choices=["none", "is", "dsl", "qbnorm"],
+    p.add_argument("--test_norm", default="none", choices=["none", "is", "dsl", "qbnorm", "sinkhorn", "qbsinkhorn"],
                    help="test-time hubness reduction, reported next to the raw metrics: is (inverted softmax), dsl (dual "
-                        "softmax), qbnorm (QB-Norm with the memory bank as querybank; DESIGN.md); none = off")
+                        "softmax), qbnorm (QB-Norm with the memory bank as querybank), sinkhorn (the model's own log-domain "
+                        "Sinkhorn balancing on the test similarity), qbsinkhorn (its querybank form; DESIGN.md); none = off")
     p.add_argument("--test_norm_beta", type=float, default=20.0, help="inverse temperature beta of --test_norm")
+    p.add_argument("--test_norm_iters", type=int, default=50,
+                   help="--test_norm sinkhorn | qbsinkhorn: Sinkhorn iterations (the reference's num_iterations)")
     p.add_argument("--qb_k", type=int, default=1,
                    help="--test_norm qbnorm: a gallery item is active when it is in the top-qb_k list of some querybank item")
     p.add_argument("--hip_graph", type=int, default=0,
@@ -109,6 +112,8 @@ def get_args():
                         "over len(train) * epochs steps) as multi-tensor HIP kernels, with the trainer's global clip and "
                         "logit-scale clamp inside; under --hip_graph 1 on one rank the update is part of the replayed graph")
     args = p.parse_args()
+    if args.test_norm_iters < 1:
+        p.error("--test_norm_iters must be >= 1")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
         raise ValueError("--batch_size must divide over the ranks (args_parser.py:149-165)")
     return args
@@ -508,7 +513,7 @@ def eval_epoch(args, model, test):
         t, v, tm, vm = gather_eval_features(t, v, mine.to(dev), tm, vm, args)
     if test_norm != "none":
         t2v, v2t = sharded_metrics_with_test_norm(model, t, v, tm.float(), vm.float(), args, test_norm, args.test_norm_beta,
-                                                  qb_k=args.qb_k, hubness_k=hubness_k)
+                                                  qb_k=args.qb_k, hubness_k=hubness_k, n_iter=args.test_norm_iters)
     elif hubness_k:
         t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k)
     else:
@@ -522,12 +527,14 @@ def eval_epoch(args, model, test):
     if test_norm != "none":
         from neighborretr_amd.metrics import RetrievalMetrics
         nt, nv = t2v["test_norm"], v2t["test_norm"]
-        tag = test_norm_label(test_norm, nt["beta"])
+        tag = test_norm_label(test_norm, nt["beta"], nt.get("iters"))
         log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
         if hubness_k:
             log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
+        if "marginal_err" in nt:
+            log(args, f"{tag} marginal error {nt['marginal_err']:.3e} / {nv['marginal_err']:.3e}")
     return t2v, v2t
 
 
@@ -573,10 +580,10 @@ def main():
                 torch.save(model.state_dict(), os.path.join(args.output_dir, f"pytorch_model.bin.{epoch}"))
             clear_memory_bank(model)
     elif args.do_eval:
-        if args.test_norm == "qbnorm":                      # QB-Norm's querybank: the memory bank of the training set
+        if args.test_norm in ("qbnorm", "qbsinkhorn"):      # the querybank: the memory bank of the training set
             load_memory_bank(args, model, train)
         eval_epoch(args, model, test)
-        if args.test_norm == "qbnorm":
+        if args.test_norm in ("qbnorm", "qbsinkhorn"):
             clear_memory_bank(model)
     if args.world_size > 1:
         dist.destroy_process_group()

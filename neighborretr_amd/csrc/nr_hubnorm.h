@@ -1,0 +1,27 @@
+// Online (max, sum) log-sum-exp pairs shared by the test-time normalisation kernels (nr_hubnorm.hip, nr_sinknorm.hip).
+#pragma once
+#include "nr_common.h"
+
+#define NR_HN_ROWS 64          // rows per column-partial block: the workspace holds ceil(n / 64) pairs per column
+
+// (m, s) <- (m, s) merged with one more pair (m2, s2); entries equal to the larger max scale by exactly 1.  Symmetric in its
+// two arguments, bit for bit (fp32 addition and multiplication commute).
+__device__ __forceinline__ void nr_hn_merge(float& m, float& s, float m2, float s2) {
+    if (s2 == 0.f) return;                       // an empty pair (no entry)
+    if (s == 0.f) { m = m2; s = s2; return; }
+    if (m2 > m) {
+        s = s2 + s * expf(m - m2);
+        m = m2;
+    } else if (m2 == m) {
+        s = s + s2;
+    } else {
+        s = s + s2 * expf(m2 - m);
+    }
+}
+
+__device__ __forceinline__ void nr_hn_add(float& m, float& s, float beta, float x) {
+    if (x != x) return;                          // NaN: skipped
+    nr_hn_merge(m, s, __fmul_rn(beta, x), 1.f);
+}
+
+__device__ __forceinline__ float nr_hn_lse(float m, float s) { return s > 0.f ? m + logf(s) : -INFINITY; }

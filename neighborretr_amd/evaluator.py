@@ -335,13 +335,23 @@ def sharded_metrics_with_hubness(model, text_feat, video_feat, text_mask, video_
 # combine in rank order, so every rank holds the same bits.  V's row normalisers are rank-local.  QB-Norm replaces the test
 # queries by a querybank (the memory bank) and normalises only the queries whose top-1 lies in the bank's activation set.
 
-TEST_NORM_MODES = ("is", "dsl", "qbnorm")
-TEST_NORM_LABELS = {"is": "IS", "dsl": "DSL", "qbnorm": "QB-Norm"}
+TEST_NORM_MODES = ("is", "dsl", "qbnorm", "sinkhorn", "qbsinkhorn")
+TEST_NORM_LABELS = {"is": "IS", "dsl": "DSL", "qbnorm": "QB-Norm", "sinkhorn": "Sinkhorn", "qbsinkhorn": "QB-Sinkhorn"}
+SINKHORN_MODES = ("sinkhorn", "qbsinkhorn")                 # the iterated modes (DESIGN.md "Test-time Sinkhorn normalisation")
+BANK_MODES = ("qbnorm", "qbsinkhorn")                       # the modes that need a querybank
 
 
-def test_norm_label(mode, beta):
-    """The tag of the log lines of the normalised metrics, e.g. "[IS b=20]"."""
+def test_norm_label(mode, beta, n_iter=None):
+    """The tag of the log lines of the normalised metrics, e.g. "[IS b=20]"; the iterated modes: "[Sinkhorn b=20 it=50]"."""
+    if mode in SINKHORN_MODES and n_iter is not None:
+        return f"[{TEST_NORM_LABELS[mode]} b={beta:g} it={int(n_iter)}]"
     return f"[{TEST_NORM_LABELS[mode]} b={beta:g}]"
+
+
+def _check_n_iter(n_iter):
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or int(n_iter) < 1:
+        raise ValueError(f"test_norm iterations must be an integer >= 1, got {n_iter!r}")
+    return int(n_iter)
 
 
 def _check_test_norm(mode, beta, qb_k, hubness_k):
@@ -428,9 +438,91 @@ def _normalised_from_slab(S_slab, n_rows, n_cols, W, rank, mode, beta, bank_slab
     return ops.hubnorm_apply(S_slab, beta, "is", col_norm=c_v, row_gate=row_gate, row_norm=c_t, col_gate=col_gate)
 
 
+# ---- test-time Sinkhorn normalisation (DESIGN.md "Test-time Sinkhorn normalisation") -------------------------------------------
+# The reference's log-domain Sinkhorn (until_module.py:223-266) on the test similarity: n_iter times a row half-step (rank-local:
+# every rank holds the whole v) and a column half-step (the ranks' [2, L] partial pairs, one all-gather, combined in rank order:
+# every rank holds the same bits of v).  The slab never leaves its rank.
+
+def _log_marginals(n_rows, n_cols, ends, dev):
+    """(log_mu [n_rows], log_nu [n_cols]) fp32 on `dev`: every row the same mass; every column the same mass, or (ends: one past
+    the last sentence of every video) the share of the rows it owns."""
+    log_mu = np.full((n_rows,), -np.log(float(n_rows)) if n_rows else 0.0)
+    if ends is None:
+        log_nu = np.full((n_cols,), -np.log(float(n_cols)) if n_cols else 0.0)
+    else:
+        sizes = np.diff(np.concatenate(([0], np.asarray(ends, dtype=np.int64)))).astype(np.float64)
+        log_nu = np.log(sizes / float(n_rows))
+    return tuple(torch.from_numpy(a.astype(np.float32)).to(dev) for a in (log_mu, log_nu))
+
+
+def _sinkhorn_potentials(A_slab, beta, log_mu, log_nu, n_iter, W):
+    """(u, v, marginal_err) of the slab A [rows of this rank, L]: n_iter iterations from u = v = 0 with the log marginals log_mu
+    (of THIS rank's rows) and log_nu [L].  u [rows] is rank-local, v [L] and marginal_err (float: the largest
+    |row mass / mu - 1| after the last iteration, over every rank's rows that take part) are the same on every rank.  One
+    all-gather of 8L bytes per iteration and one max all-reduce of 4 bytes at the end."""
+    A_slab = ops._slab_2d(A_slab)
+    n, L = A_slab.shape
+    dev = A_slab.device
+    u = torch.zeros((n,), dtype=torch.float32, device=dev)
+    v = torch.zeros((L,), dtype=torch.float32, device=dev)
+    ws = ops.sinknorm_workspace(n, L, dev)
+    allp = torch.empty((W, 2, L), dtype=torch.float32, device=dev) if W > 1 else None
+    for _ in range(n_iter):
+        ops.sinknorm_row(A_slab, beta, v, log_mu, out=u)
+        if W > 1:
+            stats = ops.sinknorm_col_stats(A_slab, beta, u, ws)
+            comm.all_gather_into_tensor(allp.view(-1), stats.view(-1))
+            ops.sinknorm_finish_cols(allp, log_nu, out=v)
+        else:                                               # one rank: the blocks' pairs are finished straight from the workspace
+            ops.sinknorm_finish_cols(ops.sinknorm_col_stats(A_slab, beta, u, ws, want_stats=False), log_nu, out=v)
+    err = torch.zeros((1,), dtype=torch.float32, device=dev)
+    if n and L:
+        err = ops.sinknorm_row_err(A_slab, beta, u, v, log_mu).max().reshape(1)
+    if W > 1:
+        comm.all_reduce(err, op="max")
+    return u, v, float(err.item())
+
+
+def _sinkhorn_from_slab(S_slab, n_rows, n_cols, W, rank, mode, beta, n_iter, ends=None, bank_slabs=None, n_bank_texts=None):
+    """(T_slab, V_slab, info) of this rank's slab.  sinkhorn: ONE output, V_slab is T_slab (text->video ranks its rows,
+    video->text its columns).  qbsinkhorn: bank_slabs = (Qt_slab, Qv_slab) as _bank_slabs scores them, n_bank_texts = the
+    bank's text count M (Qt_slab holds the rows slab_bounds(M, W, rank)); T takes the column
+    potentials of Qt, V the row potentials of Qv (the `is` apply with col_norm = -v_t, row_norm = -u_v).  info: "iters" and
+    "marginal_err" (qbsinkhorn: of Qt and of Qv)."""
+    dev = S_slab.device
+    r0, r1 = slab_bounds(n_rows, W, rank)
+    if mode == "sinkhorn":
+        log_mu, log_nu = _log_marginals(n_rows, n_cols, ends, dev)
+        u, v, err = _sinkhorn_potentials(S_slab, beta, log_mu[r0:r1].contiguous(), log_nu, n_iter, W)
+        T = ops.sinknorm_apply(S_slab, beta, u, v)
+        return T, T, dict(iters=n_iter, marginal_err=(err, err))
+    Qt, Qv = bank_slabs
+    M_t, M_v = int(n_bank_texts), Qv.shape[1]
+    q0, q1 = slab_bounds(M_t, W, rank)
+    if Qt.shape[0] != q1 - q0:
+        raise ValueError(f"Qt_slab must hold the {q1 - q0} bank rows of rank {rank}, got {Qt.shape[0]}")
+    mu_t, nu_t = _log_marginals(M_t, n_cols, None, dev)
+    _, v_t, err_t = _sinkhorn_potentials(Qt, beta, mu_t[q0:q1].contiguous(), nu_t, n_iter, W)
+    mu_v, nu_v = _log_marginals(n_rows, M_v, None, dev)
+    u_v, _, err_v = _sinkhorn_potentials(Qv, beta, mu_v[r0:r1].contiguous(), nu_v, n_iter, W)
+    T, V = ops.hubnorm_apply(S_slab, beta, "is", col_norm=-v_t, row_norm=-u_v)
+    return T, V, dict(iters=n_iter, marginal_err=(err_t, err_v))
+
+
 def _metrics_from_normalised(T_slab, V_slab, n_rows, n_cols, W, rank, ends, hubness_k):
     """(t2v, v2t): text->video ranks from the rows of T, video->text from the columns of V (multi-sentence sets: the group
-    ranks of T, the group max of V), and with hubness_k the hubness of T's row lists and V's column lists."""
+    ranks of T, the group max of V), and with hubness_k the hubness of T's row lists and V's column lists.  V_slab is T_slab
+    (sinkhorn's one output): both directions from one pass over it."""
+    if V_slab is T_slab:
+        if ends is None:
+            gt, et, gv, ev = _ranks_from_slab(T_slab, n_rows, W, rank)
+            t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
+            v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
+        else:
+            t2v, v2t = _multi_sentence_from_slab(T_slab, ends, n_rows, n_cols, W, rank)
+        if hubness_k:
+            t2v["hubness"], v2t["hubness"] = _hubness_from_slab(T_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+        return t2v, v2t
     if ends is None:
         gt, et, _, _ = _ranks_from_slab(T_slab, n_rows, W, rank)
         _, _, gv, ev = _ranks_from_slab(V_slab, n_rows, W, rank)
@@ -445,58 +537,73 @@ def _metrics_from_normalised(T_slab, V_slab, n_rows, n_cols, W, rank, ends, hubn
     return t2v, v2t
 
 
-def _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k, chunk):
-    S_slab, n_rows, n_cols, W, rank, _ = slab
-    bank_slabs = None
-    if mode == "qbnorm":
+def _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k, chunk,
+                               n_iter=50, info=None):
+    """(T_slab, V_slab); the iterated modes put "iters" and "marginal_err" into the dictionary `info`."""
+    S_slab, n_rows, n_cols, W, rank, ends = slab
+    bank_slabs, n_bank_texts = None, None
+    if mode in BANK_MODES:
         bank = _querybank(model, querybank, S_slab.device)
         bank_slabs = _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, bank, W, rank, chunk)
+        n_bank_texts = bank[0].shape[0]
+    if mode in SINKHORN_MODES:
+        T, V, extra = _sinkhorn_from_slab(S_slab, n_rows, n_cols, W, rank, mode, beta, n_iter, ends, bank_slabs, n_bank_texts)
+        if info is not None:
+            info.update(extra)
+        return T, V
     return _normalised_from_slab(S_slab, n_rows, n_cols, W, rank, mode, beta, bank_slabs, qb_k)
 
 
 def sharded_normalised_slabs(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None, qb_k=1,
-                             cut_off_points=None, chunk=256):
+                             cut_off_points=None, chunk=256, n_iter=50):
     """-> (T_slab, V_slab) fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the text->video
     scores (rows are the queries) and the video->text scores (columns are the queries) after the test-time correction `mode`
-    ("is" | "dsl" | "qbnorm", DESIGN.md "Test-time hubness reduction").  querybank: (text_feat, text_mask, video_feat,
-    video_mask) of the qbnorm querybank; None: the model's memory bank (load_memory_bank)."""
+    ("is" | "dsl" | "qbnorm", DESIGN.md "Test-time hubness reduction"; "sinkhorn" | "qbsinkhorn" with n_iter iterations,
+    DESIGN.md "Test-time Sinkhorn normalisation": "sinkhorn" has ONE output, V_slab is T_slab).  querybank: (text_feat,
+    text_mask, video_feat, video_mask) of the qbnorm / qbsinkhorn querybank; None: the model's memory bank (load_memory_bank)."""
     beta, qb_k, _ = _check_test_norm(mode, beta, qb_k, 0)
-    if mode == "qbnorm":
+    n_iter = _check_n_iter(n_iter)
+    if mode in BANK_MODES:
         _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
     slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
     return _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
-                                      chunk)
+                                      chunk, n_iter)
 
 
-def _test_norm_entry(metrics, mode, beta, qb_k):
+def _test_norm_entry(metrics, mode, beta, qb_k, info=None, side=0):
     metrics.update(mode=mode, beta=beta)
     if mode == "qbnorm":
         metrics["qb_k"] = qb_k
+    if mode in SINKHORN_MODES:                                  # side 0: text->video (qbsinkhorn: Qt's rows), 1: video->text (Qv's)
+        metrics.update(iters=info["iters"], marginal_err=info["marginal_err"][side])
     return metrics
 
 
 def sharded_normalised_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None, qb_k=1,
-                               hubness_k=0, cut_off_points=None, chunk=256):
+                               hubness_k=0, cut_off_points=None, chunk=256, n_iter=50):
     """(text->video, video->text) metric dictionaries of the normalised scores (sharded_normalised_slabs), identical on every
-    rank, each with "mode" and "beta" (and "qb_k" for qbnorm) and, with hubness_k, a "hubness" entry (sharded_hubness's
-    summary of T's row lists / V's column lists)."""
+    rank, each with "mode" and "beta" (and "qb_k" for qbnorm; "iters" and "marginal_err" for sinkhorn / qbsinkhorn) and, with
+    hubness_k, a "hubness" entry (sharded_hubness's summary of T's row lists / V's column lists)."""
     beta, qb_k, hubness_k = _check_test_norm(mode, beta, qb_k, hubness_k)
-    if mode == "qbnorm":
+    n_iter = _check_n_iter(n_iter)
+    if mode in BANK_MODES:
         _querybank(model, querybank, text_feat.device)
     slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    info = {}
     T, V = _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
-                                      chunk)
+                                      chunk, n_iter, info)
     _, n_rows, n_cols, W, rank, ends = slab
     t2v, v2t = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k)
-    return _test_norm_entry(t2v, mode, beta, qb_k), _test_norm_entry(v2t, mode, beta, qb_k)
+    return _test_norm_entry(t2v, mode, beta, qb_k, info, 0), _test_norm_entry(v2t, mode, beta, qb_k, info, 1)
 
 
 def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None,
-                                   qb_k=1, hubness_k=0, cut_off_points=None, chunk=256):
+                                   qb_k=1, hubness_k=0, cut_off_points=None, chunk=256, n_iter=50):
     """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
     each with one more entry "test_norm" = sharded_normalised_metrics, from ONE scoring of this rank's slab."""
     beta, qb_k, hubness_k = _check_test_norm(mode, beta, qb_k, hubness_k)
-    if mode == "qbnorm":
+    n_iter = _check_n_iter(n_iter)
+    if mode in BANK_MODES:
         _querybank(model, querybank, text_feat.device)
     slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
     S_slab, n_rows, n_cols, W, rank, ends = slab
@@ -508,10 +615,11 @@ def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, vide
         t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
     if hubness_k:
         t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    info = {}
     T, V = _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
-                                      chunk)
+                                      chunk, n_iter, info)
     del S_slab, slab
     nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k)
-    t2v["test_norm"] = _test_norm_entry(nt, mode, beta, qb_k)
-    v2t["test_norm"] = _test_norm_entry(nv, mode, beta, qb_k)
+    t2v["test_norm"] = _test_norm_entry(nt, mode, beta, qb_k, info, 0)
+    v2t["test_norm"] = _test_norm_entry(nv, mode, beta, qb_k, info, 1)
     return t2v, v2t

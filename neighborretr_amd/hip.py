@@ -240,6 +240,11 @@ _SIGNATURES = {
     "nr_hubnorm_col_stats": ([_P, _I, _I, _F, _P, _P, _P], _I),
     "nr_hubnorm_combine": ([_I, _P, _I, _P, _P, _P], _I),
     "nr_hubnorm_apply": ([_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P], _I),
+    "nr_sinknorm_row": ([_P, _I, _I, _F, _P, _P, _P, _P], _I),
+    "nr_sinknorm_col_stats": ([_P, _I, _I, _F, _P, _P, _P, _P], _I),
+    "nr_sinknorm_finish_cols": ([_I, _P, _I, _P, _P, _P], _I),
+    "nr_sinknorm_apply": ([_P, _I, _I, _F, _P, _P, _P, _P], _I),
+    "nr_sinknorm_row_err": ([_P, _I, _I, _F, _P, _P, _P, _P, _P], _I),
     "nr_bertadam_plan": ([ctypes.POINTER(OptimTensor), _I, ctypes.POINTER(OptimGroup), _I, ctypes.POINTER(_I)], _I),
     "nr_bertadam_workspace_bytes": ([_I, _I], _Z),
     "nr_bertadam_step": ([_P, _I, _I, _P, _I, _F, _P, _P], _I),

@@ -1048,6 +1048,88 @@ def hubnorm_apply(S, beta, mode, col_norm=None, row_gate=None, row_norm=None, co
     return T, V
 
 
+def _sink_vec(x, size, what):
+    if x.dtype != torch.float32 or x.shape != (size,) or not x.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous fp32 vector of {size} entries, got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def sinknorm_workspace(n, L, device):
+    """The column half-step's workspace for a slab [n, L]: uint8, nr_hubnorm_col_workspace(n, L) bytes."""
+    return torch.empty((int(hip.lib().nr_hubnorm_col_workspace(int(n), int(L))),), dtype=torch.uint8, device=device)
+
+
+def sinknorm_row(S, beta, v, log_mu, out=None):
+    """u [n] = log_mu - LSE_j(fl(fl(beta S) + v[j])) of every row of S [n, L], 0 for a row whose LSE is not finite
+    (nr_sinknorm_row; until_module.py:249).  out: the u to overwrite."""
+    beta = _check_beta(beta)
+    S = _slab_2d(S)
+    n, L = S.shape
+    u = torch.empty((n,), dtype=torch.float32, device=S.device) if out is None else _sink_vec(out, n, "out")
+    if n and L:
+        hip.call("nr_sinknorm_row", hip.ptr(S), n, L, beta, hip.ptr(_sink_vec(v, L, "v")), hip.ptr(_sink_vec(log_mu, n, "log_mu")),
+                 hip.ptr(u), hip.stream_ptr())
+    else:
+        u.zero_()
+    return u
+
+
+def sinknorm_col_stats(S, beta, u, workspace=None, want_stats=True):
+    """The (max, sum) pairs of fl(fl(beta S) + u[i]) down the columns of S [n, L] (nr_sinknorm_col_stats; until_module.py:250).
+    want_stats: stats [2, L], this slab's pairs merged in block order (what a rank contributes to the cross-rank gather).
+    Otherwise the blocks' pairs [ceil(n / 64), 2, L], a view of `workspace`, for sinknorm_finish_cols."""
+    beta = _check_beta(beta)
+    S = _slab_2d(S)
+    n, L = S.shape
+    ws = sinknorm_workspace(n, L, S.device) if workspace is None else workspace
+    need = int(hip.lib().nr_hubnorm_col_workspace(n, L))
+    if ws.dtype != torch.uint8 or ws.numel() < need:
+        raise ValueError(f"workspace must be uint8 with at least {need} bytes")
+    stats = torch.empty((2, L), dtype=torch.float32, device=S.device) if want_stats else None
+    if L and (n or want_stats):
+        hip.call("nr_sinknorm_col_stats", hip.ptr(S) if n else None, n, L, beta, hip.ptr(_sink_vec(u, n, "u")) if n else None,
+                 hip.ptr(ws) if need else None, hip.ptr(stats, allow_none=True), hip.stream_ptr())
+    return stats if want_stats else ws[:need].view(torch.float32).view((n + 63) // 64, 2, L)
+
+
+def sinknorm_finish_cols(parts, log_nu, out=None):
+    """v [L] = log_nu - lse of the pairs parts [P, 2, L] merged in index order, 0 where the lse is not finite
+    (nr_sinknorm_finish_cols; until_module.py:250).  out: the v to overwrite."""
+    if parts.dtype != torch.float32 or parts.dim() != 3 or parts.shape[1] != 2 or not parts.is_contiguous():
+        raise ValueError("parts must be a contiguous fp32 [P, 2, L]")
+    P, _, L = parts.shape
+    v = torch.empty((L,), dtype=torch.float32, device=parts.device) if out is None else _sink_vec(out, L, "out")
+    if L:
+        hip.call("nr_sinknorm_finish_cols", P, hip.ptr(parts) if P else None, L, hip.ptr(_sink_vec(log_nu, L, "log_nu")), hip.ptr(v),
+                 hip.stream_ptr())
+    return v
+
+
+def sinknorm_apply(S, beta, u, v):
+    """T [n, L] = fl(fl(fl(beta S) + u[i]) + v[j]) (nr_sinknorm_apply; until_module.py:253-257 in the log domain)."""
+    beta = _check_beta(beta)
+    S = _slab_2d(S)
+    n, L = S.shape
+    T = torch.empty_like(S)
+    if n and L:
+        hip.call("nr_sinknorm_apply", hip.ptr(S), n, L, beta, hip.ptr(_sink_vec(u, n, "u")), hip.ptr(_sink_vec(v, L, "v")), hip.ptr(T),
+                 hip.stream_ptr())
+    return T
+
+
+def sinknorm_row_err(S, beta, u, v, log_mu):
+    """err [n] = |exp(LSE_j(T[i, j]) - log_mu[i]) - 1|, T as sinknorm_apply gives it, 0 for a row whose LSE is not finite
+    (nr_sinknorm_row_err)."""
+    beta = _check_beta(beta)
+    S = _slab_2d(S)
+    n, L = S.shape
+    err = torch.zeros((n,), dtype=torch.float32, device=S.device)
+    if n and L:
+        hip.call("nr_sinknorm_row_err", hip.ptr(S), n, L, beta, hip.ptr(_sink_vec(u, n, "u")), hip.ptr(_sink_vec(v, L, "v")),
+                 hip.ptr(_sink_vec(log_mu, n, "log_mu")), hip.ptr(err), hip.stream_ptr())
+    return err
+
+
 def linear_x3(x, w, bias=None, residual=None):
     """Y = X W^T (+ bias) (+ residual) on the split-bf16 MFMA tile engine (nr_linear_x3): x [M,K], w [N,K] fp32, K padded to
     a multiple of 64 with zeros.  ~fp32-grade products (3 bf16 passes); used for the clustering GEMMs and for the

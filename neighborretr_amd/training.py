@@ -159,7 +159,7 @@ def eval_epoch(args, model, test_dataloader, device):
     (rank r: rows [r N/W, (r+1) N/W)).  Multi-sentence sets (`dataset.multi_sentence_per_video`): every rank walks the whole
     loader, as in the reference (:114-131), keeps the video of each group's last sentence (:137-149), and the
     sentence x video matrix is again scored in row slabs (evaluator.sharded_multi_sentence_metrics)."""
-    from .evaluator import (_check_test_norm, _querybank, dataset_order, gather_eval_features, sharded_metrics,
+    from .evaluator import (BANK_MODES, _check_n_iter, _check_test_norm, _querybank, dataset_order, gather_eval_features, sharded_metrics,
                             sharded_metrics_with_hubness, sharded_metrics_with_test_norm, sharded_multi_sentence_metrics,
                             test_norm_label)
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
@@ -169,9 +169,10 @@ def eval_epoch(args, model, test_dataloader, device):
     model = _unwrap(model).to(device)
     if test_norm != "none":          # the test-time correction (DESIGN.md "Test-time hubness reduction"): checked before any work
         beta, qb_k, _ = _check_test_norm(test_norm, getattr(args, "test_norm_beta", 20.0), getattr(args, "qb_k", 1), hubness_k)
-        if test_norm == "qbnorm":
+        if test_norm in BANK_MODES:
             _querybank(model, None, device)
-        norm = dict(mode=test_norm, beta=beta, qb_k=qb_k, hubness_k=hubness_k)
+        norm = dict(mode=test_norm, beta=beta, qb_k=qb_k, hubness_k=hubness_k,
+                    n_iter=_check_n_iter(getattr(args, "test_norm_iters", 50)))
     dataset = getattr(test_dataloader, "dataset", None)
     multi = bool(getattr(dataset, "multi_sentence_per_video", False))
     model.eval()
@@ -218,9 +219,12 @@ def eval_epoch(args, model, test_dataloader, device):
             tracker.log_hubness(t2v["hubness"], prefix="Text-to-Video ")
             tracker.log_hubness(v2t["hubness"], prefix="Video-to-Text ")
         if test_norm != "none":
-            tag = test_norm_label(test_norm, t2v["test_norm"]["beta"])
+            tag = test_norm_label(test_norm, t2v["test_norm"]["beta"], t2v["test_norm"].get("iters"))
             tracker.print_metrics(t2v["test_norm"], prefix=f"Text-to-Video {tag}: ")
             tracker.print_metrics(v2t["test_norm"], prefix=f"Video-to-Text {tag}: ")
+            if "marginal_err" in t2v["test_norm"]:
+                logger.info(f"{tag} marginal error after {t2v['test_norm']['iters']} iterations: "
+                            f"{t2v['test_norm']['marginal_err']:.3e} / {v2t['test_norm']['marginal_err']:.3e}")
             if hubness_k:
                 tracker.log_hubness(t2v["test_norm"]["hubness"], prefix=f"Text-to-Video {tag} ")
                 tracker.log_hubness(v2t["test_norm"]["hubness"], prefix=f"Video-to-Text {tag} ")
