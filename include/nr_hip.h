@@ -817,6 +817,29 @@ int nr_sinknorm_apply(const float* S, int n, int L, float beta, const float* u, 
 int nr_sinknorm_row_err(const float* S, int n, int L, float beta, const float* u, const float* v, const float* log_mu,
                         float* err, void* stream);
 
+/* Local scaling (CSLS, NICDM, LS; DESIGN.md "Local scaling"; the reference has no code for it, its project page argues from
+ * these neighbourhoods): every score of S [n, L] (cosine scale, d = 1 - s the distance) is rescaled by statistics of its row's and
+ * its column's top-k lists, as nr_slab_topk_rows / nr_slab_topk_cols / nr_topk_merge write them.  Statistics of a list with c
+ * present entries (index >= 0):
+ *   mean = fl(fl(sum of the c present values, added one by one in list order starting from the first) / fl(c)),
+ *   kth  = the c-th present value;   c = 0: both NaN.  Infinities follow IEEE.
+ * Scores, fp32, every operation rounded once (no fused multiply-add), EPS = 2^-20, max(x, .) keeps a NaN x:
+ *   csls:  T[i,j] = fl(fl(2 s - mean_row[i]) - mean_col[j])
+ *   nicdm: d = max(fl(1 - s), 0), a[i] = max(fl(1 - mean_row[i]), EPS), b[j] = max(fl(1 - mean_col[j]), EPS);
+ *          T[i,j] = -fl(d / fl(sqrt(fl(a b))))
+ *   ls:    a[i] = max(fl(1 - kth_row[i]), EPS), b[j] likewise;  T[i,j] = -fl(fl(d d) / fl(a b))   (the log of exp(-d^2 / a b))
+ * A NaN s gives a NaN T, a NaN statistic a NaN line.  No scratch, no float atomics, bitwise reproducible.  A null pointer, a
+ * negative extent, k outside [1, 128] or an unknown mode: NR_EINVAL before any launch; n = 0 or L = 0: NR_OK, no launch.
+ *   nr_localscale_stats: lists idx / val [n, k] -> mean [n], kth [n] (one thread per list).
+ *   nr_localscale_apply: one read of S, one write of T; row_stat [n] / col_stat [L] are the means (csls, nicdm) or the k-th
+ *     values (ls).  16-byte accesses when L % 4 == 0 and S, T, col_stat are 16-byte aligned, a scalar path otherwise. */
+#define NR_LOCALSCALE_CSLS 0
+#define NR_LOCALSCALE_NICDM 1
+#define NR_LOCALSCALE_LS 2
+int nr_localscale_stats(const int32_t* idx, const float* val, int n, int k, float* mean, float* kth, void* stream);
+int nr_localscale_apply(const float* S, int n, int L, int mode, const float* row_stat, const float* col_stat, float* T,
+                        void* stream);
+
 /* Multi-tensor BertAdam step (models/optimization.py:76-211 with the trainer's clip and clamp around it, trainer.py:104-119;
  * DESIGN.md "BertAdam in the captured step").  fp32 tensors only.  Per step, for every table entry t with group q:
  *   c    = min(1, global_max_norm / (sqrt(sum_t ||g_t||^2) + 1e-6))             (global_max_norm <= 0: c = 1)

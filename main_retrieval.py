@@ -101,6 +101,15 @@ def get_args():
                    help="--test_norm sinkhorn | qbsinkhorn: Sinkhorn iterations (the reference's num_iterations)")
     p.add_argument("--qb_k", type=int, default=1,
                    help="--test_norm qbnorm: a gallery item is active when it is in the top-qb_k list of some querybank item")
+    p.add_argument("--local_scaling", default="none", choices=["none", "csls", "nicdm", "ls"],
+                   help="local-scaling hubness reduction, reported next to the raw metrics: every score rescaled by statistics of "
+                        "the two items' k-nearest neighbourhoods -- csls (minus the mean neighbour similarities), nicdm (distance "
+                        "over the mean neighbour distances), ls (squared distance over the k-th neighbour distances; DESIGN.md); "
+                        "none = off.  Not together with --test_norm")
+    p.add_argument("--local_scaling_k", type=int, default=10, help="--local_scaling: neighbourhood size k (at most 128)")
+    p.add_argument("--local_scaling_bank", type=int, default=0, choices=[0, 1],
+                   help="--local_scaling: 1 takes the neighbourhoods in the memory bank (the querybank of --test_norm qbnorm) "
+                        "instead of the test set")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -114,6 +123,10 @@ def get_args():
     args = p.parse_args()
     if args.test_norm_iters < 1:
         p.error("--test_norm_iters must be >= 1")
+    if args.local_scaling != "none" and args.test_norm != "none":
+        p.error("--local_scaling and --test_norm are separate corrections: choose one of them")
+    if not 1 <= args.local_scaling_k <= 128:
+        p.error("--local_scaling_k must lie in [1, 128]")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
         raise ValueError("--batch_size must divide over the ranks (args_parser.py:149-165)")
     return args
@@ -499,8 +512,10 @@ def eval_epoch(args, model, test):
     collectives complete them."""
     from neighborretr_amd.evaluator import (gather_eval_features, rank_sample_indices, sharded_metrics, sharded_metrics_with_hubness,
                                             sharded_metrics_with_test_norm, test_norm_label)
+    from neighborretr_amd.evaluator import local_scaling_label, sharded_metrics_with_local_scaling
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
     test_norm = getattr(args, "test_norm", None) or "none"
+    local_scaling = getattr(args, "local_scaling", None) or "none"
     model.eval()
     dev = args.device
     mine = rank_sample_indices(test.n, args.world_size, args.rank)     # equal counts on every rank (padded like DistributedSampler)
@@ -514,6 +529,10 @@ def eval_epoch(args, model, test):
     if test_norm != "none":
         t2v, v2t = sharded_metrics_with_test_norm(model, t, v, tm.float(), vm.float(), args, test_norm, args.test_norm_beta,
                                                   qb_k=args.qb_k, hubness_k=hubness_k, n_iter=args.test_norm_iters)
+    elif local_scaling != "none":
+        t2v, v2t = sharded_metrics_with_local_scaling(model, t, v, tm.float(), vm.float(), args, local_scaling,
+                                                      k=args.local_scaling_k, bank=bool(args.local_scaling_bank),
+                                                      hubness_k=hubness_k)
     elif hubness_k:
         t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k)
     else:
@@ -535,6 +554,15 @@ def eval_epoch(args, model, test):
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
         if "marginal_err" in nt:
             log(args, f"{tag} marginal error {nt['marginal_err']:.3e} / {nv['marginal_err']:.3e}")
+    if local_scaling != "none":
+        from neighborretr_amd.metrics import RetrievalMetrics
+        nt, nv = t2v["local_scaling"], v2t["local_scaling"]
+        tag = local_scaling_label(local_scaling, nt["k"], nt["bank"])
+        log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
+                  f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
+        if hubness_k:
+            log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
+            log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
     return t2v, v2t
 
 
@@ -580,10 +608,11 @@ def main():
                 torch.save(model.state_dict(), os.path.join(args.output_dir, f"pytorch_model.bin.{epoch}"))
             clear_memory_bank(model)
     elif args.do_eval:
-        if args.test_norm in ("qbnorm", "qbsinkhorn"):      # the querybank: the memory bank of the training set
+        with_bank = args.test_norm in ("qbnorm", "qbsinkhorn") or (args.local_scaling != "none" and args.local_scaling_bank)
+        if with_bank:                                       # the querybank: the memory bank of the training set
             load_memory_bank(args, model, train)
         eval_epoch(args, model, test)
-        if args.test_norm in ("qbnorm", "qbsinkhorn"):
+        if with_bank:
             clear_memory_bank(model)
     if args.world_size > 1:
         dist.destroy_process_group()

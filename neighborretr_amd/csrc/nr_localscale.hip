@@ -1,0 +1,112 @@
+// Local scaling of a similarity slab (DESIGN.md "Local scaling"): CSLS, NICDM and LS rescale every score by statistics of the
+// two items' k-nearest neighbourhoods, taken from the top-k lists of nr_topk.hip.
+//
+//   mean = fl(fl(sum of the present values of a list, one by one in list order) / fl(count));   kth = the last present value
+//   csls:  T[i,j] = fl(fl(2 s - mean_row[i]) - mean_col[j])
+//   nicdm: T[i,j] = -fl(d / fl(sqrt(fl(a[i] b[j])))),  d = max(fl(1 - s), 0),  a = max(fl(1 - mean), EPS)
+//   ls:    T[i,j] = -fl(fl(d d) / fl(a[i] b[j])),                              a = max(fl(1 - kth), EPS)
+//
+// Every operation is rounded once (no fused multiply-add), NaN passes through every max, the sum of a list has a fixed order:
+// the same inputs give the same bits, whatever the slab split.  No scratch, no float atomics, no hand-off between workgroups.
+#include "nr_common.h"
+#include "../../include/nr_hip.h"
+
+#define NR_LS_K_MAX 128                          // the longest list nr_topk.hip writes
+#define NR_LS_EPS 9.5367431640625e-07f           // 2^-20: the floor of a neighbourhood's distance scale
+
+// max(x, lo) that keeps a NaN x (fmaxf would return lo)
+__device__ __forceinline__ float nr_ls_floor(float x, float lo) { return x < lo ? lo : x; }
+
+// ---- statistics of the lists: one thread per line -----------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void nr_localscale_stats_kernel(const int32_t* __restrict__ idx, const float* __restrict__ val,
+                                                                 int n, int k, float* __restrict__ mean, float* __restrict__ kth) {
+    const int line = blockIdx.x * 256 + threadIdx.x;
+    if (line >= n) return;
+    const int32_t* li = idx + (long long)line * k;
+    const float* lv = val + (long long)line * k;
+    float sum = 0.f, last = 0.f;
+    int c = 0;
+    for (int e = 0; e < k; ++e) {
+        if (li[e] < 0) continue;                 // an absent slot
+        const float x = lv[e];
+        sum = c ? __fadd_rn(sum, x) : x;         // the sum starts from the first present value
+        last = x;
+        ++c;
+    }
+    const float none = __builtin_nanf("");
+    mean[line] = c ? __fdiv_rn(sum, (float)c) : none;
+    kth[line] = c ? last : none;
+}
+
+extern "C" int nr_localscale_stats(const int32_t* idx, const float* val, int n, int k, float* mean, float* kth, void* stream) {
+    if (!idx || !val || !mean || !kth) return NR_EINVAL;
+    if (n < 0 || k < 1 || k > NR_LS_K_MAX) return NR_EINVAL;
+    if (n == 0) return NR_OK;
+    hipLaunchKernelGGL(nr_localscale_stats_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, val,
+                       n, k, mean, kth);
+    NR_LAUNCH_CHECK();
+    return NR_OK;
+}
+
+// ---- apply: one read of S, one write of T -------------------------------------------------------------------------------------
+// r: the row's statistic for csls, its floored distance scale a[i] for nicdm / ls; c: the column's raw statistic.
+template <int MODE>
+__device__ __forceinline__ float nr_ls_score(float s, float r, float c) {
+    if (MODE == NR_LOCALSCALE_CSLS) return __fsub_rn(__fsub_rn(__fmul_rn(2.f, s), r), c);
+    const float d = nr_ls_floor(__fsub_rn(1.f, s), 0.f);
+    const float ab = __fmul_rn(r, nr_ls_floor(__fsub_rn(1.f, c), NR_LS_EPS));
+    if (MODE == NR_LOCALSCALE_NICDM) return -__fdiv_rn(d, __fsqrt_rn(ab));
+    return -__fdiv_rn(__fmul_rn(d, d), ab);
+}
+
+template <int MODE, int VEC>
+__global__ __launch_bounds__(256) void nr_localscale_apply_kernel(const float* __restrict__ S, int n, int L,
+                                                                 const float* __restrict__ row_stat,
+                                                                 const float* __restrict__ col_stat, float* __restrict__ T) {
+    const long long n_groups = (long long)n * L / VEC;
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += (long long)gridDim.x * 256) {
+        const long long e0 = g * VEC;
+        const int i = (int)(e0 / L);
+        const int j0 = (int)(e0 - (long long)i * L);         // VEC == 4: L % 4 == 0, the group lies in one row
+        float r = row_stat[i];
+        if (MODE != NR_LOCALSCALE_CSLS) r = nr_ls_floor(__fsub_rn(1.f, r), NR_LS_EPS);
+        if (VEC == 4) {
+            const f32x4_t x = *reinterpret_cast<const f32x4_t*>(S + e0);
+            const f32x4_t c = *reinterpret_cast<const f32x4_t*>(col_stat + j0);
+            f32x4_t t;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) t[q] = nr_ls_score<MODE>(x[q], r, c[q]);
+            *reinterpret_cast<f32x4_t*>(T + e0) = t;
+        } else {
+            T[e0] = nr_ls_score<MODE>(S[e0], r, col_stat[j0]);
+        }
+    }
+}
+
+template <int MODE>
+static int nr_localscale_apply_launch(const float* S, int n, int L, const float* row_stat, const float* col_stat, float* T,
+                                      void* stream) {
+    const bool vec = (L % 4 == 0) && ((uintptr_t)S % 16 == 0) && ((uintptr_t)T % 16 == 0) && ((uintptr_t)col_stat % 16 == 0);
+    const long long groups = (long long)n * L / (vec ? 4 : 1);
+    const unsigned blocks = (unsigned)std::min<long long>((groups + 255) / 256, 16384);
+    if (vec) {
+        hipLaunchKernelGGL((nr_localscale_apply_kernel<MODE, 4>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, n, L, row_stat,
+                           col_stat, T);
+    } else {
+        hipLaunchKernelGGL((nr_localscale_apply_kernel<MODE, 1>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, n, L, row_stat,
+                           col_stat, T);
+    }
+    NR_LAUNCH_CHECK();
+    return NR_OK;
+}
+
+extern "C" int nr_localscale_apply(const float* S, int n, int L, int mode, const float* row_stat, const float* col_stat, float* T,
+                                   void* stream) {
+    if (!S || !row_stat || !col_stat || !T) return NR_EINVAL;
+    if (n < 0 || L < 0) return NR_EINVAL;
+    if (mode != NR_LOCALSCALE_CSLS && mode != NR_LOCALSCALE_NICDM && mode != NR_LOCALSCALE_LS) return NR_EINVAL;
+    if (n == 0 || L == 0) return NR_OK;
+    if (mode == NR_LOCALSCALE_CSLS) return nr_localscale_apply_launch<NR_LOCALSCALE_CSLS>(S, n, L, row_stat, col_stat, T, stream);
+    if (mode == NR_LOCALSCALE_NICDM) return nr_localscale_apply_launch<NR_LOCALSCALE_NICDM>(S, n, L, row_stat, col_stat, T, stream);
+    return nr_localscale_apply_launch<NR_LOCALSCALE_LS>(S, n, L, row_stat, col_stat, T, stream);
+}

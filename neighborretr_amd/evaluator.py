@@ -623,3 +623,123 @@ def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, vide
     t2v["test_norm"] = _test_norm_entry(nt, mode, beta, qb_k, info, 0)
     v2t["test_norm"] = _test_norm_entry(nv, mode, beta, qb_k, info, 1)
     return t2v, v2t
+
+
+# ---- local scaling: CSLS, NICDM, LS (DESIGN.md "Local scaling") ---------------------------------------------------------------------
+# Every score is rescaled by statistics of its text's and its video's k-nearest neighbourhoods: a text's neighbourhood is its
+# top-k videos (a rank-local row list), a video's its top-k texts (the column lists, complete on every rank after the one
+# all-gather and merge of _column_lists).  ONE output T: its rows rank text->video, its columns video->text.  The lists hold the
+# exact bits of S and their sums have a fixed order, so T has the same bits whatever the world size.
+
+LOCAL_SCALING_MODES = ("csls", "nicdm", "ls")
+LOCAL_SCALING_LABELS = {"csls": "CSLS", "nicdm": "NICDM", "ls": "LS"}
+
+
+def local_scaling_label(mode, k, bank=False):
+    """The tag of the log lines of the locally scaled metrics: "[CSLS k=10]", with a querybank "[QB-NICDM k=10]"."""
+    return f"[{'QB-' if bank else ''}{LOCAL_SCALING_LABELS[mode]} k={int(k)}]"
+
+
+def _check_local_scaling(mode, k, hubness_k=0):
+    if mode not in LOCAL_SCALING_MODES:
+        raise ValueError(f"local_scaling mode must be one of {LOCAL_SCALING_MODES}, got {mode!r}")
+    if isinstance(k, bool) or int(k) != k:
+        raise ValueError(f"local_scaling k must be an integer in [1, 128], got {k!r}")
+    k = ops._check_k(k)
+    hubness_k = int(hubness_k or 0)
+    if hubness_k:
+        ops._check_k(hubness_k)
+    return k, hubness_k
+
+
+def _local_scaling_stats(S_slab, n_rows, n_cols, W, rank, mode, k, bank_slabs=None, n_bank_texts=None):
+    """(row_stat [rows of this rank], col_stat [n_cols]) of `mode`: the neighbourhood means (csls, nicdm) or k-th values (ls).
+    Rows from this rank's lists of S (bank: of Qv), columns from the merged lists of S over n_rows (bank: of Qt over the bank's
+    n_bank_texts rows); col_stat is the same bits on every rank."""
+    if bank_slabs is None:
+        ri, rv = _slab_row_lists(S_slab, k, n_cols)
+        ci, cv = _column_lists(S_slab, n_rows, n_cols, k, W, rank)
+    else:
+        Qt, Qv = bank_slabs
+        q0, q1 = slab_bounds(int(n_bank_texts), W, rank)
+        if Qt.shape[0] != q1 - q0 or Qt.shape[1] != n_cols or Qv.shape[0] != S_slab.shape[0]:
+            raise ValueError(f"bank slabs of rank {rank} must be [{q1 - q0}, {n_cols}] and [{S_slab.shape[0]}, bank videos], got "
+                             f"{tuple(Qt.shape)} and {tuple(Qv.shape)}")
+        ri, rv = _slab_row_lists(Qv, k, Qv.shape[1])
+        ci, cv = _column_lists(Qt, int(n_bank_texts), n_cols, k, W, rank)
+    which = 1 if mode == "ls" else 0
+    return ops.localscale_stats(ri, rv)[which], ops.localscale_stats(ci, cv)[which]
+
+
+def _local_scaled_from_slab(S_slab, n_rows, n_cols, W, rank, mode, k, bank_slabs=None, n_bank_texts=None):
+    """T_slab of this rank's slab S[r0:r1] (rows: texts / sentences, columns: videos).  bank_slabs = (Qt_slab, Qv_slab) as
+    _bank_slabs scores them and n_bank_texts = the bank's text count: the neighbourhoods are taken in the querybank."""
+    row_stat, col_stat = _local_scaling_stats(S_slab, n_rows, n_cols, W, rank, mode, k, bank_slabs, n_bank_texts)
+    return ops.localscale_apply(S_slab, mode, row_stat, col_stat)
+
+
+def _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk):
+    S_slab, n_rows, n_cols, W, rank, _ = slab
+    bank_slabs, n_bank_texts = None, None
+    if bank:
+        qb = _querybank(model, querybank, S_slab.device)
+        bank_slabs = _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, qb, W, rank, chunk)
+        n_bank_texts = qb[0].shape[0]
+    return _local_scaled_from_slab(S_slab, n_rows, n_cols, W, rank, mode, k, bank_slabs, n_bank_texts)
+
+
+def sharded_local_scaled_slab(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False, querybank=None,
+                              cut_off_points=None, chunk=256):
+    """-> T_slab fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the scores after local scaling
+    `mode` ("csls" | "nicdm" | "ls", DESIGN.md "Local scaling") with neighbourhoods of k items.  Rows rank text->video, columns
+    video->text.  bank: the neighbourhoods are taken in a querybank, (text_feat, text_mask, video_feat, video_mask), None: the
+    model's memory bank (load_memory_bank)."""
+    k, _ = _check_local_scaling(mode, k)
+    if bank:
+        _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    return _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk)
+
+
+def _local_scaling_entry(metrics, mode, k, bank):
+    metrics.update(mode=mode, k=k, bank=bool(bank))
+    return metrics
+
+
+def sharded_local_scaled_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False, querybank=None,
+                                 hubness_k=0, cut_off_points=None, chunk=256):
+    """(text->video, video->text) metric dictionaries of the locally scaled scores (sharded_local_scaled_slab), identical on
+    every rank, each with "mode", "k" and "bank" and, with hubness_k, a "hubness" entry (T's row lists / column lists)."""
+    k, hubness_k = _check_local_scaling(mode, k, hubness_k)
+    if bank:
+        _querybank(model, querybank, text_feat.device)
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    T = _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk)
+    _, n_rows, n_cols, W, rank, ends = slab
+    t2v, v2t = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k)
+    return _local_scaling_entry(t2v, mode, k, bank), _local_scaling_entry(v2t, mode, k, bank)
+
+
+def sharded_metrics_with_local_scaling(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False,
+                                       querybank=None, hubness_k=0, cut_off_points=None, chunk=256):
+    """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
+    each with one more entry "local_scaling" = sharded_local_scaled_metrics, from ONE scoring of this rank's slab."""
+    k, hubness_k = _check_local_scaling(mode, k, hubness_k)
+    if bank:
+        _querybank(model, querybank, text_feat.device)
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    S_slab, n_rows, n_cols, W, rank, ends = slab
+    if ends is None:
+        gt, et, gv, ev = _ranks_from_slab(S_slab, n_rows, W, rank)
+        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
+        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
+    else:
+        t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
+    if hubness_k:
+        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    T = _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk)
+    del S_slab, slab
+    nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k)
+    t2v["local_scaling"] = _local_scaling_entry(nt, mode, k, bank)
+    v2t["local_scaling"] = _local_scaling_entry(nv, mode, k, bank)
+    return t2v, v2t

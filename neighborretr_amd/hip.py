@@ -245,12 +245,15 @@ _SIGNATURES = {
     "nr_sinknorm_finish_cols": ([_I, _P, _I, _P, _P, _P], _I),
     "nr_sinknorm_apply": ([_P, _I, _I, _F, _P, _P, _P, _P], _I),
     "nr_sinknorm_row_err": ([_P, _I, _I, _F, _P, _P, _P, _P, _P], _I),
+    "nr_localscale_stats": ([_P, _P, _I, _I, _P, _P, _P], _I),
+    "nr_localscale_apply": ([_P, _I, _I, _I, _P, _P, _P, _P], _I),
     "nr_bertadam_plan": ([ctypes.POINTER(OptimTensor), _I, ctypes.POINTER(OptimGroup), _I, ctypes.POINTER(_I)], _I),
     "nr_bertadam_workspace_bytes": ([_I, _I], _Z),
     "nr_bertadam_step": ([_P, _I, _I, _P, _I, _F, _P, _P], _I),
 }
 TOPK_MAX = 128                               # largest k of the top-k entry points
 HUBNORM_IS, HUBNORM_DSL = 0, 1               # nr_hubnorm_apply modes
+LOCALSCALE_CSLS, LOCALSCALE_NICDM, LOCALSCALE_LS = 0, 1, 2      # nr_localscale_apply modes
 SCHEDULE_IDS = {"warmup_cosine": 0, "warmup_constant": 1, "warmup_linear": 2}      # NR_SCHEDULE_*
 
 

@@ -1130,6 +1130,39 @@ def sinknorm_row_err(S, beta, u, v, log_mu):
     return err
 
 
+LOCALSCALE_MODES = {"csls": hip.LOCALSCALE_CSLS, "nicdm": hip.LOCALSCALE_NICDM, "ls": hip.LOCALSCALE_LS}
+
+
+def localscale_stats(idx, val):
+    """(mean, kth) [n] fp32 of the top-k lists idx [n, k] int32 / val [n, k] fp32 (nr_localscale_stats): the mean of a list's
+    present values (idx >= 0), summed one by one in list order, and the last of them; NaN for a list with none."""
+    if idx.dim() != 2 or idx.shape != val.shape or idx.dtype != torch.int32 or val.dtype != torch.float32:
+        raise ValueError("idx (int32) and val (fp32) must both be [n, k]")
+    n, k = idx.shape
+    k = _check_k(k)
+    idx, val = idx.contiguous(), val.contiguous()
+    mean = torch.empty((n,), dtype=torch.float32, device=idx.device)
+    kth = torch.empty((n,), dtype=torch.float32, device=idx.device)
+    if n:
+        hip.call("nr_localscale_stats", hip.ptr(idx), hip.ptr(val), n, k, hip.ptr(mean), hip.ptr(kth), hip.stream_ptr())
+    return mean, kth
+
+
+def localscale_apply(S, mode, row_stat, col_stat):
+    """T [n, L] fp32 from one read of S [n, L] (nr_localscale_apply); mode "csls" | "nicdm" | "ls".  row_stat [n] / col_stat [L]:
+    the neighbourhood means (csls, nicdm) or k-th values (ls) of localscale_stats.  S may be a view whose rows lie back to back
+    (a slice of a flat buffer): it is not copied, a misaligned one takes the kernel's scalar path."""
+    if mode not in LOCALSCALE_MODES:
+        raise ValueError(f"mode must be one of {sorted(LOCALSCALE_MODES)}, got {mode!r}")
+    S = _slab_2d(S)
+    n, L = S.shape
+    T = torch.empty_like(S)
+    if n and L:
+        hip.call("nr_localscale_apply", hip.ptr(S), n, L, LOCALSCALE_MODES[mode], hip.ptr(_sink_vec(row_stat, n, "row_stat")),
+                 hip.ptr(_sink_vec(col_stat, L, "col_stat")), hip.ptr(T), hip.stream_ptr())
+    return T
+
+
 def linear_x3(x, w, bias=None, residual=None):
     """Y = X W^T (+ bias) (+ residual) on the split-bf16 MFMA tile engine (nr_linear_x3): x [M,K], w [N,K] fp32, K padded to
     a multiple of 64 with zeros.  ~fp32-grade products (3 bf16 passes); used for the clustering GEMMs and for the

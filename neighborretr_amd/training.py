@@ -162,8 +162,12 @@ def eval_epoch(args, model, test_dataloader, device):
     from .evaluator import (BANK_MODES, _check_n_iter, _check_test_norm, _querybank, dataset_order, gather_eval_features, sharded_metrics,
                             sharded_metrics_with_hubness, sharded_metrics_with_test_norm, sharded_multi_sentence_metrics,
                             test_norm_label)
+    from .evaluator import _check_local_scaling, local_scaling_label, sharded_metrics_with_local_scaling
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
     test_norm = getattr(args, "test_norm", None) or "none"
+    local_scaling = getattr(args, "local_scaling", None) or "none"
+    if local_scaling != "none" and test_norm != "none":
+        raise ValueError("local_scaling and test_norm are separate corrections: choose one of them")
     logger = getattr(args, "logger", None)
     tracker = RetrievalMetrics(logger=logger)
     model = _unwrap(model).to(device)
@@ -173,6 +177,12 @@ def eval_epoch(args, model, test_dataloader, device):
             _querybank(model, None, device)
         norm = dict(mode=test_norm, beta=beta, qb_k=qb_k, hubness_k=hubness_k,
                     n_iter=_check_n_iter(getattr(args, "test_norm_iters", 50)))
+    if local_scaling != "none":      # local scaling (DESIGN.md "Local scaling"): checked before any work
+        ls_bank = bool(int(getattr(args, "local_scaling_bank", 0) or 0))
+        ls_k, _ = _check_local_scaling(local_scaling, getattr(args, "local_scaling_k", 10), hubness_k)
+        if ls_bank:
+            _querybank(model, None, device)
+        scaling = dict(mode=local_scaling, k=ls_k, bank=ls_bank, hubness_k=hubness_k)
     dataset = getattr(test_dataloader, "dataset", None)
     multi = bool(getattr(dataset, "multi_sentence_per_video", False))
     model.eval()
@@ -189,6 +199,9 @@ def eval_epoch(args, model, test_dataloader, device):
             if test_norm != "none":
                 t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args,
                                                           cut_off_points=cut_off_points, **norm)
+            elif local_scaling != "none":
+                t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args,
+                                                              cut_off_points=cut_off_points, **scaling)
             elif hubness_k:
                 t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, cut_off_points)
             else:
@@ -202,6 +215,8 @@ def eval_epoch(args, model, test_dataloader, device):
             toc1 = time.time()
             if test_norm != "none":
                 t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args, **norm)
+            elif local_scaling != "none":
+                t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args, **scaling)
             elif hubness_k:
                 t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k)
             else:
@@ -228,6 +243,13 @@ def eval_epoch(args, model, test_dataloader, device):
             if hubness_k:
                 tracker.log_hubness(t2v["test_norm"]["hubness"], prefix=f"Text-to-Video {tag} ")
                 tracker.log_hubness(v2t["test_norm"]["hubness"], prefix=f"Video-to-Text {tag} ")
+        if local_scaling != "none":
+            tag = local_scaling_label(local_scaling, ls_k, ls_bank)
+            tracker.print_metrics(t2v["local_scaling"], prefix=f"Text-to-Video {tag}: ")
+            tracker.print_metrics(v2t["local_scaling"], prefix=f"Video-to-Text {tag}: ")
+            if hubness_k:
+                tracker.log_hubness(t2v["local_scaling"]["hubness"], prefix=f"Text-to-Video {tag} ")
+                tracker.log_hubness(v2t["local_scaling"]["hubness"], prefix=f"Video-to-Text {tag} ")
     return t2v, v2t
 
 
