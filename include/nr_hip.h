@@ -840,6 +840,45 @@ int nr_localscale_stats(const int32_t* idx, const float* val, int n, int k, floa
 int nr_localscale_apply(const float* S, int n, int L, int mode, const float* row_stat, const float* col_stat, float* T,
                         void* stream);
 
+/* Mutual proximity (emp, gauss; DESIGN.md "Mutual proximity"; Schnitzer et al., JMLR 2012; the reference has no code for it): every
+ * score s = S[i,j] of S [n, L] becomes the probability that it beats the scores of its row's reference line and of its column's
+ * reference line, in the independent form MP_I = P_row P_col.  A line X has c(X) = #{x in X : x is not NaN} entries.
+ *   emp:   r2(s, X) = 2 #{x in X : x < s} + #{x in X : x == s}   (IEEE compares: NaN is neither, -0 == +0)
+ *          p = fl(fl(r2) / fl(2 c))   (c = 0: 0 / 0 = NaN);   T[i,j] = fl(p_row p_col);   a NaN s gives a NaN T.
+ *          Counts are exact integers: a line must hold fewer than 2^23 entries (2 c < 2^24), a longer one is NR_EINVAL.
+ *   gauss: mean and population sd (divide by c) of every line over its non-NaN entries, accumulated in fp64 in two passes and a fixed
+ *          order, delivered as fp32; c = 0: both NaN; c = 1: sd = 0; infinities follow IEEE (sd NaN).  EPS = 2^-20, max(x, .) keeps
+ *          a NaN x, every operation rounded once (no fused multiply-add):
+ *          z = fl(fl(s - mean) / max(sd, EPS));   Q(z) = fl(0.5 erfcf(fl(z fl(1 / sqrt 2))))   (the line's upper tail at s)
+ *          T[i,j] = -fl(fl(Q_r + Q_c) - fl(Q_r Q_c))   (= MP_I - 1: the same ranking, full relative precision at the top)
+ * No scratch, no float atomics, no hand-off between workgroups; the same inputs give the same bits.  A null pointer, a negative extent,
+ * `accumulate` outside {0, 1} or a line too long for exact counts: NR_EINVAL before any launch; nothing to do: NR_OK, no launch.
+ *   nr_mp_row_counts: r2[i,j] = r2(S[i,j], R[i,:]), R [n, Lr].  One wave per (row, 1024 columns), 16 scores per lane; the reference
+ *     row is staged through LDS 1024 floats at a time and read as a broadcast.
+ *   nr_mp_col_counts: c2[i,j] (+)= r2(S[i,j], Q[:,j]), Q [m, L]; accumulate 0 overwrites, 1 adds to what is there (the host feeds
+ *     the reference rows in blocks; integers: any blocking gives the same result).  Lanes own consecutive columns, a wave 16 rows.
+ *     Q may be null when m = 0.
+ *   nr_mp_line_counts: row_cnt[i] = c(R[i,:]) and / or col_cnt[j] = c(Q[:,j]) of this slab of Q (either output may be null, not
+ *     both; the input of a null output is not read).
+ *   nr_mp_emp_apply: one read of S, r2, c2, one write of T.  16-byte accesses when L % 4 == 0 and S, r2, c2, col_cnt, T are
+ *     16-byte aligned, a scalar path otherwise.
+ *   nr_mp_row_moments: mean [n], sd [n] of the rows of R [n, Lr], one wave per row.
+ *   nr_mp_col_moments: parts [3, L] fp64 = (count, mean, M2) of the columns of this slab Q [m, L] (count 0: mean = M2 = 0).
+ *   nr_mp_moments_combine: P triples per column, parts [P, 3, L], merged by Chan's update in index order -> mean [L], sd [L]
+ *     (every rank combines the same bits in rank order).
+ *   nr_mp_gauss_apply: one read of S, one write of T; the alignment rule of nr_mp_emp_apply over S, col_mean, col_sd, T. */
+int nr_mp_row_counts(const float* S, int n, int L, const float* R, int Lr, int32_t* r2, void* stream);
+int nr_mp_col_counts(const float* S, int n, int L, const float* Q, int m, int32_t* c2, int accumulate, void* stream);
+int nr_mp_line_counts(const float* R, int n, int Lr, int32_t* row_cnt, const float* Q, int m, int L, int32_t* col_cnt,
+                      void* stream);
+int nr_mp_emp_apply(const float* S, int n, int L, const int32_t* r2, const int32_t* c2, const int32_t* row_cnt,
+                    const int32_t* col_cnt, float* T, void* stream);
+int nr_mp_row_moments(const float* R, int n, int Lr, float* mean, float* sd, void* stream);
+int nr_mp_col_moments(const float* Q, int m, int L, double* parts, void* stream);
+int nr_mp_moments_combine(int P, const double* parts, int L, float* mean, float* sd, void* stream);
+int nr_mp_gauss_apply(const float* S, int n, int L, const float* row_mean, const float* row_sd, const float* col_mean,
+                      const float* col_sd, float* T, void* stream);
+
 /* Multi-tensor BertAdam step (models/optimization.py:76-211 with the trainer's clip and clamp around it, trainer.py:104-119;
  * DESIGN.md "BertAdam in the captured step").  fp32 tensors only.  Per step, for every table entry t with group q:
  *   c    = min(1, global_max_norm / (sqrt(sum_t ||g_t||^2) + 1e-6))             (global_max_norm <= 0: c = 1)

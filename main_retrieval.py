@@ -110,6 +110,14 @@ def get_args():
     p.add_argument("--local_scaling_bank", type=int, default=0, choices=[0, 1],
                    help="--local_scaling: 1 takes the neighbourhoods in the memory bank (the querybank of --test_norm qbnorm) "
                         "instead of the test set")
+    p.add_argument("--mutual_proximity", default="none", choices=["none", "emp", "gauss"],
+                   help="mutual-proximity hubness reduction, reported next to the raw metrics: every score replaced by the "
+                        "probability that it beats the scores of its text's line and of its video's line -- emp (the empirical "
+                        "ranks, ties counted half), gauss (a normal fitted to each line; DESIGN.md); no temperature, no k; none = "
+                        "off.  Not together with --test_norm or --local_scaling")
+    p.add_argument("--mutual_proximity_bank", type=int, default=0, choices=[0, 1],
+                   help="--mutual_proximity: 1 takes the lines in the memory bank (the querybank of --test_norm qbnorm) instead of "
+                        "the test set")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -125,6 +133,10 @@ def get_args():
         p.error("--test_norm_iters must be >= 1")
     if args.local_scaling != "none" and args.test_norm != "none":
         p.error("--local_scaling and --test_norm are separate corrections: choose one of them")
+    if args.mutual_proximity != "none" and args.test_norm != "none":
+        p.error("--mutual_proximity and --test_norm are separate corrections: choose one of them")
+    if args.mutual_proximity != "none" and args.local_scaling != "none":
+        p.error("--mutual_proximity and --local_scaling are separate corrections: choose one of them")
     if not 1 <= args.local_scaling_k <= 128:
         p.error("--local_scaling_k must lie in [1, 128]")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
@@ -513,9 +525,11 @@ def eval_epoch(args, model, test):
     from neighborretr_amd.evaluator import (gather_eval_features, rank_sample_indices, sharded_metrics, sharded_metrics_with_hubness,
                                             sharded_metrics_with_test_norm, test_norm_label)
     from neighborretr_amd.evaluator import local_scaling_label, sharded_metrics_with_local_scaling
+    from neighborretr_amd.evaluator import mutual_proximity_label, sharded_metrics_with_mutual_proximity
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
     test_norm = getattr(args, "test_norm", None) or "none"
     local_scaling = getattr(args, "local_scaling", None) or "none"
+    mutual_proximity = getattr(args, "mutual_proximity", None) or "none"
     model.eval()
     dev = args.device
     mine = rank_sample_indices(test.n, args.world_size, args.rank)     # equal counts on every rank (padded like DistributedSampler)
@@ -533,6 +547,9 @@ def eval_epoch(args, model, test):
         t2v, v2t = sharded_metrics_with_local_scaling(model, t, v, tm.float(), vm.float(), args, local_scaling,
                                                       k=args.local_scaling_k, bank=bool(args.local_scaling_bank),
                                                       hubness_k=hubness_k)
+    elif mutual_proximity != "none":
+        t2v, v2t = sharded_metrics_with_mutual_proximity(model, t, v, tm.float(), vm.float(), args, mutual_proximity,
+                                                         bank=bool(args.mutual_proximity_bank), hubness_k=hubness_k)
     elif hubness_k:
         t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k)
     else:
@@ -558,6 +575,15 @@ def eval_epoch(args, model, test):
         from neighborretr_amd.metrics import RetrievalMetrics
         nt, nv = t2v["local_scaling"], v2t["local_scaling"]
         tag = local_scaling_label(local_scaling, nt["k"], nt["bank"])
+        log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
+                  f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
+        if hubness_k:
+            log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
+            log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
+    if mutual_proximity != "none":
+        from neighborretr_amd.metrics import RetrievalMetrics
+        nt, nv = t2v["mutual_proximity"], v2t["mutual_proximity"]
+        tag = mutual_proximity_label(mutual_proximity, nt["bank"])
         log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
         if hubness_k:
@@ -608,7 +634,8 @@ def main():
                 torch.save(model.state_dict(), os.path.join(args.output_dir, f"pytorch_model.bin.{epoch}"))
             clear_memory_bank(model)
     elif args.do_eval:
-        with_bank = args.test_norm in ("qbnorm", "qbsinkhorn") or (args.local_scaling != "none" and args.local_scaling_bank)
+        with_bank = args.test_norm in ("qbnorm", "qbsinkhorn") or (args.local_scaling != "none" and args.local_scaling_bank) \
+            or (args.mutual_proximity != "none" and args.mutual_proximity_bank)
         if with_bank:                                       # the querybank: the memory bank of the training set
             load_memory_bank(args, model, train)
         eval_epoch(args, model, test)

@@ -743,3 +743,164 @@ def sharded_metrics_with_local_scaling(model, text_feat, video_feat, text_mask, 
     t2v["local_scaling"] = _local_scaling_entry(nt, mode, k, bank)
     v2t["local_scaling"] = _local_scaling_entry(nv, mode, k, bank)
     return t2v, v2t
+
+
+# ---- mutual proximity: emp, gauss (DESIGN.md "Mutual proximity") ---------------------------------------------------------------------
+# Every score becomes the probability that it beats its row's line and its column's line (the independent form P_row P_col).  A
+# row's line is rank-local (S_slab, or Qv_slab with a querybank).  A column's line spans the ranks: every rank needs every rank's
+# rows of the column source (S, or Qt over the bank's rows), gathered in blocks of MP_GATHER_ROWS rows per rank and fed to the
+# accumulating count kernel (emp), or one all-gather of the ranks' [3, L] fp64 (count, mean, M2) triples (gauss).  ONE output T:
+# its rows rank text->video, its columns video->text.  emp is integer counts and two divisions: the same bits whatever the split.
+
+MUTUAL_PROXIMITY_MODES = ("emp", "gauss")
+MP_GATHER_ROWS = 256            # B: rows per rank and collective of the column source; the gather buffer is W B L floats
+
+
+def mutual_proximity_label(mode, bank=False):
+    """The tag of the log lines of the mutual-proximity metrics: "[MP-emp]", with a querybank "[QB-MP-gauss]"."""
+    if mode not in MUTUAL_PROXIMITY_MODES:
+        raise ValueError(f"mutual_proximity mode must be one of {MUTUAL_PROXIMITY_MODES}, got {mode!r}")
+    return f"[{'QB-' if bank else ''}MP-{mode}]"
+
+
+def _check_mutual_proximity(mode, hubness_k=0):
+    if mode not in MUTUAL_PROXIMITY_MODES:
+        raise ValueError(f"mutual_proximity mode must be one of {MUTUAL_PROXIMITY_MODES}, got {mode!r}")
+    hubness_k = int(hubness_k or 0)
+    if hubness_k:
+        ops._check_k(hubness_k)
+    return hubness_k
+
+
+def _mp_column_counts(S_slab, src_slab, n_src, W, rank):
+    """(c2 [rows of this rank, L], col_cnt [L]) int32: the doubled rank of every score of S_slab in its column of the source
+    (src_slab: this rank's rows slab_bounds(n_src, W, rank) of it) over EVERY rank's rows, and the columns' non-NaN counts.
+    ceil(ceil(n_src / W) / B) all-gathers of B rows per rank and one int32 all-reduce; W = 1: no collective."""
+    dev = S_slab.device
+    L = S_slab.shape[1]
+    mine = src_slab.shape[0]
+    _, col_cnt = ops.mp_line_counts(Q=src_slab)
+    if W == 1:
+        return ops.mp_col_counts(S_slab, src_slab), col_cnt
+    comm.all_reduce(col_cnt)
+    B = MP_GATHER_ROWS
+    c2 = torch.zeros(tuple(S_slab.shape), dtype=torch.int32, device=dev)
+    block = torch.empty((B, L), dtype=torch.float32, device=dev)
+    allb = torch.empty((W, B, L), dtype=torch.float32, device=dev)
+    for b0 in range(0, -(-n_src // W), B):
+        have = max(0, min(B, mine - b0))
+        if have:
+            block[:have] = src_slab[b0:b0 + have]
+        if have < B:
+            block[have:].fill_(float("nan"))                          # the padding of a short block (never counted: see below)
+        comm.all_gather_into_tensor(allb.view(-1), block.view(-1))
+        for r in range(W):                                            # only the rows rank r really holds
+            q0, q1 = slab_bounds(n_src, W, r)
+            real = max(0, min(B, (q1 - q0) - b0))
+            if real:
+                ops.mp_col_counts(S_slab, allb[r, :real], out=c2)
+    return c2, col_cnt
+
+
+def _mp_column_moments(src_slab, W):
+    """(mean, sd) [L] fp32 of the columns of the source over every rank's rows: this rank's (count, mean, M2) triples, one
+    all-gather, Chan's update in rank order (the same bits on every rank)."""
+    parts = ops.mp_col_moments(src_slab)
+    if W > 1:
+        allp = torch.empty((W,) + tuple(parts.shape), dtype=torch.float64, device=parts.device)
+        comm.all_gather_into_tensor(allp.view(-1), parts.view(-1))
+    else:
+        allp = parts[None]
+    return ops.mp_moments_combine(allp)
+
+
+def _mutual_proximity_from_slab(S_slab, n_rows, n_cols, W, rank, mode, bank_slabs=None, n_bank_texts=None):
+    """T_slab of this rank's slab S[r0:r1] (rows: texts / sentences, columns: videos).  bank_slabs = (Qt_slab, Qv_slab) as
+    _bank_slabs scores them and n_bank_texts = the bank's text count: the reference lines are taken in the querybank."""
+    S_slab = ops._slab_2d(S_slab)
+    if bank_slabs is None:
+        row_src, col_src, n_src = S_slab, S_slab, n_rows
+    else:
+        Qt, Qv = bank_slabs
+        q0, q1 = slab_bounds(int(n_bank_texts), W, rank)
+        if Qt.shape[0] != q1 - q0 or Qt.shape[1] != n_cols or Qv.shape[0] != S_slab.shape[0]:
+            raise ValueError(f"bank slabs of rank {rank} must be [{q1 - q0}, {n_cols}] and [{S_slab.shape[0]}, bank videos], got "
+                             f"{tuple(Qt.shape)} and {tuple(Qv.shape)}")
+        row_src, col_src, n_src = ops._slab_2d(Qv), ops._slab_2d(Qt), int(n_bank_texts)
+    if max(n_src, row_src.shape[1]) >= ops.hip.MP_LINE_MAX:
+        raise ValueError(f"mutual proximity: a reference line of {max(n_src, row_src.shape[1])} entries is too long for exact counts")
+    if mode == "emp":
+        row_cnt, _ = ops.mp_line_counts(R=row_src)
+        r2 = ops.mp_row_counts(S_slab, row_src)
+        c2, col_cnt = _mp_column_counts(S_slab, col_src, n_src, W, rank)
+        return ops.mp_emp_apply(S_slab, r2, c2, row_cnt, col_cnt)
+    row_mean, row_sd = ops.mp_row_moments(row_src)
+    col_mean, col_sd = _mp_column_moments(col_src, W)
+    return ops.mp_gauss_apply(S_slab, row_mean, row_sd, col_mean, col_sd)
+
+
+def _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk):
+    S_slab, n_rows, n_cols, W, rank, _ = slab
+    bank_slabs, n_bank_texts = None, None
+    if bank:
+        qb = _querybank(model, querybank, S_slab.device)
+        bank_slabs = _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, qb, W, rank, chunk)
+        n_bank_texts = qb[0].shape[0]
+    return _mutual_proximity_from_slab(S_slab, n_rows, n_cols, W, rank, mode, bank_slabs, n_bank_texts)
+
+
+def sharded_mutual_proximity_slab(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False, querybank=None,
+                                  cut_off_points=None, chunk=256):
+    """-> T_slab fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the scores after mutual proximity
+    `mode` ("emp" | "gauss", DESIGN.md "Mutual proximity").  Rows rank text->video, columns video->text.  bank: the reference
+    lines are taken in a querybank, (text_feat, text_mask, video_feat, video_mask), None: the model's memory bank
+    (load_memory_bank)."""
+    _check_mutual_proximity(mode)
+    if bank:
+        _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    return _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk)
+
+
+def _mutual_proximity_entry(metrics, mode, bank):
+    metrics.update(mode=mode, bank=bool(bank))
+    return metrics
+
+
+def sharded_mutual_proximity_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False, querybank=None,
+                                     hubness_k=0, cut_off_points=None, chunk=256):
+    """(text->video, video->text) metric dictionaries of the mutual-proximity scores (sharded_mutual_proximity_slab), identical on
+    every rank, each with "mode" and "bank" and, with hubness_k, a "hubness" entry (T's row lists / column lists)."""
+    hubness_k = _check_mutual_proximity(mode, hubness_k)
+    if bank:
+        _querybank(model, querybank, text_feat.device)
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    T = _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk)
+    _, n_rows, n_cols, W, rank, ends = slab
+    t2v, v2t = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k)
+    return _mutual_proximity_entry(t2v, mode, bank), _mutual_proximity_entry(v2t, mode, bank)
+
+
+def sharded_metrics_with_mutual_proximity(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False,
+                                          querybank=None, hubness_k=0, cut_off_points=None, chunk=256):
+    """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
+    each with one more entry "mutual_proximity" = sharded_mutual_proximity_metrics, from ONE scoring of this rank's slab."""
+    hubness_k = _check_mutual_proximity(mode, hubness_k)
+    if bank:
+        _querybank(model, querybank, text_feat.device)
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    S_slab, n_rows, n_cols, W, rank, ends = slab
+    if ends is None:
+        gt, et, gv, ev = _ranks_from_slab(S_slab, n_rows, W, rank)
+        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
+        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
+    else:
+        t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
+    if hubness_k:
+        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    T = _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk)
+    del S_slab, slab
+    nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k)
+    t2v["mutual_proximity"] = _mutual_proximity_entry(nt, mode, bank)
+    v2t["mutual_proximity"] = _mutual_proximity_entry(nv, mode, bank)
+    return t2v, v2t

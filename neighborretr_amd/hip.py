@@ -247,6 +247,14 @@ _SIGNATURES = {
     "nr_sinknorm_row_err": ([_P, _I, _I, _F, _P, _P, _P, _P, _P], _I),
     "nr_localscale_stats": ([_P, _P, _I, _I, _P, _P, _P], _I),
     "nr_localscale_apply": ([_P, _I, _I, _I, _P, _P, _P, _P], _I),
+    "nr_mp_row_counts": ([_P, _I, _I, _P, _I, _P, _P], _I),
+    "nr_mp_col_counts": ([_P, _I, _I, _P, _I, _P, _I, _P], _I),
+    "nr_mp_line_counts": ([_P, _I, _I, _P, _P, _I, _I, _P, _P], _I),
+    "nr_mp_emp_apply": ([_P, _I, _I, _P, _P, _P, _P, _P, _P], _I),
+    "nr_mp_row_moments": ([_P, _I, _I, _P, _P, _P], _I),
+    "nr_mp_col_moments": ([_P, _I, _I, _P, _P], _I),
+    "nr_mp_moments_combine": ([_I, _P, _I, _P, _P, _P], _I),
+    "nr_mp_gauss_apply": ([_P, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "nr_bertadam_plan": ([ctypes.POINTER(OptimTensor), _I, ctypes.POINTER(OptimGroup), _I, ctypes.POINTER(_I)], _I),
     "nr_bertadam_workspace_bytes": ([_I, _I], _Z),
     "nr_bertadam_step": ([_P, _I, _I, _P, _I, _F, _P, _P], _I),
@@ -254,6 +262,7 @@ _SIGNATURES = {
 TOPK_MAX = 128                               # largest k of the top-k entry points
 HUBNORM_IS, HUBNORM_DSL = 0, 1               # nr_hubnorm_apply modes
 LOCALSCALE_CSLS, LOCALSCALE_NICDM, LOCALSCALE_LS = 0, 1, 2      # nr_localscale_apply modes
+MP_LINE_MAX = 1 << 23                        # a mutual-proximity reference line must be shorter: 2 c < 2^24 keeps the counts exact
 SCHEDULE_IDS = {"warmup_cosine": 0, "warmup_constant": 1, "warmup_linear": 2}      # NR_SCHEDULE_*
 
 

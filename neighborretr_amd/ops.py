@@ -1163,6 +1163,144 @@ def localscale_apply(S, mode, row_stat, col_stat):
     return T
 
 
+def _mp_matrix(x, dtype, shape, what):
+    if x.dtype != dtype or x.dim() != 2 or not x.is_contiguous() or (shape is not None and tuple(x.shape) != tuple(shape)):
+        want = "2-D" if shape is None else f"{tuple(shape)}"
+        raise ValueError(f"{what} must be a contiguous {dtype} matrix, {want}, got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def _mp_vec(x, dtype, size, what):
+    if x.dtype != dtype or x.shape != (size,) or not x.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} vector of {size} entries, got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def _mp_line(length, what):
+    if length >= hip.MP_LINE_MAX:
+        raise ValueError(f"{what}: a reference line of {length} entries is too long for exact counts (at most {hip.MP_LINE_MAX - 1})")
+
+
+def mp_row_counts(S, R):
+    """r2 [n, L] int32: r2[i, j] = 2 #{x in R[i, :] : x < S[i, j]} + #{x == S[i, j]} (nr_mp_row_counts); S [n, L], R [n, Lr] fp32.
+    NaN entries count nothing, a NaN score counts 0."""
+    S = _slab_2d(S)
+    n, L = S.shape
+    R = _mp_matrix(R, torch.float32, None, "R")
+    if R.shape[0] != n:
+        raise ValueError(f"R must have the {n} rows of S, got {tuple(R.shape)}")
+    _mp_line(R.shape[1], "mp_row_counts")
+    r2 = torch.empty((n, L), dtype=torch.int32, device=S.device)
+    if n and L:
+        hip.call("nr_mp_row_counts", hip.ptr(S), n, L, hip.ptr(R), R.shape[1], hip.ptr(r2), hip.stream_ptr())
+    return r2
+
+
+def mp_col_counts(S, Q, out=None):
+    """c2 [n, L] int32: c2[i, j] = 2 #{x in Q[:, j] : x < S[i, j]} + #{x == S[i, j]} (nr_mp_col_counts); S [n, L], Q [m, L] fp32.
+    out: the counts of earlier blocks of reference rows, added to in place and returned (integers: any blocking of the rows gives
+    the same result)."""
+    S = _slab_2d(S)
+    n, L = S.shape
+    Q = _mp_matrix(Q, torch.float32, None, "Q")
+    if Q.shape[1] != L:
+        raise ValueError(f"Q must have the {L} columns of S, got {tuple(Q.shape)}")
+    m = Q.shape[0]
+    _mp_line(m, "mp_col_counts")
+    c2 = torch.empty((n, L), dtype=torch.int32, device=S.device) if out is None else _mp_matrix(out, torch.int32, (n, L), "out")
+    if n and L and (m or out is None):
+        hip.call("nr_mp_col_counts", hip.ptr(S), n, L, hip.ptr(Q) if m else None, m, hip.ptr(c2), 0 if out is None else 1,
+                 hip.stream_ptr())
+    return c2
+
+
+def mp_line_counts(R=None, Q=None):
+    """(row_cnt [n] of R [n, Lr], col_cnt [L] of Q [m, L]) int32: the non-NaN entries of every row of R and of every column of
+    this slab of Q (nr_mp_line_counts); None for an input not given."""
+    if R is None and Q is None:
+        raise ValueError("nothing to count")
+    row_cnt = col_cnt = None
+    n = Lr = m = L = 0
+    if R is not None:
+        R = _mp_matrix(R, torch.float32, None, "R")
+        n, Lr = R.shape
+        row_cnt = torch.zeros((n,), dtype=torch.int32, device=R.device)
+    if Q is not None:
+        Q = _mp_matrix(Q, torch.float32, None, "Q")
+        m, L = Q.shape
+        col_cnt = torch.zeros((L,), dtype=torch.int32, device=Q.device)
+    p = lambda x, live: hip.ptr(x) if (x is not None and live) else None             # noqa: E731
+    rows, cols = bool(n and Lr), bool(m and L)
+    if rows or cols:
+        hip.call("nr_mp_line_counts", p(R, rows), n if rows else 0, Lr, p(row_cnt, rows), p(Q, cols), m, L if cols else 0,
+                 p(col_cnt, cols), hip.stream_ptr())
+    return row_cnt, col_cnt
+
+
+def mp_emp_apply(S, r2, c2, row_cnt, col_cnt):
+    """T [n, L] fp32 = fl(fl(r2 / 2 row_cnt[i]) fl(c2 / 2 col_cnt[j])), NaN where S is (nr_mp_emp_apply).  r2, c2 [n, L] int32 as
+    mp_row_counts / mp_col_counts give them, row_cnt [n], col_cnt [L] int32 the lines' non-NaN counts.  S may be a view whose rows
+    lie back to back (a slice of a flat buffer): it is not copied, a misaligned one takes the kernel's scalar path."""
+    S = _slab_2d(S)
+    n, L = S.shape
+    r2, c2 = _mp_matrix(r2, torch.int32, (n, L), "r2"), _mp_matrix(c2, torch.int32, (n, L), "c2")
+    row_cnt, col_cnt = _mp_vec(row_cnt, torch.int32, n, "row_cnt"), _mp_vec(col_cnt, torch.int32, L, "col_cnt")
+    T = torch.empty_like(S)
+    if n and L:
+        hip.call("nr_mp_emp_apply", hip.ptr(S), n, L, hip.ptr(r2), hip.ptr(c2), hip.ptr(row_cnt), hip.ptr(col_cnt), hip.ptr(T),
+                 hip.stream_ptr())
+    return T
+
+
+def mp_row_moments(R):
+    """(mean, sd) [n] fp32 of the rows of R [n, Lr] over their non-NaN entries (nr_mp_row_moments): fp64 accumulation, population
+    standard deviation; NaN for a row with no entry."""
+    R = _mp_matrix(_f32(R), torch.float32, None, "R")
+    n, Lr = R.shape
+    mean = torch.empty((n,), dtype=torch.float32, device=R.device)
+    sd = torch.empty((n,), dtype=torch.float32, device=R.device)
+    if n:
+        hip.call("nr_mp_row_moments", hip.ptr(R) if Lr else None, n, Lr, hip.ptr(mean), hip.ptr(sd), hip.stream_ptr())
+    return mean, sd
+
+
+def mp_col_moments(Q):
+    """parts [3, L] fp64 = (count, mean, M2) of the columns of this slab Q [m, L] over their non-NaN entries (nr_mp_col_moments):
+    what a rank contributes to the cross-rank gather, merged by mp_moments_combine."""
+    Q = _mp_matrix(_f32(Q), torch.float32, None, "Q")
+    m, L = Q.shape
+    parts = torch.zeros((3, L), dtype=torch.float64, device=Q.device)
+    if m and L:
+        hip.call("nr_mp_col_moments", hip.ptr(Q), m, L, hip.ptr(parts), hip.stream_ptr())
+    return parts
+
+
+def mp_moments_combine(parts):
+    """parts [P, 3, L] fp64 -> (mean, sd) [L] fp32, merged by Chan's update in index order (nr_mp_moments_combine); NaN for a
+    column with no entry in any part."""
+    if parts.dtype != torch.float64 or parts.dim() != 3 or parts.shape[1] != 3 or not parts.is_contiguous():
+        raise ValueError("parts must be a contiguous fp64 [P, 3, L]")
+    P, _, L = parts.shape
+    mean = torch.empty((L,), dtype=torch.float32, device=parts.device)
+    sd = torch.empty((L,), dtype=torch.float32, device=parts.device)
+    if L:
+        hip.call("nr_mp_moments_combine", P, hip.ptr(parts) if P else None, L, hip.ptr(mean), hip.ptr(sd), hip.stream_ptr())
+    return mean, sd
+
+
+def mp_gauss_apply(S, row_mean, row_sd, col_mean, col_sd):
+    """T [n, L] fp32 = -(Q_r + Q_c - Q_r Q_c), Q the upper tail 0.5 erfc(z / sqrt 2) of the row's / the column's normal at S[i, j]
+    (nr_mp_gauss_apply).  S may be a row-contiguous view, as for mp_emp_apply."""
+    S = _slab_2d(S)
+    n, L = S.shape
+    T = torch.empty_like(S)
+    vecs = (_sink_vec(row_mean, n, "row_mean"), _sink_vec(row_sd, n, "row_sd"), _sink_vec(col_mean, L, "col_mean"),
+            _sink_vec(col_sd, L, "col_sd"))
+    if n and L:
+        hip.call("nr_mp_gauss_apply", hip.ptr(S), n, L, *(hip.ptr(x) for x in vecs), hip.ptr(T), hip.stream_ptr())
+    return T
+
+
 def linear_x3(x, w, bias=None, residual=None):
     """Y = X W^T (+ bias) (+ residual) on the split-bf16 MFMA tile engine (nr_linear_x3): x [M,K], w [N,K] fp32, K padded to
     a multiple of 64 with zeros.  ~fp32-grade products (3 bf16 passes); used for the clustering GEMMs and for the

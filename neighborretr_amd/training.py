@@ -163,9 +163,13 @@ def eval_epoch(args, model, test_dataloader, device):
                             sharded_metrics_with_hubness, sharded_metrics_with_test_norm, sharded_multi_sentence_metrics,
                             test_norm_label)
     from .evaluator import _check_local_scaling, local_scaling_label, sharded_metrics_with_local_scaling
+    from .evaluator import _check_mutual_proximity, mutual_proximity_label, sharded_metrics_with_mutual_proximity
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
     test_norm = getattr(args, "test_norm", None) or "none"
     local_scaling = getattr(args, "local_scaling", None) or "none"
+    mutual_proximity = getattr(args, "mutual_proximity", None) or "none"
+    if mutual_proximity != "none" and (test_norm != "none" or local_scaling != "none"):
+        raise ValueError("mutual_proximity, local_scaling and test_norm are separate corrections: choose one of them")
     if local_scaling != "none" and test_norm != "none":
         raise ValueError("local_scaling and test_norm are separate corrections: choose one of them")
     logger = getattr(args, "logger", None)
@@ -183,6 +187,12 @@ def eval_epoch(args, model, test_dataloader, device):
         if ls_bank:
             _querybank(model, None, device)
         scaling = dict(mode=local_scaling, k=ls_k, bank=ls_bank, hubness_k=hubness_k)
+    if mutual_proximity != "none":   # mutual proximity (DESIGN.md "Mutual proximity"): checked before any work
+        mp_bank = bool(int(getattr(args, "mutual_proximity_bank", 0) or 0))
+        _check_mutual_proximity(mutual_proximity, hubness_k)
+        if mp_bank:
+            _querybank(model, None, device)
+        proximity = dict(mode=mutual_proximity, bank=mp_bank, hubness_k=hubness_k)
     dataset = getattr(test_dataloader, "dataset", None)
     multi = bool(getattr(dataset, "multi_sentence_per_video", False))
     model.eval()
@@ -202,6 +212,9 @@ def eval_epoch(args, model, test_dataloader, device):
             elif local_scaling != "none":
                 t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args,
                                                               cut_off_points=cut_off_points, **scaling)
+            elif mutual_proximity != "none":
+                t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args,
+                                                                 cut_off_points=cut_off_points, **proximity)
             elif hubness_k:
                 t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, cut_off_points)
             else:
@@ -217,6 +230,8 @@ def eval_epoch(args, model, test_dataloader, device):
                 t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args, **norm)
             elif local_scaling != "none":
                 t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args, **scaling)
+            elif mutual_proximity != "none":
+                t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args, **proximity)
             elif hubness_k:
                 t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k)
             else:
@@ -250,6 +265,13 @@ def eval_epoch(args, model, test_dataloader, device):
             if hubness_k:
                 tracker.log_hubness(t2v["local_scaling"]["hubness"], prefix=f"Text-to-Video {tag} ")
                 tracker.log_hubness(v2t["local_scaling"]["hubness"], prefix=f"Video-to-Text {tag} ")
+        if mutual_proximity != "none":
+            tag = mutual_proximity_label(mutual_proximity, mp_bank)
+            tracker.print_metrics(t2v["mutual_proximity"], prefix=f"Text-to-Video {tag}: ")
+            tracker.print_metrics(v2t["mutual_proximity"], prefix=f"Video-to-Text {tag}: ")
+            if hubness_k:
+                tracker.log_hubness(t2v["mutual_proximity"]["hubness"], prefix=f"Text-to-Video {tag} ")
+                tracker.log_hubness(v2t["mutual_proximity"]["hubness"], prefix=f"Video-to-Text {tag} ")
     return t2v, v2t
 
 
