@@ -879,6 +879,25 @@ int nr_mp_moments_combine(int P, const double* parts, int L, float* mean, float*
 int nr_mp_gauss_apply(const float* S, int n, int L, const float* row_mean, const float* row_sd, const float* col_mean,
                       const float* col_sd, float* T, void* stream);
 
+/* Bootstrap of rank statistics (DESIGN.md "Bootstrap confidence intervals"; Efron 1979; the reference has no code for it): n_boot
+ * resamples of U units (queries; the videos of a multi-sentence set) drawn with replacement, for V = 1 or 2 rankings over the same
+ * units (ranks_b NULL: V = 1, unit_end_b and E_b are ignored).  Ranking v: ranks_v [E_v] int32, 0-based, 0 <= r < 2^30; unit_end_v [U]
+ * int32 = index of the LAST entry of unit u (non-decreasing, unit_end_v[U-1] = E_v - 1, the unit before unit 0 ends at -1, a unit
+ * may be empty).  Draws are counter-based:  SM64(seed, c) = the (c+1)-th output of SplitMix64 seeded with `seed`,
+ *   z = seed + (c + 1) 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) 0x94D049BB133111EB;  z ^= z >> 31
+ *   u(b, t) = ((SM64(seed, (b << 32) | t) >> 32) * U) >> 32,   t in [0, U);   both rankings of a call use the same u(b, t).
+ * out [n_boot, V, 4 + K] int64, exact integers: for resample b0 + i and ranking v, over the multiset of entries of its U drawn units,
+ *   (n, sum, med_lo, med_hi, hits[0..K-1]):  the entry count, the sum of ranks, the order statistics at sorted positions (n-1)/2 and
+ *   n/2 (both -1 when n = 0), hits[k] = #{r < cuts[k]}.  cuts [K] is HOST memory: K strictly increasing positive cut-offs.
+ * One workgroup per resample; the order statistics by a radix select on the rank value (LDS histograms of 1024 bins, at most three
+ * passes), the draws recomputed in every pass.  No global atomics, no scratch: the result depends on (seed, b, inputs) alone, whatever
+ * the grid and the split of the resamples over calls.  A resample must hold fewer than 2^32 entries (U times the largest unit < 2^32
+ * guarantees it).  NR_EINVAL before any launch: U outside [1, 2^24], K outside [1, 8], cuts not positive and increasing, E < 0,
+ * b0 < 0, n_boot < 0, b0 + n_boot > 2^31 - 1, a null required pointer; n_boot = 0: NR_OK, no launch. */
+int nr_bootstrap_rank_stats(const int32_t* ranks_a, const int32_t* unit_end_a, int E_a, const int32_t* ranks_b,
+                            const int32_t* unit_end_b, int E_b, int U, const int32_t* cuts, int K, uint64_t seed, int b0, int n_boot,
+                            int64_t* out, void* stream);
+
 /* Multi-tensor BertAdam step (models/optimization.py:76-211 with the trainer's clip and clamp around it, trainer.py:104-119;
  * DESIGN.md "BertAdam in the captured step").  fp32 tensors only.  Per step, for every table entry t with group q:
  *   c    = min(1, global_max_norm / (sqrt(sum_t ||g_t||^2) + 1e-6))             (global_max_norm <= 0: c = 1)

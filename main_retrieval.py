@@ -118,6 +118,13 @@ def get_args():
     p.add_argument("--mutual_proximity_bank", type=int, default=0, choices=[0, 1],
                    help="--mutual_proximity: 1 takes the lines in the memory bank (the querybank of --test_norm qbnorm) instead of "
                         "the test set")
+    p.add_argument("--bootstrap", type=int, default=0,
+                   help="N > 0: N bootstrap resamples of the test queries (the videos of a multi-sentence set) on the GPU: a percentile "
+                        "confidence interval for every reported metric and, for a correction, a paired interval of its difference "
+                        "to the raw ranking (DESIGN.md 6.7); at most 2^20; 0 = off")
+    p.add_argument("--bootstrap_seed", type=int, default=0,
+                   help="--bootstrap: seed of the counter-based draws (text->video uses it, video->text seed + 1)")
+    p.add_argument("--bootstrap_level", type=float, default=0.95, help="--bootstrap: coverage of the intervals, in (0, 1)")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -139,6 +146,12 @@ def get_args():
         p.error("--mutual_proximity and --local_scaling are separate corrections: choose one of them")
     if not 1 <= args.local_scaling_k <= 128:
         p.error("--local_scaling_k must lie in [1, 128]")
+    if not 0 <= args.bootstrap <= 1 << 20:
+        p.error("--bootstrap must lie in [0, 2^20]")
+    if not 0 <= args.bootstrap_seed < (1 << 64) - 1:
+        p.error("--bootstrap_seed must lie in [0, 2^64 - 1)")
+    if not 0.0 < args.bootstrap_level < 1.0:
+        p.error("--bootstrap_level must lie in (0, 1)")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
         raise ValueError("--batch_size must divide over the ranks (args_parser.py:149-165)")
     return args
@@ -526,6 +539,20 @@ def eval_epoch(args, model, test):
                                             sharded_metrics_with_test_norm, test_norm_label)
     from neighborretr_amd.evaluator import local_scaling_label, sharded_metrics_with_local_scaling
     from neighborretr_amd.evaluator import mutual_proximity_label, sharded_metrics_with_mutual_proximity
+    from neighborretr_amd.evaluator import _check_bootstrap
+    from neighborretr_amd.metrics import RetrievalMetrics
+    boot = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
+                bootstrap_level=getattr(args, "bootstrap_level", 0.95))
+    _check_bootstrap(boot["bootstrap"], boot["bootstrap_seed"], boot["bootstrap_level"])         # before any work
+
+    def log_bootstrap(nt, nv, tag=""):
+        """The interval line of each direction after its metrics line, and for a correction the paired line against raw."""
+        if not boot["bootstrap"]:
+            return
+        for side, m in (("text->video", nt), ("video->text", nv)):
+            log(args, RetrievalMetrics.format_bootstrap(m["bootstrap"], prefix=f"{side} {tag}".rstrip() + " "))
+            if "bootstrap_vs_raw" in m:
+                log(args, RetrievalMetrics.format_bootstrap(m["bootstrap_vs_raw"], prefix=f"{side} {tag} - raw "))
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
     test_norm = getattr(args, "test_norm", None) or "none"
     local_scaling = getattr(args, "local_scaling", None) or "none"
@@ -542,20 +569,21 @@ def eval_epoch(args, model, test):
         t, v, tm, vm = gather_eval_features(t, v, mine.to(dev), tm, vm, args)
     if test_norm != "none":
         t2v, v2t = sharded_metrics_with_test_norm(model, t, v, tm.float(), vm.float(), args, test_norm, args.test_norm_beta,
-                                                  qb_k=args.qb_k, hubness_k=hubness_k, n_iter=args.test_norm_iters)
+                                                  qb_k=args.qb_k, hubness_k=hubness_k, n_iter=args.test_norm_iters, **boot)
     elif local_scaling != "none":
         t2v, v2t = sharded_metrics_with_local_scaling(model, t, v, tm.float(), vm.float(), args, local_scaling,
                                                       k=args.local_scaling_k, bank=bool(args.local_scaling_bank),
-                                                      hubness_k=hubness_k)
+                                                      hubness_k=hubness_k, **boot)
     elif mutual_proximity != "none":
         t2v, v2t = sharded_metrics_with_mutual_proximity(model, t, v, tm.float(), vm.float(), args, mutual_proximity,
-                                                         bank=bool(args.mutual_proximity_bank), hubness_k=hubness_k)
+                                                         bank=bool(args.mutual_proximity_bank), hubness_k=hubness_k, **boot)
     elif hubness_k:
-        t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k)
+        t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k, **boot)
     else:
-        t2v, v2t = sharded_metrics(model, t, v, tm.float(), vm.float(), args)
+        t2v, v2t = sharded_metrics(model, t, v, tm.float(), vm.float(), args, **boot)
     log(args, f"text->video R@1 {t2v['R1']:.1f} R@5 {t2v['R5']:.1f} R@10 {t2v['R10']:.1f} MedR {t2v['MR']:.1f} | "
               f"video->text R@1 {v2t['R1']:.1f} R@5 {v2t['R5']:.1f} R@10 {v2t['R10']:.1f} MedR {v2t['MR']:.1f}")
+    log_bootstrap(t2v, v2t)
     if hubness_k:
         from neighborretr_amd.metrics import RetrievalMetrics
         log(args, RetrievalMetrics.format_hubness(t2v["hubness"], prefix="text->video "))
@@ -566,6 +594,7 @@ def eval_epoch(args, model, test):
         tag = test_norm_label(test_norm, nt["beta"], nt.get("iters"))
         log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
+        log_bootstrap(nt, nv, tag)
         if hubness_k:
             log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
@@ -577,6 +606,7 @@ def eval_epoch(args, model, test):
         tag = local_scaling_label(local_scaling, nt["k"], nt["bank"])
         log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
+        log_bootstrap(nt, nv, tag)
         if hubness_k:
             log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
@@ -586,6 +616,7 @@ def eval_epoch(args, model, test):
         tag = mutual_proximity_label(mutual_proximity, nt["bank"])
         log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
+        log_bootstrap(nt, nv, tag)
         if hubness_k:
             log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))

@@ -135,15 +135,19 @@ def _ranks_from_slab(S_slab, N, W, rank):
     return gt.astype(np.int64), et.astype(np.int64), cols[0].astype(np.int64), cols[1].astype(np.int64)
 
 
-def sharded_metrics(model, text_feat, video_feat, text_mask, video_mask, args):
-    """(text->video metrics, video->text metrics) as RetrievalMetrics.compute_metrics(S) / (S.T) would give them."""
+def sharded_metrics(model, text_feat, video_feat, text_mask, video_mask, args, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95):
+    """(text->video metrics, video->text metrics) as RetrievalMetrics.compute_metrics(S) / (S.T) would give them.  bootstrap > 0:
+    each with a "bootstrap" entry (DESIGN.md "Bootstrap confidence intervals")."""
+    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
     gt, et, gv, ev = sharded_retrieval_ranks(model, text_feat, video_feat, text_mask, video_mask, args)
-    t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
-    v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
+    units = _query_units(gt, et), _query_units(gv, ev)
+    t2v, v2t = (RetrievalMetrics.metrics_from_ranks(u[0]) for u in units)
+    _add_bootstrap(t2v, v2t, units, boot, text_feat.device)
     return t2v, v2t
 
 
-def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, video_mask, cut_off_points, args, chunk=256):
+def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, video_mask, cut_off_points, args, chunk=256, bootstrap=0,
+                                   bootstrap_seed=0, bootstrap_level=0.95):
     """Several captions per video (evaluator.py:114-149 features, :225-262 metrics): text_feat [Ns,...] holds every
     sentence in dataset order, video_feat [V,...] one entry per video, cut_off_points[g] = index of the LAST sentence of
     video g (the dataset's cut_off_points minus one, evaluator.py:98).  -> (text->video, video->text) metric dictionaries.
@@ -151,18 +155,33 @@ def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, vide
     The reference pads the Ns x V matrix to [V, max_sentences, V] with -inf on the host and ranks it with two argsorts
     (metrics.py:82-126) and a max over the padded axis (:128-148).  Here rank r scores its slab of sentence rows, one
     launch (nr_group_slab_ranks) gives every row's rank and the slab's per-video best scores, and a MAX all-reduce of
-    the V x V best-score matrix + an all-gather of the Ns ranks complete them; no padded tensor exists."""
+    the V x V best-score matrix + an all-gather of the Ns ranks complete them; no padded tensor exists.  bootstrap > 0: each
+    dictionary gains a "bootstrap" entry that resamples VIDEOS (DESIGN.md "Bootstrap confidence intervals")."""
+    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
     W = _world(args)
     rank = comm.get_rank() if W > 1 else 0
     Ns, V = text_feat.shape[0], video_feat.shape[0]
     ends = _group_ends(cut_off_points, Ns, V)
     r0, r1 = slab_bounds(Ns, W, rank)
     S_slab = _slab_similarity(model, text_feat, video_feat, text_mask, video_mask, r0, r1, chunk)
-    return _multi_sentence_from_slab(S_slab, ends, Ns, V, W, rank)
+    if not boot:
+        return _multi_sentence_from_slab(S_slab, ends, Ns, V, W, rank)
+    t2v, v2t, units = _metrics_and_units(S_slab, S_slab, Ns, V, W, rank, ends)
+    _add_bootstrap(t2v, v2t, units, boot, S_slab.device)
+    return t2v, v2t
 
 
 def _multi_sentence_from_slab(S_slab, ends, Ns, V, W, rank):
     """sharded_multi_sentence_metrics from this rank's slab of sentence rows (two collectives)."""
+    ranks, gmax = _multi_sentence_ranks(S_slab, ends, Ns, V, W, rank)
+    t2v = RetrievalMetrics.multi_sentence_metrics_from_ranks(ranks[ranks >= 0])      # < 0: own score NaN / inf, not ranked
+    v2t = RetrievalMetrics.compute_metrics(gmax.T.contiguous())          # [video, caption group], metrics.py:146-148
+    return t2v, v2t
+
+
+def _multi_sentence_ranks(S_slab, ends, Ns, V, W, rank):
+    """(ranks [Ns] int32 on the device: every sentence's rank of its own video, < 0 where it is not ranked; gmax [V, V]: every
+    caption group's best score against every video), the same on every rank (two collectives)."""
     dev = S_slab.device
     group_end = torch.from_numpy(ends.astype(np.int32)).to(dev)
     r0, r1 = slab_bounds(Ns, W, rank)
@@ -181,9 +200,7 @@ def _multi_sentence_from_slab(S_slab, ends, Ns, V, W, rank):
         ranks = torch.cat([allr[r, :slab_bounds(Ns, W, r)[1] - slab_bounds(Ns, W, r)[0]] for r in range(W)])
     else:
         ranks = mine[:n]
-    t2v = RetrievalMetrics.multi_sentence_metrics_from_ranks(ranks[ranks >= 0])      # < 0: own score NaN / inf, not ranked
-    v2t = RetrievalMetrics.compute_metrics(gmax.T.contiguous())          # [video, caption group], metrics.py:146-148
-    return t2v, v2t
+    return ranks, gmax
 
 
 # ---- top-k lists and hubness (DESIGN.md "Top-k lists and hubness") ------------------------------------------------------
@@ -313,19 +330,17 @@ def sharded_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k
     return _hubness_from_slab(S_slab, n_rows, n_cols, int(k), W, rank, ends)
 
 
-def sharded_metrics_with_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k, cut_off_points=None, chunk=256):
+def sharded_metrics_with_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k, cut_off_points=None, chunk=256,
+                                 bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95):
     """sharded_metrics (cut_off_points None) or sharded_multi_sentence_metrics, plus a "hubness" entry in each dictionary
-    (sharded_hubness), from ONE scoring of this rank's slab."""
+    (sharded_hubness), from ONE scoring of this rank's slab.  bootstrap > 0: a "bootstrap" entry too."""
+    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
     S_slab, n_rows, n_cols, W, rank, ends = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points,
                                                        chunk)
     ops._check_k(k)
-    if ends is None:
-        gt, et, gv, ev = _ranks_from_slab(S_slab, n_rows, W, rank)
-        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
-        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
-    else:
-        t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
+    t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
     t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, int(k), W, rank, ends)
+    _add_bootstrap(t2v, v2t, raw_units, boot, S_slab.device)
     return t2v, v2t
 
 
@@ -509,32 +524,103 @@ def _sinkhorn_from_slab(S_slab, n_rows, n_cols, W, rank, mode, beta, n_iter, end
     return T, V, dict(iters=n_iter, marginal_err=(err_t, err_v))
 
 
-def _metrics_from_normalised(T_slab, V_slab, n_rows, n_cols, W, rank, ends, hubness_k):
-    """(t2v, v2t): text->video ranks from the rows of T, video->text from the columns of V (multi-sentence sets: the group
-    ranks of T, the group max of V), and with hubness_k the hubness of T's row lists and V's column lists.  V_slab is T_slab
-    (sinkhorn's one output): both directions from one pass over it."""
-    if V_slab is T_slab:
-        if ends is None:
-            gt, et, gv, ev = _ranks_from_slab(T_slab, n_rows, W, rank)
-            t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
-            v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
-        else:
-            t2v, v2t = _multi_sentence_from_slab(T_slab, ends, n_rows, n_cols, W, rank)
-        if hubness_k:
-            t2v["hubness"], v2t["hubness"] = _hubness_from_slab(T_slab, n_rows, n_cols, hubness_k, W, rank, ends)
-        return t2v, v2t
+def _metrics_and_units(T_slab, V_slab, n_rows, n_cols, W, rank, ends):
+    """(t2v, v2t, units): text->video ranks from the rows of T, video->text from the columns of V (multi-sentence sets: the group
+    ranks of T, the group max of V; V_slab is T_slab: both directions from one pass), and the two directions' resampling units
+    (entries, unit_end, median) of the bootstrap (_query_units / _video_units)."""
     if ends is None:
-        gt, et, _, _ = _ranks_from_slab(T_slab, n_rows, W, rank)
-        _, _, gv, ev = _ranks_from_slab(V_slab, n_rows, W, rank)
-        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
-        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
-    else:
-        t2v, _ = _multi_sentence_from_slab(T_slab, ends, n_rows, n_cols, W, rank)
-        _, v2t = _multi_sentence_from_slab(V_slab, ends, n_rows, n_cols, W, rank)
-    if hubness_k:
+        gt, et, gv, ev = _ranks_from_slab(T_slab, n_rows, W, rank)
+        if V_slab is not T_slab:
+            _, _, gv, ev = _ranks_from_slab(V_slab, n_rows, W, rank)
+        units = _query_units(gt, et), _query_units(gv, ev)
+        t2v, v2t = (RetrievalMetrics.metrics_from_ranks(u[0]) for u in units)
+        return t2v, v2t, units
+    ranks, gmax = _multi_sentence_ranks(T_slab, ends, n_rows, n_cols, W, rank)
+    if V_slab is not T_slab:
+        _, gmax = _multi_sentence_ranks(V_slab, ends, n_rows, n_cols, W, rank)
+    t2v = RetrievalMetrics.multi_sentence_metrics_from_ranks(ranks[ranks >= 0])      # < 0: own score NaN / inf, not ranked
+    gv, ev = (x.cpu().numpy() for x in ops.diag_ranks(gmax.T.contiguous()))          # [video, caption group], metrics.py:146-148
+    video_units = _query_units(gv, ev)
+    return t2v, RetrievalMetrics.metrics_from_ranks(video_units[0]), (_video_units(ranks, ends), video_units)
+
+
+def _metrics_from_normalised(T_slab, V_slab, n_rows, n_cols, W, rank, ends, hubness_k, units=None):
+    """(t2v, v2t) of _metrics_and_units, and with hubness_k the hubness of T's row lists and V's column lists.  units: a list
+    that receives the two directions' resampling units."""
+    t2v, v2t, u = _metrics_and_units(T_slab, V_slab, n_rows, n_cols, W, rank, ends)
+    if units is not None:
+        units.extend(u)
+    if hubness_k and V_slab is T_slab:
+        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(T_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    elif hubness_k:
         t2v["hubness"] = _row_hubness(T_slab, n_rows, n_cols, hubness_k, W, rank, ends)
         v2t["hubness"] = _col_hubness(V_slab, n_rows, n_cols, hubness_k, W, rank, ends)
     return t2v, v2t
+
+
+# ---- bootstrap confidence intervals (DESIGN.md "Bootstrap confidence intervals") ------------------------------------------------------
+# The queries are resampled with replacement, n_boot times, on the GPU (nr_bootstrap_rank_stats): percentile intervals for every
+# reported metric and, for a correction, a paired bootstrap (the same draws) of "corrected minus raw".  The unit of resampling is the
+# query (its equal[i] tied entries stay together); in a multi-sentence set it is the VIDEO in both directions, since the sentences
+# of one video are not independent.  Every rank holds the same rank vectors and computes every resample itself: no collective.
+
+BOOTSTRAP_MAX = 1 << 20
+BOOTSTRAP_CUTS = (1, 5, 10, 50)
+
+
+def _check_bootstrap(bootstrap, seed=0, level=0.95):
+    """None for bootstrap = 0, else (n_boot, seed, level); an integer in [0, 2^20], a seed in [0, 2^64 - 1), a level in (0, 1)."""
+    if isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, np.integer)) or not 0 <= int(bootstrap) <= BOOTSTRAP_MAX:
+        raise ValueError(f"bootstrap must be an integer in [0, 2^20], got {bootstrap!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64) - 1:
+        raise ValueError(f"bootstrap_seed must be an integer in [0, 2^64 - 1), got {seed!r}")
+    if isinstance(level, bool) or not isinstance(level, (int, float, np.floating)) or not 0.0 < float(level) < 1.0:
+        raise ValueError(f"bootstrap_level must lie in (0, 1), got {level!r}")
+    return (int(bootstrap), int(seed), float(level)) if int(bootstrap) else None
+
+
+def _query_units(greater, equal):
+    """(entries, unit_end, median) of a direction ranked by counts: entries = ranks_from_counts (the `ind` its metrics come from),
+    query i owns its equal[i] consecutive entries; the median is np.median's."""
+    equal = np.asarray(equal, dtype=np.int64)
+    return RetrievalMetrics.ranks_from_counts(greater, equal), np.cumsum(equal) - 1, "mid"
+
+
+def _video_units(ranks, ends):
+    """Multi-sentence text->video units: video g owns its ranked sentences (an unranked one, rank < 0, is dropped: a video may be
+    left empty); ends[g] = one past its last sentence; the median is torch.median's (the lower one)."""
+    ranks = ranks.cpu().numpy().astype(np.int64)
+    kept = np.cumsum(ranks >= 0)
+    return ranks[ranks >= 0], kept[np.asarray(ends, dtype=np.int64) - 1] - 1, "low"
+
+
+def _bootstrap_direction(units, boot, seed, dev, raw_units=None):
+    """{"bootstrap": summary of `units`} and, with raw_units, "bootstrap_vs_raw": the paired summary of units minus raw_units from ONE
+    launch (the same draws); summaries carry the units they resampled ("entries", "unit_end")."""
+    n_boot, _, level = boot
+    entries, unit_end, median = units
+
+    def dev32(a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+    args = [dev32(entries), dev32(unit_end)]
+    if raw_units is not None:
+        args += [dev32(raw_units[0]), dev32(raw_units[1])]
+    stats = ops.bootstrap_rank_stats(*args, cuts=BOOTSTRAP_CUTS, seed=seed, b0=0, n_boot=n_boot).cpu().numpy()
+    out = {"bootstrap": RetrievalMetrics.bootstrap_summary(stats[:, 0], BOOTSTRAP_CUTS, entries, level, median)}
+    out["bootstrap"].update(seed=seed, entries=np.asarray(entries, dtype=np.int64), unit_end=np.asarray(unit_end, dtype=np.int64))
+    if raw_units is not None:
+        out["bootstrap_vs_raw"] = RetrievalMetrics.paired_bootstrap_summary(stats[:, 0], stats[:, 1], BOOTSTRAP_CUTS, entries,
+                                                                           raw_units[0], level, median)
+        out["bootstrap_vs_raw"]["seed"] = seed
+    return out
+
+
+def _add_bootstrap(t2v, v2t, units, boot, dev, raw_units=None):
+    """Adds the bootstrap entries to the two directions' dictionaries: seed for text->video, seed + 1 for video->text."""
+    if not boot:
+        return
+    for side, metrics in enumerate((t2v, v2t)):
+        metrics.update(_bootstrap_direction(units[side], boot, boot[1] + side, dev, None if raw_units is None else raw_units[side]))
 
 
 def _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k, chunk,
@@ -598,28 +684,29 @@ def sharded_normalised_metrics(model, text_feat, video_feat, text_mask, video_ma
 
 
 def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None,
-                                   qb_k=1, hubness_k=0, cut_off_points=None, chunk=256, n_iter=50):
+                                   qb_k=1, hubness_k=0, cut_off_points=None, chunk=256, n_iter=50, bootstrap=0, bootstrap_seed=0,
+                                   bootstrap_level=0.95):
     """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
-    each with one more entry "test_norm" = sharded_normalised_metrics, from ONE scoring of this rank's slab."""
+    each with one more entry "test_norm" = sharded_normalised_metrics, from ONE scoring of this rank's slab.  bootstrap > 0: the
+    raw dictionaries gain "bootstrap", the "test_norm" ones "bootstrap" and "bootstrap_vs_raw" (paired on the same draws)."""
+    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
     beta, qb_k, hubness_k = _check_test_norm(mode, beta, qb_k, hubness_k)
     n_iter = _check_n_iter(n_iter)
     if mode in BANK_MODES:
         _querybank(model, querybank, text_feat.device)
     slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
     S_slab, n_rows, n_cols, W, rank, ends = slab
-    if ends is None:
-        gt, et, gv, ev = _ranks_from_slab(S_slab, n_rows, W, rank)
-        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
-        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
-    else:
-        t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
+    t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
     if hubness_k:
         t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
     info = {}
     T, V = _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
                                       chunk, n_iter, info)
     del S_slab, slab
-    nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k)
+    units = []
+    nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k, units)
+    _add_bootstrap(t2v, v2t, raw_units, boot, T.device)
+    _add_bootstrap(nt, nv, units, boot, T.device, raw_units)
     t2v["test_norm"] = _test_norm_entry(nt, mode, beta, qb_k, info, 0)
     v2t["test_norm"] = _test_norm_entry(nv, mode, beta, qb_k, info, 1)
     return t2v, v2t
@@ -721,25 +808,26 @@ def sharded_local_scaled_metrics(model, text_feat, video_feat, text_mask, video_
 
 
 def sharded_metrics_with_local_scaling(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False,
-                                       querybank=None, hubness_k=0, cut_off_points=None, chunk=256):
+                                       querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0, bootstrap_seed=0,
+                                       bootstrap_level=0.95):
     """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
-    each with one more entry "local_scaling" = sharded_local_scaled_metrics, from ONE scoring of this rank's slab."""
+    each with one more entry "local_scaling" = sharded_local_scaled_metrics, from ONE scoring of this rank's slab.  bootstrap > 0:
+    the raw dictionaries gain "bootstrap", the "local_scaling" ones "bootstrap" and "bootstrap_vs_raw" (paired on the same draws)."""
+    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
     k, hubness_k = _check_local_scaling(mode, k, hubness_k)
     if bank:
         _querybank(model, querybank, text_feat.device)
     slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
     S_slab, n_rows, n_cols, W, rank, ends = slab
-    if ends is None:
-        gt, et, gv, ev = _ranks_from_slab(S_slab, n_rows, W, rank)
-        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
-        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
-    else:
-        t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
+    t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
     if hubness_k:
         t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
     T = _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk)
     del S_slab, slab
-    nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k)
+    units = []
+    nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k, units)
+    _add_bootstrap(t2v, v2t, raw_units, boot, T.device)
+    _add_bootstrap(nt, nv, units, boot, T.device, raw_units)
     t2v["local_scaling"] = _local_scaling_entry(nt, mode, k, bank)
     v2t["local_scaling"] = _local_scaling_entry(nv, mode, k, bank)
     return t2v, v2t
@@ -882,25 +970,27 @@ def sharded_mutual_proximity_metrics(model, text_feat, video_feat, text_mask, vi
 
 
 def sharded_metrics_with_mutual_proximity(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False,
-                                          querybank=None, hubness_k=0, cut_off_points=None, chunk=256):
+                                          querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0,
+                                          bootstrap_seed=0, bootstrap_level=0.95):
     """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
-    each with one more entry "mutual_proximity" = sharded_mutual_proximity_metrics, from ONE scoring of this rank's slab."""
+    each with one more entry "mutual_proximity" = sharded_mutual_proximity_metrics, from ONE scoring of this rank's slab.
+    bootstrap > 0: the raw dictionaries gain "bootstrap", the "mutual_proximity" ones "bootstrap" and "bootstrap_vs_raw" (paired
+    on the same draws)."""
+    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
     hubness_k = _check_mutual_proximity(mode, hubness_k)
     if bank:
         _querybank(model, querybank, text_feat.device)
     slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
     S_slab, n_rows, n_cols, W, rank, ends = slab
-    if ends is None:
-        gt, et, gv, ev = _ranks_from_slab(S_slab, n_rows, W, rank)
-        t2v = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gt, et))
-        v2t = RetrievalMetrics.metrics_from_ranks(RetrievalMetrics.ranks_from_counts(gv, ev))
-    else:
-        t2v, v2t = _multi_sentence_from_slab(S_slab, ends, n_rows, n_cols, W, rank)
+    t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
     if hubness_k:
         t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
     T = _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk)
     del S_slab, slab
-    nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k)
+    units = []
+    nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k, units)
+    _add_bootstrap(t2v, v2t, raw_units, boot, T.device)
+    _add_bootstrap(nt, nv, units, boot, T.device, raw_units)
     t2v["mutual_proximity"] = _mutual_proximity_entry(nt, mode, bank)
     v2t["mutual_proximity"] = _mutual_proximity_entry(nv, mode, bank)
     return t2v, v2t

@@ -139,6 +139,112 @@ class RetrievalMetrics:
         if self.logger is not None:
             self.logger.info(self.format_hubness(hub, prefix))
 
+    # ---- bootstrap confidence intervals (DESIGN.md "Bootstrap confidence intervals") ----------------------------------------------
+    BOOTSTRAP_LOGGED = ("R1", "R5", "R10", "MedianR", "MeanR")            # the metrics of the log line, where present
+
+    @staticmethod
+    def _bootstrap_values(stats, cuts, median):
+        """({metric: fp64 array over the rows of stats}, n) from rows (n, sum, med_lo, med_hi, hits...); rows with n = 0 give NaN."""
+        if median not in ("mid", "low"):
+            raise ValueError(f"median must be 'mid' (np.median) or 'low' (torch.median), got {median!r}")
+        if torch.is_tensor(stats):
+            stats = stats.cpu().numpy()
+        stats = np.asarray(stats, dtype=np.int64)
+        cuts = [int(c) for c in cuts]
+        if stats.ndim != 2 or stats.shape[1] != 4 + len(cuts):
+            raise ValueError(f"stats must be [n_boot, {4 + len(cuts)}] for {len(cuts)} cut-offs, got {stats.shape}")
+        n = stats[:, 0].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            vals = {f"R{c}": 100 * stats[:, 4 + k].astype(np.float64) / n for k, c in enumerate(cuts)}
+            med_hi = stats[:, 3] if median == "mid" else stats[:, 2]
+            vals["MedianR"] = np.where(n > 0, (stats[:, 2] + med_hi).astype(np.float64) / 2 + 1, np.nan)
+            vals["MeanR"] = stats[:, 1].astype(np.float64) / n + 1
+        return vals, stats[:, 0]
+
+    @staticmethod
+    def _entry_stats(entries, cuts):
+        """The row (n, sum, med_lo, med_hi, hits...) of the un-resampled entries."""
+        r = np.sort(np.asarray(entries, dtype=np.int64).reshape(-1))
+        n = len(r)
+        med = [int(r[(n - 1) // 2]), int(r[n // 2])] if n else [-1, -1]
+        return np.asarray([[n, int(r.sum())] + med + [int((r < int(c)).sum()) for c in cuts]], dtype=np.int64)
+
+    @staticmethod
+    def _interval(x, point, level):
+        """point, standard error (population sd) and percentile interval of the resampled values x."""
+        if len(x) == 0:
+            return {"point": point, "se": float("nan"), "lo": float("nan"), "hi": float("nan")}
+        lo, hi = np.percentile(x, [100 * (1 - level) / 2, 100 * (1 + level) / 2])
+        return {"point": point, "se": float(np.std(x)), "lo": float(lo), "hi": float(hi)}
+
+    @staticmethod
+    def _check_level(level):
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError(f"bootstrap level must lie in (0, 1), got {level!r}")
+        return level
+
+    @staticmethod
+    def bootstrap_summary(stats, cuts, entries, level=0.95, median="mid"):
+        """Percentile bootstrap of one ranking: stats [n_boot, 4 + K] int64 (ops.bootstrap_rank_stats[:, v]), entries = its
+        un-resampled ranks.  Per resample with n > 0: R{c} = 100 hits / n, MeanR = sum / n + 1, MedianR = (med_lo + med_hi) / 2 + 1
+        (median "mid": np.median) or med_lo + 1 ("low": torch.median).  -> {"n_boot", "n_empty" (resamples with n = 0, dropped),
+        "level", "median", and per metric {"point" (the formula on `entries`), "se" (population sd over the resamples), "lo", "hi"
+        (np.percentile at 100 (1 -+ level) / 2)}}."""
+        level = RetrievalMetrics._check_level(level)
+        vals, n = RetrievalMetrics._bootstrap_values(stats, cuts, median)
+        point, _ = RetrievalMetrics._bootstrap_values(RetrievalMetrics._entry_stats(entries, cuts), cuts, median)
+        keep = n > 0
+        out = {"n_boot": int(len(n)), "n_empty": int(np.sum(~keep)), "level": level, "median": median}
+        for name, x in vals.items():
+            out[name] = RetrievalMetrics._interval(x[keep], float(point[name][0]), level)
+        return out
+
+    @staticmethod
+    def paired_bootstrap_summary(stats, stats_raw, cuts, entries, entries_raw, level=0.95, median="mid"):
+        """Paired bootstrap of "corrected minus raw": stats / stats_raw [n_boot, 4 + K] of the two rankings of ONE V = 2 call (the
+        same draws).  The fields of bootstrap_summary for the per-resample differences, and per metric "frac_le0" / "frac_ge0": the
+        share of resamples whose difference is <= 0 / >= 0.  A resample empty in either ranking is dropped (n_empty)."""
+        level = RetrievalMetrics._check_level(level)
+        a, na = RetrievalMetrics._bootstrap_values(stats, cuts, median)
+        b, nb = RetrievalMetrics._bootstrap_values(stats_raw, cuts, median)
+        if len(na) != len(nb):
+            raise ValueError("paired bootstrap: the two rankings must come from one call (the same resamples)")
+        pa, _ = RetrievalMetrics._bootstrap_values(RetrievalMetrics._entry_stats(entries, cuts), cuts, median)
+        pb, _ = RetrievalMetrics._bootstrap_values(RetrievalMetrics._entry_stats(entries_raw, cuts), cuts, median)
+        keep = (na > 0) & (nb > 0)
+        out = {"n_boot": int(len(na)), "n_empty": int(np.sum(~keep)), "level": level, "median": median}
+        for name in a:
+            d = a[name][keep] - b[name][keep]
+            out[name] = RetrievalMetrics._interval(d, float(pa[name][0] - pb[name][0]), level)
+            out[name]["frac_le0"] = float(np.mean(d <= 0)) if len(d) else float("nan")
+            out[name]["frac_ge0"] = float(np.mean(d >= 0)) if len(d) else float("nan")
+        return out
+
+    @staticmethod
+    def format_bootstrap(summary, prefix=""):
+        """One line: every logged metric with its interval; a paired summary prints signed differences and frac_le0."""
+        paired = any(isinstance(v, dict) and "frac_le0" in v for v in summary.values())
+        label = {"R1": "R@1", "R5": "R@5", "R10": "R@10", "MedianR": "Median R", "MeanR": "Mean R"}
+        parts = []
+        for name in RetrievalMetrics.BOOTSTRAP_LOGGED:
+            if name not in summary:
+                continue
+            m = summary[name]
+            if paired:
+                parts.append(f"{label[name]}: {m['point']:+.1f} [{m['lo']:+.1f}, {m['hi']:+.1f}] frac<=0 {m['frac_le0']:.3f}")
+            else:
+                parts.append(f"{label[name]}: {m['point']:.1f} [{m['lo']:.1f}, {m['hi']:.1f}]")
+        kind = "paired bootstrap vs raw" if paired else "bootstrap"
+        tail = f" ({100 * summary['level']:g}% {kind}, {summary['n_boot']} resamples"
+        tail += f", {summary['n_empty']} empty)" if summary["n_empty"] else ")"
+        return prefix + " - ".join(parts) + tail
+
+    def log_bootstrap(self, summary, prefix=""):
+        """One line per summary, in the style of print_metrics (silent without a logger)."""
+        if self.logger is not None:
+            self.logger.info(self.format_bootstrap(summary, prefix))
+
     def print_metrics(self, metrics, prefix=""):
         msg = (f"{prefix}R@1: {metrics['R1']:.1f} - R@5: {metrics['R5']:.1f} - R@10: {metrics['R10']:.1f} - "
                f"R@50: {metrics.get('R50', 0.0):.1f} - Median R: {metrics['MR']:.1f} - Mean R: {metrics['MeanR']:.1f}")

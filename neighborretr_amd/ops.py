@@ -1301,6 +1301,77 @@ def mp_gauss_apply(S, row_mean, row_sd, col_mean, col_sd):
     return T
 
 
+def _boot_cuts(cuts):
+    cuts = [c for c in cuts]
+    if not 1 <= len(cuts) <= hip.BOOT_MAX_CUTS:
+        raise ValueError(f"cuts must hold 1 to {hip.BOOT_MAX_CUTS} cut-offs, got {len(cuts)}")
+    if any(isinstance(c, bool) or int(c) != c for c in cuts):
+        raise ValueError(f"cuts must be integers, got {cuts!r}")
+    cuts = [int(c) for c in cuts]
+    if cuts[0] < 1 or cuts[-1] >= 1 << 31 or any(b <= a for a, b in zip(cuts, cuts[1:])):
+        raise ValueError(f"cuts must be positive and strictly increasing, got {cuts!r}")
+    return cuts
+
+
+def _boot_ranking(ranks, unit_end, which, dev=None, U=None):
+    """The checked (ranks, unit_end, E) of one ranking of bootstrap_rank_stats."""
+    for name, t in ((f"ranks_{which}", ranks), (f"unit_end_{which}", unit_end)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1:
+            raise ValueError(f"{name} must be a 1-D int32 tensor")
+        if not t.is_cuda or (dev is not None and t.device != dev):
+            raise ValueError(f"{name} must be on the GPU, on one device with the other operands (no CPU fallback)")
+    if ranks.device != unit_end.device:
+        raise ValueError(f"ranks_{which} and unit_end_{which} must be on one device")
+    ranks, unit_end = ranks.contiguous(), unit_end.contiguous()
+    E, n_units = ranks.numel(), unit_end.numel()
+    if not 1 <= n_units <= hip.BOOT_MAX_UNITS or (U is not None and n_units != U):
+        raise ValueError(f"unit_end_{which} must hold the same 1 to 2^24 units as the other ranking, got {n_units}")
+    if E and (int(ranks.min()) < 0 or int(ranks.max()) >= hip.BOOT_RANK_LIMIT):
+        raise ValueError(f"ranks_{which} must lie in [0, 2^30)")
+    ends = unit_end.to(torch.int64)
+    size = torch.diff(ends, prepend=ends.new_full((1,), -1))
+    if int(size.min()) < 0 or int(ends[-1]) != E - 1:
+        raise ValueError(f"unit_end_{which} must be non-decreasing from -1 and end at E - 1 = {E - 1}")
+    if n_units * int(size.max()) >= 1 << 32:
+        raise ValueError(f"ranking {which}: a resample could hold 2^32 entries or more (units times the largest unit)")
+    if E == 0:
+        ranks = torch.zeros((1,), dtype=torch.int32, device=ranks.device)        # never read: a pointer for the entry point
+    return ranks, unit_end, E
+
+
+def bootstrap_rank_stats(ranks_a, unit_end_a, ranks_b=None, unit_end_b=None, cuts=(1, 5, 10, 50), seed=0, b0=0, n_boot=1000):
+    """int64 [n_boot, V, 4 + K] on the device (nr_bootstrap_rank_stats): for resamples b0 .. b0 + n_boot - 1 of the U units drawn
+    with replacement and ranking v (V = 2 with ranks_b / unit_end_b, paired: the same draws), over the entries of the drawn units:
+    n, the sum of ranks, the order statistics at positions (n - 1) // 2 and n // 2 (-1 when n = 0) and #{r < cuts[k]}.  ranks_v
+    [E_v] int32 in [0, 2^30); unit_end_v [U] int32 = the index of the last entry of unit u (non-decreasing, from -1, ends at
+    E_v - 1).  The result depends on (seed, b, inputs) alone."""
+    cuts = _boot_cuts(cuts)
+    if (ranks_b is None) != (unit_end_b is None):
+        raise ValueError("ranks_b and unit_end_b come together")
+    for name, v in (("seed", seed), ("b0", b0), ("n_boot", n_boot)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    seed, b0, n_boot = int(seed), int(b0), int(n_boot)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must lie in [0, 2^64), got {seed}")
+    if b0 < 0 or n_boot < 0 or b0 + n_boot > (1 << 31) - 1:
+        raise ValueError(f"b0 and n_boot must be >= 0 with b0 + n_boot <= 2^31 - 1, got {b0} and {n_boot}")
+    ra, ea, E_a = _boot_ranking(ranks_a, unit_end_a, "a")
+    U = ea.numel()
+    rb = eb = None
+    E_b = 0
+    if ranks_b is not None:
+        rb, eb, E_b = _boot_ranking(ranks_b, unit_end_b, "b", ra.device, U)
+    V = 1 if rb is None else 2
+    K = len(cuts)
+    out = torch.empty((n_boot, V, 4 + K), dtype=torch.int64, device=ra.device)
+    if n_boot:
+        import ctypes
+        hip.call("nr_bootstrap_rank_stats", hip.ptr(ra), hip.ptr(ea), E_a, hip.ptr(rb, allow_none=True), hip.ptr(eb, allow_none=True),
+                 E_b, U, (ctypes.c_int32 * K)(*cuts), K, ctypes.c_uint64(seed), b0, n_boot, hip.ptr(out), hip.stream_ptr())
+    return out
+
+
 def linear_x3(x, w, bias=None, residual=None):
     """Y = X W^T (+ bias) (+ residual) on the split-bf16 MFMA tile engine (nr_linear_x3): x [M,K], w [N,K] fp32, K padded to
     a multiple of 64 with zeros.  ~fp32-grade products (3 bf16 passes); used for the clustering GEMMs and for the

@@ -164,6 +164,11 @@ def eval_epoch(args, model, test_dataloader, device):
                             test_norm_label)
     from .evaluator import _check_local_scaling, local_scaling_label, sharded_metrics_with_local_scaling
     from .evaluator import _check_mutual_proximity, mutual_proximity_label, sharded_metrics_with_mutual_proximity
+    from .evaluator import _check_bootstrap
+    # bootstrap confidence intervals (DESIGN.md "Bootstrap confidence intervals"): checked before any work
+    boot = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
+                bootstrap_level=getattr(args, "bootstrap_level", 0.95))
+    _check_bootstrap(boot["bootstrap"], boot["bootstrap_seed"], boot["bootstrap_level"])
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
     test_norm = getattr(args, "test_norm", None) or "none"
     local_scaling = getattr(args, "local_scaling", None) or "none"
@@ -208,17 +213,17 @@ def eval_epoch(args, model, test_dataloader, device):
             toc1 = time.time()
             if test_norm != "none":
                 t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args,
-                                                          cut_off_points=cut_off_points, **norm)
+                                                          cut_off_points=cut_off_points, **norm, **boot)
             elif local_scaling != "none":
                 t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args,
-                                                              cut_off_points=cut_off_points, **scaling)
+                                                              cut_off_points=cut_off_points, **scaling, **boot)
             elif mutual_proximity != "none":
                 t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args,
-                                                                 cut_off_points=cut_off_points, **proximity)
+                                                                 cut_off_points=cut_off_points, **proximity, **boot)
             elif hubness_k:
-                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, cut_off_points)
+                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, cut_off_points, **boot)
             else:
-                t2v, v2t = sharded_multi_sentence_metrics(model, tf, vf, tm.float(), vm.float(), cut_off_points, args)
+                t2v, v2t = sharded_multi_sentence_metrics(model, tf, vf, tm.float(), vm.float(), cut_off_points, args, **boot)
         else:
             ind, tf, tm, vf, vm = _cache_features(model, test_dataloader, device, separate=False)
             if int(getattr(args, "world_size", 1)) > 1 and dist.is_initialized():
@@ -227,15 +232,15 @@ def eval_epoch(args, model, test_dataloader, device):
                 tf, vf, tm, vm = dataset_order(tf, vf, ind, tm, vm)
             toc1 = time.time()
             if test_norm != "none":
-                t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args, **norm)
+                t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args, **norm, **boot)
             elif local_scaling != "none":
-                t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args, **scaling)
+                t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args, **scaling, **boot)
             elif mutual_proximity != "none":
-                t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args, **proximity)
+                t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args, **proximity, **boot)
             elif hubness_k:
-                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k)
+                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, **boot)
             else:
-                t2v, v2t = sharded_metrics(model, tf, vf, tm.float(), vm.float(), args)
+                t2v, v2t = sharded_metrics(model, tf, vf, tm.float(), vm.float(), args, **boot)
     toc2 = time.time()
     if is_main_process() and logger is not None:
         logger.info("Evaluation timing breakdown:")
@@ -245,6 +250,16 @@ def eval_epoch(args, model, test_dataloader, device):
         logger.info("EVALUATION RESULTS")
         logger.info("=" * 80)
         tracker.log_current_metrics(t2v, v2t, (t2v["R1"] + v2t["R1"]) / 2)
+
+        def log_bootstrap(nt, nv, tag=""):
+            """The interval line of each direction after its metrics line, and for a correction the paired line against raw."""
+            if not boot["bootstrap"]:
+                return
+            for side, m in (("Text-to-Video", nt), ("Video-to-Text", nv)):
+                tracker.log_bootstrap(m["bootstrap"], prefix=f"{side} {tag}".rstrip() + ": ")
+                if "bootstrap_vs_raw" in m:
+                    tracker.log_bootstrap(m["bootstrap_vs_raw"], prefix=f"{side} {tag} - raw: ")
+        log_bootstrap(t2v, v2t)
         if hubness_k:
             tracker.log_hubness(t2v["hubness"], prefix="Text-to-Video ")
             tracker.log_hubness(v2t["hubness"], prefix="Video-to-Text ")
@@ -252,6 +267,7 @@ def eval_epoch(args, model, test_dataloader, device):
             tag = test_norm_label(test_norm, t2v["test_norm"]["beta"], t2v["test_norm"].get("iters"))
             tracker.print_metrics(t2v["test_norm"], prefix=f"Text-to-Video {tag}: ")
             tracker.print_metrics(v2t["test_norm"], prefix=f"Video-to-Text {tag}: ")
+            log_bootstrap(t2v["test_norm"], v2t["test_norm"], tag)
             if "marginal_err" in t2v["test_norm"]:
                 logger.info(f"{tag} marginal error after {t2v['test_norm']['iters']} iterations: "
                             f"{t2v['test_norm']['marginal_err']:.3e} / {v2t['test_norm']['marginal_err']:.3e}")
@@ -262,6 +278,7 @@ def eval_epoch(args, model, test_dataloader, device):
             tag = local_scaling_label(local_scaling, ls_k, ls_bank)
             tracker.print_metrics(t2v["local_scaling"], prefix=f"Text-to-Video {tag}: ")
             tracker.print_metrics(v2t["local_scaling"], prefix=f"Video-to-Text {tag}: ")
+            log_bootstrap(t2v["local_scaling"], v2t["local_scaling"], tag)
             if hubness_k:
                 tracker.log_hubness(t2v["local_scaling"]["hubness"], prefix=f"Text-to-Video {tag} ")
                 tracker.log_hubness(v2t["local_scaling"]["hubness"], prefix=f"Video-to-Text {tag} ")
@@ -269,6 +286,7 @@ def eval_epoch(args, model, test_dataloader, device):
             tag = mutual_proximity_label(mutual_proximity, mp_bank)
             tracker.print_metrics(t2v["mutual_proximity"], prefix=f"Text-to-Video {tag}: ")
             tracker.print_metrics(v2t["mutual_proximity"], prefix=f"Video-to-Text {tag}: ")
+            log_bootstrap(t2v["mutual_proximity"], v2t["mutual_proximity"], tag)
             if hubness_k:
                 tracker.log_hubness(t2v["mutual_proximity"]["hubness"], prefix=f"Text-to-Video {tag} ")
                 tracker.log_hubness(v2t["mutual_proximity"]["hubness"], prefix=f"Video-to-Text {tag} ")
