@@ -898,6 +898,34 @@ int nr_bootstrap_rank_stats(const int32_t* ranks_a, const int32_t* unit_end_a, i
                             const int32_t* unit_end_b, int E_b, int U, const int32_t* cuts, int K, uint64_t seed, int b0, int n_boot,
                             int64_t* out, void* stream);
 
+/* Ranks of every relevant (sentence, video) pair from a row slab (DESIGN.md "Rank-aware IR metrics"; the reference has no code for
+ * it).  M_slab [n_rows, V] = rows [row0, row0 + n_rows) of the n_total x V matrix being ranked (rows: sentences, columns: videos);
+ * group_end [V] DEVICE int32: video g owns the rows [group_end[g-1], group_end[g]) (nr_group_slab_ranks's convention; increasing,
+ * group_end[0] > 0, group_end[V-1] = n_total; the kernels stay in bounds whatever it holds, the caller checks it); pair s = (row s, column g(s));
+ * own [n_total] DEVICE fp32 = M[s, g(s)], gathered by the caller.  Entry x at index i of a line is AHEAD of pair s when x > own[s], or
+ * x == own[s] and i is lower than the pair's own index on that line (IEEE compares: -0.0 == +0.0, a NaN entry is never ahead).  A
+ * pair whose own[s] is NaN or infinite is unranked.
+ *   row_rank [n_rows]   = entries of row row0 + i ahead of its pair (index: the column, own index g(s)): the complete text->video
+ *                         rank, 0-based; -1 when unranked.  May be NULL.
+ *   col_ahead [n_total] = THIS SLAB's rows ahead of pair s in column g(s) (index: the global row, own index s); 0 when unranked.
+ *                         Overwritten, not accumulated: the sum over the slabs of a split is the video->text rank of sentence s among
+ *                         all sentences.  May be NULL.
+ * Row side: one wave per row, one pass.  Column side: a workgroup per 64 pairs, own[s] in registers, its four waves stream
+ * interleaved rows of column g(s) past it (element stride V) and add their counts in LDS.  Integers only, no atomics, one writer
+ * per output: a function of the inputs alone.
+ * NR_EINVAL before any launch: a null required pointer, a negative extent, V < 1, row0 + n_rows > n_total.  n_rows = 0: NR_OK,
+ * col_ahead is zeroed, M_slab may be NULL. */
+int nr_pair_ranks(const float* M_slab, int n_rows, int V, int row0, int n_total, const int32_t* group_end, const float* own,
+                  int32_t* row_rank, int32_t* col_ahead, void* stream);
+
+/* Bootstrap of per-unit sums (DESIGN.md "Rank-aware IR metrics"): values [U, Q] int64 row-major, U in [1, 2^24], Q in [1, 16];
+ *   out[i, q] = sum over t < U of values[u(b0 + i, t), q],   out [n_boot, Q] int64,
+ * with exactly the draws u(b, t) of nr_bootstrap_rank_stats: resample b is the same multiset of units in both entry points.  One
+ * workgroup per resample, int64 sums in registers, combined by wave shuffles and through LDS; nothing is stored per resample, no
+ * global atomics: the result depends on (seed, b, inputs) alone.  The caller keeps U max|value| below 2^62.  NR_EINVAL before any
+ * launch: U or Q out of range, b0 < 0, n_boot < 0, b0 + n_boot > 2^31 - 1, a null pointer; n_boot = 0: NR_OK, no launch. */
+int nr_bootstrap_unit_sums(const int64_t* values, int U, int Q, uint64_t seed, int b0, int n_boot, int64_t* out, void* stream);
+
 /* Multi-tensor BertAdam step (models/optimization.py:76-211 with the trainer's clip and clamp around it, trainer.py:104-119;
  * DESIGN.md "BertAdam in the captured step").  fp32 tensors only.  Per step, for every table entry t with group q:
  *   c    = min(1, global_max_norm / (sqrt(sum_t ||g_t||^2) + 1e-6))             (global_max_norm <= 0: c = 1)

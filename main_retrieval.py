@@ -125,6 +125,10 @@ def get_args():
     p.add_argument("--bootstrap_seed", type=int, default=0,
                    help="--bootstrap: seed of the counter-based draws (text->video uses it, video->text seed + 1)")
     p.add_argument("--bootstrap_level", type=float, default=0.95, help="--bootstrap: coverage of the intervals, in (0, 1)")
+    p.add_argument("--ir_metrics", type=int, default=0, choices=[0, 1],
+                   help="1: the rank-aware IR metrics MRR, mAP, nDCG@10 and R-precision of every relevant (text, video) pair in both "
+                        "directions, next to R@K, for the raw ranking and for a correction; with --bootstrap their intervals too "
+                        "(DESIGN.md 6.8); 0 = off")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -539,11 +543,24 @@ def eval_epoch(args, model, test):
                                             sharded_metrics_with_test_norm, test_norm_label)
     from neighborretr_amd.evaluator import local_scaling_label, sharded_metrics_with_local_scaling
     from neighborretr_amd.evaluator import mutual_proximity_label, sharded_metrics_with_mutual_proximity
-    from neighborretr_amd.evaluator import _check_bootstrap
+    from neighborretr_amd.evaluator import _check_bootstrap, _check_ir
     from neighborretr_amd.metrics import RetrievalMetrics
     boot = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
                 bootstrap_level=getattr(args, "bootstrap_level", 0.95))
     _check_bootstrap(boot["bootstrap"], boot["bootstrap_seed"], boot["bootstrap_level"])         # before any work
+    ir = _check_ir(getattr(args, "ir_metrics", 0) or 0)                                          # before any work
+    extras = dict(boot, ir=ir)                                                                   # what every evaluator call takes
+
+    def log_ir(nt, nv, tag=""):
+        """The IR line of each direction (MRR, mAP, nDCG@10, R-Prec) and its interval lines."""
+        if not ir:
+            return
+        for side, m in (("text->video", nt), ("video->text", nv)):
+            prefix = f"{side} {tag}".rstrip() + ": "
+            log(args, RetrievalMetrics.format_ir(m["ir"], prefix=prefix))
+            for key in ("bootstrap", "bootstrap_vs_raw"):
+                if key in m["ir"]:
+                    log(args, RetrievalMetrics.format_ir_bootstrap(m["ir"][key], prefix=prefix))
 
     def log_bootstrap(nt, nv, tag=""):
         """The interval line of each direction after its metrics line, and for a correction the paired line against raw."""
@@ -569,21 +586,22 @@ def eval_epoch(args, model, test):
         t, v, tm, vm = gather_eval_features(t, v, mine.to(dev), tm, vm, args)
     if test_norm != "none":
         t2v, v2t = sharded_metrics_with_test_norm(model, t, v, tm.float(), vm.float(), args, test_norm, args.test_norm_beta,
-                                                  qb_k=args.qb_k, hubness_k=hubness_k, n_iter=args.test_norm_iters, **boot)
+                                                  qb_k=args.qb_k, hubness_k=hubness_k, n_iter=args.test_norm_iters, **extras)
     elif local_scaling != "none":
         t2v, v2t = sharded_metrics_with_local_scaling(model, t, v, tm.float(), vm.float(), args, local_scaling,
                                                       k=args.local_scaling_k, bank=bool(args.local_scaling_bank),
-                                                      hubness_k=hubness_k, **boot)
+                                                      hubness_k=hubness_k, **extras)
     elif mutual_proximity != "none":
         t2v, v2t = sharded_metrics_with_mutual_proximity(model, t, v, tm.float(), vm.float(), args, mutual_proximity,
-                                                         bank=bool(args.mutual_proximity_bank), hubness_k=hubness_k, **boot)
+                                                         bank=bool(args.mutual_proximity_bank), hubness_k=hubness_k, **extras)
     elif hubness_k:
-        t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k, **boot)
+        t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k, **extras)
     else:
-        t2v, v2t = sharded_metrics(model, t, v, tm.float(), vm.float(), args, **boot)
+        t2v, v2t = sharded_metrics(model, t, v, tm.float(), vm.float(), args, **extras)
     log(args, f"text->video R@1 {t2v['R1']:.1f} R@5 {t2v['R5']:.1f} R@10 {t2v['R10']:.1f} MedR {t2v['MR']:.1f} | "
               f"video->text R@1 {v2t['R1']:.1f} R@5 {v2t['R5']:.1f} R@10 {v2t['R10']:.1f} MedR {v2t['MR']:.1f}")
     log_bootstrap(t2v, v2t)
+    log_ir(t2v, v2t)
     if hubness_k:
         from neighborretr_amd.metrics import RetrievalMetrics
         log(args, RetrievalMetrics.format_hubness(t2v["hubness"], prefix="text->video "))
@@ -595,6 +613,7 @@ def eval_epoch(args, model, test):
         log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
         log_bootstrap(nt, nv, tag)
+        log_ir(nt, nv, tag)
         if hubness_k:
             log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
@@ -607,6 +626,7 @@ def eval_epoch(args, model, test):
         log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
         log_bootstrap(nt, nv, tag)
+        log_ir(nt, nv, tag)
         if hubness_k:
             log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
@@ -617,6 +637,7 @@ def eval_epoch(args, model, test):
         log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
         log_bootstrap(nt, nv, tag)
+        log_ir(nt, nv, tag)
         if hubness_k:
             log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))

@@ -248,3 +248,52 @@ extern "C" int nr_bootstrap_rank_stats(const int32_t* ranks_a, const int32_t* un
     NR_LAUNCH_CHECK();
     return NR_OK;
 }
+
+// ---- bootstrap of per-unit sums (DESIGN.md "Rank-aware IR metrics") --------------------------------------------------------------
+// out[b, q] = sum over t < U of values[u(b, t), q] with the draws u(b, t) of the kernel above (nr_boot_draw): resample b is the same
+// multiset of units in both.  One workgroup per resample; every thread keeps its Q <= 16 sums in int64 registers, the waves combine
+// by shuffles, the workgroup through LDS.  Nothing is stored per resample, no atomics: a function of (seed, b, inputs) alone.
+#define NR_BOOT_MAX_COLS 16
+
+__global__ __launch_bounds__(NR_BOOT_THREADS) void nr_bootstrap_unit_sums_kernel(const int64_t* __restrict__ values, uint32_t U, int Q,
+                                                                                 uint64_t seed, uint32_t b0,
+                                                                                 int64_t* __restrict__ out) {
+    __shared__ int64_t red[NR_BOOT_WAVES][NR_BOOT_MAX_COLS];
+    const int tid = threadIdx.x, lane = tid & (NR_WAVE - 1), wave = tid / NR_WAVE;
+    const uint64_t b = (uint64_t)b0 + blockIdx.x;
+    const uint64_t base = seed + ((b << 32) + 1ull) * NR_BOOT_GOLDEN;
+    int64_t acc[NR_BOOT_MAX_COLS];
+#pragma unroll
+    for (int q = 0; q < NR_BOOT_MAX_COLS; ++q) acc[q] = 0;
+    for (int t = tid; t < (int)U; t += NR_BOOT_THREADS) {
+        const int64_t* row = values + (size_t)nr_boot_draw(base, t, U) * Q;
+#pragma unroll
+        for (int q = 0; q < NR_BOOT_MAX_COLS; ++q)
+            if (q < Q) acc[q] += row[q];
+    }
+#pragma unroll
+    for (int q = 0; q < NR_BOOT_MAX_COLS; ++q) acc[q] = nr_boot_wave_sum(acc[q]);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NR_BOOT_MAX_COLS; ++q) red[wave][q] = acc[q];
+    }
+    __syncthreads();
+    if (tid < Q) {
+        int64_t s = 0;
+#pragma unroll
+        for (int w = 0; w < NR_BOOT_WAVES; ++w) s += red[w][tid];
+        out[(size_t)blockIdx.x * Q + tid] = s;
+    }
+}
+
+extern "C" int nr_bootstrap_unit_sums(const int64_t* values, int U, int Q, uint64_t seed, int b0, int n_boot, int64_t* out,
+                                      void* stream) {
+    if (U < 1 || U > NR_BOOT_MAX_UNITS || Q < 1 || Q > NR_BOOT_MAX_COLS) return NR_EINVAL;
+    if (b0 < 0 || n_boot < 0 || (int64_t)b0 + n_boot > 2147483647ll) return NR_EINVAL;
+    if (!values || !out) return NR_EINVAL;
+    if (n_boot == 0) return NR_OK;
+    hipLaunchKernelGGL(nr_bootstrap_unit_sums_kernel, dim3((unsigned)n_boot), dim3(NR_BOOT_THREADS), 0, (hipStream_t)stream, values,
+                       (uint32_t)U, Q, seed, (uint32_t)b0, out);
+    NR_LAUNCH_CHECK();
+    return NR_OK;
+}

@@ -135,10 +135,14 @@ def _ranks_from_slab(S_slab, N, W, rank):
     return gt.astype(np.int64), et.astype(np.int64), cols[0].astype(np.int64), cols[1].astype(np.int64)
 
 
-def sharded_metrics(model, text_feat, video_feat, text_mask, video_mask, args, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95):
+def sharded_metrics(model, text_feat, video_feat, text_mask, video_mask, args, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95,
+                    ir=False):
     """(text->video metrics, video->text metrics) as RetrievalMetrics.compute_metrics(S) / (S.T) would give them.  bootstrap > 0:
-    each with a "bootstrap" entry (DESIGN.md "Bootstrap confidence intervals")."""
+    each with a "bootstrap" entry (DESIGN.md "Bootstrap confidence intervals").  ir: each with an "ir" entry (DESIGN.md "Rank-aware
+    IR metrics")."""
     boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    if _check_ir(ir):
+        return _raw_metrics_with_ir(model, text_feat, video_feat, text_mask, video_mask, args, None, 256, boot)
     gt, et, gv, ev = sharded_retrieval_ranks(model, text_feat, video_feat, text_mask, video_mask, args)
     units = _query_units(gt, et), _query_units(gv, ev)
     t2v, v2t = (RetrievalMetrics.metrics_from_ranks(u[0]) for u in units)
@@ -146,8 +150,23 @@ def sharded_metrics(model, text_feat, video_feat, text_mask, video_mask, args, b
     return t2v, v2t
 
 
+def _raw_metrics_with_ir(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk, boot):
+    """The raw dictionaries of both directions with their "ir" entries (and "bootstrap" ones), from one scoring of the slab.
+
+    Why ir leaves the callers' plain route: the pair ranks are counted over the slab itself, and sharded_retrieval_ranks and the
+    multi-sentence body drop their slab once its ranks are out; scoring it a second time would double the evaluation's cost.  So
+    this route keeps the slab and takes the R@K dictionaries from _metrics_and_units, the route every correction already takes for
+    its raw entry (and the multi-sentence body itself with a bootstrap).  Both routes rank with the same slab helpers
+    (_ranks_from_slab, _multi_sentence_ranks); tests/test_irmetrics_gpu.py holds their dictionaries equal key for key."""
+    S_slab, n_rows, n_cols, W, rank, ends = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    t2v, v2t, units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
+    _add_bootstrap(t2v, v2t, units, boot, S_slab.device)
+    _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot)
+    return t2v, v2t
+
+
 def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, video_mask, cut_off_points, args, chunk=256, bootstrap=0,
-                                   bootstrap_seed=0, bootstrap_level=0.95):
+                                   bootstrap_seed=0, bootstrap_level=0.95, ir=False):
     """Several captions per video (evaluator.py:114-149 features, :225-262 metrics): text_feat [Ns,...] holds every
     sentence in dataset order, video_feat [V,...] one entry per video, cut_off_points[g] = index of the LAST sentence of
     video g (the dataset's cut_off_points minus one, evaluator.py:98).  -> (text->video, video->text) metric dictionaries.
@@ -156,8 +175,11 @@ def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, vide
     (metrics.py:82-126) and a max over the padded axis (:128-148).  Here rank r scores its slab of sentence rows, one
     launch (nr_group_slab_ranks) gives every row's rank and the slab's per-video best scores, and a MAX all-reduce of
     the V x V best-score matrix + an all-gather of the Ns ranks complete them; no padded tensor exists.  bootstrap > 0: each
-    dictionary gains a "bootstrap" entry that resamples VIDEOS (DESIGN.md "Bootstrap confidence intervals")."""
+    dictionary gains a "bootstrap" entry that resamples VIDEOS (DESIGN.md "Bootstrap confidence intervals").  ir: each gains an "ir"
+    entry (DESIGN.md "Rank-aware IR metrics")."""
     boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    if _check_ir(ir):
+        return _raw_metrics_with_ir(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk, boot)
     W = _world(args)
     rank = comm.get_rank() if W > 1 else 0
     Ns, V = text_feat.shape[0], video_feat.shape[0]
@@ -331,16 +353,19 @@ def sharded_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k
 
 
 def sharded_metrics_with_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k, cut_off_points=None, chunk=256,
-                                 bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95):
+                                 bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, ir=False):
     """sharded_metrics (cut_off_points None) or sharded_multi_sentence_metrics, plus a "hubness" entry in each dictionary
-    (sharded_hubness), from ONE scoring of this rank's slab.  bootstrap > 0: a "bootstrap" entry too."""
+    (sharded_hubness), from ONE scoring of this rank's slab.  bootstrap > 0: a "bootstrap" entry too; ir: an "ir" entry too."""
     boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    ir = _check_ir(ir)
     S_slab, n_rows, n_cols, W, rank, ends = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points,
                                                        chunk)
     ops._check_k(k)
     t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
     t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, int(k), W, rank, ends)
     _add_bootstrap(t2v, v2t, raw_units, boot, S_slab.device)
+    if ir:
+        _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot)
     return t2v, v2t
 
 
@@ -685,11 +710,13 @@ def sharded_normalised_metrics(model, text_feat, video_feat, text_mask, video_ma
 
 def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None,
                                    qb_k=1, hubness_k=0, cut_off_points=None, chunk=256, n_iter=50, bootstrap=0, bootstrap_seed=0,
-                                   bootstrap_level=0.95):
+                                   bootstrap_level=0.95, ir=False):
     """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
     each with one more entry "test_norm" = sharded_normalised_metrics, from ONE scoring of this rank's slab.  bootstrap > 0: the
-    raw dictionaries gain "bootstrap", the "test_norm" ones "bootstrap" and "bootstrap_vs_raw" (paired on the same draws)."""
+    raw dictionaries gain "bootstrap", the "test_norm" ones "bootstrap" and "bootstrap_vs_raw" (paired on the same draws).  ir: the
+    raw and the "test_norm" dictionaries gain "ir" (DESIGN.md "Rank-aware IR metrics"), with the same bootstrap entries inside."""
     boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    ir = _check_ir(ir)
     beta, qb_k, hubness_k = _check_test_norm(mode, beta, qb_k, hubness_k)
     n_iter = _check_n_iter(n_iter)
     if mode in BANK_MODES:
@@ -699,6 +726,7 @@ def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, vide
     t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
     if hubness_k:
         t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    raw_columns = _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot) if ir else None
     info = {}
     T, V = _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
                                       chunk, n_iter, info)
@@ -707,6 +735,8 @@ def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, vide
     nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k, units)
     _add_bootstrap(t2v, v2t, raw_units, boot, T.device)
     _add_bootstrap(nt, nv, units, boot, T.device, raw_units)
+    if ir:
+        _add_ir(nt, nv, T, V, n_rows, n_cols, W, rank, ends, boot, raw_columns)
     t2v["test_norm"] = _test_norm_entry(nt, mode, beta, qb_k, info, 0)
     v2t["test_norm"] = _test_norm_entry(nv, mode, beta, qb_k, info, 1)
     return t2v, v2t
@@ -809,11 +839,13 @@ def sharded_local_scaled_metrics(model, text_feat, video_feat, text_mask, video_
 
 def sharded_metrics_with_local_scaling(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False,
                                        querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0, bootstrap_seed=0,
-                                       bootstrap_level=0.95):
+                                       bootstrap_level=0.95, ir=False):
     """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
     each with one more entry "local_scaling" = sharded_local_scaled_metrics, from ONE scoring of this rank's slab.  bootstrap > 0:
-    the raw dictionaries gain "bootstrap", the "local_scaling" ones "bootstrap" and "bootstrap_vs_raw" (paired on the same draws)."""
+    the raw dictionaries gain "bootstrap", the "local_scaling" ones "bootstrap" and "bootstrap_vs_raw" (paired on the same draws).
+    ir: the raw and the "local_scaling" dictionaries gain "ir" (DESIGN.md "Rank-aware IR metrics")."""
     boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    ir = _check_ir(ir)
     k, hubness_k = _check_local_scaling(mode, k, hubness_k)
     if bank:
         _querybank(model, querybank, text_feat.device)
@@ -822,12 +854,15 @@ def sharded_metrics_with_local_scaling(model, text_feat, video_feat, text_mask, 
     t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
     if hubness_k:
         t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    raw_columns = _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot) if ir else None
     T = _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk)
     del S_slab, slab
     units = []
     nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k, units)
     _add_bootstrap(t2v, v2t, raw_units, boot, T.device)
     _add_bootstrap(nt, nv, units, boot, T.device, raw_units)
+    if ir:
+        _add_ir(nt, nv, T, T, n_rows, n_cols, W, rank, ends, boot, raw_columns)
     t2v["local_scaling"] = _local_scaling_entry(nt, mode, k, bank)
     v2t["local_scaling"] = _local_scaling_entry(nv, mode, k, bank)
     return t2v, v2t
@@ -971,12 +1006,13 @@ def sharded_mutual_proximity_metrics(model, text_feat, video_feat, text_mask, vi
 
 def sharded_metrics_with_mutual_proximity(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False,
                                           querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0,
-                                          bootstrap_seed=0, bootstrap_level=0.95):
+                                          bootstrap_seed=0, bootstrap_level=0.95, ir=False):
     """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
     each with one more entry "mutual_proximity" = sharded_mutual_proximity_metrics, from ONE scoring of this rank's slab.
     bootstrap > 0: the raw dictionaries gain "bootstrap", the "mutual_proximity" ones "bootstrap" and "bootstrap_vs_raw" (paired
-    on the same draws)."""
+    on the same draws).  ir: the raw and the "mutual_proximity" dictionaries gain "ir" (DESIGN.md "Rank-aware IR metrics")."""
     boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    ir = _check_ir(ir)
     hubness_k = _check_mutual_proximity(mode, hubness_k)
     if bank:
         _querybank(model, querybank, text_feat.device)
@@ -985,12 +1021,129 @@ def sharded_metrics_with_mutual_proximity(model, text_feat, video_feat, text_mas
     t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
     if hubness_k:
         t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    raw_columns = _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot) if ir else None
     T = _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk)
     del S_slab, slab
     units = []
     nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k, units)
     _add_bootstrap(t2v, v2t, raw_units, boot, T.device)
     _add_bootstrap(nt, nv, units, boot, T.device, raw_units)
+    if ir:
+        _add_ir(nt, nv, T, T, n_rows, n_cols, W, rank, ends, boot, raw_columns)
     t2v["mutual_proximity"] = _mutual_proximity_entry(nt, mode, bank)
     v2t["mutual_proximity"] = _mutual_proximity_entry(nv, mode, bank)
     return t2v, v2t
+
+
+# ---- rank-aware IR metrics: MRR, mAP, nDCG@10, R-precision (DESIGN.md "Rank-aware IR metrics") ------------------------------------
+# R@K ranks only the best caption of a video; these metrics need the rank of EVERY relevant (sentence, video) pair in both
+# directions.  Pair s is (row s, column g(s)).  rt[s] (text->video) is row-local.  rv[s] (video->text: the rank of sentence s among
+# all sentences in the column of its video) is a column count against the pair's own score, which lives on another rank's slab:
+# the own scores are gathered first (4 n_total bytes), every rank counts its rows ahead of every pair (nr_pair_ranks), and one
+# int32 SUM all-reduce (4 n_total bytes) completes the counts.  rt travels like the multi-sentence ranks: one int32 all-gather.
+
+def _check_ir(ir):
+    """ir as a bool: the flag of the public functions (--ir_metrics {0,1})."""
+    if isinstance(ir, (bool, np.bool_)):
+        return bool(ir)
+    if isinstance(ir, (int, np.integer)) and int(ir) in (0, 1):
+        return bool(ir)
+    raise ValueError(f"ir_metrics must be 0 or 1, got {ir!r}")
+
+
+def _pair_ends(n_rows, n_cols, ends):
+    """group_end of the pairs as int64 numpy: ends, or 1 .. N for a single-sentence set."""
+    if ends is None:
+        if n_rows != n_cols:
+            raise ValueError("single-sentence retrieval: one text per video expected")
+        return np.arange(1, n_rows + 1, dtype=np.int64)
+    return np.asarray(ends, dtype=np.int64)
+
+
+def _gathered_rows(mine, n_rows, W):
+    """[K, width] of this rank (row r0 + i at column i, width = ceil(n_rows / W)) -> [K, n_rows] of every rank's rows: one padded
+    all-gather, as the diagonal in _ranks_from_slab."""
+    K, width = mine.shape
+    if W == 1:
+        return mine[:, :n_rows].contiguous()
+    allv = torch.empty((W, K, width), dtype=mine.dtype, device=mine.device)
+    comm.all_gather_into_tensor(allv.view(-1), mine.reshape(-1))
+    return torch.cat([allv[r, :, :slab_bounds(n_rows, W, r)[1] - slab_bounds(n_rows, W, r)[0]] for r in range(W)], dim=1).contiguous()
+
+
+def _pair_ranks_from_slab(T_slab, V_slab, n_rows, n_cols, W, rank, ends):
+    """(rt, rv, ranked): int64 numpy [n_rows] each, identical on every rank.  rt[s] = the text->video rank of pair s from the rows
+    of T, rv[s] = its video->text rank among all sentences from the columns of V (each against its OWN matrix's scores), -1 where
+    the pair is unranked in that matrix; ranked = (rt >= 0) & (rv >= 0).  V_slab is T_slab: one kernel call gives both.  Three
+    collectives: the own scores (padded all-gather), rt (int32 all-gather), rv (int32 SUM all-reduce of the slabs' parts)."""
+    dev = T_slab.device
+    pair_ends = _pair_ends(n_rows, n_cols, ends)
+    group_end = torch.from_numpy(pair_ends.astype(np.int32)).to(dev)
+    r0, r1 = slab_bounds(n_rows, W, rank)
+    n = r1 - r0
+    width = -(-n_rows // W)
+    slabs = (T_slab,) if V_slab is T_slab else (T_slab, V_slab)
+    slabs = tuple(ops._slab_2d(M) for M in slabs)
+    mine = torch.full((len(slabs), width), float("nan"), dtype=torch.float32, device=dev)
+    if n:
+        cols = torch.from_numpy(np.searchsorted(pair_ends, np.arange(r0, r1), side="right")).to(dev)
+        rows = torch.arange(n, device=dev)
+        for k, M in enumerate(slabs):
+            mine[k, :n] = M[rows, cols]
+    own = _gathered_rows(mine, n_rows, W)
+    row_rank, col_ahead = ops.pair_ranks(slabs[0], r0, group_end, own[0].contiguous(), want_col=len(slabs) == 1)
+    if len(slabs) == 2:
+        _, col_ahead = ops.pair_ranks(slabs[1], r0, group_end, own[1].contiguous(), want_row=False)
+    if W > 1:
+        comm.all_reduce(col_ahead)                                        # the slabs' parts -> the whole column's count
+    rt_mine = torch.full((1, width), -1, dtype=torch.int32, device=dev)
+    rt_mine[0, :n] = row_rank
+    rt = _gathered_rows(rt_mine, n_rows, W)[0].cpu().numpy().astype(np.int64)
+    own_v = own[-1].cpu().numpy()
+    rv = np.where(np.isfinite(own_v), col_ahead.cpu().numpy().astype(np.int64), -1)
+    return rt, rv, (rt >= 0) & (rv >= 0)
+
+
+def _ir_bootstrap(columns, boot, seed, dev, raw_columns=None):
+    """{"bootstrap": summary of `columns`} and, with raw_columns, "bootstrap_vs_raw": both rankings' columns in ONE launch."""
+    n_boot, _, level = boot
+    both = columns if raw_columns is None else np.concatenate([columns, raw_columns], axis=1)
+    sums = ops.bootstrap_unit_sums(torch.from_numpy(np.ascontiguousarray(both)).to(dev), seed=seed, b0=0, n_boot=n_boot).cpu().numpy()
+    out = {"bootstrap": RetrievalMetrics.ir_bootstrap_summary(sums[:, :columns.shape[1]], columns, level)}
+    out["bootstrap"].update(seed=seed, columns=columns)
+    if raw_columns is not None:
+        out["bootstrap_vs_raw"] = RetrievalMetrics.ir_paired_bootstrap_summary(sums, columns, raw_columns, level)
+        out["bootstrap_vs_raw"]["seed"] = seed
+    return out
+
+
+def _ir_from_slab(T_slab, V_slab, n_rows, n_cols, W, rank, ends, boot=None, raw_columns=None):
+    """((text->video "ir", video->text "ir"), columns): the IR dictionaries of RetrievalMetrics.ir_from_ranks -- text->video: every
+    sentence a query, from the rows of T; video->text: every video a query over its sentences, from the columns of V -- and the two
+    directions' bootstrap columns (ir_unit_columns; the unit of a multi-sentence set is the video in both directions).  boot: each
+    gains "bootstrap" (seed for text->video, seed + 1 for video->text) and, with raw_columns, "bootstrap_vs_raw"."""
+    rt, rv, _ = _pair_ranks_from_slab(T_slab, V_slab, n_rows, n_cols, W, rank, ends)
+    groups = None if ends is None else np.asarray(ends, dtype=np.int64)
+    out = RetrievalMetrics.ir_from_ranks(rt), RetrievalMetrics.ir_from_ranks(rv, groups)
+    columns = RetrievalMetrics.ir_unit_columns(rt, None, groups), RetrievalMetrics.ir_unit_columns(rv, groups)
+    if boot:
+        for side in range(2):
+            out[side].update(_ir_bootstrap(columns[side], boot, boot[1] + side, T_slab.device,
+                                           None if raw_columns is None else raw_columns[side]))
+    return out, columns
+
+
+def _add_ir(t2v, v2t, T_slab, V_slab, n_rows, n_cols, W, rank, ends, boot, raw_columns=None):
+    """Puts "ir" into the two directions' dictionaries -> the bootstrap columns (a correction pairs with them)."""
+    (t2v["ir"], v2t["ir"]), columns = _ir_from_slab(T_slab, V_slab, n_rows, n_cols, W, rank, ends, boot, raw_columns)
+    return columns
+
+
+def sharded_ir_metrics(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points=None, bootstrap=0, bootstrap_seed=0,
+                       bootstrap_level=0.95, chunk=256):
+    """(text->video, video->text) IR dictionaries of the raw similarity, identical on every rank: MRR, mAP, nDCG10, RPrec (x 100),
+    n_queries, n_unranked and the rank of every relevant pair ("ranks": rt resp. rv, -1 where unranked).  cut_off_points as in
+    sharded_multi_sentence_metrics; None: a single-sentence set.  bootstrap > 0: each gains "bootstrap"."""
+    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    S_slab, n_rows, n_cols, W, rank, ends = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    return _ir_from_slab(S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot)[0]

@@ -245,6 +245,162 @@ class RetrievalMetrics:
         if self.logger is not None:
             self.logger.info(self.format_bootstrap(summary, prefix))
 
+    # ---- rank-aware IR metrics: MRR, mAP, nDCG@10, R-precision (DESIGN.md "Rank-aware IR metrics") --------------------------------
+    IR_METRICS = ("MRR", "mAP", "nDCG10", "RPrec")
+    IR_LABELS = {"MRR": "MRR", "mAP": "mAP", "nDCG10": "nDCG@10", "RPrec": "R-Prec"}
+    IR_FIXED_ONE = 1 << 32                                                # the fixed-point image of 1.0 in the bootstrap's columns
+
+    @staticmethod
+    def _ir_group_ends(group_end, n):
+        ends = np.asarray(group_end, dtype=np.int64).reshape(-1)
+        if len(ends) == 0 or ends[0] < 1 or (np.diff(ends) < 1).any() or ends[-1] != n:
+            raise ValueError(f"group_end must be positive, increasing and end at the {n} ranks")
+        return ends
+
+    @staticmethod
+    def _ir_queries(ranks, group_end=None):
+        """(values fp64 [n_slots, 4]: RR, AP, nDCG10, RPrec in [0, 1] of every query slot, zeros where the slot has no ranked pair;
+        valid bool [n_slots]).  group_end None: every entry of `ranks` is a query with one relevant item (m = 1); otherwise slot g
+        is the query of the entries [group_end[g-1], group_end[g]).  ranks < 0 are unranked pairs."""
+        ranks = np.asarray(ranks, dtype=np.int64).reshape(-1)
+        if group_end is None:
+            valid = ranks >= 0
+            r = np.where(valid, ranks, 0).astype(np.float64)
+            rr = np.where(valid, 1.0 / (r + 1.0), 0.0)
+            ndcg = np.where(valid & (ranks < 10), 1.0 / np.log2(r + 2.0), 0.0)          # IDCG of m = 1 is 1 / log2(2) = 1
+            return np.stack([rr, rr, ndcg, (valid & (ranks == 0)).astype(np.float64)], axis=1), valid
+        ends = RetrievalMetrics._ir_group_ends(group_end, len(ranks))
+        values = np.zeros((len(ends), 4), dtype=np.float64)
+        valid = np.zeros((len(ends),), dtype=bool)
+        begin = 0
+        for g, end in enumerate(ends):
+            seg = ranks[begin:end]
+            begin = end
+            r = np.sort(seg[seg >= 0]).astype(np.float64)
+            m = len(r)
+            if m == 0:
+                continue
+            k = np.arange(1, m + 1, dtype=np.float64)
+            dcg = float(np.sum(1.0 / np.log2(r[r < 10] + 2.0)))
+            idcg = float(np.sum(1.0 / np.log2(k[:10] + 1.0)))
+            values[g] = (1.0 / (r[0] + 1.0), float(np.sum(k / (r + 1.0))) / m, dcg / idcg, float(np.sum(r < m)) / m)
+            valid[g] = True
+        return values, valid
+
+    @staticmethod
+    def ir_from_ranks(ranks, group_end=None):
+        """MRR, mAP, nDCG@10 and R-precision (means over the queries x 100, like R@K) from the 0-based ranks of the relevant
+        (sentence, video) pairs, < 0 where a pair is unranked.  group_end None: every pair is a query of its own (text->video, and
+        both directions of a single-sentence set); otherwise query g (a video) owns the pairs [group_end[g-1], group_end[g]) and
+        its ranks are distinct (video->text over all sentences).  Per query with sorted ranked ranks r_1 < ... < r_m:
+        RR = 1 / (r_1 + 1), AP = mean_k k / (r_k + 1), nDCG10 = sum_{r_k < 10} 1 / log2(r_k + 2) over sum_{k <= min(m, 10)}
+        1 / log2(k + 1), RPrec = #{r_k < m} / m.  A query without a ranked pair is dropped.  -> {"MRR", "mAP", "nDCG10", "RPrec",
+        "n_queries", "n_unranked" (pairs), "ranks" (int64, -1 for unranked pairs)}."""
+        ranks = np.asarray(ranks.cpu() if torch.is_tensor(ranks) else ranks, dtype=np.int64).reshape(-1)
+        values, valid = RetrievalMetrics._ir_queries(ranks, group_end)
+        n = int(valid.sum())
+        out = {name: float(values[valid, i].mean()) * 100 if n else float("nan") for i, name in enumerate(RetrievalMetrics.IR_METRICS)}
+        out.update(n_queries=n, n_unranked=int(np.sum(ranks < 0)), ranks=np.where(ranks < 0, -1, ranks))
+        return out
+
+    @staticmethod
+    def ir_unit_columns(ranks, group_end=None, unit_end=None):
+        """int64 [U, 5], the bootstrap's columns of one ranking: per resampling unit its query count and the sums over its queries
+        of int(rint(x 2^32)) for x = RR, AP, nDCG10, RPrec.  Queries as in ir_from_ranks; the unit is the query, or with unit_end
+        (group_end None: multi-sentence text->video) unit u owns the queries [unit_end[u-1], unit_end[u]).  A unit without a
+        ranked pair is a row of zeros."""
+        ranks = np.asarray(ranks.cpu() if torch.is_tensor(ranks) else ranks, dtype=np.int64).reshape(-1)
+        values, valid = RetrievalMetrics._ir_queries(ranks, group_end)
+        cols = np.concatenate([valid[:, None].astype(np.int64), np.rint(values * RetrievalMetrics.IR_FIXED_ONE).astype(np.int64)], axis=1)
+        if unit_end is None:
+            return cols
+        if group_end is not None:
+            raise ValueError("unit_end groups single-pair queries: it cannot be combined with group_end")
+        ends = RetrievalMetrics._ir_group_ends(unit_end, len(ranks))
+        run = np.concatenate([np.zeros((1, cols.shape[1]), dtype=np.int64), np.cumsum(cols, axis=0)])
+        return run[ends] - run[np.concatenate(([0], ends[:-1]))]
+
+    @staticmethod
+    def _ir_values(sums):
+        """({metric: 100 sum_fixed / (2^32 count), NaN where count = 0}, count) of rows (count, RR, AP, nDCG10, RPrec sums)."""
+        sums = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, dtype=np.int64)
+        if sums.ndim != 2 or sums.shape[1] != 1 + len(RetrievalMetrics.IR_METRICS):
+            raise ValueError(f"sums must be [n, {1 + len(RetrievalMetrics.IR_METRICS)}], got {sums.shape}")
+        count = sums[:, 0]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            vals = {name: np.where(count > 0, 100 * sums[:, 1 + i].astype(np.float64)
+                                   / (float(RetrievalMetrics.IR_FIXED_ONE) * count.astype(np.float64)), np.nan)
+                    for i, name in enumerate(RetrievalMetrics.IR_METRICS)}
+        return vals, count
+
+    @staticmethod
+    def ir_bootstrap_summary(sums, columns, level=0.95):
+        """Percentile bootstrap of one ranking's IR metrics: sums [n_boot, 5] int64 (ops.bootstrap_unit_sums of `columns`), columns
+        = ir_unit_columns.  Per resample with count > 0: metric = 100 sum_fixed / (2^32 count).  -> {"n_boot", "n_empty" (resamples
+        with count 0, dropped), "level", and per metric "point" (the formula on the columns' totals), "se", "lo", "hi" as in
+        bootstrap_summary}."""
+        level = RetrievalMetrics._check_level(level)
+        vals, count = RetrievalMetrics._ir_values(sums)
+        point, _ = RetrievalMetrics._ir_values(np.asarray(columns, dtype=np.int64).sum(axis=0, keepdims=True))
+        keep = count > 0
+        out = {"n_boot": int(len(count)), "n_empty": int(np.sum(~keep)), "level": level}
+        for name, x in vals.items():
+            out[name] = RetrievalMetrics._interval(x[keep], float(point[name][0]), level)
+        return out
+
+    @staticmethod
+    def ir_paired_bootstrap_summary(sums, columns, columns_raw, level=0.95):
+        """Paired bootstrap of "corrected minus raw": sums [n_boot, 10] int64 of ONE ops.bootstrap_unit_sums call on the corrected
+        ranking's columns next to the raw ranking's (the same draws).  The fields of ir_bootstrap_summary for the per-resample
+        differences, and per metric "frac_le0" / "frac_ge0".  A resample with count 0 in either ranking is dropped (n_empty)."""
+        level = RetrievalMetrics._check_level(level)
+        sums = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, dtype=np.int64)
+        q = 1 + len(RetrievalMetrics.IR_METRICS)
+        if sums.ndim != 2 or sums.shape[1] != 2 * q:
+            raise ValueError(f"paired sums must be [n_boot, {2 * q}] (corrected, then raw), got {sums.shape}")
+        a, na = RetrievalMetrics._ir_values(sums[:, :q])
+        b, nb = RetrievalMetrics._ir_values(sums[:, q:])
+        pa, _ = RetrievalMetrics._ir_values(np.asarray(columns, dtype=np.int64).sum(axis=0, keepdims=True))
+        pb, _ = RetrievalMetrics._ir_values(np.asarray(columns_raw, dtype=np.int64).sum(axis=0, keepdims=True))
+        keep = (na > 0) & (nb > 0)
+        out = {"n_boot": int(len(na)), "n_empty": int(np.sum(~keep)), "level": level}
+        for name in a:
+            d = a[name][keep] - b[name][keep]
+            out[name] = RetrievalMetrics._interval(d, float(pa[name][0] - pb[name][0]), level)
+            out[name]["frac_le0"] = float(np.mean(d <= 0)) if len(d) else float("nan")
+            out[name]["frac_ge0"] = float(np.mean(d >= 0)) if len(d) else float("nan")
+        return out
+
+    @staticmethod
+    def format_ir(ir, prefix=""):
+        return prefix + " - ".join(f"{RetrievalMetrics.IR_LABELS[name]} {ir[name]:.1f}" for name in RetrievalMetrics.IR_METRICS)
+
+    @staticmethod
+    def format_ir_bootstrap(summary, prefix=""):
+        """One line: every IR metric with its interval; a paired summary prints signed differences and frac_le0."""
+        paired = any(isinstance(v, dict) and "frac_le0" in v for v in summary.values())
+        parts = []
+        for name in RetrievalMetrics.IR_METRICS:
+            m = summary[name]
+            if paired:
+                parts.append(f"{RetrievalMetrics.IR_LABELS[name]} {m['point']:+.1f} [{m['lo']:+.1f}, {m['hi']:+.1f}] "
+                             f"frac<=0 {m['frac_le0']:.3f}")
+            else:
+                parts.append(f"{RetrievalMetrics.IR_LABELS[name]} {m['point']:.1f} [{m['lo']:.1f}, {m['hi']:.1f}]")
+        kind = "paired bootstrap vs raw" if paired else "bootstrap"
+        tail = f" ({100 * summary['level']:g}% {kind}, {summary['n_boot']} resamples"
+        tail += f", {summary['n_empty']} empty)" if summary["n_empty"] else ")"
+        return prefix + " - ".join(parts) + tail
+
+    def log_ir(self, ir, prefix=""):
+        """The IR line of one direction and, when present, its interval lines (silent without a logger)."""
+        if self.logger is None:
+            return
+        self.logger.info(self.format_ir(ir, prefix))
+        for key in ("bootstrap", "bootstrap_vs_raw"):
+            if key in ir:
+                self.logger.info(self.format_ir_bootstrap(ir[key], prefix))
+
     def print_metrics(self, metrics, prefix=""):
         msg = (f"{prefix}R@1: {metrics['R1']:.1f} - R@5: {metrics['R5']:.1f} - R@10: {metrics['R10']:.1f} - "
                f"R@50: {metrics.get('R50', 0.0):.1f} - Median R: {metrics['MR']:.1f} - Mean R: {metrics['MeanR']:.1f}")

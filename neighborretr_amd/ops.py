@@ -1372,6 +1372,70 @@ def bootstrap_rank_stats(ranks_a, unit_end_a, ranks_b=None, unit_end_b=None, cut
     return out
 
 
+def pair_ranks(M_slab, row0, group_end, own, want_row=True, want_col=True):
+    """(row_rank [n] int32 | None, col_ahead [n_total] int32 | None) of the row slab M[row0 : row0 + n, :] (nr_pair_ranks): pair s is
+    (row s, column g(s)) with group_end [V] int32 on the device (video g owns the rows [group_end[g-1], group_end[g]), increasing from
+    above 0 and ending at n_total: every video owns a sentence) and own [n_total] fp32 = M[s, g(s)].  row_rank: the complete 0-based text->video rank of the slab's pairs, -1
+    where own is NaN or infinite; col_ahead: this slab's part of every pair's video->text rank among all sentences (0 where
+    unranked): the sum over the slabs of a split is the rank.  group_end is checked on the device: ValueError."""
+    for name, t, dtype in (("M_slab", M_slab, torch.float32), ("group_end", group_end, torch.int32), ("own", own, torch.float32)):
+        if not torch.is_tensor(t) or t.dtype != dtype or not t.is_cuda:
+            raise ValueError(f"{name} must be a {dtype} tensor on the GPU (no CPU fallback)")
+    if M_slab.dim() != 2 or group_end.dim() != 1 or own.dim() != 1:
+        raise ValueError("M_slab must be [n, V], group_end [V] and own [n_total]")
+    if not (M_slab.device == group_end.device == own.device):
+        raise ValueError("M_slab, group_end and own must be on one device")
+    if isinstance(row0, bool) or int(row0) != row0:
+        raise ValueError(f"row0 must be an integer, got {row0!r}")
+    M_slab, group_end, own = M_slab.contiguous(), group_end.contiguous(), own.contiguous()
+    n, V = M_slab.shape
+    n_total, row0 = own.numel(), int(row0)
+    if V < 1 or group_end.numel() != V:
+        raise ValueError(f"group_end must hold one entry per column, got {group_end.numel()} for {V} columns")
+    if row0 < 0 or row0 + n > n_total:
+        raise ValueError(f"rows [{row0}, {row0 + n}) do not lie in the {n_total} pairs")
+    ends = group_end.to(torch.int64)
+    if int(ends[0]) < 1 or int(ends[-1]) != n_total or (V > 1 and int(torch.diff(ends).min()) < 1):
+        raise ValueError(f"group_end must be positive, increasing and end at n_total = {n_total}")
+    dev = M_slab.device
+    row_rank = torch.empty((n,), dtype=torch.int32, device=dev) if want_row else None
+    col_ahead = torch.empty((n_total,), dtype=torch.int32, device=dev) if want_col else None
+    if n_total:                                           # an empty slab has no storage: the entry point takes NULL for it
+        hip.call("nr_pair_ranks", hip.ptr(M_slab) if n else None, n, V, row0, n_total, hip.ptr(group_end), hip.ptr(own),
+                 hip.ptr(row_rank) if want_row and n else None, hip.ptr(col_ahead, allow_none=True), hip.stream_ptr())
+    return row_rank, col_ahead
+
+
+def bootstrap_unit_sums(values, seed=0, b0=0, n_boot=1000):
+    """int64 [n_boot, Q] on the device (nr_bootstrap_unit_sums): out[i, q] = the sum of values[u, q] over the U units u that resample
+    b0 + i draws with replacement -- the draws of bootstrap_rank_stats for the same (seed, b, U).  values [U, Q] int64 on the
+    device, U in [1, 2^24], Q in [1, 16], U max|value| < 2^62 (no sum can overflow)."""
+    if not torch.is_tensor(values) or values.dtype != torch.int64 or values.dim() != 2:
+        raise ValueError("values must be a 2-D int64 tensor [U, Q]")
+    if not values.is_cuda:
+        raise ValueError("values must be on the GPU (no CPU fallback)")
+    for name, v in (("seed", seed), ("b0", b0), ("n_boot", n_boot)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    seed, b0, n_boot = int(seed), int(b0), int(n_boot)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must lie in [0, 2^64), got {seed}")
+    if b0 < 0 or n_boot < 0 or b0 + n_boot > (1 << 31) - 1:
+        raise ValueError(f"b0 and n_boot must be >= 0 with b0 + n_boot <= 2^31 - 1, got {b0} and {n_boot}")
+    values = values.contiguous()
+    U, Q = values.shape
+    if not 1 <= U <= hip.BOOT_MAX_UNITS or not 1 <= Q <= hip.BOOT_MAX_COLS:
+        raise ValueError(f"values must be [U, Q] with U in [1, 2^24] and Q in [1, {hip.BOOT_MAX_COLS}], got {tuple(values.shape)}")
+    largest = max(int(values.max()), -int(values.min()))
+    if U * largest >= hip.BOOT_SUM_LIMIT:
+        raise ValueError(f"U max|value| = {U} x {largest} reaches 2^62: a resample's sum could overflow")
+    out = torch.empty((n_boot, Q), dtype=torch.int64, device=values.device)
+    if n_boot:
+        import ctypes
+        hip.call("nr_bootstrap_unit_sums", hip.ptr(values), U, Q, ctypes.c_uint64(seed), b0, n_boot, hip.ptr(out), hip.stream_ptr())
+    return out
+
+
 def linear_x3(x, w, bias=None, residual=None):
     """Y = X W^T (+ bias) (+ residual) on the split-bf16 MFMA tile engine (nr_linear_x3): x [M,K], w [N,K] fp32, K padded to
     a multiple of 64 with zeros.  ~fp32-grade products (3 bf16 passes); used for the clustering GEMMs and for the

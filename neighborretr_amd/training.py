@@ -164,11 +164,14 @@ def eval_epoch(args, model, test_dataloader, device):
                             test_norm_label)
     from .evaluator import _check_local_scaling, local_scaling_label, sharded_metrics_with_local_scaling
     from .evaluator import _check_mutual_proximity, mutual_proximity_label, sharded_metrics_with_mutual_proximity
-    from .evaluator import _check_bootstrap
+    from .evaluator import _check_bootstrap, _check_ir
     # bootstrap confidence intervals (DESIGN.md "Bootstrap confidence intervals"): checked before any work
     boot = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
                 bootstrap_level=getattr(args, "bootstrap_level", 0.95))
     _check_bootstrap(boot["bootstrap"], boot["bootstrap_seed"], boot["bootstrap_level"])
+    # rank-aware IR metrics (DESIGN.md "Rank-aware IR metrics"): checked before any work
+    ir = _check_ir(getattr(args, "ir_metrics", 0) or 0)
+    extras = dict(boot, ir=ir)                                        # what every evaluator call takes
     hubness_k = int(getattr(args, "hubness_k", 0) or 0)
     test_norm = getattr(args, "test_norm", None) or "none"
     local_scaling = getattr(args, "local_scaling", None) or "none"
@@ -213,17 +216,17 @@ def eval_epoch(args, model, test_dataloader, device):
             toc1 = time.time()
             if test_norm != "none":
                 t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args,
-                                                          cut_off_points=cut_off_points, **norm, **boot)
+                                                          cut_off_points=cut_off_points, **norm, **extras)
             elif local_scaling != "none":
                 t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args,
-                                                              cut_off_points=cut_off_points, **scaling, **boot)
+                                                              cut_off_points=cut_off_points, **scaling, **extras)
             elif mutual_proximity != "none":
                 t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args,
-                                                                 cut_off_points=cut_off_points, **proximity, **boot)
+                                                                 cut_off_points=cut_off_points, **proximity, **extras)
             elif hubness_k:
-                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, cut_off_points, **boot)
+                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, cut_off_points, **extras)
             else:
-                t2v, v2t = sharded_multi_sentence_metrics(model, tf, vf, tm.float(), vm.float(), cut_off_points, args, **boot)
+                t2v, v2t = sharded_multi_sentence_metrics(model, tf, vf, tm.float(), vm.float(), cut_off_points, args, **extras)
         else:
             ind, tf, tm, vf, vm = _cache_features(model, test_dataloader, device, separate=False)
             if int(getattr(args, "world_size", 1)) > 1 and dist.is_initialized():
@@ -232,15 +235,15 @@ def eval_epoch(args, model, test_dataloader, device):
                 tf, vf, tm, vm = dataset_order(tf, vf, ind, tm, vm)
             toc1 = time.time()
             if test_norm != "none":
-                t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args, **norm, **boot)
+                t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args, **norm, **extras)
             elif local_scaling != "none":
-                t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args, **scaling, **boot)
+                t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args, **scaling, **extras)
             elif mutual_proximity != "none":
-                t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args, **proximity, **boot)
+                t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args, **proximity, **extras)
             elif hubness_k:
-                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, **boot)
+                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, **extras)
             else:
-                t2v, v2t = sharded_metrics(model, tf, vf, tm.float(), vm.float(), args, **boot)
+                t2v, v2t = sharded_metrics(model, tf, vf, tm.float(), vm.float(), args, **extras)
     toc2 = time.time()
     if is_main_process() and logger is not None:
         logger.info("Evaluation timing breakdown:")
@@ -259,7 +262,15 @@ def eval_epoch(args, model, test_dataloader, device):
                 tracker.log_bootstrap(m["bootstrap"], prefix=f"{side} {tag}".rstrip() + ": ")
                 if "bootstrap_vs_raw" in m:
                     tracker.log_bootstrap(m["bootstrap_vs_raw"], prefix=f"{side} {tag} - raw: ")
+
+        def log_ir(nt, nv, tag=""):
+            """The IR line of each direction (MRR, mAP, nDCG@10, R-Prec) and its interval lines."""
+            if not ir:
+                return
+            for side, m in (("Text-to-Video", nt), ("Video-to-Text", nv)):
+                tracker.log_ir(m["ir"], prefix=f"{side} {tag}".rstrip() + ": ")
         log_bootstrap(t2v, v2t)
+        log_ir(t2v, v2t)
         if hubness_k:
             tracker.log_hubness(t2v["hubness"], prefix="Text-to-Video ")
             tracker.log_hubness(v2t["hubness"], prefix="Video-to-Text ")
@@ -268,6 +279,7 @@ def eval_epoch(args, model, test_dataloader, device):
             tracker.print_metrics(t2v["test_norm"], prefix=f"Text-to-Video {tag}: ")
             tracker.print_metrics(v2t["test_norm"], prefix=f"Video-to-Text {tag}: ")
             log_bootstrap(t2v["test_norm"], v2t["test_norm"], tag)
+            log_ir(t2v["test_norm"], v2t["test_norm"], tag)
             if "marginal_err" in t2v["test_norm"]:
                 logger.info(f"{tag} marginal error after {t2v['test_norm']['iters']} iterations: "
                             f"{t2v['test_norm']['marginal_err']:.3e} / {v2t['test_norm']['marginal_err']:.3e}")
@@ -279,6 +291,7 @@ def eval_epoch(args, model, test_dataloader, device):
             tracker.print_metrics(t2v["local_scaling"], prefix=f"Text-to-Video {tag}: ")
             tracker.print_metrics(v2t["local_scaling"], prefix=f"Video-to-Text {tag}: ")
             log_bootstrap(t2v["local_scaling"], v2t["local_scaling"], tag)
+            log_ir(t2v["local_scaling"], v2t["local_scaling"], tag)
             if hubness_k:
                 tracker.log_hubness(t2v["local_scaling"]["hubness"], prefix=f"Text-to-Video {tag} ")
                 tracker.log_hubness(v2t["local_scaling"]["hubness"], prefix=f"Video-to-Text {tag} ")
@@ -287,6 +300,7 @@ def eval_epoch(args, model, test_dataloader, device):
             tracker.print_metrics(t2v["mutual_proximity"], prefix=f"Text-to-Video {tag}: ")
             tracker.print_metrics(v2t["mutual_proximity"], prefix=f"Video-to-Text {tag}: ")
             log_bootstrap(t2v["mutual_proximity"], v2t["mutual_proximity"], tag)
+            log_ir(t2v["mutual_proximity"], v2t["mutual_proximity"], tag)
             if hubness_k:
                 tracker.log_hubness(t2v["mutual_proximity"]["hubness"], prefix=f"Text-to-Video {tag} ")
                 tracker.log_hubness(v2t["mutual_proximity"]["hubness"], prefix=f"Video-to-Text {tag} ")
