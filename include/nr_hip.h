@@ -936,7 +936,8 @@ int nr_bootstrap_unit_sums(const int64_t* values, int U, int Q, uint64_t seed, i
  *   p   -= lr_t u;  p = min(p, clamp_max) where has_clamp;  *step += 1.          No bias correction; g is never written.
  * Three launches whatever T is (chunk sums of g^2; one workgroup of scalars; the update), every reduction in a fixed order, no
  * float atomics: same inputs, same bits, launched eagerly or replayed from a graph.  Non-finite gradients propagate as the
- * formulas give.  `table` and `groups` are DEVICE arrays; nothing the launches read comes from the host after the call. */
+ * formulas give (nr_bertadam_step_guarded below is the form that skips such a step on the device instead).  `table` and
+ * `groups` are DEVICE arrays; nothing the launches read comes from the host after the call. */
 #define NR_SCHEDULE_WARMUP_COSINE 0   /* x / warmup if x < warmup else 0.5 (1 + cos(pi x))                  */
 #define NR_SCHEDULE_WARMUP_CONSTANT 1 /* ... else 1                                                         */
 #define NR_SCHEDULE_WARMUP_LINEAR 2   /* ... else max((x - 1) / (warmup - 1), 0)                            */
@@ -969,6 +970,45 @@ size_t nr_bertadam_workspace_bytes(int T, int n_chunks);
  * counts, a NaN global_max_norm. */
 int nr_bertadam_step(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, int G, float global_max_norm,
                      void* workspace, void* stream);
+
+/* The guarded step (DESIGN.md "Non-finite step guard"): the same three launches, the same workspace
+ * (nr_bertadam_workspace_bytes: the word launch C tests lives in NrStepGuard, not in the workspace), and for finite gradients the
+ * same bits in p, m, v, the counters and the learning rates as nr_bertadam_step.  Launch B always forms
+ * total = sum_t ||g_t||^2 in table order (with a global limit: the very sum c is made from) and calls the step BAD when total is
+ * not finite: a NaN or an infinite gradient entry anywhere, or a finite entry so large that the fp32 sum of squares of its
+ * 4096-element chunk overflows (|g| >= 2^64 always does) -- the last is treated as non-finite on purpose: such a step has no
+ * usable norm.  A bad step writes nothing to p, m, v, leaves every step counter where it was (the schedule does not move) and sets
+ * guard->skip = 1 (0 on a good step; written on every execution).  One thread of launch B is the only writer of *guard and of
+ * the ring, with plain stores and no atomics; launches on one stream are ordered, so there is one writer at a time.  Per
+ * execution it adds one attempt to the guard and writes
+ *   ring[attempts_before & (n_ring - 1)] = {attempt, (float)sqrt(total), (float)c, skipped, n_losses, losses[0 .. n_losses), 0 ...}
+ * (losses: optional DEVICE floats, copied bit for bit, read when launch B runs).  The caller zeroes *guard and the ring once, with
+ * last_skipped = -1, and reads them back whenever it likes; nothing here synchronises.
+ * NR_EINVAL before any launch: what nr_bertadam_step refuses, a null or misaligned (8 bytes) guard or ring, n_ring not a power of
+ * two in [1, NR_GUARD_MAX_RING], n_losses outside [0, NR_GUARD_MAX_LOSSES], losses NULL with n_losses > 0.  T = 0: NR_OK, no
+ * launch, no attempt counted. */
+#define NR_GUARD_MAX_LOSSES 8
+#define NR_GUARD_MAX_RING 4096
+typedef struct {
+    int64_t attempts;        /* executions of the guarded step                                                         */
+    int64_t skipped;         /* of those, bad ones                                                                     */
+    int64_t consecutive;     /* length of the run of bad steps that is open now (0 after a good step)                  */
+    int64_t max_consecutive; /* longest such run so far                                                                */
+    int64_t last_skipped;    /* attempt index of the last bad step, -1: none yet                                       */
+    int32_t skip;            /* the last execution's decision, read by launch C                                        */
+    int32_t pad_;
+} NrStepGuard; /* 48 bytes */
+typedef struct {
+    int64_t attempt;         /* 0-based index of the execution                                                         */
+    float grad_norm;         /* (float)sqrt(total): the global gradient norm before any clip; NaN / Inf on a bad step  */
+    float clip;              /* (float)c, 1 without a global limit                                                     */
+    int32_t skipped;
+    int32_t n_losses;
+    float losses[NR_GUARD_MAX_LOSSES];
+} NrStepRecord; /* 56 bytes */
+int nr_bertadam_step_guarded(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, int G,
+                             float global_max_norm, void* workspace, NrStepGuard* guard, const float* losses, int n_losses,
+                             NrStepRecord* ring, int n_ring, void* stream);
 
 #ifdef __cplusplus
 }

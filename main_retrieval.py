@@ -15,6 +15,7 @@ and the model runs in feature mode.  With real encoders, construct
       --do_train 1 --synthetic --batch_size 128 --max_words 24 --max_frames 12 --mb_batch 4 --epochs 1
 """
 import argparse
+import math
 import os
 import time
 
@@ -139,7 +140,21 @@ def get_args():
                         "(training/optimizer.py: `clip.` names at lr * coef_lr, no decay on bias / LayerNorm, warm-up + cosine "
                         "over len(train) * epochs steps) as multi-tensor HIP kernels, with the trainer's global clip and "
                         "logit-scale clamp inside; under --hip_graph 1 on one rank the update is part of the replayed graph")
+    p.add_argument("--skip_nonfinite", type=int, default=0, choices=[0, 1],
+                   help="1: a training step whose gradients are not all finite (one undecodable video gives an all-zero mask and "
+                        "NaN losses) updates nothing and is counted (DESIGN.md 6.9).  --optimizer bertadam decides on the device "
+                        "inside its three launches -- no synchronisation, also inside the replayed graph -- and logs skips and "
+                        "gradient norms at every --n_display line; --optimizer adamw tests the norm clip_grad_norm_ returns on "
+                        "the host, which costs one synchronisation per step, with this flag only; 0 = off")
+    p.add_argument("--synthetic_blank", default="", metavar="STEP[:RANK]",
+                   help="--synthetic: in global step STEP (1-based) the first video of the batch of rank RANK (default 0) comes "
+                        "back the way the reference's loader returns an undecodable one, all zeros with an all-zero mask")
     args = p.parse_args()
+    try:
+        blank = [int(v) for v in args.synthetic_blank.split(":")] if args.synthetic_blank else [0, 0]
+        args.blank_step, args.blank_rank = blank if len(blank) == 2 else (blank[0], 0)
+    except ValueError:
+        p.error("--synthetic_blank takes STEP or STEP:RANK")
     if args.test_norm_iters < 1:
         p.error("--test_norm_iters must be >= 1")
     if args.local_scaling != "none" and args.test_norm != "none":
@@ -282,6 +297,12 @@ class GraphedStep:
     that ends in optimizer.step().  Either way run() returns with the update issued, and the optimizer's step count is the
     number of run() calls.
 
+    An optimizer built with skip_nonfinite=True keeps its place: on one rank its guarded launches are captured behind the
+    backward, where issue() is captured, and they record the step's five losses from a [5] tensor stacked inside the capture
+    (static, so its address can be baked in).  On several ranks they follow the replay, after the gradient average: every rank
+    then holds the same flat gradient, takes the same decision and stays in step with the others; the losses each rank records
+    are its own.  The optimizer's step count is then the number of run() calls minus the steps the device skipped.
+
     world_size > 1: the step that is replayed is the WHOLE data-parallel step -- exchange step, loss, backward with the
     reductions of its differentiable collectives, and the gradient average over the ranks (one all-reduce of a flat buffer that
     the parameters' .grad are views of; what DistributedDataParallel's bucketed all-reduce computes, optimizer.py:79-84) --
@@ -359,6 +380,8 @@ class GraphedStep:
             if self.optimizer is not None:
                 for p, g in zip(params, grads):
                     p.grad = g
+                if self.optimizer.skip_nonfinite:
+                    self.optimizer.watch_losses(torch.stack([l.detach().float() for l in losses]))
                 self._updated = self.optimizer.issue()           # captured, not executed: advance() follows every replay
         self.losses = tuple(l.detach() for l in losses)          # the loss VALUES only (no autograd graph kept alive)
         del losses
@@ -470,6 +493,8 @@ class GraphedStep:
         for p, g in zip(self.params, grads):
             p.grad = g
         if self.optimizer is not None:
+            if self.optimizer.skip_nonfinite:
+                self.optimizer.watch_losses(torch.stack([l.detach().float() for l in losses]))
             self.optimizer.step()
         return tuple(l.detach() for l in losses)
 
@@ -485,6 +510,8 @@ class GraphedStep:
             for p, g in zip(self._used, self._views):    # optimizer.zero_grad(set_to_none=True) drops them: put them back
                 p.grad = g
             if self.optimizer is not None:
+                if self.optimizer.skip_nonfinite:
+                    self.optimizer.watch_losses(self._out["losses"].float())
                 self.optimizer.step()                    # the same table every step: the views never move
             return tuple(self._out["losses"].unbind(0))
         for p, g in zip(self.params, self.grads):    # optimizer.zero_grad(set_to_none=True) drops them: put them back
@@ -500,9 +527,18 @@ def train_epoch(args, model, ddp, data, optimizer, epoch, global_step):
     t0 = time.time()
     graphed = getattr(args, "_graphed_step", None)
     fused = args.optimizer == "bertadam"             # global clip, update and logit-scale clamp in the optimizer's kernels
+    guard = bool(getattr(args, "skip_nonfinite", 0))
+    if guard and not fused and not hasattr(args, "_host_skips"):
+        args._host_skips = dict(skipped=0, consecutive=0, max_consecutive=0, norms=[])
+    bank_steps = -(-int(getattr(model, "mb_batch", 0)) // args.batch_size)        # steps until a batch has left the memory bank
+    warned = 0
     for i in range(len(data)):
         global_step += 1
         text, text_mask, video, video_mask, idx = data.batch(i, args.device)
+        if global_step == getattr(args, "blank_step", 0) and args.rank == getattr(args, "blank_rank", 0):
+            video, video_mask = video.clone(), video_mask.clone()   # dataloader_retrieval.py:278-315 after a failed decode
+            video[0] = 0
+            video_mask[0] = 0
         if args.hip_graph:
             if graphed is None:
                 graphed = args._graphed_step = GraphedStep(model, (text, text_mask, video, video_mask, idx),
@@ -517,20 +553,66 @@ def train_epoch(args, model, ddp, data, optimizer, epoch, global_step):
             loss.backward()
         if fused:
             if not args.hip_graph:                   # (a graphed step has issued the update itself)
+                if guard:
+                    optimizer.watch_losses(torch.stack([l.detach().float() for l in losses]))
                 optimizer.step()
             optimizer.zero_grad(set_to_none=True)
         else:
-            torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
-            optimizer.step()
+            norm = torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
+            if guard:                                # the host's form of the guard: float() waits for the device, every step
+                norm, hs = float(norm), args._host_skips
+                hs["norms"].append(norm)
+                del hs["norms"][:-max(args.n_display, 1)]             # the log line's window, no more
+                if math.isfinite(norm):
+                    hs["consecutive"] = 0
+                    optimizer.step()
+                else:
+                    hs["skipped"] += 1
+                    hs["consecutive"] += 1
+                    hs["max_consecutive"] = max(hs["max_consecutive"], hs["consecutive"])
+            else:
+                optimizer.step()
             optimizer.zero_grad(set_to_none=True)
             torch.clamp_(model.clip.logit_scale.data, max=float(np.log(100)))    # trainer.py:114-119
         if global_step % args.n_display == 0 or i == len(data) - 1:
             red = reduce_losses(losses, args).tolist()                            # one reduce instead of five
             lr = f" lr {optimizer.group_lr(applied=True)[1]:.3e}" if fused else ""     # the head's (decayed, non-CLIP) group, this step
+            tail = ""
+            if guard:
+                window = min(args.n_display, i + 1)          # the steps since the last line (the records' window)
+                stats, norms = _guard_report(args, optimizer, fused, window)
+                finite = [v for v in norms if math.isfinite(v)]
+                tail = (f" skipped {stats['skipped']} longest run {stats['max_consecutive']} grad norm median "
+                        f"{float(np.median(finite)) if finite else float('nan'):.3e} max {max(finite) if finite else float('nan'):.3e}")
+                if stats["consecutive"] > max(bank_steps, 0) and stats["consecutive"] > warned:
+                    log(args, f"WARNING: {stats['consecutive']} training steps in a row had non-finite gradients and were skipped, "
+                              f"more than the {bank_steps} steps a batch stays in the memory bank: the guard does not filter the "
+                              "bank, look at the data")
+                warned = stats["consecutive"]
             log(args, f"epoch {epoch} step {i + 1}/{len(data)} loss {red[0]:.4f} centrality {red[1]:.4f} "
                       f"uniform {red[2]:.4f} neighbor {red[3]:.4f} kl {red[4]:.4f}{lr} "
-                      f"({(time.time() - t0) / (i + 1) * 1e3:.1f} ms/step)")
+                      f"({(time.time() - t0) / (i + 1) * 1e3:.1f} ms/step){tail}")
+    if guard:                                        # every rank, not only the one that logs: the ranks must agree
+        import hashlib
+        stats, _ = _guard_report(args, optimizer, fused, 0)
+        digest, finite = hashlib.sha256(), True
+        for p in model.parameters():
+            host = p.detach().cpu().numpy()
+            digest.update(host.tobytes())
+            finite = finite and bool(np.isfinite(host).all())
+        print(f"rank {args.rank} epoch {epoch} non-finite guard: skipped {stats['skipped']} parameters "
+              f"{'finite' if finite else 'NOT FINITE'} sha256 {digest.hexdigest()[:16]}", flush=True)
     return global_step
+
+
+def _guard_report(args, optimizer, fused, window):
+    """--skip_nonfinite 1 -> ({skipped, consecutive, max_consecutive}, the gradient norms of the last `window` steps): from the
+    device's guard and record ring (BertAdam; one blocking copy, at a log line only) or from the host's counts (adamw)."""
+    if fused:
+        stats = optimizer.guard_stats()
+        return stats, [float(v) for v in optimizer.records(last=window)["grad_norm"]] if window else []
+    hs = args._host_skips
+    return hs, hs["norms"][-window:] if window else []
 
 
 def eval_epoch(args, model, test):
@@ -672,7 +754,7 @@ def main():
         from neighborretr_amd.optim import prep_optimizer
         # (wrap=False: the model is wrapped above, or not at all under --hip_graph 1)
         optimizer = prep_optimizer(args, model, len(train) * args.epochs, args.device_index, global_max_norm=1.0,
-                                   clamp_logit_scale=True, wrap=False)[0]
+                                   clamp_logit_scale=True, wrap=False, skip_nonfinite=bool(args.skip_nonfinite))[0]
     else:
         optimizer = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
     os.makedirs(args.output_dir, exist_ok=True)

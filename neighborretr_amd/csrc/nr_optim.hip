@@ -12,7 +12,8 @@
 //
 // A and C use a grid capped at NR_OPT_MAX_GRID workgroups that strides over the chunks; the chunk -> tensor lookup is a binary
 // search over the table's chunk prefix (uniform per workgroup: scalar loads).  Nothing depends on a host value that changes
-// from step to step, so the same three launches replay from a graph.  No float atomics and no order that depends on which
+// from step to step, so the same three launches replay from a graph.  nr_bertadam_step_guarded is the same
+// three launches with a device-side decision in B: a step whose sum of squared gradients is not finite changes nothing.  No float atomics and no order that depends on which
 // workgroup arrives first: a chunk's sum is formed in one fixed order whether its gradient is 16-byte aligned or not, so the
 // result does not depend on alignment either.  The gradient buffers are only read.
 #include "nr_common.h"
@@ -93,13 +94,25 @@ __device__ __forceinline__ double nr_opt_clip(double limit, double norm) {
     return c > 1.0 ? 1.0 : c;
 }
 
+// What the guarded step adds to launch B.  One thread -- the only writer of the guard and of the ring, ever --
+// decides, counts and leaves the step's record; launch C reads guard->skip.
+struct NrOptGuardArgs {
+    NrStepGuard* guard;
+    const float* losses;
+    int n_losses;
+    NrStepRecord* ring;
+    int n_ring;
+};
+
+template <bool GUARDED>
 __global__ __launch_bounds__(NR_OPT_B_THREADS) void nr_bertadam_scalars_kernel(const NrOptimTensor* __restrict__ table, int T,
                                                                               int n_chunks,
                                                                               const NrOptimGroup* __restrict__ groups,
                                                                               float global_max_norm,
                                                                               const float* __restrict__ part,
                                                                               double* __restrict__ tensor_sq,
-                                                                              float* __restrict__ scale, float* __restrict__ lr) {
+                                                                              float* __restrict__ scale, float* __restrict__ lr,
+                                                                              NrOptGuardArgs ga) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int t = wave; t < T; t += NR_OPT_B_THREADS / 64) {
         const int c0 = table[t].chunk0;
@@ -112,12 +125,38 @@ __global__ __launch_bounds__(NR_OPT_B_THREADS) void nr_bertadam_scalars_kernel(c
     }
     __threadfence_block();
     __syncthreads();
-    double c = 1.0;
-    if (global_max_norm > 0.f) {
-        double total = 0.0;
+    double c = 1.0, total = 0.0;
+    if (GUARDED || global_max_norm > 0.f) {
         for (int t = 0; t < T; ++t) total += tensor_sq[t];          // table order, the same in every thread
-        c = nr_opt_clip((double)global_max_norm, sqrt(total));
+        if (global_max_norm > 0.f) c = nr_opt_clip((double)global_max_norm, sqrt(total));
     }
+    // the sum of all squares is finite exactly when no gradient entry is NaN or infinite and no chunk sum overflowed fp32
+    const bool bad = GUARDED && !(fabs(total) <= 1.79769313486231570815e308);
+    if (GUARDED && threadIdx.x == 0) {
+        NrStepGuard* gd = ga.guard;
+        const int64_t attempt = gd->attempts;
+        gd->attempts = attempt + 1;
+        if (bad) {
+            const int64_t run = gd->consecutive + 1;
+            gd->skipped += 1;
+            gd->consecutive = run;
+            if (run > gd->max_consecutive) gd->max_consecutive = run;
+            gd->last_skipped = attempt;
+        } else {
+            gd->consecutive = 0;
+        }
+        gd->skip = bad ? 1 : 0;
+        NrStepRecord rec;
+        rec.attempt = attempt;
+        rec.grad_norm = (float)sqrt(total);
+        rec.clip = (float)c;
+        rec.skipped = bad ? 1 : 0;
+        rec.n_losses = ga.n_losses;
+#pragma unroll
+        for (int i = 0; i < NR_GUARD_MAX_LOSSES; ++i) rec.losses[i] = i < ga.n_losses ? ga.losses[i] : 0.f;
+        ga.ring[attempt & (int64_t)(ga.n_ring - 1)] = rec;
+    }
+    if (bad) return;                                                // no scale, no lr, no counter moves: launch C returns too
     for (int t = threadIdx.x; t < T; t += NR_OPT_B_THREADS) {
         const NrOptimGroup g = groups[table[t].group];
         double ct = 1.0;
@@ -167,9 +206,15 @@ __device__ __forceinline__ f32x4_t nr_opt_load_g4(const float* __restrict__ g, i
     return f32x4_t{q[0], q[1], q[2], q[3]};
 }
 
+// GUARDED: one uniform load of the word launch B has just written; a skipped step touches none of p, m, v, g
+template <bool GUARDED>
 __global__ __launch_bounds__(256) void nr_bertadam_update_kernel(const NrOptimTensor* __restrict__ table, int T, int n_chunks,
                                                                 const NrOptimGroup* __restrict__ groups,
-                                                                const float* __restrict__ scale, const float* __restrict__ lr) {
+                                                                const float* __restrict__ scale, const float* __restrict__ lr,
+                                                                const NrStepGuard* __restrict__ guard) {
+    if (GUARDED) {
+        if (guard->skip != 0) return;
+    }
     const int tid = threadIdx.x;
     for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         const int t = nr_opt_find(table, T, chunk);
@@ -284,11 +329,8 @@ extern "C" size_t nr_bertadam_workspace_bytes(int T, int n_chunks) {
            nr_opt_round256((size_t)n_chunks * sizeof(float));
 }
 
-extern "C" int nr_bertadam_step(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, int G,
-                                float global_max_norm, void* workspace, void* stream) {
-    if (T < 0 || n_chunks < 0 || G < 0 || global_max_norm != global_max_norm) return NR_EINVAL;
-    if (T == 0) return n_chunks == 0 ? NR_OK : NR_EINVAL;
-    if (!table || !groups || !workspace || G == 0 || ((uintptr_t)workspace & 7) != 0) return NR_EINVAL;
+static int nr_opt_launch(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, float global_max_norm,
+                         void* workspace, const NrOptGuardArgs* ga, void* stream) {
     char* ws = static_cast<char*>(workspace);
     double* tensor_sq = reinterpret_cast<double*>(ws);
     ws += nr_opt_round256((size_t)T * sizeof(double));
@@ -303,12 +345,43 @@ extern "C" int nr_bertadam_step(const NrOptimTensor* table, int T, int n_chunks,
         hipLaunchKernelGGL(nr_bertadam_sumsq_kernel, dim3(grid), dim3(256), 0, st, table, T, n_chunks, part);
         NR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(nr_bertadam_scalars_kernel, dim3(1), dim3(NR_OPT_B_THREADS), 0, st, table, T, n_chunks, groups,
-                       global_max_norm, part, tensor_sq, scale, lr);
+    if (ga)
+        hipLaunchKernelGGL(nr_bertadam_scalars_kernel<true>, dim3(1), dim3(NR_OPT_B_THREADS), 0, st, table, T, n_chunks, groups,
+                           global_max_norm, part, tensor_sq, scale, lr, *ga);
+    else
+        hipLaunchKernelGGL(nr_bertadam_scalars_kernel<false>, dim3(1), dim3(NR_OPT_B_THREADS), 0, st, table, T, n_chunks, groups,
+                           global_max_norm, part, tensor_sq, scale, lr, NrOptGuardArgs{});
     NR_LAUNCH_CHECK();
     if (grid > 0) {
-        hipLaunchKernelGGL(nr_bertadam_update_kernel, dim3(grid), dim3(256), 0, st, table, T, n_chunks, groups, scale, lr);
+        if (ga)
+            hipLaunchKernelGGL(nr_bertadam_update_kernel<true>, dim3(grid), dim3(256), 0, st, table, T, n_chunks, groups, scale,
+                               lr, (const NrStepGuard*)ga->guard);
+        else
+            hipLaunchKernelGGL(nr_bertadam_update_kernel<false>, dim3(grid), dim3(256), 0, st, table, T, n_chunks, groups, scale,
+                               lr, (const NrStepGuard*)nullptr);
         NR_LAUNCH_CHECK();
     }
     return NR_OK;
+}
+
+extern "C" int nr_bertadam_step(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, int G,
+                                float global_max_norm, void* workspace, void* stream) {
+    if (T < 0 || n_chunks < 0 || G < 0 || global_max_norm != global_max_norm) return NR_EINVAL;
+    if (T == 0) return n_chunks == 0 ? NR_OK : NR_EINVAL;
+    if (!table || !groups || !workspace || G == 0 || ((uintptr_t)workspace & 7) != 0) return NR_EINVAL;
+    return nr_opt_launch(table, T, n_chunks, groups, global_max_norm, workspace, nullptr, stream);
+}
+
+extern "C" int nr_bertadam_step_guarded(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, int G,
+                                        float global_max_norm, void* workspace, NrStepGuard* guard, const float* losses,
+                                        int n_losses, NrStepRecord* ring, int n_ring, void* stream) {
+    if (T < 0 || n_chunks < 0 || G < 0 || global_max_norm != global_max_norm) return NR_EINVAL;
+    if (!guard || !ring || ((uintptr_t)guard & 7) != 0 || ((uintptr_t)ring & 7) != 0) return NR_EINVAL;
+    if (n_ring < 1 || n_ring > NR_GUARD_MAX_RING || (n_ring & (n_ring - 1)) != 0) return NR_EINVAL;
+    if (n_losses < 0 || n_losses > NR_GUARD_MAX_LOSSES || (n_losses > 0 && (!losses || ((uintptr_t)losses & 3) != 0)))
+        return NR_EINVAL;
+    if (T == 0) return n_chunks == 0 ? NR_OK : NR_EINVAL;            // nothing to update: no launch, not an attempt
+    if (!table || !groups || !workspace || G == 0 || ((uintptr_t)workspace & 7) != 0) return NR_EINVAL;
+    const NrOptGuardArgs ga{guard, losses, n_losses, ring, n_ring};
+    return nr_opt_launch(table, T, n_chunks, groups, global_max_norm, workspace, &ga, stream);
 }

@@ -126,7 +126,19 @@ class OptimGroup(ctypes.Structure):
                 + [("t_total", ctypes.c_int64), ("schedule", ctypes.c_int32), ("pad_", ctypes.c_int32)])
 
 
-STRUCTS = {"NrOptimTensor": OptimTensor, "NrOptimGroup": OptimGroup, "NrTokenWeightsProblem": TokenWeightsProblem, "NrBankAbsorbDesc": BankAbsorbDesc, "NrCtmStageDesc": CtmStageDesc, "NrLocalLevelProblem": LocalLevelProblem, "NrSplitItem": SplitItem,
+class StepGuard(ctypes.Structure):
+    """NrStepGuard of include/nr_hip.h."""
+    _fields_ = ([(n, ctypes.c_int64) for n in ("attempts", "skipped", "consecutive", "max_consecutive", "last_skipped")]
+                + [("skip", ctypes.c_int32), ("pad_", ctypes.c_int32)])
+
+
+class StepRecord(ctypes.Structure):
+    """NrStepRecord of include/nr_hip.h."""
+    _fields_ = [("attempt", ctypes.c_int64), ("grad_norm", _F), ("clip", _F), ("skipped", ctypes.c_int32),
+                ("n_losses", ctypes.c_int32), ("losses", _F * 8)]
+
+
+STRUCTS = {"NrOptimTensor": OptimTensor, "NrOptimGroup": OptimGroup, "NrStepGuard": StepGuard, "NrStepRecord": StepRecord, "NrTokenWeightsProblem": TokenWeightsProblem, "NrBankAbsorbDesc": BankAbsorbDesc, "NrCtmStageDesc": CtmStageDesc, "NrLocalLevelProblem": LocalLevelProblem, "NrSplitItem": SplitItem,
            "NrColsumItem": ColsumItem, "NrLinearProblem": LinearProblem, "NrCtmAttnBwdDesc": CtmAttnBwdDesc,
            "NrCtmMidBwdDesc": CtmMidBwdDesc, "NrSimBwdItem": SimBwdItem, "NrSimBwdOperand": SimBwdOperand, "NrSlabSum": SlabSum,
            "NrPoolWSrc": PoolWSrc, "NrPoolWJob": PoolWJob}
@@ -261,6 +273,7 @@ _SIGNATURES = {
     "nr_bertadam_plan": ([ctypes.POINTER(OptimTensor), _I, ctypes.POINTER(OptimGroup), _I, ctypes.POINTER(_I)], _I),
     "nr_bertadam_workspace_bytes": ([_I, _I], _Z),
     "nr_bertadam_step": ([_P, _I, _I, _P, _I, _F, _P, _P], _I),
+    "nr_bertadam_step_guarded": ([_P, _I, _I, _P, _I, _F, _P, _P, _P, _I, _P, _I, _P], _I),
 }
 TOPK_MAX = 128                               # largest k of the top-k entry points
 HUBNORM_IS, HUBNORM_DSL = 0, 1               # nr_hubnorm_apply modes
@@ -268,6 +281,7 @@ LOCALSCALE_CSLS, LOCALSCALE_NICDM, LOCALSCALE_LS = 0, 1, 2      # nr_localscale_
 MP_LINE_MAX = 1 << 23                        # a mutual-proximity reference line must be shorter: 2 c < 2^24 keeps the counts exact
 BOOT_MAX_UNITS, BOOT_MAX_CUTS, BOOT_RANK_LIMIT = 1 << 24, 8, 1 << 30      # nr_bootstrap_rank_stats: U, K and the ranks' bound
 BOOT_MAX_COLS, BOOT_SUM_LIMIT = 16, 1 << 62  # nr_bootstrap_unit_sums: Q and the bound of U max|value|
+GUARD_MAX_LOSSES, GUARD_MAX_RING = 8, 4096   # nr_bertadam_step_guarded: n_losses and n_ring (a power of two)
 SCHEDULE_IDS = {"warmup_cosine": 0, "warmup_constant": 1, "warmup_linear": 2}      # NR_SCHEDULE_*
 
 

@@ -1485,3 +1485,24 @@ def bertadam_step(groups_dev, n_groups, table_dev, n_tensors, n_chunks, workspac
     hip.call("nr_bertadam_step", ctypes.c_void_p(hip.ptr(table_dev, torch.uint8).value + int(table_offset)), int(n_tensors),
              int(n_chunks), hip.ptr(groups_dev, torch.uint8), int(n_groups), ctypes.c_float(gmn), hip.ptr(workspace, torch.uint8),
              hip.stream_ptr())
+
+
+def bertadam_step_guarded(groups_dev, n_groups, table_dev, n_tensors, n_chunks, workspace, guard, ring, global_max_norm=None,
+                          table_offset=0, losses=None):
+    """bertadam_step with the non-finite guard (nr_bertadam_step_guarded): a step whose sum of squared gradients is not finite
+    leaves p, m, v and the step counters as they were.  guard: uint8 device tensor holding one hip.StepGuard (zeroed by the
+    caller, last_skipped = -1); ring: uint8 device tensor of n_ring hip.StepRecord, n_ring a power of two in [1, 4096]; losses:
+    None or a contiguous float32 device tensor of at most 8 values, copied into the step's record when the launches execute."""
+    import ctypes
+    if workspace.numel() < bertadam_workspace_bytes(n_tensors, n_chunks):
+        raise hip.NrHipError("bertadam_step_guarded: workspace too small")
+    rec = ctypes.sizeof(hip.StepRecord)
+    n_ring = ring.numel() // rec
+    if guard.numel() < ctypes.sizeof(hip.StepGuard) or n_ring * rec != ring.numel():
+        raise hip.NrHipError("bertadam_step_guarded: guard / ring do not have the size of NrStepGuard / a whole number of NrStepRecord")
+    n_losses = 0 if losses is None else int(losses.numel())
+    gmn = -1.0 if global_max_norm is None else float(global_max_norm)
+    hip.call("nr_bertadam_step_guarded", ctypes.c_void_p(hip.ptr(table_dev, torch.uint8).value + int(table_offset)), int(n_tensors),
+             int(n_chunks), hip.ptr(groups_dev, torch.uint8), int(n_groups), ctypes.c_float(gmn), hip.ptr(workspace, torch.uint8),
+             hip.ptr(guard, torch.uint8), hip.ptr(losses, torch.float32, allow_none=True), n_losses, hip.ptr(ring, torch.uint8),
+             int(n_ring), hip.stream_ptr())

@@ -15,10 +15,17 @@ once the moments exist (the one host wait it can take: a table upload finding al
 -- so it can be captured into a HIP graph; the step counters and the schedule live on the device.  The table of
 pointers the kernels read is uploaded again only when one of its pointers (or a group's hyper-parameter) has changed.  There is
 no CPU or eager path behind it: parameters that are not on the GPU raise.
+
+`skip_nonfinite=True` takes the same three launches through nr_bertadam_step_guarded: a step whose sum of squared
+gradients is not finite -- a NaN, an infinity, or an entry whose square overflows fp32 -- changes no parameter, no moment and no
+step counter, decided on the device, so it works inside a replayed graph too.  The host cannot know the outcome without a
+synchronisation: its step mirror keeps counting every step and is corrected from the device counters (one small blocking copy)
+whenever something reads it -- get_lr(), group_lr(), state_dict(), guard_stats(), records().
 """
 import ctypes
 import math
 
+import numpy as np
 import torch
 from torch.optim import Optimizer
 
@@ -49,6 +56,11 @@ _REQUIRED = object()
 _RING = 4                     # pinned staging buffers of the eager path (a buffer is reused only after its copy has completed)
 _ENTRY = ctypes.sizeof(hip.OptimTensor)
 _GROUP = ctypes.sizeof(hip.OptimGroup)
+# one row of records(): NrStepRecord of include/nr_hip.h, field by field
+RECORD_DTYPE = np.dtype([("attempt", "<i8"), ("grad_norm", "<f4"), ("clip", "<f4"), ("skipped", "<i4"), ("n_losses", "<i4"),
+                         ("losses", "<f4", (hip.GUARD_MAX_LOSSES,))])
+assert RECORD_DTYPE.itemsize == ctypes.sizeof(hip.StepRecord)
+_GUARD_FIELDS = ("attempts", "skipped", "consecutive", "max_consecutive", "last_skipped")
 
 
 class BertAdam(Optimizer):
@@ -56,12 +68,14 @@ class BertAdam(Optimizer):
 
     The reference's constructor and argument checks, plus
       global_max_norm  None / <= 0: off; else the trainer's clip_grad_norm_(parameters, global_max_norm) fused into the step;
-      clamp_max        {parameter: upper bound} applied after the update (the trainer's logit-scale clamp).
+      clamp_max        {parameter: upper bound} applied after the update (the trainer's logit-scale clamp);
+      skip_nonfinite   True: a step whose gradients are not all finite is skipped on the device (module docstring);
+      record_ring      with skip_nonfinite, the number of per-step records kept for records(): a power of two in [1, 4096].
     `state[p] = {'step', 'next_m', 'next_v'}` as in the reference, so state dicts move between the two implementations; 'step'
     is the host's mirror of the device counter."""
 
     def __init__(self, params, lr=_REQUIRED, warmup=-1, t_total=-1, schedule="warmup_linear", b1=0.9, b2=0.999, e=1e-6,
-                 weight_decay=0.01, max_grad_norm=1.0, global_max_norm=None, clamp_max=None):
+                 weight_decay=0.01, max_grad_norm=1.0, global_max_norm=None, clamp_max=None, skip_nonfinite=False, record_ring=256):
         if lr is _REQUIRED:
             raise ValueError("BertAdam needs a learning rate")
         unit = lambda x: 0.0 <= x < 1.0                                           # noqa: E731
@@ -71,7 +85,12 @@ class BertAdam(Optimizer):
                                         ("b1", b1, unit, "in [0, 1)"), ("b2", b2, unit, "in [0, 1)"),
                                         ("e", e, lambda x: x >= 0.0, "a number >= 0"),
                                         ("global_max_norm", global_max_norm, lambda x: x is None or float(x) == float(x),
-                                         "None or a number")):
+                                         "None or a number"),
+                                        ("skip_nonfinite", skip_nonfinite, lambda x: isinstance(x, (bool, int)) and x in (0, 1),
+                                         "False / True (or 0 / 1)"),
+                                        ("record_ring", record_ring,
+                                         lambda x: isinstance(x, int) and not isinstance(x, bool) and 1 <= x <= hip.GUARD_MAX_RING
+                                         and x & (x - 1) == 0, f"a power of two in [1, {hip.GUARD_MAX_RING}]")):
             if not ok(value):
                 raise ValueError(f"BertAdam: {name} = {value!r} is not accepted, it must be {wanted}")
         defaults = dict(lr=lr, schedule=schedule, warmup=warmup, t_total=t_total, b1=b1, b2=b2, e=e, weight_decay=weight_decay,
@@ -84,6 +103,9 @@ class BertAdam(Optimizer):
             if id(p) not in known:
                 raise ValueError("clamp_max names a tensor that is not one of the optimizer's parameters")
             self.clamp_max[id(p)] = float(bound)
+        self.skip_nonfinite, self.record_ring = bool(skip_nonfinite), int(record_ring)
+        self._watched = None      # watch_losses(): the device tensor whose values go into every step's record
+        self._dirty = False       # skip_nonfinite: the step mirror has counted steps the device may have skipped
         self._dev = None          # device-side state: created by the first step() / prepare()
         self._key = None          # what the device table currently holds
         self._held = {}           # tables of captured steps, per owner: alive (and untouched) as long as that capture is in use
@@ -92,6 +114,7 @@ class BertAdam(Optimizer):
     def get_lr(self):
         """The scheduled learning rate of every parameter that has a gradient, from the host's mirror of the step counters
         ([0] before the first step, as in the reference)."""
+        self._sync_steps()
         live = [(group, self.state[p]) for group in self.param_groups for p in group["params"] if p.grad is not None]
         if any(len(state) == 0 for _, state in live):
             return [0]
@@ -100,6 +123,7 @@ class BertAdam(Optimizer):
     def group_lr(self, applied=False):
         """One scheduled learning rate per parameter group, read at its most advanced tensor: the rate the NEXT step will use
         (what get_lr() reports), or with `applied=True` the rate the last step used (0 steps: the first step's)."""
+        self._sync_steps()
         out = []
         for group in self.param_groups:
             steps = [self.state[p]["step"] for p in group["params"] if len(self.state[p])]
@@ -116,10 +140,59 @@ class BertAdam(Optimizer):
         self.advance(self.issue())
         return loss
 
+    def state_dict(self):
+        self._sync_steps()
+        return super().state_dict()
+
+    # ---- the non-finite guard (skip_nonfinite=True) ----------------------------------------------------------------------
+    def watch_losses(self, losses):
+        """Registers a float32 device tensor of at most 8 values (None: none) whose contents every later issue() / step() copies
+        into its step's record WHEN THE LAUNCHES EXECUTE: the address is baked into the launch, so inside a graph capture pass
+        a tensor of the capture (static across replays).  The optimizer keeps the tensor alive."""
+        self._need_guard("watch_losses")
+        if losses is not None:
+            if not (isinstance(losses, torch.Tensor) and losses.is_cuda and losses.dtype == torch.float32 and losses.is_contiguous()
+                    and losses.numel() <= hip.GUARD_MAX_LOSSES):
+                raise ValueError(f"watch_losses takes a contiguous float32 device tensor of at most {hip.GUARD_MAX_LOSSES} values")
+        self._watched = losses
+
+    def guard_stats(self):
+        """{attempts, skipped, consecutive, max_consecutive, last_skipped} as the device holds them now (a blocking copy)."""
+        self._need_guard("guard_stats")
+        self._sync_steps()
+        guard = hip.StepGuard.from_buffer_copy(self._device_state()["guard"].cpu().numpy().tobytes())
+        return {k: int(getattr(guard, k)) for k in _GUARD_FIELDS}
+
+    def records(self, last=None):
+        """The per-step records still in the ring, oldest first, as a NumPy structured array (RECORD_DTYPE): min(attempts,
+        record_ring) rows, every attempt index once; `last`: only the newest `last` of them.  A blocking copy."""
+        self._need_guard("records")
+        attempts = self.guard_stats()["attempts"]
+        ring = np.frombuffer(self._dev["ring_records"].cpu().numpy().tobytes(), dtype=RECORD_DTYPE)
+        n = min(attempts, self.record_ring)
+        if last is not None:
+            n = min(n, max(int(last), 0))
+        rows = ring[[a & (self.record_ring - 1) for a in range(attempts - n, attempts)]] if n else ring[:0]
+        return rows.copy()
+
+    def _need_guard(self, what):
+        if not self.skip_nonfinite:
+            raise RuntimeError(f"BertAdam.{what}() belongs to the non-finite guard: build the optimizer with skip_nonfinite=True")
+
+    def _sync_steps(self):
+        """skip_nonfinite: the device counters are the truth (a skipped step does not move them) -> the host's mirror."""
+        if not self._dirty or self._dev is None:
+            return
+        steps = self._dev["steps"].cpu().tolist()
+        for i, p in enumerate(self._all):
+            if len(self.state[p]):
+                self.state[p]["step"] = int(steps[i])
+        self._dirty = False
+
     @torch.no_grad()
     def load_state_dict(self, state_dict):
         """Moments that already exist keep their storage and take the loaded values (a captured step has their addresses in its
-        table); the device counters are set from the loaded step counts."""
+        table); the device counters are set from the loaded step counts.  The guard's counters and records are left alone."""
         mine = {p: (st["next_m"], st["next_v"]) for p, st in self.state.items() if "next_m" in st}
         super().load_state_dict(state_dict)
         for p, (m, v) in mine.items():
@@ -133,6 +206,7 @@ class BertAdam(Optimizer):
                 st.setdefault("step", 0)
             st["next_m"], st["next_v"] = m, v
         self._key = None
+        self._dirty = False                          # the loaded counts are the mirror now, and the device's below
         if self._dev is not None:
             self._upload_steps()
 
@@ -191,19 +265,27 @@ class BertAdam(Optimizer):
         else:
             launch = dev["launch"]
         buf, T, n_chunks = launch
-        ops.bertadam_step(buf, len(self.param_groups), buf, T, n_chunks, dev["workspace"], self.global_max_norm,
-                          table_offset=dev["table_off"])
+        if self.skip_nonfinite:
+            ops.bertadam_step_guarded(buf, len(self.param_groups), buf, T, n_chunks, dev["workspace"], dev["guard"],
+                                      dev["ring_records"], self.global_max_norm, table_offset=dev["table_off"],
+                                      losses=self._watched)
+        else:
+            ops.bertadam_step(buf, len(self.param_groups), buf, T, n_chunks, dev["workspace"], self.global_max_norm,
+                              table_offset=dev["table_off"])
         return live
 
     def advance(self, live):
         """After one execution of issue()'s launches: the parameters have changed outside autograd, so their version counters
         move (modeling.scorer_weights / cluster_fused.build_stage_weights key their bf16 splits on them), and so does the
-        host's mirror of the step counters."""
+        host's mirror of the step counters.  With skip_nonfinite the device may have skipped the step: the mirror counts it
+        all the same (finding out would synchronise) and is marked for correction at the next read; the version bump of a
+        skipped step only makes the derived weights be re-derived, equal."""
         if not live:
             return
         torch.autograd.graph.increment_version(live)
         for p in live:
             self.state[p]["step"] += 1
+        self._dirty = self.skip_nonfinite
 
     # ---- internals ----------------------------------------------------------------------------------------------------------
     def _device_state(self):
@@ -239,6 +321,10 @@ class BertAdam(Optimizer):
                 workspace=torch.empty(max(ws, 256), dtype=torch.uint8, device=device),
                 ring=[(torch.empty(nbytes, dtype=torch.uint8, pin_memory=True), torch.cuda.Event()) for _ in range(_RING)],
                 next=0, launch=None, spare=None)
+            if self.skip_nonfinite:
+                guard = hip.StepGuard(last_skipped=-1)
+                self._dev["guard"] = torch.frombuffer(bytearray(bytes(guard)), dtype=torch.uint8).to(device)
+                self._dev["ring_records"] = torch.zeros(self.record_ring * RECORD_DTYPE.itemsize, dtype=torch.uint8, device=device)
         self._upload_steps()
         return self._dev
 
@@ -316,13 +402,14 @@ def _group_index(name):
 
 
 def prep_optimizer(args, model, num_train_optimization_steps, local_rank, global_max_norm=None, clamp_logit_scale=False,
-                   wrap=True):
+                   wrap=True, skip_nonfinite=False):
     """training/optimizer.py:12-86 -> (optimizer, None, model).  Four groups: names with `clip.` train at lr * coef_lr, names
     containing `bias`, `LayerNorm.bias` or `LayerNorm.weight` take no weight decay; warmup_cosine over
     `num_train_optimization_steps`, b1 0.9, b2 0.98, e 1e-6, per-tensor max_grad_norm 1.0.
 
     By default the trainer's global clip and logit-scale clamp stay with the caller (training.train_epoch does both around
-    step(), like the reference's trainer); `global_max_norm=1.0` / `clamp_logit_scale=True` move them into the step.  The model
+    step(), like the reference's trainer); `global_max_norm=1.0` / `clamp_logit_scale=True` move them into the step;
+    `skip_nonfinite=True` builds the optimizer with the device-side non-finite guard (BertAdam).  The model
     comes back wrapped in DistributedDataParallel when a process group is up (the reference wraps whenever CUDA is there, which
     needs one; `wrap=False`: never), else as it came."""
     if hasattr(model, "module"):
@@ -343,7 +430,7 @@ def prep_optimizer(args, model, num_train_optimization_steps, local_rank, global
             raise ValueError("clamp_logit_scale: the model has no clip.logit_scale parameter")
     optimizer = BertAdam(groups, lr=args.lr, warmup=args.warmup_proportion, schedule="warmup_cosine", b1=0.9, b2=0.98, e=1e-6,
                          t_total=num_train_optimization_steps, weight_decay=args.weight_decay, max_grad_norm=1.0,
-                         global_max_norm=global_max_norm, clamp_max=clamp)
+                         global_max_norm=global_max_norm, clamp_max=clamp, skip_nonfinite=skip_nonfinite)
     import torch.distributed as dist
     if wrap and torch.cuda.is_available() and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local_rank], output_device=local_rank,

@@ -21,6 +21,7 @@ prep_optimizer are neighborretr_amd.optim's (multi-tensor HIP kernels), built WI
 loop, which clips and clamps around step() like the reference's trainer.
 """
 import logging
+import math
 import time
 from datetime import timedelta
 
@@ -336,7 +337,18 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
 
     One step = forward (encoders, packed exchange, the HIP loss head, bank push) + backward + clip_grad_norm(1.0) +
     optimizer / scheduler step + logit-scale clamp (:114-119), validation every 3 * n_display steps and at step 1
-    (:171-199).  The running loss stays on the device: one host sync per logged step, not one per step (:203)."""
+    (:171-199).  The running loss stays on the device: one host sync per logged step, not one per step (:203).
+
+    args.skip_nonfinite (0 / 1, default 0) = 1: a step whose gradients are not all finite updates nothing.  An
+    optim.BertAdam built with skip_nonfinite=True decides on the device, inside its launches, and this loop does not wait for
+    it; for any other optimizer the norm that clip_grad_norm_ returns is tested on the host -- one synchronisation per step,
+    with the flag only -- and optimizer.step() / scheduler.step() are left out when it is not finite.  The count of skipped
+    steps joins the log line."""
+    skip_nonfinite = getattr(args, "skip_nonfinite", 0)
+    if isinstance(skip_nonfinite, bool) or skip_nonfinite not in (0, 1):
+        raise ValueError(f"skip_nonfinite must be 0 or 1, got {skip_nonfinite!r}")
+    on_device = bool(skip_nonfinite) and bool(getattr(optimizer, "skip_nonfinite", False))
+    host_skipped = 0
     logger = getattr(args, "logger", None)
     tracker = RetrievalMetrics(logger=logger)
     meters = meters if meters is not None else _Meter()
@@ -362,10 +374,15 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
                 loss.backward()
         else:
             loss.backward()
-        torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
-        optimizer.step()
-        if scheduler is not None:
-            scheduler.step()
+        grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
+        if skip_nonfinite and not on_device and not math.isfinite(float(grad_norm)):
+            host_skipped += 1
+        else:
+            if on_device:
+                optimizer.watch_losses(torch.stack([l.detach().float() for l in losses]))
+            optimizer.step()
+            if scheduler is not None:
+                scheduler.step()
         optimizer.zero_grad()
         torch.clamp_(target.clip.logit_scale.data, max=float(np.log(100)))          # trainer.py:114-119
         total_loss = loss.detach().clone() if total_loss is None else total_loss + loss.detach()
@@ -390,7 +407,8 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
                 f"U-Loss: {_meter_value(meters, 'uniform_loss', 'median'):.4f}",
                 f"N-Loss: {_meter_value(meters, 'neighbor_loss', 'median'):.4f}",
                 f"KL-Loss: {_meter_value(meters, 'kl_loss', 'median'):.4f}", f"LR: {lr:.8f}",
-                f"LogitScale: {float(target.clip.logit_scale.detach().exp()):.2f}", f"ETA: {eta}"]))
+                f"LogitScale: {float(target.clip.logit_scale.detach().exp()):.2f}", f"ETA: {eta}"]
+                + ([f"Skipped: {optimizer.guard_stats()['skipped'] if on_device else host_skipped}"] if skip_nonfinite else [])))
         if val_dataloader is not None and (global_step % (log_step * 3) == 0 or global_step == 1):
             _info(logger, "=" * 80)
             _info(logger, f"Running validation at step {global_step}")

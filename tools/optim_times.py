@@ -13,6 +13,7 @@ the same for the parameter set of `--encoders 1` (ViT-B/32 towers + head, synthe
     python tools/optim_times.py [--out profiles/optim_step_times.txt]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/optim_times.py --kernels-only     # per-kernel times, a run of its own
     python tools/optim_times.py --summary DIR                                                 # ... read from its trace database
+    python tools/optim_times.py --guard [--out profiles/optim_guard_times.txt]                # the non-finite guard's cost (6.9)
 """
 import argparse
 import os
@@ -152,6 +153,47 @@ def update_alone(out, name, params, opt, n=100):
         "launch alone; its own time and share of the HBM peak come from the kernel trace: --summary)")
 
 
+def guard_cost(out, blocks=6, n=50):
+    """the three launches with the non-finite guard against the three without, head-only table, each replayed
+    from a graph of its own on static finite gradients; alternating blocks, device events around each block."""
+    graphs = {}
+    for name, guarded in (("unguarded", False), ("guarded", True)):
+        m = modeling.NeighborRetr(modeling.default_config(num_neighbors=K)).to(DEV).train()
+        params = list(m.parameters())
+        opt = optim.prep_optimizer(Args, m, 10 ** 6, 0, global_max_norm=1.0, clamp_logit_scale=True, wrap=False,
+                                   skip_nonfinite=guarded)[0]
+        gen = torch.Generator(device=DEV).manual_seed(1)
+        for p in params:
+            p.grad = torch.randn(p.shape, generator=gen, device=DEV) * 0.01
+        opt.prepare(params)
+        if guarded:
+            opt.watch_losses(torch.zeros(5, device=DEV))
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            opt.issue()
+        for _ in range(10):
+            g.replay()
+        graphs[name] = (g, opt, m)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = {name: [] for name in graphs}
+    for _ in range(blocks):
+        for name, (g, _, _) in graphs.items():
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(n):
+                g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / n * 1e3)
+    stats = graphs["guarded"][1].guard_stats()
+    assert stats["skipped"] == 0 and stats["attempts"] == 10 + blocks * n, stats
+    out(f"non-finite guard, head only, three launches replayed from a graph of their own, {blocks} alternating blocks of {n}:")
+    for name, t in times.items():
+        out(f"  {name:9s}: median {np.median(t):.2f} us per step   blocks {np.round(t, 2).tolist()}   spread {max(t) - min(t):.2f} us")
+    out(f"  guarded median - unguarded median: {np.median(times['guarded']) - np.median(times['unguarded']):+.2f} us")
+
+
 def adamw_tail_alone(out, name, params, n=50):
     opt = torch.optim.AdamW(params, lr=1e-4, weight_decay=0.2)
     grads = [torch.randn_like(p) * 0.01 for p in params]
@@ -206,12 +248,20 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernels-only", action="store_true", help="50 eager updates of the head's parameters and nothing else")
     ap.add_argument("--skip-encoders", action="store_true")
+    ap.add_argument("--guard", action="store_true", help="only: the three launches with the non-finite guard against without")
     args = ap.parse_args()
     lines = []
 
     def out(s):
         print(s, flush=True)
         lines.append(s)
+    if args.guard:
+        out(f"tools/optim_times.py --guard on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
+        guard_cost(out)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if args.kernels_only:
         m = modeling.NeighborRetr(modeling.default_config(num_neighbors=K)).to(DEV).train()
         params = list(m.parameters())
