@@ -621,21 +621,14 @@ def eval_epoch(args, model, test):
     they are the inputs), one packed all-gather + index scatter restores dataset order (evaluator.py:173-189), rank r
     computes rows [r N/W, (r+1) N/W) of the N x N similarity and the rank counts of its slab on the GPU, three small
     collectives complete them."""
-    from neighborretr_amd.evaluator import (gather_eval_features, rank_sample_indices, sharded_metrics, sharded_metrics_with_hubness,
-                                            sharded_metrics_with_test_norm, test_norm_label)
-    from neighborretr_amd.evaluator import local_scaling_label, sharded_metrics_with_local_scaling
-    from neighborretr_amd.evaluator import mutual_proximity_label, sharded_metrics_with_mutual_proximity
-    from neighborretr_amd.evaluator import _check_bootstrap, _check_ir
+    from neighborretr_amd.evaluator import correction_from_args, gather_eval_features, rank_sample_indices, sharded_evaluation
     from neighborretr_amd.metrics import RetrievalMetrics
-    boot = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
-                bootstrap_level=getattr(args, "bootstrap_level", 0.95))
-    _check_bootstrap(boot["bootstrap"], boot["bootstrap_seed"], boot["bootstrap_level"])         # before any work
-    ir = _check_ir(getattr(args, "ir_metrics", 0) or 0)                                          # before any work
-    extras = dict(boot, ir=ir)                                                                   # what every evaluator call takes
+    correction, extras = correction_from_args(args, model)     # every flag checked before any work
+    hubness_k = extras["hubness_k"]
 
     def log_ir(nt, nv, tag=""):
         """The IR line of each direction (MRR, mAP, nDCG@10, R-Prec) and its interval lines."""
-        if not ir:
+        if not extras["ir"]:
             return
         for side, m in (("text->video", nt), ("video->text", nv)):
             prefix = f"{side} {tag}".rstrip() + ": "
@@ -646,16 +639,12 @@ def eval_epoch(args, model, test):
 
     def log_bootstrap(nt, nv, tag=""):
         """The interval line of each direction after its metrics line, and for a correction the paired line against raw."""
-        if not boot["bootstrap"]:
+        if not extras["bootstrap"]:
             return
         for side, m in (("text->video", nt), ("video->text", nv)):
             log(args, RetrievalMetrics.format_bootstrap(m["bootstrap"], prefix=f"{side} {tag}".rstrip() + " "))
             if "bootstrap_vs_raw" in m:
                 log(args, RetrievalMetrics.format_bootstrap(m["bootstrap_vs_raw"], prefix=f"{side} {tag} - raw "))
-    hubness_k = int(getattr(args, "hubness_k", 0) or 0)
-    test_norm = getattr(args, "test_norm", None) or "none"
-    local_scaling = getattr(args, "local_scaling", None) or "none"
-    mutual_proximity = getattr(args, "mutual_proximity", None) or "none"
     model.eval()
     dev = args.device
     mine = rank_sample_indices(test.n, args.world_size, args.rank)     # equal counts on every rank (padded like DistributedSampler)
@@ -666,32 +655,16 @@ def eval_epoch(args, model, test):
         t, tm, v, vm = (torch.cat([p[k] for p in parts], 0) for k in range(4))
     if args.world_size > 1:
         t, v, tm, vm = gather_eval_features(t, v, mine.to(dev), tm, vm, args)
-    if test_norm != "none":
-        t2v, v2t = sharded_metrics_with_test_norm(model, t, v, tm.float(), vm.float(), args, test_norm, args.test_norm_beta,
-                                                  qb_k=args.qb_k, hubness_k=hubness_k, n_iter=args.test_norm_iters, **extras)
-    elif local_scaling != "none":
-        t2v, v2t = sharded_metrics_with_local_scaling(model, t, v, tm.float(), vm.float(), args, local_scaling,
-                                                      k=args.local_scaling_k, bank=bool(args.local_scaling_bank),
-                                                      hubness_k=hubness_k, **extras)
-    elif mutual_proximity != "none":
-        t2v, v2t = sharded_metrics_with_mutual_proximity(model, t, v, tm.float(), vm.float(), args, mutual_proximity,
-                                                         bank=bool(args.mutual_proximity_bank), hubness_k=hubness_k, **extras)
-    elif hubness_k:
-        t2v, v2t = sharded_metrics_with_hubness(model, t, v, tm.float(), vm.float(), args, hubness_k, **extras)
-    else:
-        t2v, v2t = sharded_metrics(model, t, v, tm.float(), vm.float(), args, **extras)
+    t2v, v2t = sharded_evaluation(model, t, v, tm.float(), vm.float(), args, correction, **extras)
     log(args, f"text->video R@1 {t2v['R1']:.1f} R@5 {t2v['R5']:.1f} R@10 {t2v['R10']:.1f} MedR {t2v['MR']:.1f} | "
               f"video->text R@1 {v2t['R1']:.1f} R@5 {v2t['R5']:.1f} R@10 {v2t['R10']:.1f} MedR {v2t['MR']:.1f}")
     log_bootstrap(t2v, v2t)
     log_ir(t2v, v2t)
     if hubness_k:
-        from neighborretr_amd.metrics import RetrievalMetrics
         log(args, RetrievalMetrics.format_hubness(t2v["hubness"], prefix="text->video "))
         log(args, RetrievalMetrics.format_hubness(v2t["hubness"], prefix="video->text "))
-    if test_norm != "none":
-        from neighborretr_amd.metrics import RetrievalMetrics
-        nt, nv = t2v["test_norm"], v2t["test_norm"]
-        tag = test_norm_label(test_norm, nt["beta"], nt.get("iters"))
+    if correction is not None:
+        nt, nv, tag = t2v[correction.key], v2t[correction.key], correction.label
         log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
         log_bootstrap(nt, nv, tag)
@@ -701,28 +674,6 @@ def eval_epoch(args, model, test):
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
         if "marginal_err" in nt:
             log(args, f"{tag} marginal error {nt['marginal_err']:.3e} / {nv['marginal_err']:.3e}")
-    if local_scaling != "none":
-        from neighborretr_amd.metrics import RetrievalMetrics
-        nt, nv = t2v["local_scaling"], v2t["local_scaling"]
-        tag = local_scaling_label(local_scaling, nt["k"], nt["bank"])
-        log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
-                  f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
-        log_bootstrap(nt, nv, tag)
-        log_ir(nt, nv, tag)
-        if hubness_k:
-            log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
-            log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
-    if mutual_proximity != "none":
-        from neighborretr_amd.metrics import RetrievalMetrics
-        nt, nv = t2v["mutual_proximity"], v2t["mutual_proximity"]
-        tag = mutual_proximity_label(mutual_proximity, nt["bank"])
-        log(args, f"text->video {tag} R@1 {nt['R1']:.1f} R@5 {nt['R5']:.1f} R@10 {nt['R10']:.1f} MedR {nt['MR']:.1f} | "
-                  f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
-        log_bootstrap(nt, nv, tag)
-        log_ir(nt, nv, tag)
-        if hubness_k:
-            log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
-            log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
     return t2v, v2t
 
 

@@ -10,6 +10,8 @@ the text->video ranks of its rows and its partial video->text column counts on t
 collectives (diagonal N floats, row counts 2n ints, column counts 2N ints) give every rank the same R@K as the
 reference's sort.  Nothing but 4N integers ever leaves the device.
 """
+from typing import Callable, NamedTuple, Optional
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -65,6 +67,23 @@ def slab_bounds(n, world, rank):
     return r0, r0 + base + (1 if rank < extra else 0)
 
 
+def slab_rows(n, world, rank):
+    """The number of rows of rank `rank`'s slab."""
+    r0, r1 = slab_bounds(n, world, rank)
+    return r1 - r0
+
+
+def _gathered_rows(mine, n_rows, W):
+    """[K, width] of this rank (row r0 + i at column i, width = ceil(n_rows / W): slabs differ by at most one row, padded to the
+    largest) -> [K, n_rows] of every rank's rows: one padded all-gather, every rank's real rows cut back out."""
+    K, width = mine.shape
+    if W == 1:
+        return mine[:, :n_rows].contiguous()
+    allv = torch.empty((W, K, width), dtype=mine.dtype, device=mine.device)
+    comm.all_gather_into_tensor(allv.view(-1), mine.reshape(-1))
+    return torch.cat([allv[r, :, :slab_rows(n_rows, W, r)] for r in range(W)], dim=1).contiguous()
+
+
 def _slab_similarity(model, text_feat, video_feat, text_mask, video_mask, r0, r1, chunk=256):
     """Rows [r0, r1) of the text x video similarity, on the rank-exact (split-bf16) path of the fused kernel."""
     old = model.precision
@@ -87,13 +106,7 @@ def sharded_retrieval_ranks(model, text_feat, video_feat, text_mask, video_mask,
     """-> (greater_t2v, equal_t2v, greater_v2t, equal_v2t), int64 numpy arrays of length N, identical on every rank:
     for text i the number of videos scoring above / equal to its own video (metrics.py:58-66 on S), and for video j the
     number of texts scoring above / equal to its own text (the same on S.T)."""
-    W = _world(args)
-    rank = comm.get_rank() if W > 1 else 0
-    N = text_feat.shape[0]
-    if video_feat.shape[0] != N:
-        raise ValueError("single-sentence retrieval: one text per video expected")
-    r0, r1 = slab_bounds(N, W, rank)
-    S_slab = _slab_similarity(model, text_feat, video_feat, text_mask, video_mask, r0, r1, chunk)
+    S_slab, N, _, W, rank, _ = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, None, chunk)
     return _ranks_from_slab(S_slab, N, W, rank)
 
 
@@ -102,18 +115,11 @@ def _ranks_from_slab(S_slab, N, W, rank):
     r0, r1 = slab_bounds(N, W, rank)
     dev = S_slab.device
     n = r1 - r0
-    # the diagonal of the whole matrix: this slab's part, gathered (slabs differ by at most one row: padded to the largest)
     width = -(-N // W)
-    mine = torch.full((width,), float("nan"), dtype=torch.float32, device=dev)
+    mine = torch.full((1, width), float("nan"), dtype=torch.float32, device=dev)      # the diagonal of the whole matrix: this slab's part
     if n:
-        mine[:n] = S_slab[torch.arange(n, device=dev), torch.arange(r0, r1, device=dev)]
-    if W > 1:
-        allv = torch.empty((W * width,), dtype=torch.float32, device=dev)
-        comm.all_gather_into_tensor(allv, mine)
-        diag = torch.cat([allv[r * width: r * width + (slab_bounds(N, W, r)[1] - slab_bounds(N, W, r)[0])] for r in range(W)])
-    else:
-        diag = mine[:n]
-    diag = diag.contiguous()
+        mine[0, :n] = S_slab[torch.arange(n, device=dev), torch.arange(r0, r1, device=dev)]
+    diag = _gathered_rows(mine, N, W)[0]
     if n:
         g_rows, e_rows, g_cols, e_cols = ops.slab_ranks(S_slab, r0, diag)
     else:
@@ -124,81 +130,9 @@ def _ranks_from_slab(S_slab, N, W, rank):
     rows_pad[0, :n], rows_pad[1, :n] = g_rows, e_rows
     if W > 1:
         comm.all_reduce(cols)                              # partial column counts -> complete
-        allr = torch.empty((W, 2, width), dtype=torch.int32, device=dev)
-        comm.all_gather_into_tensor(allr.view(-1), rows_pad.view(-1))
-    else:
-        allr = rows_pad[None]
-    allr = allr.cpu().numpy()
-    gt = np.concatenate([allr[r, 0, :slab_bounds(N, W, r)[1] - slab_bounds(N, W, r)[0]] for r in range(W)])
-    et = np.concatenate([allr[r, 1, :slab_bounds(N, W, r)[1] - slab_bounds(N, W, r)[0]] for r in range(W)])
+    rows = _gathered_rows(rows_pad, N, W).cpu().numpy()
     cols = cols.cpu().numpy()
-    return gt.astype(np.int64), et.astype(np.int64), cols[0].astype(np.int64), cols[1].astype(np.int64)
-
-
-def sharded_metrics(model, text_feat, video_feat, text_mask, video_mask, args, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95,
-                    ir=False):
-    """(text->video metrics, video->text metrics) as RetrievalMetrics.compute_metrics(S) / (S.T) would give them.  bootstrap > 0:
-    each with a "bootstrap" entry (DESIGN.md "Bootstrap confidence intervals").  ir: each with an "ir" entry (DESIGN.md "Rank-aware
-    IR metrics")."""
-    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
-    if _check_ir(ir):
-        return _raw_metrics_with_ir(model, text_feat, video_feat, text_mask, video_mask, args, None, 256, boot)
-    gt, et, gv, ev = sharded_retrieval_ranks(model, text_feat, video_feat, text_mask, video_mask, args)
-    units = _query_units(gt, et), _query_units(gv, ev)
-    t2v, v2t = (RetrievalMetrics.metrics_from_ranks(u[0]) for u in units)
-    _add_bootstrap(t2v, v2t, units, boot, text_feat.device)
-    return t2v, v2t
-
-
-def _raw_metrics_with_ir(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk, boot):
-    """The raw dictionaries of both directions with their "ir" entries (and "bootstrap" ones), from one scoring of the slab.
-
-    Why ir leaves the callers' plain route: the pair ranks are counted over the slab itself, and sharded_retrieval_ranks and the
-    multi-sentence body drop their slab once its ranks are out; scoring it a second time would double the evaluation's cost.  So
-    this route keeps the slab and takes the R@K dictionaries from _metrics_and_units, the route every correction already takes for
-    its raw entry (and the multi-sentence body itself with a bootstrap).  Both routes rank with the same slab helpers
-    (_ranks_from_slab, _multi_sentence_ranks); tests/test_irmetrics_gpu.py holds their dictionaries equal key for key."""
-    S_slab, n_rows, n_cols, W, rank, ends = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    t2v, v2t, units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
-    _add_bootstrap(t2v, v2t, units, boot, S_slab.device)
-    _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot)
-    return t2v, v2t
-
-
-def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, video_mask, cut_off_points, args, chunk=256, bootstrap=0,
-                                   bootstrap_seed=0, bootstrap_level=0.95, ir=False):
-    """Several captions per video (evaluator.py:114-149 features, :225-262 metrics): text_feat [Ns,...] holds every
-    sentence in dataset order, video_feat [V,...] one entry per video, cut_off_points[g] = index of the LAST sentence of
-    video g (the dataset's cut_off_points minus one, evaluator.py:98).  -> (text->video, video->text) metric dictionaries.
-
-    The reference pads the Ns x V matrix to [V, max_sentences, V] with -inf on the host and ranks it with two argsorts
-    (metrics.py:82-126) and a max over the padded axis (:128-148).  Here rank r scores its slab of sentence rows, one
-    launch (nr_group_slab_ranks) gives every row's rank and the slab's per-video best scores, and a MAX all-reduce of
-    the V x V best-score matrix + an all-gather of the Ns ranks complete them; no padded tensor exists.  bootstrap > 0: each
-    dictionary gains a "bootstrap" entry that resamples VIDEOS (DESIGN.md "Bootstrap confidence intervals").  ir: each gains an "ir"
-    entry (DESIGN.md "Rank-aware IR metrics")."""
-    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
-    if _check_ir(ir):
-        return _raw_metrics_with_ir(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk, boot)
-    W = _world(args)
-    rank = comm.get_rank() if W > 1 else 0
-    Ns, V = text_feat.shape[0], video_feat.shape[0]
-    ends = _group_ends(cut_off_points, Ns, V)
-    r0, r1 = slab_bounds(Ns, W, rank)
-    S_slab = _slab_similarity(model, text_feat, video_feat, text_mask, video_mask, r0, r1, chunk)
-    if not boot:
-        return _multi_sentence_from_slab(S_slab, ends, Ns, V, W, rank)
-    t2v, v2t, units = _metrics_and_units(S_slab, S_slab, Ns, V, W, rank, ends)
-    _add_bootstrap(t2v, v2t, units, boot, S_slab.device)
-    return t2v, v2t
-
-
-def _multi_sentence_from_slab(S_slab, ends, Ns, V, W, rank):
-    """sharded_multi_sentence_metrics from this rank's slab of sentence rows (two collectives)."""
-    ranks, gmax = _multi_sentence_ranks(S_slab, ends, Ns, V, W, rank)
-    t2v = RetrievalMetrics.multi_sentence_metrics_from_ranks(ranks[ranks >= 0])      # < 0: own score NaN / inf, not ranked
-    v2t = RetrievalMetrics.compute_metrics(gmax.T.contiguous())          # [video, caption group], metrics.py:146-148
-    return t2v, v2t
+    return rows[0].astype(np.int64), rows[1].astype(np.int64), cols[0].astype(np.int64), cols[1].astype(np.int64)
 
 
 def _multi_sentence_ranks(S_slab, ends, Ns, V, W, rank):
@@ -208,21 +142,15 @@ def _multi_sentence_ranks(S_slab, ends, Ns, V, W, rank):
     group_end = torch.from_numpy(ends.astype(np.int32)).to(dev)
     r0, r1 = slab_bounds(Ns, W, rank)
     n = r1 - r0
-    width = -(-Ns // W)
-    mine = torch.zeros((width,), dtype=torch.int32, device=dev)
+    mine = torch.zeros((1, -(-Ns // W)), dtype=torch.int32, device=dev)
     if n:
         greater, equal_before, gmax = ops.group_slab_ranks(S_slab, r0, group_end)
-        mine[:n] = torch.where(greater < 0, greater, greater + equal_before)
+        mine[0, :n] = torch.where(greater < 0, greater, greater + equal_before)
     else:
         gmax = torch.full((V, V), float("-inf"), dtype=torch.float32, device=dev)
     if W > 1:
         comm.all_reduce(gmax, op="max")
-        allr = torch.empty((W, width), dtype=torch.int32, device=dev)
-        comm.all_gather_into_tensor(allr.view(-1), mine)
-        ranks = torch.cat([allr[r, :slab_bounds(Ns, W, r)[1] - slab_bounds(Ns, W, r)[0]] for r in range(W)])
-    else:
-        ranks = mine[:n]
-    return ranks, gmax
+    return _gathered_rows(mine, Ns, W)[0], gmax
 
 
 # ---- top-k lists and hubness (DESIGN.md "Top-k lists and hubness") ------------------------------------------------------
@@ -280,14 +208,11 @@ def _topk_from_slab(S_slab, n_rows, n_cols, k, W, rank):
     r0, r1 = slab_bounds(n_rows, W, rank)
     dev = S_slab.device
     ri, rv = _slab_row_lists(S_slab, k, n_cols)
-    if W > 1:
-        width = -(-n_rows // W)
-        mine = torch.zeros((width, 2, k), dtype=torch.int32, device=dev)
-        mine[:r1 - r0, 0], mine[:r1 - r0, 1] = ri, rv.view(torch.int32)
-        allr = torch.empty((W, width, 2, k), dtype=torch.int32, device=dev)
-        comm.all_gather_into_tensor(allr.view(-1), mine.view(-1))
-        rows = torch.cat([allr[r, :slab_bounds(n_rows, W, r)[1] - slab_bounds(n_rows, W, r)[0]] for r in range(W)])
-        ri, rv = rows[:, 0].contiguous(), rows[:, 1].contiguous().view(torch.float32)
+    if W > 1:                                                        # every rank's row lists: indices and score bits, transposed
+        mine = torch.zeros((2 * k, -(-n_rows // W)), dtype=torch.int32, device=dev)
+        mine[:k, :r1 - r0], mine[k:, :r1 - r0] = ri.T, rv.view(torch.int32).T
+        rows = _gathered_rows(mine, n_rows, W)
+        ri, rv = rows[:k].T.contiguous(), rows[k:].T.contiguous().view(torch.float32)
     ci, cv = _column_lists(S_slab, n_rows, n_cols, k, W, rank)
     return ri, rv, ci, cv
 
@@ -317,8 +242,27 @@ def _hubness_from_slab(S_slab, n_rows, n_cols, k, W, rank, ends):
             _col_hubness(S_slab, n_rows, n_cols, k, W, rank, ends))
 
 
+def _check_hubness_k(hubness_k):
+    """hubness_k as an int: 0 or None for no hubness entry, else a list length ops._check_k accepts."""
+    hubness_k = int(hubness_k or 0)
+    if hubness_k:
+        ops._check_k(hubness_k)
+    return hubness_k
+
+
+class EvalSlab(NamedTuple):
+    """This rank's rows of the text (sentence) x video similarity and where they sit: S [r1 - r0, n_cols] for the rows
+    slab_bounds(n_rows, W, rank); ends = None for a single-sentence set, else one past the last sentence of every video."""
+    S: torch.Tensor
+    n_rows: int
+    n_cols: int
+    W: int
+    rank: int
+    ends: Optional[np.ndarray]
+
+
 def _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk):
-    """(S_slab, n_rows, n_cols, W, rank, ends) of this rank: its rows of the text (sentence) x video similarity."""
+    """The EvalSlab of this rank (it unpacks as S_slab, n_rows, n_cols, W, rank, ends)."""
     W = _world(args)
     rank = comm.get_rank() if W > 1 else 0
     n_rows, n_cols = text_feat.shape[0], video_feat.shape[0]
@@ -330,7 +274,7 @@ def _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_of
         ends = _group_ends(cut_off_points, n_rows, n_cols)
     r0, r1 = slab_bounds(n_rows, W, rank)
     S_slab = _slab_similarity(model, text_feat, video_feat, text_mask, video_mask, r0, r1, chunk)
-    return S_slab, n_rows, n_cols, W, rank, ends
+    return EvalSlab(S_slab, n_rows, n_cols, W, rank, ends)
 
 
 def sharded_topk(model, text_feat, video_feat, text_mask, video_mask, k, args, cut_off_points=None, chunk=256):
@@ -350,23 +294,6 @@ def sharded_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k
                                                        chunk)
     ops._check_k(k)
     return _hubness_from_slab(S_slab, n_rows, n_cols, int(k), W, rank, ends)
-
-
-def sharded_metrics_with_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k, cut_off_points=None, chunk=256,
-                                 bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, ir=False):
-    """sharded_metrics (cut_off_points None) or sharded_multi_sentence_metrics, plus a "hubness" entry in each dictionary
-    (sharded_hubness), from ONE scoring of this rank's slab.  bootstrap > 0: a "bootstrap" entry too; ir: an "ir" entry too."""
-    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
-    ir = _check_ir(ir)
-    S_slab, n_rows, n_cols, W, rank, ends = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points,
-                                                       chunk)
-    ops._check_k(k)
-    t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
-    t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, int(k), W, rank, ends)
-    _add_bootstrap(t2v, v2t, raw_units, boot, S_slab.device)
-    if ir:
-        _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot)
-    return t2v, v2t
 
 
 # ---- test-time hubness reduction: IS, DSL, QB-Norm (DESIGN.md "Test-time hubness reduction") -------------------------------
@@ -399,10 +326,7 @@ def _check_test_norm(mode, beta, qb_k, hubness_k):
         raise ValueError(f"test_norm mode must be one of {TEST_NORM_MODES}, got {mode!r}")
     beta = ops._check_beta(beta)
     qb_k = ops._check_k(qb_k)
-    hubness_k = int(hubness_k or 0)
-    if hubness_k:
-        ops._check_k(hubness_k)
-    return beta, qb_k, hubness_k
+    return beta, qb_k, _check_hubness_k(hubness_k)
 
 
 def _querybank(model, querybank, dev):
@@ -430,6 +354,14 @@ def _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, bank, W, ra
     Qt = _slab_similarity(model, btf, video_feat, btm, video_mask, q0, q1, chunk)
     Qv = _slab_similarity(model, text_feat, bvf, text_mask, bvm, r0, r1, chunk)
     return Qt, Qv
+
+
+def _check_bank_slabs(Qt, Qv, S_slab, n_cols, n_bank_texts, W, rank):
+    """The shapes _bank_slabs gives rank `rank`: its bank texts x every test video, its test texts x every bank video."""
+    q = slab_rows(int(n_bank_texts), W, rank)
+    if Qt.shape[0] != q or Qt.shape[1] != n_cols or Qv.shape[0] != S_slab.shape[0]:
+        raise ValueError(f"bank slabs of rank {rank} must be [{q}, {n_cols}] and [{S_slab.shape[0]}, bank videos], got "
+                         f"{tuple(Qt.shape)} and {tuple(Qv.shape)}")
 
 
 def _gathered_lse(stats, W):
@@ -648,100 +580,6 @@ def _add_bootstrap(t2v, v2t, units, boot, dev, raw_units=None):
         metrics.update(_bootstrap_direction(units[side], boot, boot[1] + side, dev, None if raw_units is None else raw_units[side]))
 
 
-def _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k, chunk,
-                               n_iter=50, info=None):
-    """(T_slab, V_slab); the iterated modes put "iters" and "marginal_err" into the dictionary `info`."""
-    S_slab, n_rows, n_cols, W, rank, ends = slab
-    bank_slabs, n_bank_texts = None, None
-    if mode in BANK_MODES:
-        bank = _querybank(model, querybank, S_slab.device)
-        bank_slabs = _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, bank, W, rank, chunk)
-        n_bank_texts = bank[0].shape[0]
-    if mode in SINKHORN_MODES:
-        T, V, extra = _sinkhorn_from_slab(S_slab, n_rows, n_cols, W, rank, mode, beta, n_iter, ends, bank_slabs, n_bank_texts)
-        if info is not None:
-            info.update(extra)
-        return T, V
-    return _normalised_from_slab(S_slab, n_rows, n_cols, W, rank, mode, beta, bank_slabs, qb_k)
-
-
-def sharded_normalised_slabs(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None, qb_k=1,
-                             cut_off_points=None, chunk=256, n_iter=50):
-    """-> (T_slab, V_slab) fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the text->video
-    scores (rows are the queries) and the video->text scores (columns are the queries) after the test-time correction `mode`
-    ("is" | "dsl" | "qbnorm", DESIGN.md "Test-time hubness reduction"; "sinkhorn" | "qbsinkhorn" with n_iter iterations,
-    DESIGN.md "Test-time Sinkhorn normalisation": "sinkhorn" has ONE output, V_slab is T_slab).  querybank: (text_feat,
-    text_mask, video_feat, video_mask) of the qbnorm / qbsinkhorn querybank; None: the model's memory bank (load_memory_bank)."""
-    beta, qb_k, _ = _check_test_norm(mode, beta, qb_k, 0)
-    n_iter = _check_n_iter(n_iter)
-    if mode in BANK_MODES:
-        _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
-    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    return _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
-                                      chunk, n_iter)
-
-
-def _test_norm_entry(metrics, mode, beta, qb_k, info=None, side=0):
-    metrics.update(mode=mode, beta=beta)
-    if mode == "qbnorm":
-        metrics["qb_k"] = qb_k
-    if mode in SINKHORN_MODES:                                  # side 0: text->video (qbsinkhorn: Qt's rows), 1: video->text (Qv's)
-        metrics.update(iters=info["iters"], marginal_err=info["marginal_err"][side])
-    return metrics
-
-
-def sharded_normalised_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None, qb_k=1,
-                               hubness_k=0, cut_off_points=None, chunk=256, n_iter=50):
-    """(text->video, video->text) metric dictionaries of the normalised scores (sharded_normalised_slabs), identical on every
-    rank, each with "mode" and "beta" (and "qb_k" for qbnorm; "iters" and "marginal_err" for sinkhorn / qbsinkhorn) and, with
-    hubness_k, a "hubness" entry (sharded_hubness's summary of T's row lists / V's column lists)."""
-    beta, qb_k, hubness_k = _check_test_norm(mode, beta, qb_k, hubness_k)
-    n_iter = _check_n_iter(n_iter)
-    if mode in BANK_MODES:
-        _querybank(model, querybank, text_feat.device)
-    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    info = {}
-    T, V = _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
-                                      chunk, n_iter, info)
-    _, n_rows, n_cols, W, rank, ends = slab
-    t2v, v2t = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k)
-    return _test_norm_entry(t2v, mode, beta, qb_k, info, 0), _test_norm_entry(v2t, mode, beta, qb_k, info, 1)
-
-
-def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None,
-                                   qb_k=1, hubness_k=0, cut_off_points=None, chunk=256, n_iter=50, bootstrap=0, bootstrap_seed=0,
-                                   bootstrap_level=0.95, ir=False):
-    """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
-    each with one more entry "test_norm" = sharded_normalised_metrics, from ONE scoring of this rank's slab.  bootstrap > 0: the
-    raw dictionaries gain "bootstrap", the "test_norm" ones "bootstrap" and "bootstrap_vs_raw" (paired on the same draws).  ir: the
-    raw and the "test_norm" dictionaries gain "ir" (DESIGN.md "Rank-aware IR metrics"), with the same bootstrap entries inside."""
-    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
-    ir = _check_ir(ir)
-    beta, qb_k, hubness_k = _check_test_norm(mode, beta, qb_k, hubness_k)
-    n_iter = _check_n_iter(n_iter)
-    if mode in BANK_MODES:
-        _querybank(model, querybank, text_feat.device)
-    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    S_slab, n_rows, n_cols, W, rank, ends = slab
-    t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
-    if hubness_k:
-        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
-    raw_columns = _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot) if ir else None
-    info = {}
-    T, V = _normalised_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, beta, querybank, qb_k,
-                                      chunk, n_iter, info)
-    del S_slab, slab
-    units = []
-    nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k, units)
-    _add_bootstrap(t2v, v2t, raw_units, boot, T.device)
-    _add_bootstrap(nt, nv, units, boot, T.device, raw_units)
-    if ir:
-        _add_ir(nt, nv, T, V, n_rows, n_cols, W, rank, ends, boot, raw_columns)
-    t2v["test_norm"] = _test_norm_entry(nt, mode, beta, qb_k, info, 0)
-    v2t["test_norm"] = _test_norm_entry(nv, mode, beta, qb_k, info, 1)
-    return t2v, v2t
-
-
 # ---- local scaling: CSLS, NICDM, LS (DESIGN.md "Local scaling") ---------------------------------------------------------------------
 # Every score is rescaled by statistics of its text's and its video's k-nearest neighbourhoods: a text's neighbourhood is its
 # top-k videos (a rank-local row list), a video's its top-k texts (the column lists, complete on every rank after the one
@@ -763,10 +601,7 @@ def _check_local_scaling(mode, k, hubness_k=0):
     if isinstance(k, bool) or int(k) != k:
         raise ValueError(f"local_scaling k must be an integer in [1, 128], got {k!r}")
     k = ops._check_k(k)
-    hubness_k = int(hubness_k or 0)
-    if hubness_k:
-        ops._check_k(hubness_k)
-    return k, hubness_k
+    return k, _check_hubness_k(hubness_k)
 
 
 def _local_scaling_stats(S_slab, n_rows, n_cols, W, rank, mode, k, bank_slabs=None, n_bank_texts=None):
@@ -778,10 +613,7 @@ def _local_scaling_stats(S_slab, n_rows, n_cols, W, rank, mode, k, bank_slabs=No
         ci, cv = _column_lists(S_slab, n_rows, n_cols, k, W, rank)
     else:
         Qt, Qv = bank_slabs
-        q0, q1 = slab_bounds(int(n_bank_texts), W, rank)
-        if Qt.shape[0] != q1 - q0 or Qt.shape[1] != n_cols or Qv.shape[0] != S_slab.shape[0]:
-            raise ValueError(f"bank slabs of rank {rank} must be [{q1 - q0}, {n_cols}] and [{S_slab.shape[0]}, bank videos], got "
-                             f"{tuple(Qt.shape)} and {tuple(Qv.shape)}")
+        _check_bank_slabs(Qt, Qv, S_slab, n_cols, n_bank_texts, W, rank)
         ri, rv = _slab_row_lists(Qv, k, Qv.shape[1])
         ci, cv = _column_lists(Qt, int(n_bank_texts), n_cols, k, W, rank)
     which = 1 if mode == "ls" else 0
@@ -793,79 +625,6 @@ def _local_scaled_from_slab(S_slab, n_rows, n_cols, W, rank, mode, k, bank_slabs
     _bank_slabs scores them and n_bank_texts = the bank's text count: the neighbourhoods are taken in the querybank."""
     row_stat, col_stat = _local_scaling_stats(S_slab, n_rows, n_cols, W, rank, mode, k, bank_slabs, n_bank_texts)
     return ops.localscale_apply(S_slab, mode, row_stat, col_stat)
-
-
-def _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk):
-    S_slab, n_rows, n_cols, W, rank, _ = slab
-    bank_slabs, n_bank_texts = None, None
-    if bank:
-        qb = _querybank(model, querybank, S_slab.device)
-        bank_slabs = _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, qb, W, rank, chunk)
-        n_bank_texts = qb[0].shape[0]
-    return _local_scaled_from_slab(S_slab, n_rows, n_cols, W, rank, mode, k, bank_slabs, n_bank_texts)
-
-
-def sharded_local_scaled_slab(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False, querybank=None,
-                              cut_off_points=None, chunk=256):
-    """-> T_slab fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the scores after local scaling
-    `mode` ("csls" | "nicdm" | "ls", DESIGN.md "Local scaling") with neighbourhoods of k items.  Rows rank text->video, columns
-    video->text.  bank: the neighbourhoods are taken in a querybank, (text_feat, text_mask, video_feat, video_mask), None: the
-    model's memory bank (load_memory_bank)."""
-    k, _ = _check_local_scaling(mode, k)
-    if bank:
-        _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
-    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    return _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk)
-
-
-def _local_scaling_entry(metrics, mode, k, bank):
-    metrics.update(mode=mode, k=k, bank=bool(bank))
-    return metrics
-
-
-def sharded_local_scaled_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False, querybank=None,
-                                 hubness_k=0, cut_off_points=None, chunk=256):
-    """(text->video, video->text) metric dictionaries of the locally scaled scores (sharded_local_scaled_slab), identical on
-    every rank, each with "mode", "k" and "bank" and, with hubness_k, a "hubness" entry (T's row lists / column lists)."""
-    k, hubness_k = _check_local_scaling(mode, k, hubness_k)
-    if bank:
-        _querybank(model, querybank, text_feat.device)
-    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    T = _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk)
-    _, n_rows, n_cols, W, rank, ends = slab
-    t2v, v2t = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k)
-    return _local_scaling_entry(t2v, mode, k, bank), _local_scaling_entry(v2t, mode, k, bank)
-
-
-def sharded_metrics_with_local_scaling(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False,
-                                       querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0, bootstrap_seed=0,
-                                       bootstrap_level=0.95, ir=False):
-    """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
-    each with one more entry "local_scaling" = sharded_local_scaled_metrics, from ONE scoring of this rank's slab.  bootstrap > 0:
-    the raw dictionaries gain "bootstrap", the "local_scaling" ones "bootstrap" and "bootstrap_vs_raw" (paired on the same draws).
-    ir: the raw and the "local_scaling" dictionaries gain "ir" (DESIGN.md "Rank-aware IR metrics")."""
-    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
-    ir = _check_ir(ir)
-    k, hubness_k = _check_local_scaling(mode, k, hubness_k)
-    if bank:
-        _querybank(model, querybank, text_feat.device)
-    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    S_slab, n_rows, n_cols, W, rank, ends = slab
-    t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
-    if hubness_k:
-        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
-    raw_columns = _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot) if ir else None
-    T = _local_scaled_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, k, bank, querybank, chunk)
-    del S_slab, slab
-    units = []
-    nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k, units)
-    _add_bootstrap(t2v, v2t, raw_units, boot, T.device)
-    _add_bootstrap(nt, nv, units, boot, T.device, raw_units)
-    if ir:
-        _add_ir(nt, nv, T, T, n_rows, n_cols, W, rank, ends, boot, raw_columns)
-    t2v["local_scaling"] = _local_scaling_entry(nt, mode, k, bank)
-    v2t["local_scaling"] = _local_scaling_entry(nv, mode, k, bank)
-    return t2v, v2t
 
 
 # ---- mutual proximity: emp, gauss (DESIGN.md "Mutual proximity") ---------------------------------------------------------------------
@@ -889,10 +648,7 @@ def mutual_proximity_label(mode, bank=False):
 def _check_mutual_proximity(mode, hubness_k=0):
     if mode not in MUTUAL_PROXIMITY_MODES:
         raise ValueError(f"mutual_proximity mode must be one of {MUTUAL_PROXIMITY_MODES}, got {mode!r}")
-    hubness_k = int(hubness_k or 0)
-    if hubness_k:
-        ops._check_k(hubness_k)
-    return hubness_k
+    return _check_hubness_k(hubness_k)
 
 
 def _mp_column_counts(S_slab, src_slab, n_src, W, rank):
@@ -918,8 +674,7 @@ def _mp_column_counts(S_slab, src_slab, n_src, W, rank):
             block[have:].fill_(float("nan"))                          # the padding of a short block (never counted: see below)
         comm.all_gather_into_tensor(allb.view(-1), block.view(-1))
         for r in range(W):                                            # only the rows rank r really holds
-            q0, q1 = slab_bounds(n_src, W, r)
-            real = max(0, min(B, (q1 - q0) - b0))
+            real = max(0, min(B, slab_rows(n_src, W, r) - b0))
             if real:
                 ops.mp_col_counts(S_slab, allb[r, :real], out=c2)
     return c2, col_cnt
@@ -945,10 +700,7 @@ def _mutual_proximity_from_slab(S_slab, n_rows, n_cols, W, rank, mode, bank_slab
         row_src, col_src, n_src = S_slab, S_slab, n_rows
     else:
         Qt, Qv = bank_slabs
-        q0, q1 = slab_bounds(int(n_bank_texts), W, rank)
-        if Qt.shape[0] != q1 - q0 or Qt.shape[1] != n_cols or Qv.shape[0] != S_slab.shape[0]:
-            raise ValueError(f"bank slabs of rank {rank} must be [{q1 - q0}, {n_cols}] and [{S_slab.shape[0]}, bank videos], got "
-                             f"{tuple(Qt.shape)} and {tuple(Qv.shape)}")
+        _check_bank_slabs(Qt, Qv, S_slab, n_cols, n_bank_texts, W, rank)
         row_src, col_src, n_src = ops._slab_2d(Qv), ops._slab_2d(Qt), int(n_bank_texts)
     if max(n_src, row_src.shape[1]) >= ops.hip.MP_LINE_MAX:
         raise ValueError(f"mutual proximity: a reference line of {max(n_src, row_src.shape[1])} entries is too long for exact counts")
@@ -960,79 +712,6 @@ def _mutual_proximity_from_slab(S_slab, n_rows, n_cols, W, rank, mode, bank_slab
     row_mean, row_sd = ops.mp_row_moments(row_src)
     col_mean, col_sd = _mp_column_moments(col_src, W)
     return ops.mp_gauss_apply(S_slab, row_mean, row_sd, col_mean, col_sd)
-
-
-def _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk):
-    S_slab, n_rows, n_cols, W, rank, _ = slab
-    bank_slabs, n_bank_texts = None, None
-    if bank:
-        qb = _querybank(model, querybank, S_slab.device)
-        bank_slabs = _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, qb, W, rank, chunk)
-        n_bank_texts = qb[0].shape[0]
-    return _mutual_proximity_from_slab(S_slab, n_rows, n_cols, W, rank, mode, bank_slabs, n_bank_texts)
-
-
-def sharded_mutual_proximity_slab(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False, querybank=None,
-                                  cut_off_points=None, chunk=256):
-    """-> T_slab fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the scores after mutual proximity
-    `mode` ("emp" | "gauss", DESIGN.md "Mutual proximity").  Rows rank text->video, columns video->text.  bank: the reference
-    lines are taken in a querybank, (text_feat, text_mask, video_feat, video_mask), None: the model's memory bank
-    (load_memory_bank)."""
-    _check_mutual_proximity(mode)
-    if bank:
-        _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
-    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    return _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk)
-
-
-def _mutual_proximity_entry(metrics, mode, bank):
-    metrics.update(mode=mode, bank=bool(bank))
-    return metrics
-
-
-def sharded_mutual_proximity_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False, querybank=None,
-                                     hubness_k=0, cut_off_points=None, chunk=256):
-    """(text->video, video->text) metric dictionaries of the mutual-proximity scores (sharded_mutual_proximity_slab), identical on
-    every rank, each with "mode" and "bank" and, with hubness_k, a "hubness" entry (T's row lists / column lists)."""
-    hubness_k = _check_mutual_proximity(mode, hubness_k)
-    if bank:
-        _querybank(model, querybank, text_feat.device)
-    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    T = _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk)
-    _, n_rows, n_cols, W, rank, ends = slab
-    t2v, v2t = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k)
-    return _mutual_proximity_entry(t2v, mode, bank), _mutual_proximity_entry(v2t, mode, bank)
-
-
-def sharded_metrics_with_mutual_proximity(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False,
-                                          querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0,
-                                          bootstrap_seed=0, bootstrap_level=0.95, ir=False):
-    """The raw dictionaries of sharded_metrics / sharded_multi_sentence_metrics (sharded_metrics_with_hubness with hubness_k),
-    each with one more entry "mutual_proximity" = sharded_mutual_proximity_metrics, from ONE scoring of this rank's slab.
-    bootstrap > 0: the raw dictionaries gain "bootstrap", the "mutual_proximity" ones "bootstrap" and "bootstrap_vs_raw" (paired
-    on the same draws).  ir: the raw and the "mutual_proximity" dictionaries gain "ir" (DESIGN.md "Rank-aware IR metrics")."""
-    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
-    ir = _check_ir(ir)
-    hubness_k = _check_mutual_proximity(mode, hubness_k)
-    if bank:
-        _querybank(model, querybank, text_feat.device)
-    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
-    S_slab, n_rows, n_cols, W, rank, ends = slab
-    t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
-    if hubness_k:
-        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
-    raw_columns = _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot) if ir else None
-    T = _mutual_proximity_from_eval_slab(model, text_feat, video_feat, text_mask, video_mask, slab, mode, bank, querybank, chunk)
-    del S_slab, slab
-    units = []
-    nt, nv = _metrics_from_normalised(T, T, n_rows, n_cols, W, rank, ends, hubness_k, units)
-    _add_bootstrap(t2v, v2t, raw_units, boot, T.device)
-    _add_bootstrap(nt, nv, units, boot, T.device, raw_units)
-    if ir:
-        _add_ir(nt, nv, T, T, n_rows, n_cols, W, rank, ends, boot, raw_columns)
-    t2v["mutual_proximity"] = _mutual_proximity_entry(nt, mode, bank)
-    v2t["mutual_proximity"] = _mutual_proximity_entry(nv, mode, bank)
-    return t2v, v2t
 
 
 # ---- rank-aware IR metrics: MRR, mAP, nDCG@10, R-precision (DESIGN.md "Rank-aware IR metrics") ------------------------------------
@@ -1058,17 +737,6 @@ def _pair_ends(n_rows, n_cols, ends):
             raise ValueError("single-sentence retrieval: one text per video expected")
         return np.arange(1, n_rows + 1, dtype=np.int64)
     return np.asarray(ends, dtype=np.int64)
-
-
-def _gathered_rows(mine, n_rows, W):
-    """[K, width] of this rank (row r0 + i at column i, width = ceil(n_rows / W)) -> [K, n_rows] of every rank's rows: one padded
-    all-gather, as the diagonal in _ranks_from_slab."""
-    K, width = mine.shape
-    if W == 1:
-        return mine[:, :n_rows].contiguous()
-    allv = torch.empty((W, K, width), dtype=mine.dtype, device=mine.device)
-    comm.all_gather_into_tensor(allv.view(-1), mine.reshape(-1))
-    return torch.cat([allv[r, :, :slab_bounds(n_rows, W, r)[1] - slab_bounds(n_rows, W, r)[0]] for r in range(W)], dim=1).contiguous()
 
 
 def _pair_ranks_from_slab(T_slab, V_slab, n_rows, n_cols, W, rank, ends):
@@ -1147,3 +815,271 @@ def sharded_ir_metrics(model, text_feat, video_feat, text_mask, video_mask, args
     boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
     S_slab, n_rows, n_cols, W, rank, ends = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
     return _ir_from_slab(S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot)[0]
+
+
+# ---- the evaluation: one slab, one driver, an optional correction (DESIGN.md "The evaluation driver") ---------------------------------
+# Every metric dictionary comes from sharded_evaluation: ONE scoring of this rank's slab, the raw dictionaries, then the corrected
+# ones under the correction's key.  A correction is a value: what its entry says, whether it needs a querybank, and the call that
+# turns the slab into (T, V).  Every rank issues the same collectives in the same order; the order below is part of the contract.
+
+class Correction(NamedTuple):
+    """One test-time correction of the similarity.  apply(slab, bank_slabs, n_bank_texts) -> (T_slab, V_slab, info): T's rows rank
+    text->video, V's columns video->text (V_slab is T_slab for the one-output corrections); info holds "iters" and "marginal_err"
+    (text->video, video->text) for the iterated modes and is empty otherwise."""
+    key: str                     # the dictionary entry: "test_norm" | "local_scaling" | "mutual_proximity"
+    label: str                   # the tag of its log lines
+    needs_bank: bool             # scored against a querybank (bank_slabs, n_bank_texts) instead of the test set alone
+    entry: dict                  # the fields written into each direction's corrected dictionary
+    apply: Callable
+
+
+def test_norm_correction(mode, beta=20.0, qb_k=1, n_iter=50):
+    """IS, DSL, QB-Norm (DESIGN.md "Test-time hubness reduction"); Sinkhorn, QB-Sinkhorn with n_iter iterations (DESIGN.md
+    "Test-time Sinkhorn normalisation")."""
+    beta, qb_k, _ = _check_test_norm(mode, beta, qb_k, 0)
+    n_iter = _check_n_iter(n_iter)
+    entry = dict(mode=mode, beta=beta)
+    if mode == "qbnorm":
+        entry["qb_k"] = qb_k
+
+    def apply(slab, bank_slabs, n_bank_texts):
+        S, n_rows, n_cols, W, rank, ends = slab
+        if mode in SINKHORN_MODES:
+            return _sinkhorn_from_slab(S, n_rows, n_cols, W, rank, mode, beta, n_iter, ends, bank_slabs, n_bank_texts)
+        return _normalised_from_slab(S, n_rows, n_cols, W, rank, mode, beta, bank_slabs, qb_k) + ({},)
+    return Correction("test_norm", test_norm_label(mode, beta, n_iter), mode in BANK_MODES, entry, apply)
+
+
+def local_scaling_correction(mode, k=10, bank=False):
+    """CSLS, NICDM, LS with neighbourhoods of k items, taken in the querybank with `bank` (DESIGN.md "Local scaling")."""
+    k, _ = _check_local_scaling(mode, k)
+
+    def apply(slab, bank_slabs, n_bank_texts):
+        T = _local_scaled_from_slab(slab.S, slab.n_rows, slab.n_cols, slab.W, slab.rank, mode, k, bank_slabs, n_bank_texts)
+        return T, T, {}
+    return Correction("local_scaling", local_scaling_label(mode, k, bank), bool(bank), dict(mode=mode, k=k, bank=bool(bank)), apply)
+
+
+def mutual_proximity_correction(mode, bank=False):
+    """emp, gauss, the reference lines taken in the querybank with `bank` (DESIGN.md "Mutual proximity")."""
+    _check_mutual_proximity(mode)
+
+    def apply(slab, bank_slabs, n_bank_texts):
+        T = _mutual_proximity_from_slab(slab.S, slab.n_rows, slab.n_cols, slab.W, slab.rank, mode, bank_slabs, n_bank_texts)
+        return T, T, {}
+    return Correction("mutual_proximity", mutual_proximity_label(mode, bank), bool(bank), dict(mode=mode, bank=bool(bank)), apply)
+
+
+def _apply_correction(model, text_feat, video_feat, text_mask, video_mask, slab, correction, querybank, chunk):
+    """correction.apply on this rank's slab; the one place where the querybank's slabs are scored."""
+    bank_slabs, n_bank_texts = None, None
+    if correction.needs_bank:
+        bank = _querybank(model, querybank, slab.S.device)
+        bank_slabs = _bank_slabs(model, text_feat, video_feat, text_mask, video_mask, bank, slab.W, slab.rank, chunk)
+        n_bank_texts = bank[0].shape[0]
+    return correction.apply(slab, bank_slabs, n_bank_texts)
+
+
+def _corrected_entry(metrics, correction, info, side):
+    """The corrected dictionary of one direction (side 0: text->video, 1: video->text) with the correction's fields."""
+    metrics.update(correction.entry)
+    if info:
+        metrics.update(iters=info["iters"], marginal_err=info["marginal_err"][side])
+    return metrics
+
+
+def sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, correction=None, hubness_k=0, cut_off_points=None,
+                       chunk=256, querybank=None, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, ir=False):
+    """-> (text->video, video->text) metric dictionaries, identical on every rank, from ONE scoring of this rank's slab: R@K as
+    RetrievalMetrics.compute_metrics(S) / (S.T) would give them (cut_off_points: the multi-sentence metrics, see
+    sharded_multi_sentence_metrics).  hubness_k: each with a "hubness" entry (sharded_hubness).  ir: an "ir" entry (DESIGN.md
+    "Rank-aware IR metrics").  bootstrap > 0: a "bootstrap" entry, also inside "ir" (DESIGN.md "Bootstrap confidence intervals").
+    correction: each with one more entry correction.key, the same dictionary of the corrected scores with correction.entry's
+    fields; its bootstrap entries are "bootstrap" and "bootstrap_vs_raw" (paired with the raw ranking on the same draws).
+    querybank: (text_feat, text_mask, video_feat, video_mask) for a correction that needs one; None: the model's memory bank."""
+    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    ir = _check_ir(ir)
+    hubness_k = _check_hubness_k(hubness_k)
+    if correction is not None and correction.needs_bank:
+        _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    S_slab, n_rows, n_cols, W, rank, ends = slab
+    dev = S_slab.device
+    t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
+    if hubness_k:
+        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+    raw_columns = _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot) if ir else None
+    _add_bootstrap(t2v, v2t, raw_units, boot, dev)
+    if correction is None:
+        return t2v, v2t
+    T, V, info = _apply_correction(model, text_feat, video_feat, text_mask, video_mask, slab, correction, querybank, chunk)
+    del S_slab, slab                       # the raw slab, the largest buffer of the evaluation, goes before the corrected metrics
+    units = []
+    nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k, units)
+    _add_bootstrap(nt, nv, units, boot, dev, raw_units)
+    if ir:
+        _add_ir(nt, nv, T, V, n_rows, n_cols, W, rank, ends, boot, raw_columns)
+    t2v[correction.key] = _corrected_entry(nt, correction, info, 0)
+    v2t[correction.key] = _corrected_entry(nv, correction, info, 1)
+    return t2v, v2t
+
+
+def _corrected_slabs(model, text_feat, video_feat, text_mask, video_mask, args, correction, querybank, cut_off_points, chunk):
+    """(slab, T_slab, V_slab, info): this rank's slab and its corrected copies, nothing else computed."""
+    if correction.needs_bank:
+        _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
+    slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
+    return (slab,) + _apply_correction(model, text_feat, video_feat, text_mask, video_mask, slab, correction, querybank, chunk)
+
+
+def _corrected_metrics(model, text_feat, video_feat, text_mask, video_mask, args, correction, querybank, hubness_k, cut_off_points,
+                       chunk):
+    """The corrected dictionaries alone: what sharded_evaluation puts under correction.key, without bootstrap and ir."""
+    hubness_k = _check_hubness_k(hubness_k)
+    slab, T, V, info = _corrected_slabs(model, text_feat, video_feat, text_mask, video_mask, args, correction, querybank,
+                                        cut_off_points, chunk)
+    t2v, v2t = _metrics_from_normalised(T, V, slab.n_rows, slab.n_cols, slab.W, slab.rank, slab.ends, hubness_k)
+    return _corrected_entry(t2v, correction, info, 0), _corrected_entry(v2t, correction, info, 1)
+
+
+def sharded_metrics(model, text_feat, video_feat, text_mask, video_mask, args, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95,
+                    ir=False):
+    """(text->video metrics, video->text metrics) as RetrievalMetrics.compute_metrics(S) / (S.T) would give them.  bootstrap > 0:
+    each with a "bootstrap" entry (DESIGN.md "Bootstrap confidence intervals").  ir: each with an "ir" entry (DESIGN.md "Rank-aware
+    IR metrics")."""
+    return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, bootstrap=bootstrap,
+                              bootstrap_seed=bootstrap_seed, bootstrap_level=bootstrap_level, ir=ir)
+
+
+def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, video_mask, cut_off_points, args, chunk=256, bootstrap=0,
+                                   bootstrap_seed=0, bootstrap_level=0.95, ir=False):
+    """Several captions per video (evaluator.py:114-149 features, :225-262 metrics): text_feat [Ns,...] holds every
+    sentence in dataset order, video_feat [V,...] one entry per video, cut_off_points[g] = index of the LAST sentence of
+    video g (the dataset's cut_off_points minus one, evaluator.py:98).  -> (text->video, video->text) metric dictionaries.
+
+    The reference pads the Ns x V matrix to [V, max_sentences, V] with -inf on the host and ranks it with two argsorts
+    (metrics.py:82-126) and a max over the padded axis (:128-148).  Here rank r scores its slab of sentence rows, one
+    launch (nr_group_slab_ranks) gives every row's rank and the slab's per-video best scores, and a MAX all-reduce of
+    the V x V best-score matrix + an all-gather of the Ns ranks complete them; no padded tensor exists.  bootstrap > 0: each
+    dictionary gains a "bootstrap" entry that resamples VIDEOS (DESIGN.md "Bootstrap confidence intervals").  ir: each gains an "ir"
+    entry (DESIGN.md "Rank-aware IR metrics")."""
+    return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points=cut_off_points, chunk=chunk,
+                              bootstrap=bootstrap, bootstrap_seed=bootstrap_seed, bootstrap_level=bootstrap_level, ir=ir)
+
+
+def sharded_metrics_with_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k, cut_off_points=None, chunk=256,
+                                 bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, ir=False):
+    """sharded_evaluation with a "hubness" entry of the top-k lists in each dictionary."""
+    return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, hubness_k=ops._check_k(k),
+                              cut_off_points=cut_off_points, chunk=chunk, bootstrap=bootstrap, bootstrap_seed=bootstrap_seed,
+                              bootstrap_level=bootstrap_level, ir=ir)
+
+
+def sharded_normalised_slabs(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None, qb_k=1,
+                             cut_off_points=None, chunk=256, n_iter=50):
+    """-> (T_slab, V_slab) fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the text->video
+    scores (rows are the queries) and the video->text scores (columns are the queries) after test_norm_correction(mode, beta,
+    qb_k, n_iter) ("sinkhorn" has ONE output, V_slab is T_slab).  querybank: (text_feat, text_mask, video_feat, video_mask) of
+    the qbnorm / qbsinkhorn querybank; None: the model's memory bank (load_memory_bank)."""
+    return _corrected_slabs(model, text_feat, video_feat, text_mask, video_mask, args, test_norm_correction(mode, beta, qb_k, n_iter),
+                            querybank, cut_off_points, chunk)[1:3]
+
+
+def sharded_normalised_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None, qb_k=1,
+                               hubness_k=0, cut_off_points=None, chunk=256, n_iter=50):
+    """(text->video, video->text) metric dictionaries of the normalised scores (sharded_normalised_slabs), identical on every
+    rank, each with "mode" and "beta" (and "qb_k" for qbnorm; "iters" and "marginal_err" for sinkhorn / qbsinkhorn) and, with
+    hubness_k, a "hubness" entry (sharded_hubness's summary of T's row lists / V's column lists)."""
+    return _corrected_metrics(model, text_feat, video_feat, text_mask, video_mask, args, test_norm_correction(mode, beta, qb_k, n_iter),
+                              querybank, hubness_k, cut_off_points, chunk)
+
+
+def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None,
+                                   qb_k=1, hubness_k=0, cut_off_points=None, chunk=256, n_iter=50, bootstrap=0, bootstrap_seed=0,
+                                   bootstrap_level=0.95, ir=False):
+    """sharded_evaluation with test_norm_correction(mode, beta, qb_k, n_iter): the raw dictionaries, each with one more entry
+    "test_norm" = sharded_normalised_metrics."""
+    return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, test_norm_correction(mode, beta, qb_k, n_iter),
+                              hubness_k, cut_off_points, chunk, querybank, bootstrap, bootstrap_seed, bootstrap_level, ir)
+
+
+def sharded_local_scaled_slab(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False, querybank=None,
+                              cut_off_points=None, chunk=256):
+    """-> T_slab fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the scores after
+    local_scaling_correction(mode, k, bank).  Rows rank text->video, columns video->text.  querybank: (text_feat, text_mask,
+    video_feat, video_mask) for `bank`; None: the model's memory bank (load_memory_bank)."""
+    return _corrected_slabs(model, text_feat, video_feat, text_mask, video_mask, args, local_scaling_correction(mode, k, bank),
+                            querybank, cut_off_points, chunk)[1]
+
+
+def sharded_local_scaled_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False, querybank=None,
+                                 hubness_k=0, cut_off_points=None, chunk=256):
+    """(text->video, video->text) metric dictionaries of the locally scaled scores (sharded_local_scaled_slab), identical on
+    every rank, each with "mode", "k" and "bank" and, with hubness_k, a "hubness" entry (T's row lists / column lists)."""
+    return _corrected_metrics(model, text_feat, video_feat, text_mask, video_mask, args, local_scaling_correction(mode, k, bank),
+                              querybank, hubness_k, cut_off_points, chunk)
+
+
+def sharded_metrics_with_local_scaling(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False,
+                                       querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0, bootstrap_seed=0,
+                                       bootstrap_level=0.95, ir=False):
+    """sharded_evaluation with local_scaling_correction(mode, k, bank): the raw dictionaries, each with one more entry
+    "local_scaling" = sharded_local_scaled_metrics."""
+    return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, local_scaling_correction(mode, k, bank),
+                              hubness_k, cut_off_points, chunk, querybank, bootstrap, bootstrap_seed, bootstrap_level, ir)
+
+
+def sharded_mutual_proximity_slab(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False, querybank=None,
+                                  cut_off_points=None, chunk=256):
+    """-> T_slab fp32 [r1 - r0, V] of this rank's rows [r0, r1) = slab_bounds(n_texts, W, rank): the scores after
+    mutual_proximity_correction(mode, bank).  Rows rank text->video, columns video->text.  querybank: (text_feat, text_mask,
+    video_feat, video_mask) for `bank`; None: the model's memory bank (load_memory_bank)."""
+    return _corrected_slabs(model, text_feat, video_feat, text_mask, video_mask, args, mutual_proximity_correction(mode, bank),
+                            querybank, cut_off_points, chunk)[1]
+
+
+def sharded_mutual_proximity_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False, querybank=None,
+                                     hubness_k=0, cut_off_points=None, chunk=256):
+    """(text->video, video->text) metric dictionaries of the mutual-proximity scores (sharded_mutual_proximity_slab), identical on
+    every rank, each with "mode" and "bank" and, with hubness_k, a "hubness" entry (T's row lists / column lists)."""
+    return _corrected_metrics(model, text_feat, video_feat, text_mask, video_mask, args, mutual_proximity_correction(mode, bank),
+                              querybank, hubness_k, cut_off_points, chunk)
+
+
+def sharded_metrics_with_mutual_proximity(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False,
+                                          querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0,
+                                          bootstrap_seed=0, bootstrap_level=0.95, ir=False):
+    """sharded_evaluation with mutual_proximity_correction(mode, bank): the raw dictionaries, each with one more entry
+    "mutual_proximity" = sharded_mutual_proximity_metrics."""
+    return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, mutual_proximity_correction(mode, bank),
+                              hubness_k, cut_off_points, chunk, querybank, bootstrap, bootstrap_seed, bootstrap_level, ir)
+
+
+def correction_from_args(args, model):
+    """What the command-line flags ask of the evaluation -> (correction or None, the keyword arguments of sharded_evaluation:
+    hubness_k, the bootstrap triple and ir), everything checked before any work: the values, that at most one correction is chosen,
+    and that a correction that needs a querybank finds the model's memory bank filled."""
+    kw = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
+              bootstrap_level=getattr(args, "bootstrap_level", 0.95))
+    _check_bootstrap(kw["bootstrap"], kw["bootstrap_seed"], kw["bootstrap_level"])
+    kw["ir"] = _check_ir(getattr(args, "ir_metrics", 0) or 0)
+    test_norm = getattr(args, "test_norm", None) or "none"
+    local_scaling = getattr(args, "local_scaling", None) or "none"
+    mutual_proximity = getattr(args, "mutual_proximity", None) or "none"
+    if mutual_proximity != "none" and (test_norm != "none" or local_scaling != "none"):
+        raise ValueError("mutual_proximity, local_scaling and test_norm are separate corrections: choose one of them")
+    if local_scaling != "none" and test_norm != "none":
+        raise ValueError("local_scaling and test_norm are separate corrections: choose one of them")
+    correction = None
+    if test_norm != "none":
+        correction = test_norm_correction(test_norm, getattr(args, "test_norm_beta", 20.0), getattr(args, "qb_k", 1),
+                                          getattr(args, "test_norm_iters", 50))
+    elif local_scaling != "none":
+        correction = local_scaling_correction(local_scaling, getattr(args, "local_scaling_k", 10),
+                                              bool(int(getattr(args, "local_scaling_bank", 0) or 0)))
+    elif mutual_proximity != "none":
+        correction = mutual_proximity_correction(mutual_proximity, bool(int(getattr(args, "mutual_proximity_bank", 0) or 0)))
+    kw["hubness_k"] = _check_hubness_k(getattr(args, "hubness_k", 0))
+    if correction is not None and correction.needs_bank:
+        _querybank(model, None, model.mb_feat_t.device)         # checked where it lies: nothing is copied
+    return correction, kw

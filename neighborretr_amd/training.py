@@ -159,53 +159,18 @@ def eval_epoch(args, model, test_dataloader, device):
     scatter puts them into dataset order (:173-189), then the N x N similarity and both rank counts are computed SHARDED
     (rank r: rows [r N/W, (r+1) N/W)).  Multi-sentence sets (`dataset.multi_sentence_per_video`): every rank walks the whole
     loader, as in the reference (:114-131), keeps the video of each group's last sentence (:137-149), and the
-    sentence x video matrix is again scored in row slabs (evaluator.sharded_multi_sentence_metrics)."""
-    from .evaluator import (BANK_MODES, _check_n_iter, _check_test_norm, _querybank, dataset_order, gather_eval_features, sharded_metrics,
-                            sharded_metrics_with_hubness, sharded_metrics_with_test_norm, sharded_multi_sentence_metrics,
-                            test_norm_label)
-    from .evaluator import _check_local_scaling, local_scaling_label, sharded_metrics_with_local_scaling
-    from .evaluator import _check_mutual_proximity, mutual_proximity_label, sharded_metrics_with_mutual_proximity
-    from .evaluator import _check_bootstrap, _check_ir
-    # bootstrap confidence intervals (DESIGN.md "Bootstrap confidence intervals"): checked before any work
-    boot = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
-                bootstrap_level=getattr(args, "bootstrap_level", 0.95))
-    _check_bootstrap(boot["bootstrap"], boot["bootstrap_seed"], boot["bootstrap_level"])
-    # rank-aware IR metrics (DESIGN.md "Rank-aware IR metrics"): checked before any work
-    ir = _check_ir(getattr(args, "ir_metrics", 0) or 0)
-    extras = dict(boot, ir=ir)                                        # what every evaluator call takes
-    hubness_k = int(getattr(args, "hubness_k", 0) or 0)
-    test_norm = getattr(args, "test_norm", None) or "none"
-    local_scaling = getattr(args, "local_scaling", None) or "none"
-    mutual_proximity = getattr(args, "mutual_proximity", None) or "none"
-    if mutual_proximity != "none" and (test_norm != "none" or local_scaling != "none"):
-        raise ValueError("mutual_proximity, local_scaling and test_norm are separate corrections: choose one of them")
-    if local_scaling != "none" and test_norm != "none":
-        raise ValueError("local_scaling and test_norm are separate corrections: choose one of them")
+    sentence x video matrix is again scored in row slabs.  Both go through evaluator.sharded_evaluation."""
+    from .evaluator import correction_from_args, dataset_order, gather_eval_features, sharded_evaluation
+    correction, extras = correction_from_args(args, _unwrap(model))        # every flag checked before any work
+    hubness_k = extras["hubness_k"]
     logger = getattr(args, "logger", None)
     tracker = RetrievalMetrics(logger=logger)
     model = _unwrap(model).to(device)
-    if test_norm != "none":          # the test-time correction (DESIGN.md "Test-time hubness reduction"): checked before any work
-        beta, qb_k, _ = _check_test_norm(test_norm, getattr(args, "test_norm_beta", 20.0), getattr(args, "qb_k", 1), hubness_k)
-        if test_norm in BANK_MODES:
-            _querybank(model, None, device)
-        norm = dict(mode=test_norm, beta=beta, qb_k=qb_k, hubness_k=hubness_k,
-                    n_iter=_check_n_iter(getattr(args, "test_norm_iters", 50)))
-    if local_scaling != "none":      # local scaling (DESIGN.md "Local scaling"): checked before any work
-        ls_bank = bool(int(getattr(args, "local_scaling_bank", 0) or 0))
-        ls_k, _ = _check_local_scaling(local_scaling, getattr(args, "local_scaling_k", 10), hubness_k)
-        if ls_bank:
-            _querybank(model, None, device)
-        scaling = dict(mode=local_scaling, k=ls_k, bank=ls_bank, hubness_k=hubness_k)
-    if mutual_proximity != "none":   # mutual proximity (DESIGN.md "Mutual proximity"): checked before any work
-        mp_bank = bool(int(getattr(args, "mutual_proximity_bank", 0) or 0))
-        _check_mutual_proximity(mutual_proximity, hubness_k)
-        if mp_bank:
-            _querybank(model, None, device)
-        proximity = dict(mode=mutual_proximity, bank=mp_bank, hubness_k=hubness_k)
     dataset = getattr(test_dataloader, "dataset", None)
     multi = bool(getattr(dataset, "multi_sentence_per_video", False))
     model.eval()
     tic = time.time()
+    cut_off_points = None
     with torch.no_grad():
         if multi:
             cut_off_points = [p - 1 for p in dataset.cut_off_points]             # evaluator.py:98
@@ -214,37 +179,14 @@ def eval_epoch(args, model, test_dataloader, device):
             ind, tf, tm, vf, vm = _cache_features(model, test_dataloader, device, separate=True)
             keep = torch.isin(ind, torch.tensor(cut_off_points, device=ind.device))      # evaluator.py:137-149
             vf, vm = vf[keep], vm[keep]
-            toc1 = time.time()
-            if test_norm != "none":
-                t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args,
-                                                          cut_off_points=cut_off_points, **norm, **extras)
-            elif local_scaling != "none":
-                t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args,
-                                                              cut_off_points=cut_off_points, **scaling, **extras)
-            elif mutual_proximity != "none":
-                t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args,
-                                                                 cut_off_points=cut_off_points, **proximity, **extras)
-            elif hubness_k:
-                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, cut_off_points, **extras)
-            else:
-                t2v, v2t = sharded_multi_sentence_metrics(model, tf, vf, tm.float(), vm.float(), cut_off_points, args, **extras)
         else:
             ind, tf, tm, vf, vm = _cache_features(model, test_dataloader, device, separate=False)
             if int(getattr(args, "world_size", 1)) > 1 and dist.is_initialized():
                 tf, vf, tm, vm = gather_eval_features(tf, vf, ind, tm, vm, args)
             else:
                 tf, vf, tm, vm = dataset_order(tf, vf, ind, tm, vm)
-            toc1 = time.time()
-            if test_norm != "none":
-                t2v, v2t = sharded_metrics_with_test_norm(model, tf, vf, tm.float(), vm.float(), args, **norm, **extras)
-            elif local_scaling != "none":
-                t2v, v2t = sharded_metrics_with_local_scaling(model, tf, vf, tm.float(), vm.float(), args, **scaling, **extras)
-            elif mutual_proximity != "none":
-                t2v, v2t = sharded_metrics_with_mutual_proximity(model, tf, vf, tm.float(), vm.float(), args, **proximity, **extras)
-            elif hubness_k:
-                t2v, v2t = sharded_metrics_with_hubness(model, tf, vf, tm.float(), vm.float(), args, hubness_k, **extras)
-            else:
-                t2v, v2t = sharded_metrics(model, tf, vf, tm.float(), vm.float(), args, **extras)
+        toc1 = time.time()
+        t2v, v2t = sharded_evaluation(model, tf, vf, tm.float(), vm.float(), args, correction, cut_off_points=cut_off_points, **extras)
     toc2 = time.time()
     if is_main_process() and logger is not None:
         logger.info("Evaluation timing breakdown:")
@@ -257,7 +199,7 @@ def eval_epoch(args, model, test_dataloader, device):
 
         def log_bootstrap(nt, nv, tag=""):
             """The interval line of each direction after its metrics line, and for a correction the paired line against raw."""
-            if not boot["bootstrap"]:
+            if not extras["bootstrap"]:
                 return
             for side, m in (("Text-to-Video", nt), ("Video-to-Text", nv)):
                 tracker.log_bootstrap(m["bootstrap"], prefix=f"{side} {tag}".rstrip() + ": ")
@@ -266,7 +208,7 @@ def eval_epoch(args, model, test_dataloader, device):
 
         def log_ir(nt, nv, tag=""):
             """The IR line of each direction (MRR, mAP, nDCG@10, R-Prec) and its interval lines."""
-            if not ir:
+            if not extras["ir"]:
                 return
             for side, m in (("Text-to-Video", nt), ("Video-to-Text", nv)):
                 tracker.log_ir(m["ir"], prefix=f"{side} {tag}".rstrip() + ": ")
@@ -275,36 +217,17 @@ def eval_epoch(args, model, test_dataloader, device):
         if hubness_k:
             tracker.log_hubness(t2v["hubness"], prefix="Text-to-Video ")
             tracker.log_hubness(v2t["hubness"], prefix="Video-to-Text ")
-        if test_norm != "none":
-            tag = test_norm_label(test_norm, t2v["test_norm"]["beta"], t2v["test_norm"].get("iters"))
-            tracker.print_metrics(t2v["test_norm"], prefix=f"Text-to-Video {tag}: ")
-            tracker.print_metrics(v2t["test_norm"], prefix=f"Video-to-Text {tag}: ")
-            log_bootstrap(t2v["test_norm"], v2t["test_norm"], tag)
-            log_ir(t2v["test_norm"], v2t["test_norm"], tag)
-            if "marginal_err" in t2v["test_norm"]:
-                logger.info(f"{tag} marginal error after {t2v['test_norm']['iters']} iterations: "
-                            f"{t2v['test_norm']['marginal_err']:.3e} / {v2t['test_norm']['marginal_err']:.3e}")
+        if correction is not None:
+            nt, nv, tag = t2v[correction.key], v2t[correction.key], correction.label
+            tracker.print_metrics(nt, prefix=f"Text-to-Video {tag}: ")
+            tracker.print_metrics(nv, prefix=f"Video-to-Text {tag}: ")
+            log_bootstrap(nt, nv, tag)
+            log_ir(nt, nv, tag)
+            if "marginal_err" in nt:
+                logger.info(f"{tag} marginal error after {nt['iters']} iterations: {nt['marginal_err']:.3e} / {nv['marginal_err']:.3e}")
             if hubness_k:
-                tracker.log_hubness(t2v["test_norm"]["hubness"], prefix=f"Text-to-Video {tag} ")
-                tracker.log_hubness(v2t["test_norm"]["hubness"], prefix=f"Video-to-Text {tag} ")
-        if local_scaling != "none":
-            tag = local_scaling_label(local_scaling, ls_k, ls_bank)
-            tracker.print_metrics(t2v["local_scaling"], prefix=f"Text-to-Video {tag}: ")
-            tracker.print_metrics(v2t["local_scaling"], prefix=f"Video-to-Text {tag}: ")
-            log_bootstrap(t2v["local_scaling"], v2t["local_scaling"], tag)
-            log_ir(t2v["local_scaling"], v2t["local_scaling"], tag)
-            if hubness_k:
-                tracker.log_hubness(t2v["local_scaling"]["hubness"], prefix=f"Text-to-Video {tag} ")
-                tracker.log_hubness(v2t["local_scaling"]["hubness"], prefix=f"Video-to-Text {tag} ")
-        if mutual_proximity != "none":
-            tag = mutual_proximity_label(mutual_proximity, mp_bank)
-            tracker.print_metrics(t2v["mutual_proximity"], prefix=f"Text-to-Video {tag}: ")
-            tracker.print_metrics(v2t["mutual_proximity"], prefix=f"Video-to-Text {tag}: ")
-            log_bootstrap(t2v["mutual_proximity"], v2t["mutual_proximity"], tag)
-            log_ir(t2v["mutual_proximity"], v2t["mutual_proximity"], tag)
-            if hubness_k:
-                tracker.log_hubness(t2v["mutual_proximity"]["hubness"], prefix=f"Text-to-Video {tag} ")
-                tracker.log_hubness(v2t["mutual_proximity"]["hubness"], prefix=f"Video-to-Text {tag} ")
+                tracker.log_hubness(nt["hubness"], prefix=f"Text-to-Video {tag} ")
+                tracker.log_hubness(nv["hubness"], prefix=f"Video-to-Text {tag} ")
     return t2v, v2t
 
 
