@@ -926,6 +926,36 @@ int nr_pair_ranks(const float* M_slab, int n_rows, int V, int row0, int n_total,
  * launch: U or Q out of range, b0 < 0, n_boot < 0, b0 + n_boot > 2^31 - 1, a null pointer; n_boot = 0: NR_OK, no launch. */
 int nr_bootstrap_unit_sums(const int64_t* values, int U, int Q, uint64_t seed, int b0, int n_boot, int64_t* out, void* stream);
 
+/* Paired permutation test of rank statistics (DESIGN.md "Paired permutation tests"; Fisher's randomisation test as used for retrieval
+ * metrics, Smucker et al. 2007; the reference has no code for it): two rankings A and B over the same U units, with the conventions of
+ * nr_bootstrap_rank_stats (ranks_x [E_x] int32, 0 <= r < 2^30; unit_end_x [U] int32 = index of the LAST entry of unit u,
+ * non-decreasing, a unit may be empty, E_a != E_b allowed).  Swap bits, counter-based with the SplitMix64 above:
+ *   s(p, u) = SM64(seed ^ 0x7065726D74657374, (p << 32) | u) >> 63,   u in [0, U);   the salt keeps the stream apart from the draws of
+ *   the bootstrap at equal seeds; the identity labelling is not one of the draws.
+ * In permutation p side X takes unit u's entries from A when s = 0 and from B when s = 1; side Y takes the other ranking's entries.
+ * out [n_perm, 2, 4 + K] int64, exact integers: for permutation p0 + i and side (X, Y), over the multiset of its entries,
+ *   (n, sum, med_lo, med_hi, hits[0..K-1]):  the entry count, the sum of ranks, the order statistics at sorted positions (n-1)/2 and
+ *   n/2 (both -1 when n = 0), hits[k] = #{r < cuts[k]}.  cuts [K] is HOST memory: K strictly increasing positive cut-offs.
+ *   n_X + n_Y = E_a + E_b, and the same for the sum and the hits.
+ * One workgroup per permutation, its threads stride over u: unit_end and the entries are read coalesced.  The order statistics by a
+ * radix select on the rank value (LDS histograms of 1024 bins, LDS atomics, at most three passes), the swap bits recomputed in every
+ * pass.  No global atomics, no scratch: the result depends on (seed, p, inputs) alone, whatever the grid and the split over p0.
+ * NR_EINVAL before any launch: U outside [1, 2^24], K outside [1, 8], cuts not positive and increasing, E < 0, p0 < 0, n_perm < 0,
+ * p0 + n_perm > 2^31 - 1, a null pointer; n_perm = 0: NR_OK, no launch. */
+int nr_permtest_rank_stats(const int32_t* ranks_a, const int32_t* unit_end_a, int E_a, const int32_t* ranks_b,
+                           const int32_t* unit_end_b, int E_b, int U, const int32_t* cuts, int K, uint64_t seed, int p0, int n_perm,
+                           int64_t* out, void* stream);
+
+/* Paired permutation test of per-unit sums (DESIGN.md "Paired permutation tests"): values_a, values_b [U, Q] int64 row-major, U in
+ * [1, 2^24], Q in [1, 16];
+ *   out[i, q] = sum over u < U of (s(p0 + i, u) ? values_b : values_a)[u, q],   out [n_perm, Q] int64,
+ * side X with exactly the swap bits s(p, u) of nr_permtest_rank_stats; side Y is total_a + total_b - X, which the caller takes.  One
+ * workgroup per permutation, rows read coalesced, int64 sums in registers, combined by wave shuffles and through LDS; no global
+ * atomics: the result depends on (seed, p, inputs) alone.  The caller keeps U max|value| below 2^62 for either input.  NR_EINVAL
+ * before any launch: U or Q out of range, p0 < 0, n_perm < 0, p0 + n_perm > 2^31 - 1, a null pointer; n_perm = 0: NR_OK, no launch. */
+int nr_permtest_unit_sums(const int64_t* values_a, const int64_t* values_b, int U, int Q, uint64_t seed, int p0, int n_perm,
+                          int64_t* out, void* stream);
+
 /* Multi-tensor BertAdam step (models/optimization.py:76-211 with the trainer's clip and clamp around it, trainer.py:104-119;
  * DESIGN.md "BertAdam in the captured step").  fp32 tensors only.  Per step, for every table entry t with group q:
  *   c    = min(1, global_max_norm / (sqrt(sum_t ||g_t||^2) + 1e-6))             (global_max_norm <= 0: c = 1)

@@ -130,6 +130,16 @@ def get_args():
                    help="1: the rank-aware IR metrics MRR, mAP, nDCG@10 and R-precision of every relevant (text, video) pair in both "
                         "directions, next to R@K, for the raw ranking and for a correction; with --bootstrap their intervals too "
                         "(DESIGN.md 6.8); 0 = off")
+    p.add_argument("--permutation", type=int, default=0,
+                   help="N > 0: a paired permutation (randomisation) test with N relabellings on the GPU: for a correction, is it "
+                        "significantly better than the raw ranking; with --compare_model, is this model better than that one: the "
+                        "difference of every metric with its two-sided p-value (DESIGN.md 6.10); at most 2^20; 0 = off")
+    p.add_argument("--permutation_seed", type=int, default=0,
+                   help="--permutation: seed of the counter-based swap bits (text->video uses it, video->text seed + 1)")
+    p.add_argument("--compare_model", default=None, type=str, metavar="PATH",
+                   help="--do_eval with --permutation N: the test set is scored again with the same architecture loaded from PATH, and "
+                        "'model - compared' lines give the paired permutation test (with --bootstrap the paired interval too) of "
+                        "this model against it")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -171,6 +181,16 @@ def get_args():
         p.error("--bootstrap_seed must lie in [0, 2^64 - 1)")
     if not 0.0 < args.bootstrap_level < 1.0:
         p.error("--bootstrap_level must lie in (0, 1)")
+    if not 0 <= args.permutation <= 1 << 20:
+        p.error("--permutation must lie in [0, 2^20]")
+    if not 0 <= args.permutation_seed < (1 << 64) - 1:
+        p.error("--permutation_seed must lie in [0, 2^64 - 1)")
+    if args.compare_model and not (args.do_eval and not args.do_train and args.permutation > 0):
+        p.error("--compare_model works with --do_eval (without --do_train) and needs --permutation > 0")
+    corrected = args.test_norm != "none" or args.local_scaling != "none" or args.mutual_proximity != "none"
+    if args.permutation and not (corrected or args.compare_model):
+        p.error("--permutation needs a correction (--test_norm, --local_scaling, --mutual_proximity) or --compare_model: there is "
+                "nothing to compare")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
         raise ValueError("--batch_size must divide over the ranks (args_parser.py:149-165)")
     return args
@@ -645,6 +665,14 @@ def eval_epoch(args, model, test):
             log(args, RetrievalMetrics.format_bootstrap(m["bootstrap"], prefix=f"{side} {tag}".rstrip() + " "))
             if "bootstrap_vs_raw" in m:
                 log(args, RetrievalMetrics.format_bootstrap(m["bootstrap_vs_raw"], prefix=f"{side} {tag} - raw "))
+
+    def log_permutation(nt, nv, tag):
+        """The paired permutation test of a correction against raw: one line per direction, and one for its IR metrics."""
+        for side, m in (("text->video", nt), ("video->text", nv)):
+            if "permutation_vs_raw" in m:
+                log(args, RetrievalMetrics.format_permutation(m["permutation_vs_raw"], prefix=f"{side} {tag} - raw "))
+            if "permutation_vs_raw" in m.get("ir", {}):
+                log(args, RetrievalMetrics.format_permutation(m["ir"]["permutation_vs_raw"], prefix=f"{side} {tag} - raw "))
     model.eval()
     dev = args.device
     mine = rank_sample_indices(test.n, args.world_size, args.rank)     # equal counts on every rank (padded like DistributedSampler)
@@ -669,12 +697,47 @@ def eval_epoch(args, model, test):
                   f"video->text {tag} R@1 {nv['R1']:.1f} R@5 {nv['R5']:.1f} R@10 {nv['R10']:.1f} MedR {nv['MR']:.1f}")
         log_bootstrap(nt, nv, tag)
         log_ir(nt, nv, tag)
+        log_permutation(nt, nv, tag)
         if hubness_k:
             log(args, RetrievalMetrics.format_hubness(nt["hubness"], prefix=f"text->video {tag} "))
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
         if "marginal_err" in nt:
             log(args, f"{tag} marginal error {nt['marginal_err']:.3e} / {nv['marginal_err']:.3e}")
     return t2v, v2t
+
+
+def compare_with_model(args, result, train, test, with_bank):
+    """--compare_model PATH: the test set scored again with the same architecture loaded from PATH, then the "model - compared"
+    lines of evaluator.compare_evaluations (result minus that evaluation).  The second model is released before returning."""
+    from neighborretr_amd.evaluator import CORRECTION_KEYS, compare_evaluations
+    from neighborretr_amd.metrics import RetrievalMetrics
+    from neighborretr_amd.modeling import NeighborRetr
+    other = NeighborRetr(args, precision=args.precision, with_encoders=bool(args.encoders))
+    missing, unexpected = other.load_state_dict(torch.load(args.compare_model, map_location="cpu"), strict=False)
+    log(args, f"compare_model {args.compare_model}: {len(missing)} missing / {len(unexpected)} unexpected keys")
+    other = other.to(args.device)
+    if with_bank:
+        load_memory_bank(args, other, train)
+    compared = eval_epoch(args, other, test)
+    del other                                               # the second model (and its memory bank) goes before the summaries
+    torch.cuda.empty_cache()
+    cmp = compare_evaluations(result, compared, args.permutation, args.permutation_seed, args.bootstrap, args.bootstrap_seed,
+                              args.bootstrap_level, device=args.device)
+
+    def lines(c, prefix):
+        log(args, RetrievalMetrics.format_permutation(c["permutation"], prefix=prefix, versus="compared"))
+        if "bootstrap" in c:
+            log(args, RetrievalMetrics.format_bootstrap(c["bootstrap"], prefix=prefix, versus="compared"))
+        if "ir" in c:
+            log(args, RetrievalMetrics.format_permutation(c["ir"]["permutation"], prefix=prefix, versus="compared"))
+            if "bootstrap" in c["ir"]:
+                log(args, RetrievalMetrics.format_ir_bootstrap(c["ir"]["bootstrap"], prefix=prefix, versus="compared"))
+    for side, c in zip(("text->video", "video->text"), cmp):
+        lines(c, f"model - compared {side} ")
+        for key in CORRECTION_KEYS:
+            if key in c:
+                lines(c[key], f"model - compared {side} [{key}] ")
+    return cmp
 
 
 def main():
@@ -723,9 +786,11 @@ def main():
             or (args.mutual_proximity != "none" and args.mutual_proximity_bank)
         if with_bank:                                       # the querybank: the memory bank of the training set
             load_memory_bank(args, model, train)
-        eval_epoch(args, model, test)
+        result = eval_epoch(args, model, test)
         if with_bank:
             clear_memory_bank(model)
+        if args.compare_model:
+            compare_with_model(args, result, train, test, with_bank)
     if args.world_size > 1:
         dist.destroy_process_group()
 

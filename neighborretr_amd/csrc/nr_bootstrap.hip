@@ -12,54 +12,8 @@
 // last entry equal to it, in which case one more pass takes the smallest larger rank.  No global atomics, no scratch; the result is
 // a function of (seed, b, inputs) alone, the same for any grid and any split of the resamples over calls.
 #include "nr_common.h"
+#include "nr_resample.h"
 #include "../../include/nr_hip.h"
-
-#define NR_BOOT_THREADS 256
-#define NR_BOOT_WAVES (NR_BOOT_THREADS / NR_WAVE)
-#define NR_BOOT_DIGIT 10
-#define NR_BOOT_BINS (1 << NR_BOOT_DIGIT)
-#define NR_BOOT_BINS_PER_THREAD (NR_BOOT_BINS / NR_BOOT_THREADS)
-#define NR_BOOT_MAX_CUTS 8
-#define NR_BOOT_MAX_UNITS (1 << 24)
-#define NR_BOOT_RANK_LIMIT (1 << 30)
-#define NR_BOOT_GOLDEN 0x9E3779B97F4A7C15ull
-
-struct NrBootCuts {
-    int32_t c[NR_BOOT_MAX_CUTS];          // cuts beyond K are 0: no rank lies below them
-};
-
-struct NrBootRanking {
-    const int32_t* ranks;
-    const int32_t* unit_end;
-    int E;
-};
-
-// SplitMix64's output function of the state z
-__device__ __forceinline__ uint64_t nr_boot_mix(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// the unit that position t of the resample draws; base = seed + ((b << 32) + 1) * golden
-__device__ __forceinline__ int nr_boot_draw(uint64_t base, int t, uint32_t U) {
-    const uint64_t x = nr_boot_mix(base + (uint64_t)(uint32_t)t * NR_BOOT_GOLDEN);
-    return (int)__umulhi((uint32_t)(x >> 32), U);
-}
-
-// entries [lo, hi] of unit u, clamped to the ranking's extent
-__device__ __forceinline__ void nr_boot_unit(const NrBootRanking& R, int u, int& lo, int& hi) {
-    lo = u > 0 ? R.unit_end[u - 1] + 1 : 0;
-    hi = R.unit_end[u];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi >= R.E ? R.E - 1 : hi;
-}
-
-__device__ __forceinline__ int64_t nr_boot_wave_sum(int64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, NR_WAVE);
-    return v;
-}
 
 // the statistics of one ranking of resample b into out[4 + K]
 __device__ __forceinline__ void nr_boot_ranking(const NrBootRanking R, uint32_t U, const NrBootCuts cuts, int K, uint64_t base,
@@ -253,8 +207,6 @@ extern "C" int nr_bootstrap_rank_stats(const int32_t* ranks_a, const int32_t* un
 // out[b, q] = sum over t < U of values[u(b, t), q] with the draws u(b, t) of the kernel above (nr_boot_draw): resample b is the same
 // multiset of units in both.  One workgroup per resample; every thread keeps its Q <= 16 sums in int64 registers, the waves combine
 // by shuffles, the workgroup through LDS.  Nothing is stored per resample, no atomics: a function of (seed, b, inputs) alone.
-#define NR_BOOT_MAX_COLS 16
-
 __global__ __launch_bounds__(NR_BOOT_THREADS) void nr_bootstrap_unit_sums_kernel(const int64_t* __restrict__ values, uint32_t U, int Q,
                                                                                  uint64_t seed, uint32_t b0,
                                                                                  int64_t* __restrict__ out) {

@@ -817,6 +817,138 @@ def sharded_ir_metrics(model, text_feat, video_feat, text_mask, video_mask, args
     return _ir_from_slab(S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot)[0]
 
 
+# ---- paired permutation tests (DESIGN.md "Paired permutation tests") --------------------------------------------------------------------
+# Is the corrected ranking (or model A) significantly better than the raw one (model B)?  The two rankings' entries are swapped unit
+# by unit, n_perm times, on the GPU (nr_permtest_rank_stats, nr_permtest_unit_sums); the host compares every relabelling's difference
+# with the observed one in exact integers.  Units as in the bootstrap.  Every rank holds the same integers and computes every
+# permutation itself: no collective.
+
+PERMUTATION_MAX = 1 << 20
+CORRECTION_KEYS = ("test_norm", "local_scaling", "mutual_proximity")
+
+
+def _check_permutation(permutation, seed=0):
+    """None for permutation = 0, else (n_perm, seed); an integer in [0, 2^20], a seed in [0, 2^64 - 1)."""
+    if isinstance(permutation, bool) or not isinstance(permutation, (int, np.integer)) or not 0 <= int(permutation) <= PERMUTATION_MAX:
+        raise ValueError(f"permutation must be an integer in [0, 2^20], got {permutation!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64) - 1:
+        raise ValueError(f"permutation_seed must be an integer in [0, 2^64 - 1), got {seed!r}")
+    return (int(permutation), int(seed)) if int(permutation) else None
+
+
+def _units_entry(units):
+    """What a direction's dictionary carries of its resampling units under "units"."""
+    entries, unit_end, median = units
+    return {"entries": np.asarray(entries, dtype=np.int64), "unit_end": np.asarray(unit_end, dtype=np.int64), "median": median}
+
+
+def _dev32(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+
+
+def _check_comparable(a, b, what="permutation test"):
+    """Refuses two dictionaries whose "units" (and, where both carry "ir", whose IR "columns") do not pair up."""
+    for name, m in (("a", a), ("b", b)):
+        if "units" not in m:
+            raise ValueError(f"{what}: result {name} carries no units: evaluate it with permutation > 0")
+    ua, ub = a["units"], b["units"]
+    if len(ua["unit_end"]) != len(ub["unit_end"]):
+        raise ValueError(f"{what}: the two rankings have {len(ua['unit_end'])} and {len(ub['unit_end'])} units")
+    if ua["median"] != ub["median"]:
+        raise ValueError(f"{what}: the two rankings take different medians ({ua['median']!r}, {ub['median']!r})")
+    if "ir" in a and "ir" in b:
+        if "columns" not in a["ir"] or "columns" not in b["ir"]:
+            raise ValueError(f"{what}: an \"ir\" entry carries no columns: evaluate it with permutation > 0")
+        ca, cb = np.asarray(a["ir"]["columns"]), np.asarray(b["ir"]["columns"])
+        if ca.shape != cb.shape or ca.ndim != 2 or ca.shape[0] != len(ua["unit_end"]):
+            raise ValueError(f"{what}: the two rankings' IR columns are {ca.shape} and {cb.shape} over {len(ua['unit_end'])} units")
+
+
+def _permutation_of_units(units, other, n_perm, seed, dev):
+    """RetrievalMetrics.permutation_summary of `units` minus `other` (two "units" entries over the same units): one launch."""
+    stats = ops.permtest_rank_stats(_dev32(units["entries"], dev), _dev32(units["unit_end"], dev), _dev32(other["entries"], dev),
+                                    _dev32(other["unit_end"], dev), cuts=BOOTSTRAP_CUTS, seed=seed, p0=0, n_perm=n_perm).cpu().numpy()
+    return RetrievalMetrics.permutation_summary(stats, BOOTSTRAP_CUTS, units["entries"], other["entries"], units["median"], seed)
+
+
+def _permutation_of_columns(columns, other, n_perm, seed, dev):
+    """RetrievalMetrics.ir_permutation_summary of the IR columns `columns` minus `other` [U, 5]: one launch."""
+    columns, other = np.asarray(columns, dtype=np.int64), np.asarray(other, dtype=np.int64)
+    sums = ops.permtest_unit_sums(torch.from_numpy(np.ascontiguousarray(columns)).to(dev),
+                                  torch.from_numpy(np.ascontiguousarray(other)).to(dev), seed=seed, p0=0, n_perm=n_perm).cpu().numpy()
+    return RetrievalMetrics.ir_permutation_summary(sums, columns, other, seed)
+
+
+def _compare_direction(a, b, side, perm, boot, dev):
+    """One direction (or one correction's sub-dictionary) of compare_evaluations: "permutation", with boot "bootstrap", and the same
+    under "ir" when both carry it."""
+    n_perm, seed = perm
+    out = {"permutation": _permutation_of_units(a["units"], b["units"], n_perm, seed + side, dev)}
+    ir = "ir" in a and "ir" in b
+    if ir:
+        out["ir"] = {"permutation": _permutation_of_columns(a["ir"]["columns"], b["ir"]["columns"], n_perm, seed + side, dev)}
+    if boot:
+        n_boot, bseed, level = boot
+        ua, ub = a["units"], b["units"]
+        stats = ops.bootstrap_rank_stats(_dev32(ua["entries"], dev), _dev32(ua["unit_end"], dev), _dev32(ub["entries"], dev),
+                                         _dev32(ub["unit_end"], dev), cuts=BOOTSTRAP_CUTS, seed=bseed + side, b0=0,
+                                         n_boot=n_boot).cpu().numpy()
+        out["bootstrap"] = RetrievalMetrics.paired_bootstrap_summary(stats[:, 0], stats[:, 1], BOOTSTRAP_CUTS, ua["entries"],
+                                                                     ub["entries"], level, ua["median"])
+        out["bootstrap"]["seed"] = bseed + side
+        if ir:
+            ca, cb = a["ir"]["columns"], b["ir"]["columns"]
+            both = torch.from_numpy(np.ascontiguousarray(np.concatenate([ca, cb], axis=1))).to(dev)
+            sums = ops.bootstrap_unit_sums(both, seed=bseed + side, b0=0, n_boot=n_boot).cpu().numpy()
+            out["ir"]["bootstrap"] = RetrievalMetrics.ir_paired_bootstrap_summary(sums, ca, cb, level)
+            out["ir"]["bootstrap"]["seed"] = bseed + side
+    return out
+
+
+def compare_evaluations(a, b, permutation, permutation_seed=0, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, device="cuda"):
+    """Is evaluation a better than evaluation b on this test set?  a, b: the (text->video, video->text) results of two
+    sharded_evaluation calls with permutation > 0 (two checkpoints, or two settings, scored on the SAME test set).  ->
+    (text->video, video->text) comparison dictionaries of "a minus b": "permutation" (RetrievalMetrics.permutation_summary; seed for
+    text->video, seed + 1 for video->text); with bootstrap > 0 "bootstrap" (paired_bootstrap_summary on the draws of the bootstrap);
+    the same two under "ir" when both results carry "ir", and all of it under a correction's key when both carry the same one.
+    ValueError when the units, the median kind or the column layout of the two results differ."""
+    perm = _check_permutation(permutation, permutation_seed)
+    if perm is None:
+        raise ValueError("compare_evaluations needs permutation > 0: there is nothing else to compare with")
+    boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    for side in range(2):                                   # everything is checked before the first launch
+        _check_comparable(a[side], b[side], "compare_evaluations")
+        for key in CORRECTION_KEYS:
+            if key in a[side] and key in b[side]:
+                _check_comparable(a[side][key], b[side][key], "compare_evaluations")
+    out = []
+    for side in range(2):
+        cmp = _compare_direction(a[side], b[side], side, perm, boot, device)
+        for key in CORRECTION_KEYS:
+            if key in a[side] and key in b[side]:
+                cmp[key] = _compare_direction(a[side][key], b[side][key], side, perm, boot, device)
+        out.append(cmp)
+    return tuple(out)
+
+
+def _carry_units(t2v, v2t, units, columns=None):
+    """Puts "units" into the two directions' dictionaries and, with the IR columns, "columns" into their "ir" entries."""
+    for side, m in enumerate((t2v, v2t)):
+        m["units"] = _units_entry(units[side])
+        if columns is not None:
+            m["ir"]["columns"] = columns[side]
+
+
+def _add_permutation(nt, nv, units, raw_units, perm, dev, columns=None, raw_columns=None):
+    """Puts "permutation_vs_raw" into a correction's two dictionaries (corrected minus raw: seed for text->video, seed + 1 for
+    video->text), and with the IR columns into their "ir" entries too."""
+    n_perm, seed = perm
+    for side, m in enumerate((nt, nv)):
+        m["permutation_vs_raw"] = _permutation_of_units(_units_entry(units[side]), _units_entry(raw_units[side]), n_perm, seed + side, dev)
+        if columns is not None:
+            m["ir"]["permutation_vs_raw"] = _permutation_of_columns(columns[side], raw_columns[side], n_perm, seed + side, dev)
+
+
 # ---- the evaluation: one slab, one driver, an optional correction (DESIGN.md "The evaluation driver") ---------------------------------
 # Every metric dictionary comes from sharded_evaluation: ONE scoring of this rank's slab, the raw dictionaries, then the corrected
 # ones under the correction's key.  A correction is a value: what its entry says, whether it needs a querybank, and the call that
@@ -889,15 +1021,20 @@ def _corrected_entry(metrics, correction, info, side):
 
 
 def sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, correction=None, hubness_k=0, cut_off_points=None,
-                       chunk=256, querybank=None, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, ir=False):
+                       chunk=256, querybank=None, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, ir=False, permutation=0,
+                       permutation_seed=0):
     """-> (text->video, video->text) metric dictionaries, identical on every rank, from ONE scoring of this rank's slab: R@K as
     RetrievalMetrics.compute_metrics(S) / (S.T) would give them (cut_off_points: the multi-sentence metrics, see
     sharded_multi_sentence_metrics).  hubness_k: each with a "hubness" entry (sharded_hubness).  ir: an "ir" entry (DESIGN.md
     "Rank-aware IR metrics").  bootstrap > 0: a "bootstrap" entry, also inside "ir" (DESIGN.md "Bootstrap confidence intervals").
     correction: each with one more entry correction.key, the same dictionary of the corrected scores with correction.entry's
     fields; its bootstrap entries are "bootstrap" and "bootstrap_vs_raw" (paired with the raw ranking on the same draws).
-    querybank: (text_feat, text_mask, video_feat, video_mask) for a correction that needs one; None: the model's memory bank."""
+    querybank: (text_feat, text_mask, video_feat, video_mask) for a correction that needs one; None: the model's memory bank.
+    permutation > 0 (DESIGN.md "Paired permutation tests"): every dictionary, the correction's too, also carries its resampling
+    "units" (entries, unit_end, median) and its "ir" entry its "columns" -- what compare_evaluations reads --, and the correction's
+    dictionary and its "ir" entry gain "permutation_vs_raw", the paired permutation test of corrected minus raw."""
     boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
+    perm = _check_permutation(permutation, permutation_seed)
     ir = _check_ir(ir)
     hubness_k = _check_hubness_k(hubness_k)
     if correction is not None and correction.needs_bank:
@@ -910,6 +1047,8 @@ def sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args
         t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
     raw_columns = _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot) if ir else None
     _add_bootstrap(t2v, v2t, raw_units, boot, dev)
+    if perm:
+        _carry_units(t2v, v2t, raw_units, raw_columns)
     if correction is None:
         return t2v, v2t
     T, V, info = _apply_correction(model, text_feat, video_feat, text_mask, video_mask, slab, correction, querybank, chunk)
@@ -917,8 +1056,10 @@ def sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args
     units = []
     nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k, units)
     _add_bootstrap(nt, nv, units, boot, dev, raw_units)
-    if ir:
-        _add_ir(nt, nv, T, V, n_rows, n_cols, W, rank, ends, boot, raw_columns)
+    columns = _add_ir(nt, nv, T, V, n_rows, n_cols, W, rank, ends, boot, raw_columns) if ir else None
+    if perm:
+        _carry_units(nt, nv, units, columns)
+        _add_permutation(nt, nv, units, raw_units, perm, dev, columns, raw_columns)
     t2v[correction.key] = _corrected_entry(nt, correction, info, 0)
     v2t[correction.key] = _corrected_entry(nv, correction, info, 1)
     return t2v, v2t
@@ -943,16 +1084,17 @@ def _corrected_metrics(model, text_feat, video_feat, text_mask, video_mask, args
 
 
 def sharded_metrics(model, text_feat, video_feat, text_mask, video_mask, args, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95,
-                    ir=False):
+                    ir=False, permutation=0, permutation_seed=0):
     """(text->video metrics, video->text metrics) as RetrievalMetrics.compute_metrics(S) / (S.T) would give them.  bootstrap > 0:
     each with a "bootstrap" entry (DESIGN.md "Bootstrap confidence intervals").  ir: each with an "ir" entry (DESIGN.md "Rank-aware
     IR metrics")."""
     return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, bootstrap=bootstrap,
-                              bootstrap_seed=bootstrap_seed, bootstrap_level=bootstrap_level, ir=ir)
+                              bootstrap_seed=bootstrap_seed, bootstrap_level=bootstrap_level, ir=ir, permutation=permutation,
+                              permutation_seed=permutation_seed)
 
 
 def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, video_mask, cut_off_points, args, chunk=256, bootstrap=0,
-                                   bootstrap_seed=0, bootstrap_level=0.95, ir=False):
+                                   bootstrap_seed=0, bootstrap_level=0.95, ir=False, permutation=0, permutation_seed=0):
     """Several captions per video (evaluator.py:114-149 features, :225-262 metrics): text_feat [Ns,...] holds every
     sentence in dataset order, video_feat [V,...] one entry per video, cut_off_points[g] = index of the LAST sentence of
     video g (the dataset's cut_off_points minus one, evaluator.py:98).  -> (text->video, video->text) metric dictionaries.
@@ -964,15 +1106,16 @@ def sharded_multi_sentence_metrics(model, text_feat, video_feat, text_mask, vide
     dictionary gains a "bootstrap" entry that resamples VIDEOS (DESIGN.md "Bootstrap confidence intervals").  ir: each gains an "ir"
     entry (DESIGN.md "Rank-aware IR metrics")."""
     return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points=cut_off_points, chunk=chunk,
-                              bootstrap=bootstrap, bootstrap_seed=bootstrap_seed, bootstrap_level=bootstrap_level, ir=ir)
+                              bootstrap=bootstrap, bootstrap_seed=bootstrap_seed, bootstrap_level=bootstrap_level, ir=ir,
+                              permutation=permutation, permutation_seed=permutation_seed)
 
 
 def sharded_metrics_with_hubness(model, text_feat, video_feat, text_mask, video_mask, args, k, cut_off_points=None, chunk=256,
-                                 bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, ir=False):
+                                 bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, ir=False, permutation=0, permutation_seed=0):
     """sharded_evaluation with a "hubness" entry of the top-k lists in each dictionary."""
     return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, hubness_k=ops._check_k(k),
                               cut_off_points=cut_off_points, chunk=chunk, bootstrap=bootstrap, bootstrap_seed=bootstrap_seed,
-                              bootstrap_level=bootstrap_level, ir=ir)
+                              bootstrap_level=bootstrap_level, ir=ir, permutation=permutation, permutation_seed=permutation_seed)
 
 
 def sharded_normalised_slabs(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None, qb_k=1,
@@ -996,11 +1139,12 @@ def sharded_normalised_metrics(model, text_feat, video_feat, text_mask, video_ma
 
 def sharded_metrics_with_test_norm(model, text_feat, video_feat, text_mask, video_mask, args, mode, beta=20.0, querybank=None,
                                    qb_k=1, hubness_k=0, cut_off_points=None, chunk=256, n_iter=50, bootstrap=0, bootstrap_seed=0,
-                                   bootstrap_level=0.95, ir=False):
+                                   bootstrap_level=0.95, ir=False, permutation=0, permutation_seed=0):
     """sharded_evaluation with test_norm_correction(mode, beta, qb_k, n_iter): the raw dictionaries, each with one more entry
     "test_norm" = sharded_normalised_metrics."""
     return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, test_norm_correction(mode, beta, qb_k, n_iter),
-                              hubness_k, cut_off_points, chunk, querybank, bootstrap, bootstrap_seed, bootstrap_level, ir)
+                              hubness_k, cut_off_points, chunk, querybank, bootstrap, bootstrap_seed, bootstrap_level, ir,
+                              permutation, permutation_seed)
 
 
 def sharded_local_scaled_slab(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False, querybank=None,
@@ -1022,11 +1166,12 @@ def sharded_local_scaled_metrics(model, text_feat, video_feat, text_mask, video_
 
 def sharded_metrics_with_local_scaling(model, text_feat, video_feat, text_mask, video_mask, args, mode, k=10, bank=False,
                                        querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0, bootstrap_seed=0,
-                                       bootstrap_level=0.95, ir=False):
+                                       bootstrap_level=0.95, ir=False, permutation=0, permutation_seed=0):
     """sharded_evaluation with local_scaling_correction(mode, k, bank): the raw dictionaries, each with one more entry
     "local_scaling" = sharded_local_scaled_metrics."""
     return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, local_scaling_correction(mode, k, bank),
-                              hubness_k, cut_off_points, chunk, querybank, bootstrap, bootstrap_seed, bootstrap_level, ir)
+                              hubness_k, cut_off_points, chunk, querybank, bootstrap, bootstrap_seed, bootstrap_level, ir,
+                              permutation, permutation_seed)
 
 
 def sharded_mutual_proximity_slab(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False, querybank=None,
@@ -1048,21 +1193,24 @@ def sharded_mutual_proximity_metrics(model, text_feat, video_feat, text_mask, vi
 
 def sharded_metrics_with_mutual_proximity(model, text_feat, video_feat, text_mask, video_mask, args, mode, bank=False,
                                           querybank=None, hubness_k=0, cut_off_points=None, chunk=256, bootstrap=0,
-                                          bootstrap_seed=0, bootstrap_level=0.95, ir=False):
+                                          bootstrap_seed=0, bootstrap_level=0.95, ir=False, permutation=0, permutation_seed=0):
     """sharded_evaluation with mutual_proximity_correction(mode, bank): the raw dictionaries, each with one more entry
     "mutual_proximity" = sharded_mutual_proximity_metrics."""
     return sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, mutual_proximity_correction(mode, bank),
-                              hubness_k, cut_off_points, chunk, querybank, bootstrap, bootstrap_seed, bootstrap_level, ir)
+                              hubness_k, cut_off_points, chunk, querybank, bootstrap, bootstrap_seed, bootstrap_level, ir,
+                              permutation, permutation_seed)
 
 
 def correction_from_args(args, model):
     """What the command-line flags ask of the evaluation -> (correction or None, the keyword arguments of sharded_evaluation:
-    hubness_k, the bootstrap triple and ir), everything checked before any work: the values, that at most one correction is chosen,
-    and that a correction that needs a querybank finds the model's memory bank filled."""
+    hubness_k, the bootstrap triple, ir and, when asked for, permutation and its seed), everything checked before any work: the
+    values, that at most one correction is chosen, that a permutation test has something to compare (a correction, or
+    args.compare_model), and that a correction that needs a querybank finds the model's memory bank filled."""
     kw = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
               bootstrap_level=getattr(args, "bootstrap_level", 0.95))
     _check_bootstrap(kw["bootstrap"], kw["bootstrap_seed"], kw["bootstrap_level"])
     kw["ir"] = _check_ir(getattr(args, "ir_metrics", 0) or 0)
+    perm = _check_permutation(getattr(args, "permutation", 0) or 0, getattr(args, "permutation_seed", 0) or 0)
     test_norm = getattr(args, "test_norm", None) or "none"
     local_scaling = getattr(args, "local_scaling", None) or "none"
     mutual_proximity = getattr(args, "mutual_proximity", None) or "none"
@@ -1080,6 +1228,11 @@ def correction_from_args(args, model):
     elif mutual_proximity != "none":
         correction = mutual_proximity_correction(mutual_proximity, bool(int(getattr(args, "mutual_proximity_bank", 0) or 0)))
     kw["hubness_k"] = _check_hubness_k(getattr(args, "hubness_k", 0))
+    if perm is not None:
+        if correction is None and not getattr(args, "compare_model", None):
+            raise ValueError("permutation needs a correction (test_norm, local_scaling, mutual_proximity) or compare_model: there is "
+                             "nothing to compare")
+        kw.update(permutation=perm[0], permutation_seed=perm[1])
     if correction is not None and correction.needs_bank:
         _querybank(model, None, model.mb_feat_t.device)         # checked where it lies: nothing is copied
     return correction, kw

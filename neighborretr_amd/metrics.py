@@ -222,8 +222,9 @@ class RetrievalMetrics:
         return out
 
     @staticmethod
-    def format_bootstrap(summary, prefix=""):
-        """One line: every logged metric with its interval; a paired summary prints signed differences and frac_le0."""
+    def format_bootstrap(summary, prefix="", versus="raw"):
+        """One line: every logged metric with its interval; a paired summary prints signed differences and frac_le0 (versus: what
+        the pair's second ranking is called)."""
         paired = any(isinstance(v, dict) and "frac_le0" in v for v in summary.values())
         label = {"R1": "R@1", "R5": "R@5", "R10": "R@10", "MedianR": "Median R", "MeanR": "Mean R"}
         parts = []
@@ -235,7 +236,7 @@ class RetrievalMetrics:
                 parts.append(f"{label[name]}: {m['point']:+.1f} [{m['lo']:+.1f}, {m['hi']:+.1f}] frac<=0 {m['frac_le0']:.3f}")
             else:
                 parts.append(f"{label[name]}: {m['point']:.1f} [{m['lo']:.1f}, {m['hi']:.1f}]")
-        kind = "paired bootstrap vs raw" if paired else "bootstrap"
+        kind = f"paired bootstrap vs {versus}" if paired else "bootstrap"
         tail = f" ({100 * summary['level']:g}% {kind}, {summary['n_boot']} resamples"
         tail += f", {summary['n_empty']} empty)" if summary["n_empty"] else ")"
         return prefix + " - ".join(parts) + tail
@@ -376,8 +377,9 @@ class RetrievalMetrics:
         return prefix + " - ".join(f"{RetrievalMetrics.IR_LABELS[name]} {ir[name]:.1f}" for name in RetrievalMetrics.IR_METRICS)
 
     @staticmethod
-    def format_ir_bootstrap(summary, prefix=""):
-        """One line: every IR metric with its interval; a paired summary prints signed differences and frac_le0."""
+    def format_ir_bootstrap(summary, prefix="", versus="raw"):
+        """One line: every IR metric with its interval; a paired summary prints signed differences and frac_le0 (versus: what the
+        pair's second ranking is called)."""
         paired = any(isinstance(v, dict) and "frac_le0" in v for v in summary.values())
         parts = []
         for name in RetrievalMetrics.IR_METRICS:
@@ -387,7 +389,7 @@ class RetrievalMetrics:
                              f"frac<=0 {m['frac_le0']:.3f}")
             else:
                 parts.append(f"{RetrievalMetrics.IR_LABELS[name]} {m['point']:.1f} [{m['lo']:.1f}, {m['hi']:.1f}]")
-        kind = "paired bootstrap vs raw" if paired else "bootstrap"
+        kind = f"paired bootstrap vs {versus}" if paired else "bootstrap"
         tail = f" ({100 * summary['level']:g}% {kind}, {summary['n_boot']} resamples"
         tail += f", {summary['n_empty']} empty)" if summary["n_empty"] else ")"
         return prefix + " - ".join(parts) + tail
@@ -400,6 +402,106 @@ class RetrievalMetrics:
         for key in ("bootstrap", "bootstrap_vs_raw"):
             if key in ir:
                 self.logger.info(self.format_ir_bootstrap(ir[key], prefix))
+
+    # ---- paired permutation tests (DESIGN.md "Paired permutation tests") ----------------------------------------------------------------
+    @staticmethod
+    def _permutation_p_values(out, ratios_x, ratios_y, ratios_a, ratios_b, keep):
+        """Fills out[metric] = {"diff", "p_two", "p_ge", "p_le"} from {metric: (numerator, denominator)} of the sides X, Y (object
+        arrays of Python ints over the kept permutations, denominators > 0) and of the un-permuted A, B (Python ints, or None when
+        one of them is empty: every figure is NaN).  d_p = x - y against d_0 = a - b on cross-multiplied integers: never in fp64."""
+        kept = int(np.sum(keep))
+        for name in ratios_x:
+            if ratios_a is None:
+                out[name] = {"diff": float("nan"), "p_two": float("nan"), "p_ge": float("nan"), "p_le": float("nan")}
+                continue
+            (xn, xd), (yn, yd), (an, ad), (bn, bd) = ratios_x[name], ratios_y[name], ratios_a[name], ratios_b[name]
+            n0, m0 = an * bd - bn * ad, ad * bd                                  # d_0 = n0 / m0
+            left = (xn * yd - yn * xd) * m0                                      # d_p >= d_0  <=>  left >= right (all denominators > 0)
+            right = n0 * (xd * yd)
+            two, ge, le = (int(np.sum(c)) for c in (abs(left) >= abs(right), left >= right, left <= right)) if kept else (0, 0, 0)
+            out[name] = {"diff": n0 / m0, "p_two": (1 + two) / (1 + kept), "p_ge": (1 + ge) / (1 + kept), "p_le": (1 + le) / (1 + kept)}
+        return out
+
+    @staticmethod
+    def _rank_ratios(stats, cuts, median):
+        """{metric: (numerator, denominator)} of rows (n, sum, med_lo, med_hi, hits...) as Python ints (object arrays): R{c} =
+        100 hits / n, MeanR = sum / n, MedianR = (med_lo + med_hi) / 2 or 2 med_lo / 2; the "+ 1" of the rank metrics cancels."""
+        stats = np.asarray(stats, dtype=np.int64).astype(object)
+        n = stats[..., 0]
+        out = {f"R{int(c)}": (100 * stats[..., 4 + k], n) for k, c in enumerate(cuts)}
+        out["MedianR"] = (stats[..., 2] + (stats[..., 3] if median == "mid" else stats[..., 2]), 2 + 0 * n)
+        out["MeanR"] = (stats[..., 1], n)
+        return out
+
+    @staticmethod
+    def permutation_summary(stats, cuts, entries, entries_other, median="mid", seed=0):
+        """Paired permutation (randomisation) test of "ranking A minus ranking B": stats [n_perm, 2, 4 + K] int64
+        (ops.permtest_rank_stats: the sides X, Y of every relabelling), entries / entries_other = the un-permuted ranks of A / B.
+        Per side the formulas of bootstrap_summary; d_p = m(X_p) - m(Y_p), d_0 = m(A) - m(B).  Permutations with an empty side are
+        dropped (n_empty); kept = the rest.  -> {"n_perm", "n_empty", "kept", "seed", "median", and per metric "diff" (d_0),
+        "p_two" = (1 + #{|d_p| >= |d_0|}) / (1 + kept), "p_ge" (d_p >= d_0), "p_le" (d_p <= d_0)}.  The comparisons are made on
+        cross-multiplied Python integers: the statistic is discrete, ties with d_0 are common and fp64 would break them."""
+        if median not in ("mid", "low"):
+            raise ValueError(f"median must be 'mid' (np.median) or 'low' (torch.median), got {median!r}")
+        stats = np.asarray(stats.cpu() if torch.is_tensor(stats) else stats, dtype=np.int64)
+        cuts = [int(c) for c in cuts]
+        if stats.ndim != 3 or stats.shape[1:] != (2, 4 + len(cuts)):
+            raise ValueError(f"stats must be [n_perm, 2, {4 + len(cuts)}] for {len(cuts)} cut-offs, got {stats.shape}")
+        keep = (stats[:, 0, 0] > 0) & (stats[:, 1, 0] > 0)
+        out = {"n_perm": int(len(stats)), "n_empty": int(np.sum(~keep)), "kept": int(np.sum(keep)), "seed": int(seed), "median": median}
+        x = RetrievalMetrics._rank_ratios(stats[keep, 0], cuts, median)
+        y = RetrievalMetrics._rank_ratios(stats[keep, 1], cuts, median)
+        a, b = RetrievalMetrics._entry_stats(entries, cuts)[0], RetrievalMetrics._entry_stats(entries_other, cuts)[0]
+        if a[0] == 0 or b[0] == 0:
+            return RetrievalMetrics._permutation_p_values(out, x, y, None, None, keep)
+        return RetrievalMetrics._permutation_p_values(out, x, y, RetrievalMetrics._rank_ratios(a, cuts, median),
+                                                      RetrievalMetrics._rank_ratios(b, cuts, median), keep)
+
+    @staticmethod
+    def _ir_ratios(sums):
+        """{metric: (100 sum_fixed, 2^32 count)} of rows (count, RR, AP, nDCG10, RPrec sums) as Python ints (object arrays)."""
+        sums = np.asarray(sums).astype(object)
+        return {name: (100 * sums[..., 1 + i], RetrievalMetrics.IR_FIXED_ONE * sums[..., 0])
+                for i, name in enumerate(RetrievalMetrics.IR_METRICS)}
+
+    @staticmethod
+    def ir_permutation_summary(sums, columns, columns_other, seed=0):
+        """Paired permutation test of the IR metrics of "ranking A minus ranking B": sums [n_perm, 5] int64 (ops.permtest_unit_sums of
+        the two rankings' ir_unit_columns: side X), columns / columns_other = those columns [U, 5] of A / B; side Y is the two totals
+        minus X, in exact integers.  Per side the formula of ir_bootstrap_summary (100 sum_fixed / (2^32 count)); the fields of
+        permutation_summary without "median", the comparisons on the fixed-point sums over the counts."""
+        sums = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, dtype=np.int64)
+        q = 1 + len(RetrievalMetrics.IR_METRICS)
+        cols = [np.asarray(c, dtype=np.int64) for c in (columns, columns_other)]
+        if sums.ndim != 2 or sums.shape[1] != q or any(c.ndim != 2 or c.shape != (cols[0].shape[0], q) for c in cols):
+            raise ValueError(f"sums must be [n_perm, {q}] and both columns [U, {q}], got {sums.shape}, {cols[0].shape} and {cols[1].shape}")
+        ta, tb = (c.astype(object).sum(axis=0) for c in cols)
+        x = sums.astype(object)
+        y = (ta + tb)[None, :] - x
+        keep = np.asarray((x[:, 0] > 0) & (y[:, 0] > 0), dtype=bool)
+        out = {"n_perm": int(len(sums)), "n_empty": int(np.sum(~keep)), "kept": int(np.sum(keep)), "seed": int(seed)}
+        rx, ry = RetrievalMetrics._ir_ratios(x[keep]), RetrievalMetrics._ir_ratios(y[keep])
+        if ta[0] == 0 or tb[0] == 0:
+            return RetrievalMetrics._permutation_p_values(out, rx, ry, None, None, keep)
+        return RetrievalMetrics._permutation_p_values(out, rx, ry, RetrievalMetrics._ir_ratios(ta), RetrievalMetrics._ir_ratios(tb), keep)
+
+    @staticmethod
+    def format_permutation(summary, prefix="", versus="raw"):
+        """One line: every logged metric's signed difference and its two-sided p-value (a rank summary or an IR summary)."""
+        if "median" in summary:
+            label = {"R1": "R@1", "R5": "R@5", "R10": "R@10", "MedianR": "Median R", "MeanR": "Mean R"}
+            names = [n for n in RetrievalMetrics.BOOTSTRAP_LOGGED if n in summary]
+        else:
+            label, names = RetrievalMetrics.IR_LABELS, list(RetrievalMetrics.IR_METRICS)
+        parts = [f"{label[n]}: {summary[n]['diff']:+.2f} p={summary[n]['p_two']:.4f}" for n in names]
+        tail = f" (paired permutation test vs {versus}, {summary['n_perm']} permutations"
+        tail += f", {summary['n_empty']} empty)" if summary["n_empty"] else ")"
+        return prefix + " - ".join(parts) + tail
+
+    def log_permutation(self, summary, prefix="", versus="raw"):
+        """One line per summary, in the style of print_metrics (silent without a logger)."""
+        if self.logger is not None:
+            self.logger.info(self.format_permutation(summary, prefix, versus))
 
     def print_metrics(self, metrics, prefix=""):
         msg = (f"{prefix}R@1: {metrics['R1']:.1f} - R@5: {metrics['R5']:.1f} - R@10: {metrics['R10']:.1f} - "

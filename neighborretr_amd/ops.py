@@ -1436,6 +1436,68 @@ def bootstrap_unit_sums(values, seed=0, b0=0, n_boot=1000):
     return out
 
 
+def _resample_range(seed, first, count, names):
+    """The checked integers (seed, first, count) of a resampling call; names = what the last two are called."""
+    for name, v in (("seed", seed), (names[0], first), (names[1], count)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    seed, first, count = int(seed), int(first), int(count)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must lie in [0, 2^64), got {seed}")
+    if first < 0 or count < 0 or first + count > (1 << 31) - 1:
+        raise ValueError(f"{names[0]} and {names[1]} must be >= 0 with {names[0]} + {names[1]} <= 2^31 - 1, got {first} and {count}")
+    return seed, first, count
+
+
+def permtest_rank_stats(ranks_a, unit_end_a, ranks_b, unit_end_b, cuts=(1, 5, 10, 50), seed=0, p0=0, n_perm=1000):
+    """int64 [n_perm, 2, 4 + K] on the device (nr_permtest_rank_stats): for permutations p0 .. p0 + n_perm - 1 and the sides X, Y of
+    the relabelling -- X takes unit u's entries from ranking a when the swap bit s(p, u) is 0 and from b when it is 1, Y the other
+    ranking's -- over the side's entries: n, the sum of ranks, the order statistics at positions (n - 1) // 2 and n // 2 (-1 when
+    n = 0) and #{r < cuts[k]}.  Rankings as in bootstrap_rank_stats (checked on the device: ValueError); both are required.  The
+    result depends on (seed, p, inputs) alone."""
+    cuts = _boot_cuts(cuts)
+    seed, p0, n_perm = _resample_range(seed, p0, n_perm, ("p0", "n_perm"))
+    ra, ea, E_a = _boot_ranking(ranks_a, unit_end_a, "a")
+    U = ea.numel()
+    rb, eb, E_b = _boot_ranking(ranks_b, unit_end_b, "b", ra.device, U)
+    K = len(cuts)
+    out = torch.empty((n_perm, 2, 4 + K), dtype=torch.int64, device=ra.device)
+    if n_perm:
+        import ctypes
+        hip.call("nr_permtest_rank_stats", hip.ptr(ra), hip.ptr(ea), E_a, hip.ptr(rb), hip.ptr(eb), E_b, U, (ctypes.c_int32 * K)(*cuts),
+                 K, ctypes.c_uint64(seed), p0, n_perm, hip.ptr(out), hip.stream_ptr())
+    return out
+
+
+def permtest_unit_sums(values_a, values_b, seed=0, p0=0, n_perm=1000):
+    """int64 [n_perm, Q] on the device (nr_permtest_unit_sums): out[i, q] = the sum over the units u of values_b[u, q] where the swap
+    bit s(p0 + i, u) of permtest_rank_stats is 1 and of values_a[u, q] where it is 0: side X; side Y is the two inputs' totals minus
+    it.  values_a, values_b [U, Q] int64 on one device, U in [1, 2^24], Q in [1, 16], U max|value| < 2^62 for either."""
+    for name, v in (("values_a", values_a), ("values_b", values_b)):
+        if not torch.is_tensor(v) or v.dtype != torch.int64 or v.dim() != 2:
+            raise ValueError(f"{name} must be a 2-D int64 tensor [U, Q]")
+        if not v.is_cuda:
+            raise ValueError(f"{name} must be on the GPU (no CPU fallback)")
+    if values_a.shape != values_b.shape or values_a.device != values_b.device:
+        raise ValueError(f"values_a and values_b must have one shape and one device, got {tuple(values_a.shape)} and "
+                         f"{tuple(values_b.shape)}")
+    seed, p0, n_perm = _resample_range(seed, p0, n_perm, ("p0", "n_perm"))
+    values_a, values_b = values_a.contiguous(), values_b.contiguous()
+    U, Q = values_a.shape
+    if not 1 <= U <= hip.BOOT_MAX_UNITS or not 1 <= Q <= hip.BOOT_MAX_COLS:
+        raise ValueError(f"values must be [U, Q] with U in [1, 2^24] and Q in [1, {hip.BOOT_MAX_COLS}], got {tuple(values_a.shape)}")
+    for name, v in (("values_a", values_a), ("values_b", values_b)):
+        largest = max(int(v.max()), -int(v.min()))
+        if U * largest >= hip.BOOT_SUM_LIMIT:
+            raise ValueError(f"{name}: U max|value| = {U} x {largest} reaches 2^62: a side's sum could overflow")
+    out = torch.empty((n_perm, Q), dtype=torch.int64, device=values_a.device)
+    if n_perm:
+        import ctypes
+        hip.call("nr_permtest_unit_sums", hip.ptr(values_a), hip.ptr(values_b), U, Q, ctypes.c_uint64(seed), p0, n_perm, hip.ptr(out),
+                 hip.stream_ptr())
+    return out
+
+
 def linear_x3(x, w, bias=None, residual=None):
     """Y = X W^T (+ bias) (+ residual) on the split-bf16 MFMA tile engine (nr_linear_x3): x [M,K], w [N,K] fp32, K padded to
     a multiple of 64 with zeros.  ~fp32-grade products (3 bf16 passes); used for the clustering GEMMs and for the

@@ -206,6 +206,14 @@ def eval_epoch(args, model, test_dataloader, device):
                 if "bootstrap_vs_raw" in m:
                     tracker.log_bootstrap(m["bootstrap_vs_raw"], prefix=f"{side} {tag} - raw: ")
 
+        def log_permutation(nt, nv, tag):
+            """The paired permutation test of a correction against raw: one line per direction, and one for its IR metrics."""
+            for side, m in (("Text-to-Video", nt), ("Video-to-Text", nv)):
+                if "permutation_vs_raw" in m:
+                    tracker.log_permutation(m["permutation_vs_raw"], prefix=f"{side} {tag} - raw: ")
+                if "permutation_vs_raw" in m.get("ir", {}):
+                    tracker.log_permutation(m["ir"]["permutation_vs_raw"], prefix=f"{side} {tag} - raw: ")
+
         def log_ir(nt, nv, tag=""):
             """The IR line of each direction (MRR, mAP, nDCG@10, R-Prec) and its interval lines."""
             if not extras["ir"]:
@@ -223,6 +231,7 @@ def eval_epoch(args, model, test_dataloader, device):
             tracker.print_metrics(nv, prefix=f"Video-to-Text {tag}: ")
             log_bootstrap(nt, nv, tag)
             log_ir(nt, nv, tag)
+            log_permutation(nt, nv, tag)
             if "marginal_err" in nt:
                 logger.info(f"{tag} marginal error after {nt['iters']} iterations: {nt['marginal_err']:.3e} / {nv['marginal_err']:.3e}")
             if hubness_k:
