@@ -1040,6 +1040,46 @@ int nr_bertadam_step_guarded(const NrOptimTensor* table, int T, int n_chunks, co
                              float global_max_norm, void* workspace, NrStepGuard* guard, const float* losses, int n_losses,
                              NrStepRecord* ring, int n_ring, void* stream);
 
+/* Exponential moving average of the weights (DESIGN.md "Weight EMA").  Per averaged element, AFTER the parameter's update of the
+ * same step, with n = state->updates (the updates that have happened before this one):
+ *   d   = warmup ? min(decay, (1 + n) / (10 + n)) : decay      in double
+ *   omd = (float)(1.0 - d)                                     rounded once
+ *   e   = fmaf(omd, p_new - e, e)                              fp32, the difference rounded; e is the fp32 shadow
+ *   state->updates = n + 1
+ * One device function holds the element's arithmetic: the fused and the stand-alone form, 16-byte and dword accesses give the same
+ * bits.  No float atomics, nothing read from the host after a call: every form replays from a graph. */
+typedef struct {
+    double decay;      /* in [0, 1)                                                                                    */
+    int64_t updates;   /* good updates so far                                                                          */
+    int32_t warmup;    /* != 0: the decay ramps up as (1 + n) / (10 + n) until it reaches `decay`                      */
+    float omd;         /* (float)(1 - d) of the last update, written on every good update                              */
+} NrEmaState; /* 24 bytes */
+typedef struct {
+    float* p;          /* parameter, n elements, 4-byte aligned (16-byte aligned p and ema take the vector path)       */
+    float* ema;        /* its shadow                                                                                   */
+    int64_t n;
+    int32_t chunk0;    /* first chunk of this tensor: written by nr_ema_plan                                           */
+    int32_t pad_;
+} NrEmaTensor; /* 32 bytes */
+/* nr_bertadam_step_guarded's arguments (guard == NULL: the unguarded step, ring and losses are ignored) plus `ema`, a DEVICE
+ * array of T pointers parallel to `table` (NULL entry: that tensor is not averaged), and the DEVICE state.  The same three
+ * launches and workspace: in launch B the thread that owns the guard forms omd and counts the update (on a bad step it touches
+ * nothing of *state and no shadow moves), launch C averages the chunks it is streaming.  p, m, v, the counters and the learning
+ * rates get the bits nr_bertadam_step / _guarded give.  NR_EINVAL before any launch: what those refuse, a null or misaligned
+ * (8 bytes) ema or state.  T = 0: NR_OK, no launch, no update counted. */
+int nr_bertadam_step_ema(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, int G, float global_max_norm,
+                         void* workspace, NrStepGuard* guard, const float* losses, int n_losses, NrStepRecord* ring, int n_ring,
+                         float* const* ema, NrEmaState* state, void* stream);
+/* Host-only: validates the HOST copies of a stand-alone table and of the state (null or misaligned pointers, negative counts, a
+ * decay outside [0, 1) or NaN: NR_EINVAL), writes every entry's chunk0 and returns the number of chunks in *n_chunks. */
+int nr_ema_plan(NrEmaTensor* entries, int T, const NrEmaState* state, int* n_chunks);
+/* Stand-alone update of every tensor of the DEVICE table: a one-thread launch that forms omd and counts the update, then the
+ * streaming launch (12 bytes per element).  NR_EINVAL before any launch for null or misaligned (8 bytes) table or state and
+ * negative counts.  T = 0: NR_OK, no launch, no update counted. */
+int nr_ema_update(const NrEmaTensor* table, int T, int n_chunks, NrEmaState* state, void* stream);
+/* Exchanges the contents of p and ema of every table entry in place: one launch, no state, bit-exact. */
+int nr_ema_swap(const NrEmaTensor* table, int T, int n_chunks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

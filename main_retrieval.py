@@ -156,6 +156,14 @@ def get_args():
                         "inside its three launches -- no synchronisation, also inside the replayed graph -- and logs skips and "
                         "gradient norms at every --n_display line; --optimizer adamw tests the norm clip_grad_norm_ returns on "
                         "the host, which costs one synchronisation per step, with this flag only; 0 = off")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="D in (0, 1): an exponential moving average of the weights with decay D, updated on the device after "
+                        "every update that happened (DESIGN.md 6.11): inside the optimizer's launches with --optimizer bertadam "
+                        "(so inside the replayed graph and under --skip_nonfinite 1), two launches after optimizer.step() with "
+                        "adamw.  Every epoch is evaluated a second time with the average (lines tagged EMA) and, with "
+                        "--save_model, saved as pytorch_model_ema.bin.N, which --init_model / --compare_model load; 0 = off")
+    p.add_argument("--ema_warmup", type=int, default=1, choices=[0, 1],
+                   help="--ema_decay: 1 ramps the decay up as min(D, (1 + n) / (10 + n)) over the first updates; 0 uses D throughout")
     p.add_argument("--synthetic_blank", default="", metavar="STEP[:RANK]",
                    help="--synthetic: in global step STEP (1-based) the first video of the batch of rank RANK (default 0) comes "
                         "back the way the reference's loader returns an undecodable one, all zeros with an all-zero mask")
@@ -185,12 +193,16 @@ def get_args():
         p.error("--permutation must lie in [0, 2^20]")
     if not 0 <= args.permutation_seed < (1 << 64) - 1:
         p.error("--permutation_seed must lie in [0, 2^64 - 1)")
+    if not (args.ema_decay == 0.0 or 0.0 < args.ema_decay < 1.0):
+        p.error("--ema_decay must be 0 (off) or lie in (0, 1)")
+    if args.ema_decay and not args.do_train:
+        p.error("--ema_decay belongs to training (--do_train 1); evaluate a saved average with --init_model")
     if args.compare_model and not (args.do_eval and not args.do_train and args.permutation > 0):
         p.error("--compare_model works with --do_eval (without --do_train) and needs --permutation > 0")
     corrected = args.test_norm != "none" or args.local_scaling != "none" or args.mutual_proximity != "none"
-    if args.permutation and not (corrected or args.compare_model):
-        p.error("--permutation needs a correction (--test_norm, --local_scaling, --mutual_proximity) or --compare_model: there is "
-                "nothing to compare")
+    if args.permutation and not (corrected or args.compare_model or args.ema_decay):
+        p.error("--permutation needs a correction (--test_norm, --local_scaling, --mutual_proximity), --compare_model or "
+                "--ema_decay: there is nothing to compare")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
         raise ValueError("--batch_size must divide over the ranks (args_parser.py:149-165)")
     return args
@@ -222,6 +234,11 @@ def setup_distributed(args):
 def log(args, msg):
     if args.rank == 0:
         print(time.strftime("%H:%M:%S"), msg, flush=True)
+
+
+def _tagged_log(tag):
+    """log, or with a tag a log that puts the tag in front of every message."""
+    return log if not tag else (lambda args, msg: log(args, f"{tag} {msg}"))
 
 
 class SyntheticFeatures:
@@ -541,7 +558,9 @@ class GraphedStep:
         return self.losses
 
 
-def train_epoch(args, model, ddp, data, optimizer, epoch, global_step):
+def train_epoch(args, model, ddp, data, optimizer, epoch, global_step, ema=None):
+    """ema: the run's WeightEma.  --optimizer bertadam drives it from its own launches; after an AdamW step that happened it
+    takes its stand-alone update here."""
     from neighborretr_amd.dist import reduce_losses
     model.train()
     t0 = time.time()
@@ -586,12 +605,16 @@ def train_epoch(args, model, ddp, data, optimizer, epoch, global_step):
                 if math.isfinite(norm):
                     hs["consecutive"] = 0
                     optimizer.step()
+                    if ema is not None:
+                        ema.update()
                 else:
                     hs["skipped"] += 1
                     hs["consecutive"] += 1
                     hs["max_consecutive"] = max(hs["max_consecutive"], hs["consecutive"])
             else:
                 optimizer.step()
+                if ema is not None:
+                    ema.update()
             optimizer.zero_grad(set_to_none=True)
             torch.clamp_(model.clip.logit_scale.data, max=float(np.log(100)))    # trainer.py:114-119
         if global_step % args.n_display == 0 or i == len(data) - 1:
@@ -625,6 +648,25 @@ def train_epoch(args, model, ddp, data, optimizer, epoch, global_step):
     return global_step
 
 
+def ema_epoch(args, model, ema, raw_result, test, epoch):
+    """--ema_decay, after an epoch's evaluation: the same evaluation with the average in the parameters (every line tagged EMA),
+    the state's line, with --permutation the paired test of the average against the raw model, with --save_model the average
+    as a checkpoint of the model's keys; last, on every rank, the digest of the shadows (the ranks must agree)."""
+    with ema.applied():
+        ema_result = eval_epoch(args, model, test, tag="EMA")
+    n, d = ema.updates(), ema.last_decay()
+    log(args, f"ema updates {n} decay {d if d is not None else float('nan'):.6f}")
+    if args.permutation:
+        from neighborretr_amd.evaluator import compare_evaluations
+        cmp = compare_evaluations(ema_result, raw_result, args.permutation, args.permutation_seed, args.bootstrap,
+                                  args.bootstrap_seed, args.bootstrap_level, device=args.device)
+        _log_comparison(args, cmp, "EMA - model", versus="model")
+    if args.rank == 0 and args.save_model:
+        torch.save(ema.model_state_dict(model), os.path.join(args.output_dir, f"pytorch_model_ema.bin.{epoch}"))
+    print(f"rank {args.rank} epoch {epoch + 1} ema sha256 {ema.sha256()[:16]}", flush=True)
+    return ema_result
+
+
 def _guard_report(args, optimizer, fused, window):
     """--skip_nonfinite 1 -> ({skipped, consecutive, max_consecutive}, the gradient norms of the last `window` steps): from the
     device's guard and record ring (BertAdam; one blocking copy, at a log line only) or from the host's counts (adamw)."""
@@ -635,8 +677,10 @@ def _guard_report(args, optimizer, fused, window):
     return hs, hs["norms"][-window:] if window else []
 
 
-def eval_epoch(args, model, test):
-    """evaluator.py:66-291 for the single-sentence case with the work SHARDED over the ranks (neighborretr_amd.evaluator):
+def eval_epoch(args, model, test, tag=""):
+    """`tag`: a word every line of this run starts with (EMA: the evaluation of the averaged weights).
+
+    evaluator.py:66-291 for the single-sentence case with the work SHARDED over the ranks (neighborretr_amd.evaluator):
     every rank "extracts" the features of its samples (rank, rank + W, ...: a DistributedSampler's split; feature mode:
     they are the inputs), one packed all-gather + index scatter restores dataset order (evaluator.py:173-189), rank r
     computes rows [r N/W, (r+1) N/W) of the N x N similarity and the rank counts of its slab on the GPU, three small
@@ -645,6 +689,7 @@ def eval_epoch(args, model, test):
     from neighborretr_amd.metrics import RetrievalMetrics
     correction, extras = correction_from_args(args, model)     # every flag checked before any work
     hubness_k = extras["hubness_k"]
+    log = _tagged_log(tag)
 
     def log_ir(nt, nv, tag=""):
         """The IR line of each direction (MRR, mAP, nDCG@10, R-Prec) and its interval lines."""
@@ -709,8 +754,7 @@ def eval_epoch(args, model, test):
 def compare_with_model(args, result, train, test, with_bank):
     """--compare_model PATH: the test set scored again with the same architecture loaded from PATH, then the "model - compared"
     lines of evaluator.compare_evaluations (result minus that evaluation).  The second model is released before returning."""
-    from neighborretr_amd.evaluator import CORRECTION_KEYS, compare_evaluations
-    from neighborretr_amd.metrics import RetrievalMetrics
+    from neighborretr_amd.evaluator import compare_evaluations
     from neighborretr_amd.modeling import NeighborRetr
     other = NeighborRetr(args, precision=args.precision, with_encoders=bool(args.encoders))
     missing, unexpected = other.load_state_dict(torch.load(args.compare_model, map_location="cpu"), strict=False)
@@ -724,20 +768,28 @@ def compare_with_model(args, result, train, test, with_bank):
     cmp = compare_evaluations(result, compared, args.permutation, args.permutation_seed, args.bootstrap, args.bootstrap_seed,
                               args.bootstrap_level, device=args.device)
 
+    _log_comparison(args, cmp, "model - compared", versus="compared")
+    return cmp
+
+
+def _log_comparison(args, cmp, what, versus):
+    """The lines of evaluator.compare_evaluations' result `cmp` under the prefix `what` ("a - b"; versus: what b is called)."""
+    from neighborretr_amd.evaluator import CORRECTION_KEYS
+    from neighborretr_amd.metrics import RetrievalMetrics
+
     def lines(c, prefix):
-        log(args, RetrievalMetrics.format_permutation(c["permutation"], prefix=prefix, versus="compared"))
+        log(args, RetrievalMetrics.format_permutation(c["permutation"], prefix=prefix, versus=versus))
         if "bootstrap" in c:
-            log(args, RetrievalMetrics.format_bootstrap(c["bootstrap"], prefix=prefix, versus="compared"))
+            log(args, RetrievalMetrics.format_bootstrap(c["bootstrap"], prefix=prefix, versus=versus))
         if "ir" in c:
-            log(args, RetrievalMetrics.format_permutation(c["ir"]["permutation"], prefix=prefix, versus="compared"))
+            log(args, RetrievalMetrics.format_permutation(c["ir"]["permutation"], prefix=prefix, versus=versus))
             if "bootstrap" in c["ir"]:
-                log(args, RetrievalMetrics.format_ir_bootstrap(c["ir"]["bootstrap"], prefix=prefix, versus="compared"))
+                log(args, RetrievalMetrics.format_ir_bootstrap(c["ir"]["bootstrap"], prefix=prefix, versus=versus))
     for side, c in zip(("text->video", "video->text"), cmp):
-        lines(c, f"model - compared {side} ")
+        lines(c, f"{what} {side} ")
         for key in CORRECTION_KEYS:
             if key in c:
-                lines(c[key], f"model - compared {side} [{key}] ")
-    return cmp
+                lines(c[key], f"{what} {side} [{key}] ")
 
 
 def main():
@@ -764,11 +816,15 @@ def main():
     Data = SyntheticClips if args.encoders else SyntheticFeatures
     train = Data(args, args.synthetic_train, "train", args.seed)
     test = Data(args, args.synthetic_test, "test", args.seed + 1)
+    ema = None
+    if args.ema_decay:
+        from neighborretr_amd.optim import WeightEma
+        ema = WeightEma(model.named_parameters(), decay=args.ema_decay, warmup=bool(args.ema_warmup))
     if args.optimizer == "bertadam":
         from neighborretr_amd.optim import prep_optimizer
         # (wrap=False: the model is wrapped above, or not at all under --hip_graph 1)
         optimizer = prep_optimizer(args, model, len(train) * args.epochs, args.device_index, global_max_norm=1.0,
-                                   clamp_logit_scale=True, wrap=False, skip_nonfinite=bool(args.skip_nonfinite))[0]
+                                   clamp_logit_scale=True, wrap=False, skip_nonfinite=bool(args.skip_nonfinite), ema=ema)[0]
     else:
         optimizer = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -776,10 +832,13 @@ def main():
     if args.do_train:
         for epoch in range(args.epochs):
             load_memory_bank(args, model, train)
-            global_step = train_epoch(args, model, ddp, train, optimizer, epoch + 1, global_step)
-            eval_epoch(args, model, test)
+            global_step = train_epoch(args, model, ddp, train, optimizer, epoch + 1, global_step,
+                                      ema=ema if args.optimizer != "bertadam" else None)
+            raw_result = eval_epoch(args, model, test)
             if args.rank == 0 and args.save_model:
                 torch.save(model.state_dict(), os.path.join(args.output_dir, f"pytorch_model.bin.{epoch}"))
+            if ema is not None:
+                ema_epoch(args, model, ema, raw_result, test, epoch)
             clear_memory_bank(model)
     elif args.do_eval:
         with_bank = args.test_norm in ("qbnorm", "qbsinkhorn") or (args.local_scaling != "none" and args.local_scaling_bank) \

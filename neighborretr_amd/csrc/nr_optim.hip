@@ -16,6 +16,12 @@
 // three launches with a device-side decision in B: a step whose sum of squared gradients is not finite changes nothing.  No float atomics and no order that depends on which
 // workgroup arrives first: a chunk's sum is formed in one fixed order whether its gradient is 16-byte aligned or not, so the
 // result does not depend on alignment either.  The gradient buffers are only read.
+//
+// Weight EMA: e += (1 - d) (p_new - e) per averaged element, d from a device-resident NrEmaState.  Fused form
+// (nr_bertadam_step_ema): the owner of the guard in launch B forms (float)(1 - d) and counts the update, launch C averages the
+// chunks it is streaming anyway (36 instead of 28 bytes per element).  Stand-alone form (nr_ema_update): a one-thread launch
+// for the state, then a streaming launch over a table of (p, shadow) pairs, 12 bytes per element.  nr_ema_swap exchanges the
+// contents of p and shadow.  One __device__ function holds the element's arithmetic, so every form and path gives the same bits.
 #include "nr_common.h"
 #include "../../include/nr_hip.h"
 
@@ -25,7 +31,8 @@
 
 // the table entry that owns chunk `chunk`: the last one whose chunk0 is <= chunk (entries without elements share their
 // successor's chunk0 and are never selected)
-__device__ __forceinline__ int nr_opt_find(const NrOptimTensor* __restrict__ table, int T, int chunk) {
+template <typename Entry>
+__device__ __forceinline__ int nr_opt_find(const Entry* __restrict__ table, int T, int chunk) {
     int lo = 0, hi = T;                      // invariant: table[lo].chunk0 <= chunk, answer in [lo, hi)
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
@@ -36,6 +43,48 @@ __device__ __forceinline__ int nr_opt_find(const NrOptimTensor* __restrict__ tab
 }
 
 __device__ __forceinline__ bool nr_opt_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// ---- weight EMA: the state's advance (one thread, ever) and the element ---------------------------------------------------------
+// d = warmup ? min(decay, (1 + n) / (10 + n)) : decay with n the updates so far, in double; 1 - d rounded to fp32 once
+__device__ __forceinline__ void nr_ema_advance(NrEmaState* __restrict__ st) {
+    const int64_t n = st->updates;
+    double d = st->decay;
+    if (st->warmup != 0) {
+        const double w = (1.0 + (double)n) / (10.0 + (double)n);
+        d = w < d ? w : d;
+    }
+    st->omd = (float)(1.0 - d);
+    st->updates = n + 1;
+}
+
+// roundings spelled out, as in nr_opt_update: the vector path, the dword path, the fused and the stand-alone form agree in bits
+__device__ __forceinline__ float nr_ema_elem(float omd, float p, float e) { return fmaf(omd, __fsub_rn(p, e), e); }
+
+__device__ __forceinline__ f32x4_t nr_ema_elem4(float omd, const f32x4_t& p, const f32x4_t& e) {
+    f32x4_t r;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r[q] = nr_ema_elem(omd, p[q], e[q]);
+    return r;
+}
+
+// elements 4 i .. 4 i + 3 of a 4-byte aligned array: one 16-byte access, or four dword accesses
+__device__ __forceinline__ f32x4_t nr_opt_load4(const float* __restrict__ x, int i, bool vec) {
+    if (vec) return reinterpret_cast<const f32x4_t*>(x)[i];
+    const float* q = x + 4 * i;
+    return f32x4_t{q[0], q[1], q[2], q[3]};
+}
+
+__device__ __forceinline__ void nr_opt_store4(float* __restrict__ x, int i, bool vec, const f32x4_t& val) {
+    if (vec) {
+        reinterpret_cast<f32x4_t*>(x)[i] = val;
+    } else {
+        float* q = x + 4 * i;
+        q[0] = val[0];
+        q[1] = val[1];
+        q[2] = val[2];
+        q[3] = val[3];
+    }
+}
 
 // ---- launch A ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void nr_bertadam_sumsq_kernel(const NrOptimTensor* __restrict__ table, int T, int n_chunks,
@@ -104,7 +153,7 @@ struct NrOptGuardArgs {
     int n_ring;
 };
 
-template <bool GUARDED>
+template <bool GUARDED, bool EMA>
 __global__ __launch_bounds__(NR_OPT_B_THREADS) void nr_bertadam_scalars_kernel(const NrOptimTensor* __restrict__ table, int T,
                                                                               int n_chunks,
                                                                               const NrOptimGroup* __restrict__ groups,
@@ -112,7 +161,7 @@ __global__ __launch_bounds__(NR_OPT_B_THREADS) void nr_bertadam_scalars_kernel(c
                                                                               const float* __restrict__ part,
                                                                               double* __restrict__ tensor_sq,
                                                                               float* __restrict__ scale, float* __restrict__ lr,
-                                                                              NrOptGuardArgs ga) {
+                                                                              NrOptGuardArgs ga, NrEmaState* __restrict__ ema_state) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int t = wave; t < T; t += NR_OPT_B_THREADS / 64) {
         const int c0 = table[t].chunk0;
@@ -157,6 +206,7 @@ __global__ __launch_bounds__(NR_OPT_B_THREADS) void nr_bertadam_scalars_kernel(c
         ga.ring[attempt & (int64_t)(ga.n_ring - 1)] = rec;
     }
     if (bad) return;                                                // no scale, no lr, no counter moves: launch C returns too
+    if (EMA && threadIdx.x == 0) nr_ema_advance(ema_state);         // the guard's owner; a bad step has touched nothing of it
     for (int t = threadIdx.x; t < T; t += NR_OPT_B_THREADS) {
         const NrOptimGroup g = groups[table[t].group];
         double ct = 1.0;
@@ -207,15 +257,21 @@ __device__ __forceinline__ f32x4_t nr_opt_load_g4(const float* __restrict__ g, i
 }
 
 // GUARDED: one uniform load of the word launch B has just written; a skipped step touches none of p, m, v, g
-template <bool GUARDED>
+// EMA: shadows[t] (NULL: tensor t is not averaged) takes nr_ema_elem of the new p with the 1 - d launch B has just written; a
+// shadow joins the 16-byte path when it is aligned, and is read and written as four dwords per lane otherwise, like the gradient
+template <bool GUARDED, bool EMA>
 __global__ __launch_bounds__(256) void nr_bertadam_update_kernel(const NrOptimTensor* __restrict__ table, int T, int n_chunks,
                                                                 const NrOptimGroup* __restrict__ groups,
                                                                 const float* __restrict__ scale, const float* __restrict__ lr,
-                                                                const NrStepGuard* __restrict__ guard) {
+                                                                const NrStepGuard* __restrict__ guard,
+                                                                float* const* __restrict__ shadows,
+                                                                const NrEmaState* __restrict__ ema_state) {
     if (GUARDED) {
         if (guard->skip != 0) return;
     }
     const int tid = threadIdx.x;
+    float omd = 0.f;
+    if (EMA) omd = ema_state->omd;
     for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         const int t = nr_opt_find(table, T, chunk);
         const NrOptimTensor ent = table[t];
@@ -239,12 +295,18 @@ __global__ __launch_bounds__(256) void nr_bertadam_update_kernel(const NrOptimTe
         const float* g = ent.g + e0;
         float* m = ent.m + e0;
         float* v = ent.v + e0;
+        float* sh = nullptr;                                        // this chunk of the tensor's shadow
+        if (EMA) {
+            sh = shadows[t];
+            if (sh) sh += e0;
+        }
         // 16-byte accesses for p, m, v when the three are aligned; the gradient joins them when it is aligned too, and is read
         // as four dwords per lane otherwise (the multi-rank step's gradients are views of one flat buffer at any 4-byte offset,
         // while p, m, v come from the allocator): 24 of the 28 bytes per element stay vector accesses
         if (nr_opt_al16(p) && nr_opt_al16(m) && nr_opt_al16(v)) {
             const int n4 = len >> 2;
             const bool g_vec = nr_opt_al16(g);
+            const bool s_vec = EMA && nr_opt_al16(sh);
             f32x4_t* p4 = reinterpret_cast<f32x4_t*>(p);
             f32x4_t* m4 = reinterpret_cast<f32x4_t*>(m);
             f32x4_t* v4 = reinterpret_cast<f32x4_t*>(v);
@@ -266,6 +328,13 @@ __global__ __launch_bounds__(256) void nr_bertadam_update_kernel(const NrOptimTe
                     m4[i] = xm[j];
                     v4[i] = xv[j];
                 }
+                if (EMA && sh) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int i = tid + 256 * j;
+                        nr_opt_store4(sh, i, s_vec, nr_ema_elem4(omd, xp[j], nr_opt_load4(sh, i, s_vec)));
+                    }
+                }
             } else {
                 for (int i = tid; i < n4; i += 256) {
                     f32x4_t xp = p4[i], xm = m4[i], xv = v4[i];
@@ -274,6 +343,7 @@ __global__ __launch_bounds__(256) void nr_bertadam_update_kernel(const NrOptimTe
                     p4[i] = xp;
                     m4[i] = xm;
                     v4[i] = xv;
+                    if (EMA && sh) nr_opt_store4(sh, i, s_vec, nr_ema_elem4(omd, xp, nr_opt_load4(sh, i, s_vec)));
                 }
                 const int e = 4 * n4 + tid;                        // at most 3 elements left over
                 if (e < len) {
@@ -282,6 +352,7 @@ __global__ __launch_bounds__(256) void nr_bertadam_update_kernel(const NrOptimTe
                     p[e] = xp;
                     m[e] = xm;
                     v[e] = xv;
+                    if (EMA && sh) sh[e] = nr_ema_elem(omd, xp, sh[e]);
                 }
             }
         } else {
@@ -291,6 +362,83 @@ __global__ __launch_bounds__(256) void nr_bertadam_update_kernel(const NrOptimTe
                 p[e] = xp;
                 m[e] = xm;
                 v[e] = xv;
+                if (EMA && sh) sh[e] = nr_ema_elem(omd, xp, sh[e]);
+            }
+        }
+    }
+}
+
+// ---- weight EMA, stand-alone ----------------------------------------------------------------------------------------------------
+// A launch of its own: no workgroup of the streaming kernel can then read the state after another has changed it
+__global__ void nr_ema_state_kernel(NrEmaState* __restrict__ st) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) nr_ema_advance(st);
+}
+
+// SWAP: exchange the contents of p and shadow (bit-exact, no state); else shadow = nr_ema_elem(omd, p, shadow), p only read
+template <bool SWAP>
+__global__ __launch_bounds__(256) void nr_ema_stream_kernel(const NrEmaTensor* __restrict__ table, int T, int n_chunks,
+                                                           const NrEmaState* __restrict__ st) {
+    const int tid = threadIdx.x;
+    float omd = 0.f;
+    if (!SWAP) omd = st->omd;
+    for (int chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const int t = nr_opt_find(table, T, chunk);
+        const NrEmaTensor ent = table[t];
+        const long long e0 = (long long)(chunk - ent.chunk0) * NR_OPT_CHUNK;
+        const long long left = ent.n - e0;
+        const int len = left < NR_OPT_CHUNK ? (int)left : NR_OPT_CHUNK;
+        float* p = ent.p + e0;
+        float* sh = ent.ema + e0;
+        if (nr_opt_al16(p) && nr_opt_al16(sh)) {
+            const int n4 = len >> 2;
+            f32x4_t* p4 = reinterpret_cast<f32x4_t*>(p);
+            f32x4_t* s4 = reinterpret_cast<f32x4_t*>(sh);
+            if (n4 == NR_OPT_CHUNK / 4) {                           // a whole chunk: all eight 16-byte loads in flight at once
+                f32x4_t xp[4], xs[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    xp[j] = p4[tid + 256 * j];
+                    xs[j] = s4[tid + 256 * j];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (SWAP) {
+                        p4[tid + 256 * j] = xs[j];
+                        s4[tid + 256 * j] = xp[j];
+                    } else {
+                        s4[tid + 256 * j] = nr_ema_elem4(omd, xp[j], xs[j]);
+                    }
+                }
+                continue;
+            }
+            for (int i = tid; i < n4; i += 256) {
+                const f32x4_t xp = p4[i], xs = s4[i];
+                if (SWAP) {
+                    p4[i] = xs;
+                    s4[i] = xp;
+                } else {
+                    s4[i] = nr_ema_elem4(omd, xp, xs);
+                }
+            }
+            const int e = 4 * n4 + tid;                            // at most 3 elements left over
+            if (e < len) {
+                const float xp = p[e], xs = sh[e];
+                if (SWAP) {
+                    p[e] = xs;
+                    sh[e] = xp;
+                } else {
+                    sh[e] = nr_ema_elem(omd, xp, xs);
+                }
+            }
+        } else {
+            for (int e = tid; e < len; e += 256) {
+                const float xp = p[e], xs = sh[e];
+                if (SWAP) {
+                    p[e] = xs;
+                    sh[e] = xp;
+                } else {
+                    sh[e] = nr_ema_elem(omd, xp, xs);
+                }
             }
         }
     }
@@ -330,7 +478,7 @@ extern "C" size_t nr_bertadam_workspace_bytes(int T, int n_chunks) {
 }
 
 static int nr_opt_launch(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, float global_max_norm,
-                         void* workspace, const NrOptGuardArgs* ga, void* stream) {
+                         void* workspace, const NrOptGuardArgs* ga, float* const* ema, NrEmaState* es, void* stream) {
     char* ws = static_cast<char*>(workspace);
     double* tensor_sq = reinterpret_cast<double*>(ws);
     ws += nr_opt_round256((size_t)T * sizeof(double));
@@ -345,22 +493,28 @@ static int nr_opt_launch(const NrOptimTensor* table, int T, int n_chunks, const 
         hipLaunchKernelGGL(nr_bertadam_sumsq_kernel, dim3(grid), dim3(256), 0, st, table, T, n_chunks, part);
         NR_LAUNCH_CHECK();
     }
-    if (ga)
-        hipLaunchKernelGGL(nr_bertadam_scalars_kernel<true>, dim3(1), dim3(NR_OPT_B_THREADS), 0, st, table, T, n_chunks, groups,
-                           global_max_norm, part, tensor_sq, scale, lr, *ga);
-    else
-        hipLaunchKernelGGL(nr_bertadam_scalars_kernel<false>, dim3(1), dim3(NR_OPT_B_THREADS), 0, st, table, T, n_chunks, groups,
-                           global_max_norm, part, tensor_sq, scale, lr, NrOptGuardArgs{});
+    const NrOptGuardArgs gargs = ga ? *ga : NrOptGuardArgs{};
+    const NrStepGuard* guard = ga ? ga->guard : nullptr;
+#define NR_OPT_LAUNCH_B(GUARDED, EMA)                                                                                          \
+    hipLaunchKernelGGL((nr_bertadam_scalars_kernel<GUARDED, EMA>), dim3(1), dim3(NR_OPT_B_THREADS), 0, st, table, T, n_chunks, \
+                       groups, global_max_norm, part, tensor_sq, scale, lr, gargs, es)
+#define NR_OPT_LAUNCH_C(GUARDED, EMA)                                                                                          \
+    hipLaunchKernelGGL((nr_bertadam_update_kernel<GUARDED, EMA>), dim3(grid), dim3(256), 0, st, table, T, n_chunks, groups,    \
+                       scale, lr, guard, ema, (const NrEmaState*)es)
+    if (ga && ema) NR_OPT_LAUNCH_B(true, true);
+    else if (ga) NR_OPT_LAUNCH_B(true, false);
+    else if (ema) NR_OPT_LAUNCH_B(false, true);
+    else NR_OPT_LAUNCH_B(false, false);
     NR_LAUNCH_CHECK();
     if (grid > 0) {
-        if (ga)
-            hipLaunchKernelGGL(nr_bertadam_update_kernel<true>, dim3(grid), dim3(256), 0, st, table, T, n_chunks, groups, scale,
-                               lr, (const NrStepGuard*)ga->guard);
-        else
-            hipLaunchKernelGGL(nr_bertadam_update_kernel<false>, dim3(grid), dim3(256), 0, st, table, T, n_chunks, groups, scale,
-                               lr, (const NrStepGuard*)nullptr);
+        if (ga && ema) NR_OPT_LAUNCH_C(true, true);
+        else if (ga) NR_OPT_LAUNCH_C(true, false);
+        else if (ema) NR_OPT_LAUNCH_C(false, true);
+        else NR_OPT_LAUNCH_C(false, false);
         NR_LAUNCH_CHECK();
     }
+#undef NR_OPT_LAUNCH_B
+#undef NR_OPT_LAUNCH_C
     return NR_OK;
 }
 
@@ -369,7 +523,7 @@ extern "C" int nr_bertadam_step(const NrOptimTensor* table, int T, int n_chunks,
     if (T < 0 || n_chunks < 0 || G < 0 || global_max_norm != global_max_norm) return NR_EINVAL;
     if (T == 0) return n_chunks == 0 ? NR_OK : NR_EINVAL;
     if (!table || !groups || !workspace || G == 0 || ((uintptr_t)workspace & 7) != 0) return NR_EINVAL;
-    return nr_opt_launch(table, T, n_chunks, groups, global_max_norm, workspace, nullptr, stream);
+    return nr_opt_launch(table, T, n_chunks, groups, global_max_norm, workspace, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int nr_bertadam_step_guarded(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, int G,
@@ -383,5 +537,67 @@ extern "C" int nr_bertadam_step_guarded(const NrOptimTensor* table, int T, int n
     if (T == 0) return n_chunks == 0 ? NR_OK : NR_EINVAL;            // nothing to update: no launch, not an attempt
     if (!table || !groups || !workspace || G == 0 || ((uintptr_t)workspace & 7) != 0) return NR_EINVAL;
     const NrOptGuardArgs ga{guard, losses, n_losses, ring, n_ring};
-    return nr_opt_launch(table, T, n_chunks, groups, global_max_norm, workspace, &ga, stream);
+    return nr_opt_launch(table, T, n_chunks, groups, global_max_norm, workspace, &ga, nullptr, nullptr, stream);
+}
+
+// ---- weight EMA: host -------------------------------------------------------------------------------------------------------------
+extern "C" int nr_bertadam_step_ema(const NrOptimTensor* table, int T, int n_chunks, const NrOptimGroup* groups, int G,
+                                    float global_max_norm, void* workspace, NrStepGuard* guard, const float* losses, int n_losses,
+                                    NrStepRecord* ring, int n_ring, float* const* ema, NrEmaState* state, void* stream) {
+    if (T < 0 || n_chunks < 0 || G < 0 || global_max_norm != global_max_norm) return NR_EINVAL;
+    if (!ema || !state || ((uintptr_t)ema & 7) != 0 || ((uintptr_t)state & 7) != 0) return NR_EINVAL;
+    if (guard) {
+        if (!ring || ((uintptr_t)guard & 7) != 0 || ((uintptr_t)ring & 7) != 0) return NR_EINVAL;
+        if (n_ring < 1 || n_ring > NR_GUARD_MAX_RING || (n_ring & (n_ring - 1)) != 0) return NR_EINVAL;
+        if (n_losses < 0 || n_losses > NR_GUARD_MAX_LOSSES || (n_losses > 0 && (!losses || ((uintptr_t)losses & 3) != 0)))
+            return NR_EINVAL;
+    }
+    if (T == 0) return n_chunks == 0 ? NR_OK : NR_EINVAL;            // nothing to update: no launch, no update counted
+    if (!table || !groups || !workspace || G == 0 || ((uintptr_t)workspace & 7) != 0) return NR_EINVAL;
+    const NrOptGuardArgs ga{guard, losses, n_losses, ring, n_ring};
+    return nr_opt_launch(table, T, n_chunks, groups, global_max_norm, workspace, guard ? &ga : nullptr, ema, state, stream);
+}
+
+extern "C" int nr_ema_plan(NrEmaTensor* entries, int T, const NrEmaState* state, int* n_chunks) {
+    if (!n_chunks || !state || T < 0 || (T > 0 && !entries)) return NR_EINVAL;
+    if (!(state->decay >= 0.0 && state->decay < 1.0) || state->updates < 0) return NR_EINVAL;       // (a NaN decay fails both)
+    long long chunks = 0;
+    for (int t = 0; t < T; ++t) {
+        NrEmaTensor& e = entries[t];
+        if (e.n < 0 || (e.n > 0 && (!e.p || !e.ema))) return NR_EINVAL;
+        if ((((uintptr_t)e.p | (uintptr_t)e.ema) & 3) != 0) return NR_EINVAL;
+        e.chunk0 = (int32_t)chunks;
+        chunks += (e.n + NR_OPT_CHUNK - 1) / NR_OPT_CHUNK;
+        if (chunks > 0x7fffffffLL) return NR_EUNSUPPORTED;
+    }
+    *n_chunks = (int)chunks;
+    return NR_OK;
+}
+
+extern "C" int nr_ema_update(const NrEmaTensor* table, int T, int n_chunks, NrEmaState* state, void* stream) {
+    if (T < 0 || n_chunks < 0 || !state || ((uintptr_t)state & 7) != 0) return NR_EINVAL;
+    if (T == 0) return n_chunks == 0 ? NR_OK : NR_EINVAL;            // nothing to average: no launch, no update counted
+    if (!table || ((uintptr_t)table & 7) != 0) return NR_EINVAL;
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nr_ema_state_kernel, dim3(1), dim3(1), 0, st, state);
+    NR_LAUNCH_CHECK();
+    const unsigned grid = (unsigned)(n_chunks < NR_OPT_MAX_GRID ? n_chunks : NR_OPT_MAX_GRID);
+    if (grid > 0) {
+        hipLaunchKernelGGL(nr_ema_stream_kernel<false>, dim3(grid), dim3(256), 0, st, table, T, n_chunks, (const NrEmaState*)state);
+        NR_LAUNCH_CHECK();
+    }
+    return NR_OK;
+}
+
+extern "C" int nr_ema_swap(const NrEmaTensor* table, int T, int n_chunks, void* stream) {
+    if (T < 0 || n_chunks < 0) return NR_EINVAL;
+    if (T == 0) return n_chunks == 0 ? NR_OK : NR_EINVAL;
+    if (!table || ((uintptr_t)table & 7) != 0) return NR_EINVAL;
+    const unsigned grid = (unsigned)(n_chunks < NR_OPT_MAX_GRID ? n_chunks : NR_OPT_MAX_GRID);
+    if (grid > 0) {
+        hipLaunchKernelGGL(nr_ema_stream_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, table, T, n_chunks,
+                           (const NrEmaState*)nullptr);
+        NR_LAUNCH_CHECK();
+    }
+    return NR_OK;
 }

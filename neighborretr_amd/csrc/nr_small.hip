@@ -16,7 +16,7 @@ extern "C" size_t nr_struct_size(const char* name) {
     NR_SIZE_OF(NrLinearProblem); NR_SIZE_OF(NrCtmAttnBwdDesc); NR_SIZE_OF(NrCtmMidBwdDesc); NR_SIZE_OF(NrSimBwdItem);
     NR_SIZE_OF(NrSimBwdOperand); NR_SIZE_OF(NrSlabSum); NR_SIZE_OF(NrPoolWSrc); NR_SIZE_OF(NrPoolWJob); NR_SIZE_OF(NrBankAbsorbDesc);
     NR_SIZE_OF(NrTokenWeightsProblem); NR_SIZE_OF(NrOptimTensor); NR_SIZE_OF(NrOptimGroup);
-    NR_SIZE_OF(NrStepGuard); NR_SIZE_OF(NrStepRecord);
+    NR_SIZE_OF(NrStepGuard); NR_SIZE_OF(NrStepRecord); NR_SIZE_OF(NrEmaState); NR_SIZE_OF(NrEmaTensor);
 #undef NR_SIZE_OF
     return 0;
 }

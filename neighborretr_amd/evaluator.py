@@ -1204,8 +1204,8 @@ def sharded_metrics_with_mutual_proximity(model, text_feat, video_feat, text_mas
 def correction_from_args(args, model):
     """What the command-line flags ask of the evaluation -> (correction or None, the keyword arguments of sharded_evaluation:
     hubness_k, the bootstrap triple, ir and, when asked for, permutation and its seed), everything checked before any work: the
-    values, that at most one correction is chosen, that a permutation test has something to compare (a correction, or
-    args.compare_model), and that a correction that needs a querybank finds the model's memory bank filled."""
+    values, that at most one correction is chosen, that a permutation test has something to compare (a correction,
+    args.compare_model, or the weight average of args.ema_decay), and that a correction that needs a querybank finds the model's memory bank filled."""
     kw = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
               bootstrap_level=getattr(args, "bootstrap_level", 0.95))
     _check_bootstrap(kw["bootstrap"], kw["bootstrap_seed"], kw["bootstrap_level"])
@@ -1229,9 +1229,9 @@ def correction_from_args(args, model):
         correction = mutual_proximity_correction(mutual_proximity, bool(int(getattr(args, "mutual_proximity_bank", 0) or 0)))
     kw["hubness_k"] = _check_hubness_k(getattr(args, "hubness_k", 0))
     if perm is not None:
-        if correction is None and not getattr(args, "compare_model", None):
-            raise ValueError("permutation needs a correction (test_norm, local_scaling, mutual_proximity) or compare_model: there is "
-                             "nothing to compare")
+        if correction is None and not getattr(args, "compare_model", None) and not getattr(args, "ema_decay", 0):
+            raise ValueError("permutation needs a correction (test_norm, local_scaling, mutual_proximity) or compare_model or "
+                             "ema_decay: there is nothing to compare")
         kw.update(permutation=perm[0], permutation_seed=perm[1])
     if correction is not None and correction.needs_bank:
         _querybank(model, None, model.mb_feat_t.device)         # checked where it lies: nothing is copied

@@ -138,7 +138,17 @@ class StepRecord(ctypes.Structure):
                 ("n_losses", ctypes.c_int32), ("losses", _F * 8)]
 
 
-STRUCTS = {"NrOptimTensor": OptimTensor, "NrOptimGroup": OptimGroup, "NrStepGuard": StepGuard, "NrStepRecord": StepRecord, "NrTokenWeightsProblem": TokenWeightsProblem, "NrBankAbsorbDesc": BankAbsorbDesc, "NrCtmStageDesc": CtmStageDesc, "NrLocalLevelProblem": LocalLevelProblem, "NrSplitItem": SplitItem,
+class EmaState(ctypes.Structure):
+    """NrEmaState of include/nr_hip.h."""
+    _fields_ = [("decay", ctypes.c_double), ("updates", ctypes.c_int64), ("warmup", ctypes.c_int32), ("omd", _F)]
+
+
+class EmaTensor(ctypes.Structure):
+    """NrEmaTensor of include/nr_hip.h."""
+    _fields_ = [("p", _P), ("ema", _P), ("n", ctypes.c_int64), ("chunk0", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+STRUCTS = {"NrEmaState": EmaState, "NrEmaTensor": EmaTensor, "NrOptimTensor": OptimTensor, "NrOptimGroup": OptimGroup, "NrStepGuard": StepGuard, "NrStepRecord": StepRecord, "NrTokenWeightsProblem": TokenWeightsProblem, "NrBankAbsorbDesc": BankAbsorbDesc, "NrCtmStageDesc": CtmStageDesc, "NrLocalLevelProblem": LocalLevelProblem, "NrSplitItem": SplitItem,
            "NrColsumItem": ColsumItem, "NrLinearProblem": LinearProblem, "NrCtmAttnBwdDesc": CtmAttnBwdDesc,
            "NrCtmMidBwdDesc": CtmMidBwdDesc, "NrSimBwdItem": SimBwdItem, "NrSimBwdOperand": SimBwdOperand, "NrSlabSum": SlabSum,
            "NrPoolWSrc": PoolWSrc, "NrPoolWJob": PoolWJob}
@@ -276,6 +286,10 @@ _SIGNATURES = {
     "nr_bertadam_workspace_bytes": ([_I, _I], _Z),
     "nr_bertadam_step": ([_P, _I, _I, _P, _I, _F, _P, _P], _I),
     "nr_bertadam_step_guarded": ([_P, _I, _I, _P, _I, _F, _P, _P, _P, _I, _P, _I, _P], _I),
+    "nr_bertadam_step_ema": ([_P, _I, _I, _P, _I, _F, _P, _P, _P, _I, _P, _I, _P, _P, _P], _I),
+    "nr_ema_plan": ([ctypes.POINTER(EmaTensor), _I, ctypes.POINTER(EmaState), ctypes.POINTER(_I)], _I),
+    "nr_ema_update": ([_P, _I, _I, _P, _P], _I),
+    "nr_ema_swap": ([_P, _I, _I, _P], _I),
 }
 TOPK_MAX = 128                               # largest k of the top-k entry points
 HUBNORM_IS, HUBNORM_DSL = 0, 1               # nr_hubnorm_apply modes

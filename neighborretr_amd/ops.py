@@ -1568,3 +1568,59 @@ def bertadam_step_guarded(groups_dev, n_groups, table_dev, n_tensors, n_chunks, 
              int(n_chunks), hip.ptr(groups_dev, torch.uint8), int(n_groups), ctypes.c_float(gmn), hip.ptr(workspace, torch.uint8),
              hip.ptr(guard, torch.uint8), hip.ptr(losses, torch.float32, allow_none=True), n_losses, hip.ptr(ring, torch.uint8),
              int(n_ring), hip.stream_ptr())
+
+
+def bertadam_step_ema(groups_dev, n_groups, table_dev, n_tensors, n_chunks, workspace, shadows_dev, state, guard=None, ring=None,
+                      global_max_norm=None, table_offset=0, shadows_offset=0, losses=None):
+    """bertadam_step / bertadam_step_guarded (guard and ring given) with the weight EMA inside (nr_bertadam_step_ema).
+    shadows_dev: uint8 device tensor holding, `shadows_offset` bytes in, n_tensors 8-byte pointers parallel to the table (0: that
+    tensor is not averaged); state: uint8 device tensor holding one hip.EmaState."""
+    import ctypes
+    if workspace.numel() < bertadam_workspace_bytes(n_tensors, n_chunks):
+        raise hip.NrHipError("bertadam_step_ema: workspace too small")
+    if state.numel() < ctypes.sizeof(hip.EmaState) or shadows_dev.numel() < int(shadows_offset) + 8 * int(n_tensors):
+        raise hip.NrHipError("bertadam_step_ema: state / shadows do not have the size of NrEmaState / n_tensors pointers")
+    n_ring = n_losses = 0
+    if guard is not None:
+        rec = ctypes.sizeof(hip.StepRecord)
+        n_ring = ring.numel() // rec
+        if guard.numel() < ctypes.sizeof(hip.StepGuard) or n_ring * rec != ring.numel():
+            raise hip.NrHipError("bertadam_step_ema: guard / ring do not have the size of NrStepGuard / a whole number of NrStepRecord")
+        n_losses = 0 if losses is None else int(losses.numel())
+    else:
+        losses = None
+    gmn = -1.0 if global_max_norm is None else float(global_max_norm)
+    hip.call("nr_bertadam_step_ema", ctypes.c_void_p(hip.ptr(table_dev, torch.uint8).value + int(table_offset)), int(n_tensors),
+             int(n_chunks), hip.ptr(groups_dev, torch.uint8), int(n_groups), ctypes.c_float(gmn), hip.ptr(workspace, torch.uint8),
+             hip.ptr(guard, torch.uint8, allow_none=True), hip.ptr(losses, torch.float32, allow_none=True), n_losses,
+             hip.ptr(ring, torch.uint8, allow_none=True) if guard is not None else None, int(n_ring),
+             ctypes.c_void_p(hip.ptr(shadows_dev, torch.uint8).value + int(shadows_offset)), hip.ptr(state, torch.uint8),
+             hip.stream_ptr())
+
+
+def ema_plan(entries, state):
+    """Host-only check of a weight-EMA table and state before their upload (nr_ema_plan): `entries` a ctypes array of
+    hip.EmaTensor, `state` a hip.EmaState.  Writes every entry's chunk0 -> the number of chunks; raises on a null / misaligned
+    pointer, a negative count or a decay outside [0, 1)."""
+    import ctypes
+    n_chunks = ctypes.c_int(0)
+    hip._check("nr_ema_plan", hip.lib().nr_ema_plan(entries, len(entries), ctypes.byref(state), ctypes.byref(n_chunks)))
+    return int(n_chunks.value)
+
+
+def ema_update(table_dev, n_tensors, n_chunks, state):
+    """One stand-alone update of every shadow of the uploaded hip.EmaTensor table (nr_ema_update: two launches on the current
+    stream); state: uint8 device tensor holding one hip.EmaState."""
+    import ctypes
+    if state.numel() < ctypes.sizeof(hip.EmaState) or table_dev.numel() < int(n_tensors) * ctypes.sizeof(hip.EmaTensor):
+        raise hip.NrHipError("ema_update: state / table do not have the size of NrEmaState / n_tensors NrEmaTensor")
+    hip.call("nr_ema_update", hip.ptr(table_dev, torch.uint8), int(n_tensors), int(n_chunks), hip.ptr(state, torch.uint8),
+             hip.stream_ptr())
+
+
+def ema_swap(table_dev, n_tensors, n_chunks):
+    """Exchanges the contents of every (parameter, shadow) pair of the uploaded hip.EmaTensor table in place (nr_ema_swap)."""
+    import ctypes
+    if table_dev.numel() < int(n_tensors) * ctypes.sizeof(hip.EmaTensor):
+        raise hip.NrHipError("ema_swap: the table does not hold n_tensors NrEmaTensor")
+    hip.call("nr_ema_swap", hip.ptr(table_dev, torch.uint8), int(n_tensors), int(n_chunks), hip.stream_ptr())

@@ -21,7 +21,13 @@ gradients is not finite -- a NaN, an infinity, or an entry whose square overflow
 step counter, decided on the device, so it works inside a replayed graph too.  The host cannot know the outcome without a
 synchronisation: its step mirror keeps counting every step and is corrected from the device counters (one small blocking copy)
 whenever something reads it -- get_lr(), group_lr(), state_dict(), guard_stats(), records().
+
+`WeightEma` keeps an exponential moving average of the weights in fp32 shadows with its decay, warm-up and
+count of updates in a device-resident state.  It has two drivers, one per average: attached to a BertAdam (`ema=`), launch C of
+the step averages every tensor it updates, under the guard and inside a captured step included; on its own, `update()` averages
+every tensor in two launches.  A tensor that never receives a gradient equals its shadow either way.
 """
+import contextlib
 import ctypes
 import math
 
@@ -63,6 +69,174 @@ assert RECORD_DTYPE.itemsize == ctypes.sizeof(hip.StepRecord)
 _GUARD_FIELDS = ("attempts", "skipped", "consecutive", "max_consecutive", "last_skipped")
 
 
+def ema_decay_at(decay, warmup, n):
+    """The decay update number n (0-based) uses: min(decay, (1 + n) / (10 + n)) under warm-up, else decay."""
+    return min(float(decay), (1.0 + n) / (10.0 + n)) if warmup else float(decay)
+
+
+class WeightEma:
+    """Exponential moving average of parameters: e += (1 - d) (p - e) after every update, d = ema_decay_at(decay, warmup, n)
+    with n the updates so far (counted on the device: a step the non-finite guard skipped is no update).
+
+    params: an iterable of parameters or of (name, parameter) pairs as from named_parameters().  Every parameter gets one
+    contiguous fp32 shadow, a copy of it at construction.  The kernels are HIP: parameters that are not on the GPU, not fp32 or
+    not contiguous raise NrHipError.
+
+    Attached to a BertAdam (BertAdam(..., ema=this)) a tensor is averaged in the steps that update it; stand-alone every tensor
+    is averaged on every update()."""
+
+    def __init__(self, params, decay=0.999, warmup=True):
+        for name, value, ok, wanted in (("decay", decay, lambda x: isinstance(x, (int, float)) and 0.0 <= x < 1.0, "in [0, 1)"),
+                                        ("warmup", warmup, lambda x: isinstance(x, (bool, int)) and x in (0, 1),
+                                         "False / True (or 0 / 1)")):
+            if not ok(value):
+                raise ValueError(f"WeightEma: {name} = {value!r} is not accepted, it must be {wanted}")
+        items = list(params)
+        if items and isinstance(items[0], (tuple, list)):
+            self.names, self.params = [str(n) for n, _ in items], [p for _, p in items]
+        else:
+            self.names, self.params = list(range(len(items))), items
+        if not self.params:
+            raise ValueError("WeightEma has no parameters")
+        if len({id(p) for p in self.params}) != len(self.params) or len(set(self.names)) != len(self.names):
+            raise ValueError("WeightEma: a parameter or a name is given twice")
+        for p in self.params:
+            if not isinstance(p, torch.Tensor):
+                raise TypeError(f"WeightEma takes parameters or (name, parameter) pairs, got {type(p).__name__}")
+            if not p.is_cuda:
+                raise hip.NrHipError(f"WeightEma: a parameter of shape {tuple(p.shape)} lives on '{p.device}', not on a GPU; the "
+                                     "average runs in HIP kernels and has no CPU fallback")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise hip.NrHipError(f"WeightEma: parameters must be contiguous float32 tensors, got {p.dtype} "
+                                     f"{'contiguous' if p.is_contiguous() else 'non-contiguous'} of shape {tuple(p.shape)}")
+        self.device = self.params[0].device
+        if any(p.device != self.device for p in self.params):
+            raise hip.NrHipError("WeightEma: all parameters must live on one device")
+        hip.lib()
+        self.decay, self.warmup = float(decay), bool(warmup)
+        with torch.no_grad():
+            self.shadows = [p.detach().clone(memory_format=torch.contiguous_format) for p in self.params]
+        self._shadow_of = {id(p): e for p, e in zip(self.params, self.shadows)}
+        self._state = torch.zeros(ctypes.sizeof(hip.EmaState), dtype=torch.uint8, device=self.device)
+        self._table = torch.empty(len(self.params) * ctypes.sizeof(hip.EmaTensor), dtype=torch.uint8, device=self.device)
+        self._key = None
+        self._driver = None       # the BertAdam this average is attached to
+        self._applied = False
+        self._write_state(0)
+        self._upload()
+
+    # ---- internals ----------------------------------------------------------------------------------------------------------
+    def _write_state(self, updates):
+        state = hip.EmaState(decay=self.decay, updates=int(updates), warmup=int(self.warmup), omd=0.0)
+        if updates > 0:
+            state.omd = 1.0 - ema_decay_at(self.decay, self.warmup, updates - 1)
+        self._state.copy_(torch.frombuffer(bytearray(bytes(state)), dtype=torch.uint8))
+
+    def _read_state(self):
+        return hip.EmaState.from_buffer_copy(self._state.cpu().numpy().tobytes())
+
+    def _upload(self):
+        """The (parameter, shadow) table on the device, checked by nr_ema_plan; again only when a parameter has moved."""
+        key = tuple(p.data_ptr() for p in self.params)
+        if key == self._key:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("WeightEma: a parameter's storage has moved since the table was uploaded; call update() or swap() "
+                               "once outside the graph capture first")
+        entries = (hip.EmaTensor * len(self.params))()
+        for ent, p, e in zip(entries, self.params, self.shadows):
+            ent.p, ent.ema, ent.n = p.data_ptr(), e.data_ptr(), p.numel()
+        self._n_chunks = ops.ema_plan(entries, hip.EmaState(decay=self.decay, updates=0, warmup=int(self.warmup)))
+        self._table.copy_(torch.frombuffer(bytearray(bytes(entries)), dtype=torch.uint8))
+        self._key = key
+
+    def shadow(self, p):
+        """The shadow of parameter p, None when p is not averaged."""
+        return self._shadow_of.get(id(p))
+
+    # ---- the interface --------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def update(self):
+        """The stand-alone form: every shadow takes one update, two launches on the current stream, no allocation: capturable."""
+        if self._driver is not None:
+            raise RuntimeError("WeightEma.update(): this average is attached to an optimizer, whose step updates it -- there is "
+                               "one driver per average")
+        if self._applied:
+            raise RuntimeError("WeightEma.update() inside applied(): the parameters hold the average now")
+        self._upload()
+        ops.ema_update(self._table, len(self.params), self._n_chunks, self._state)
+
+    @torch.no_grad()
+    def swap(self):
+        """Exchanges the contents of parameters and shadows in place (a captured step has the addresses baked in) and moves the
+        parameters' version counters: modeling.scorer_weights / cluster_fused.build_stage_weights key their bf16 splits on
+        them and would serve the splits of the other weights otherwise."""
+        self._upload()
+        ops.ema_swap(self._table, len(self.params), self._n_chunks)
+        torch.autograd.graph.increment_version(self.params)
+
+    @contextlib.contextmanager
+    def applied(self):
+        """with ema.applied(): the parameters hold the average (evaluate here); swapped back on exit, also when the body raises."""
+        if self._applied:
+            raise RuntimeError("WeightEma.applied() does not nest")
+        self.swap()
+        self._applied = True
+        try:
+            yield self
+        finally:
+            self._applied = False
+            self.swap()
+
+    def updates(self):
+        """The number of updates so far, from the device (a blocking copy)."""
+        return int(self._read_state().updates)
+
+    def last_decay(self):
+        """The decay the last update used (None before the first), from the device's count (a blocking copy)."""
+        n = self.updates()
+        return ema_decay_at(self.decay, self.warmup, n - 1) if n > 0 else None
+
+    def state_dict(self):
+        return dict(decay=self.decay, warmup=self.warmup, updates=self.updates(),
+                    shadows={name: e.detach().clone() for name, e in zip(self.names, self.shadows)})
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """Values go into the existing shadows and device state: a captured step holds their addresses."""
+        shadows = state_dict["shadows"]
+        if set(shadows) != set(self.names):
+            raise KeyError(f"WeightEma.load_state_dict: the shadows' names differ: {sorted(map(str, set(shadows) ^ set(self.names)))[:8]}")
+        decay, warmup, updates = float(state_dict["decay"]), state_dict["warmup"], int(state_dict["updates"])
+        if not 0.0 <= decay < 1.0 or warmup not in (0, 1) or updates < 0:
+            raise ValueError("WeightEma.load_state_dict: decay must lie in [0, 1), warmup be False / True and updates be >= 0")
+        for name, e in zip(self.names, self.shadows):
+            src = shadows[name]
+            if tuple(src.shape) != tuple(e.shape):
+                raise ValueError(f"WeightEma.load_state_dict: shadow {name!r} has shape {tuple(src.shape)}, not {tuple(e.shape)}")
+            e.copy_(src)
+        self.decay, self.warmup = decay, bool(warmup)
+        self._write_state(updates)
+
+    def model_state_dict(self, model):
+        """model.state_dict() with every averaged parameter replaced by a clone of its shadow; buffers and the parameters the
+        average does not know stay as the model has them.  The keys are the model's: --init_model loads it unchanged."""
+        sd = model.state_dict()
+        for name, p in model.named_parameters():
+            e = self._shadow_of.get(id(p))
+            if e is not None and name in sd:
+                sd[name] = e.detach().clone()
+        return sd
+
+    def sha256(self):
+        """Digest over the shadows' bytes in order (a blocking copy): ranks that agree print the same one."""
+        import hashlib
+        digest = hashlib.sha256()
+        for e in self.shadows:
+            digest.update(e.detach().cpu().numpy().tobytes())
+        return digest.hexdigest()
+
+
 class BertAdam(Optimizer):
     """Adam without bias correction, with decoupled weight decay, a per-tensor gradient clip and a built-in warm-up schedule.
 
@@ -70,12 +244,15 @@ class BertAdam(Optimizer):
       global_max_norm  None / <= 0: off; else the trainer's clip_grad_norm_(parameters, global_max_norm) fused into the step;
       clamp_max        {parameter: upper bound} applied after the update (the trainer's logit-scale clamp);
       skip_nonfinite   True: a step whose gradients are not all finite is skipped on the device (module docstring);
-      record_ring      with skip_nonfinite, the number of per-step records kept for records(): a power of two in [1, 4096].
+      record_ring      with skip_nonfinite, the number of per-step records kept for records(): a power of two in [1, 4096];
+      ema              a WeightEma: launch C averages every tensor it updates into its shadow (nr_bertadam_step_ema), guarded
+                       or not; a parameter the average does not know is left out.  The optimizer is then the average's driver.
     `state[p] = {'step', 'next_m', 'next_v'}` as in the reference, so state dicts move between the two implementations; 'step'
     is the host's mirror of the device counter."""
 
     def __init__(self, params, lr=_REQUIRED, warmup=-1, t_total=-1, schedule="warmup_linear", b1=0.9, b2=0.999, e=1e-6,
-                 weight_decay=0.01, max_grad_norm=1.0, global_max_norm=None, clamp_max=None, skip_nonfinite=False, record_ring=256):
+                 weight_decay=0.01, max_grad_norm=1.0, global_max_norm=None, clamp_max=None, skip_nonfinite=False, record_ring=256,
+                 ema=None):
         if lr is _REQUIRED:
             raise ValueError("BertAdam needs a learning rate")
         unit = lambda x: 0.0 <= x < 1.0                                           # noqa: E731
@@ -93,6 +270,11 @@ class BertAdam(Optimizer):
                                          and x & (x - 1) == 0, f"a power of two in [1, {hip.GUARD_MAX_RING}]")):
             if not ok(value):
                 raise ValueError(f"BertAdam: {name} = {value!r} is not accepted, it must be {wanted}")
+        if ema is not None:
+            if not isinstance(ema, WeightEma):
+                raise TypeError(f"BertAdam: ema takes a WeightEma, got {type(ema).__name__}")
+            if ema._driver is not None:
+                raise ValueError("BertAdam: this WeightEma is attached to another optimizer already")
         defaults = dict(lr=lr, schedule=schedule, warmup=warmup, t_total=t_total, b1=b1, b2=b2, e=e, weight_decay=weight_decay,
                         max_grad_norm=max_grad_norm)
         super().__init__(params, defaults)
@@ -104,6 +286,9 @@ class BertAdam(Optimizer):
                 raise ValueError("clamp_max names a tensor that is not one of the optimizer's parameters")
             self.clamp_max[id(p)] = float(bound)
         self.skip_nonfinite, self.record_ring = bool(skip_nonfinite), int(record_ring)
+        self.ema = ema
+        if ema is not None:
+            ema._driver = self
         self._watched = None      # watch_losses(): the device tensor whose values go into every step's record
         self._dirty = False       # skip_nonfinite: the step mirror has counted steps the device may have skipped
         self._dev = None          # device-side state: created by the first step() / prepare()
@@ -265,7 +450,13 @@ class BertAdam(Optimizer):
         else:
             launch = dev["launch"]
         buf, T, n_chunks = launch
-        if self.skip_nonfinite:
+        if self.ema is not None:
+            guarded = self.skip_nonfinite
+            ops.bertadam_step_ema(buf, len(self.param_groups), buf, T, n_chunks, dev["workspace"], buf, self.ema._state,
+                                  guard=dev["guard"] if guarded else None, ring=dev["ring_records"] if guarded else None,
+                                  global_max_norm=self.global_max_norm, table_offset=dev["table_off"],
+                                  shadows_offset=dev["ema_off"], losses=self._watched if guarded else None)
+        elif self.skip_nonfinite:
             ops.bertadam_step_guarded(buf, len(self.param_groups), buf, T, n_chunks, dev["workspace"], dev["guard"],
                                       dev["ring_records"], self.global_max_norm, table_offset=dev["table_off"],
                                       losses=self._watched)
@@ -305,17 +496,23 @@ class BertAdam(Optimizer):
         device = self._all[0].device
         if any(p.device != device for p in self._all):
             raise hip.NrHipError("BertAdam: all parameters must live on one device")
+        if self.ema is not None and self.ema.device != device:
+            raise hip.NrHipError("BertAdam: the WeightEma lives on another device than the parameters")
         hip.lib()
         N, G = len(self._all), len(self.param_groups)
         self._index = {id(p): i for i, p in enumerate(self._all)}
         self._group_of = [gi for gi, g in enumerate(self.param_groups) for _ in g["params"]]
         table_off = (G * _GROUP + 63) // 64 * 64
         nbytes = table_off + N * _ENTRY
+        ema_off = 0
+        if self.ema is not None:                                   # third section: one shadow pointer per table entry
+            ema_off = (nbytes + 63) // 64 * 64
+            nbytes = ema_off + N * 8
         max_chunks = sum((p.numel() + 4095) // 4096 for p in self._all)
         ws = ops.bertadam_workspace_bytes(N, max_chunks)
         with torch.cuda.device(device):
             self._dev = dict(
-                device=device, bytes=nbytes, table_off=table_off,
+                device=device, bytes=nbytes, table_off=table_off, ema_off=ema_off,
                 steps=torch.zeros(N, dtype=torch.int32, device=device),
                 table=torch.empty(nbytes, dtype=torch.uint8, device=device),
                 workspace=torch.empty(max(ws, 256), dtype=torch.uint8, device=device),
@@ -346,7 +543,10 @@ class BertAdam(Optimizer):
                      for g in self.param_groups)
 
     def _table_key(self, live):
-        return (tuple((id(p), p.data_ptr(), p.grad.data_ptr()) for p in live), self._group_values(), self.global_max_norm)
+        shadows = None
+        if self.ema is not None:
+            shadows = tuple(0 if e is None else e.data_ptr() for e in map(self.ema.shadow, live))
+        return (tuple((id(p), p.data_ptr(), p.grad.data_ptr()) for p in live), self._group_values(), self.global_max_norm, shadows)
 
     def _build(self, live):
         """Host image of [groups | table] for the tensors in `live`, checked and chunked by nr_bertadam_plan."""
@@ -384,6 +584,9 @@ class BertAdam(Optimizer):
         image = bytearray(dev["bytes"])
         image[:G * _GROUP] = bytes(groups)
         image[dev["table_off"]:dev["table_off"] + len(live) * _ENTRY] = bytes(entries)
+        if self.ema is not None:
+            shadows = (ctypes.c_uint64 * len(live))(*(0 if e is None else e.data_ptr() for e in map(self.ema.shadow, live)))
+            image[dev["ema_off"]:dev["ema_off"] + 8 * len(live)] = bytes(shadows)
         return (ctypes.c_char * len(image)).from_buffer(image), n_chunks
 
 
@@ -402,14 +605,15 @@ def _group_index(name):
 
 
 def prep_optimizer(args, model, num_train_optimization_steps, local_rank, global_max_norm=None, clamp_logit_scale=False,
-                   wrap=True, skip_nonfinite=False):
+                   wrap=True, skip_nonfinite=False, ema=None):
     """training/optimizer.py:12-86 -> (optimizer, None, model).  Four groups: names with `clip.` train at lr * coef_lr, names
     containing `bias`, `LayerNorm.bias` or `LayerNorm.weight` take no weight decay; warmup_cosine over
     `num_train_optimization_steps`, b1 0.9, b2 0.98, e 1e-6, per-tensor max_grad_norm 1.0.
 
     By default the trainer's global clip and logit-scale clamp stay with the caller (training.train_epoch does both around
     step(), like the reference's trainer); `global_max_norm=1.0` / `clamp_logit_scale=True` move them into the step;
-    `skip_nonfinite=True` builds the optimizer with the device-side non-finite guard (BertAdam).  The model
+    `skip_nonfinite=True` builds the optimizer with the device-side non-finite guard (BertAdam); `ema`: a WeightEma the
+    optimizer's step drives (BertAdam).  The model
     comes back wrapped in DistributedDataParallel when a process group is up (the reference wraps whenever CUDA is there, which
     needs one; `wrap=False`: never), else as it came."""
     if hasattr(model, "module"):
@@ -430,7 +634,7 @@ def prep_optimizer(args, model, num_train_optimization_steps, local_rank, global
             raise ValueError("clamp_logit_scale: the model has no clip.logit_scale parameter")
     optimizer = BertAdam(groups, lr=args.lr, warmup=args.warmup_proportion, schedule="warmup_cosine", b1=0.9, b2=0.98, e=1e-6,
                          t_total=num_train_optimization_steps, weight_decay=args.weight_decay, max_grad_norm=1.0,
-                         global_max_norm=global_max_norm, clamp_max=clamp, skip_nonfinite=skip_nonfinite)
+                         global_max_norm=global_max_norm, clamp_max=clamp, skip_nonfinite=skip_nonfinite, ema=ema)
     import torch.distributed as dist
     if wrap and torch.cuda.is_available() and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local_rank], output_device=local_rank,

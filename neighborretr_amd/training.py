@@ -152,8 +152,9 @@ def _cache_features(model, loader, device, separate):
     return tuple(torch.cat(out[k], 0) for k in ("ind", "tf", "tm", "vf", "vm"))
 
 
-def eval_epoch(args, model, test_dataloader, device):
-    """evaluator.py:66-291 -> (text_to_video_metrics, video_to_text_metrics), the same on every rank.
+def eval_epoch(args, model, test_dataloader, device, tag=""):
+    """evaluator.py:66-291 -> (text_to_video_metrics, video_to_text_metrics), the same on every rank.  `tag` (EMA: the
+    evaluation of the averaged weights, optim.WeightEma) marks the results' header line.
 
     Single-sentence sets: every rank caches the features of the batches its sampler gives it, one packed all-gather + index
     scatter puts them into dataset order (:173-189), then the N x N similarity and both rank counts are computed SHARDED
@@ -193,7 +194,7 @@ def eval_epoch(args, model, test_dataloader, device):
         logger.info(f"  - Feature extraction: {toc1 - tic:.2f}s")
         logger.info(f"  - Similarity + metrics: {toc2 - toc1:.2f}s")
         logger.info("=" * 80)
-        logger.info("EVALUATION RESULTS")
+        logger.info("EVALUATION RESULTS" + (f" [{tag}]" if tag else ""))
         logger.info("=" * 80)
         tracker.log_current_metrics(t2v, v2t, (t2v["R1"] + v2t["R1"]) / 2)
 
@@ -275,7 +276,13 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
     optim.BertAdam built with skip_nonfinite=True decides on the device, inside its launches, and this loop does not wait for
     it; for any other optimizer the norm that clip_grad_norm_ returns is tested on the host -- one synchronisation per step,
     with the flag only -- and optimizer.step() / scheduler.step() are left out when it is not finite.  The count of skipped
-    steps joins the log line."""
+    steps joins the log line.
+
+    args.weight_ema (optional, an optim.WeightEma): after an update that happened it takes its stand-alone
+    update(), unless it is attached to the optimizer, whose launches then average; every validation runs a second time with the
+    average in the parameters (header tagged EMA).  The best metrics stay those of the raw model."""
+    ema = getattr(args, "weight_ema", None)
+    ema_by_hand = ema is not None and ema._driver is None
     skip_nonfinite = getattr(args, "skip_nonfinite", 0)
     if isinstance(skip_nonfinite, bool) or skip_nonfinite not in (0, 1):
         raise ValueError(f"skip_nonfinite must be 0 or 1, got {skip_nonfinite!r}")
@@ -307,7 +314,8 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
         else:
             loss.backward()
         grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
-        if skip_nonfinite and not on_device and not math.isfinite(float(grad_norm)):
+        stepped = not (skip_nonfinite and not on_device and not math.isfinite(float(grad_norm)))
+        if not stepped:
             host_skipped += 1
         else:
             if on_device:
@@ -317,6 +325,8 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
                 scheduler.step()
         optimizer.zero_grad()
         torch.clamp_(target.clip.logit_scale.data, max=float(np.log(100)))          # trainer.py:114-119
+        if ema_by_hand and stepped:
+            ema.update()
         total_loss = loss.detach().clone() if total_loss is None else total_loss + loss.detach()
         batch_time = time.time() - end
         end = time.time()
@@ -345,6 +355,9 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
             _info(logger, "=" * 80)
             _info(logger, f"Running validation at step {global_step}")
             t2v, v2t = eval_epoch(args, model, val_dataloader, device)
+            if ema is not None:
+                with ema.applied():
+                    eval_epoch(args, model, val_dataloader, device, tag="EMA")
             if int(getattr(args, "local_rank", 0)) == 0:
                 updated, _ = tracker.update_best_metrics(t2v, v2t, t2v["R1"], v2t["R1"])
                 if updated:

@@ -14,6 +14,7 @@ the same for the parameter set of `--encoders 1` (ViT-B/32 towers + head, synthe
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/optim_times.py --kernels-only     # per-kernel times, a run of its own
     python tools/optim_times.py --summary DIR                                                 # ... read from its trace database
     python tools/optim_times.py --guard [--out profiles/optim_guard_times.txt]                # the non-finite guard's cost (6.9)
+    python tools/optim_times.py --ema [--out profiles/optim_ema_times.txt]                    # the weight EMA's cost (6.11)
 """
 import argparse
 import os
@@ -194,6 +195,62 @@ def guard_cost(out, blocks=6, n=50):
     out(f"  guarded median - unguarded median: {np.median(times['guarded']) - np.median(times['unguarded']):+.2f} us")
 
 
+def ema_cost(out, encoders, blocks=6, n=50):
+    """the three launches with the weight EMA attached against the three without, and the stand-alone
+    update() (two launches), each replayed from a graph of its own on static finite gradients; alternating blocks, device
+    events around each block.  By bytes the update launch moves 36 instead of 28 per element, update() 12."""
+    graphs = {}
+    for name in ("without", "with ema", "update()"):
+        if encoders:
+            m, params = encoder_params()
+        else:
+            m = modeling.NeighborRetr(modeling.default_config(num_neighbors=K)).to(DEV).train()
+            params = list(m.parameters())
+        ema = optim.WeightEma(m.named_parameters(), decay=0.999) if name != "without" else None
+        g = torch.cuda.CUDAGraph()
+        if name == "update()":
+            ema.update()
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g):
+                ema.update()
+            opt = None
+        else:
+            opt = optim.prep_optimizer(Args, m, 10 ** 6, 0, global_max_norm=1.0, clamp_logit_scale=True, wrap=False, ema=ema)[0]
+            gen = torch.Generator(device=DEV).manual_seed(1)
+            for p in params:
+                p.grad = torch.randn(p.shape, generator=gen, device=DEV) * 0.01
+            opt.prepare(params)
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g):
+                opt.issue()
+        for _ in range(10):
+            g.replay()
+        graphs[name] = (g, opt, ema, m)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = {name: [] for name in graphs}
+    for _ in range(blocks):
+        for name, (g, _, _, _) in graphs.items():
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(n):
+                g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / n * 1e3)
+    assert graphs["with ema"][2].updates() == 10 + blocks * n and graphs["update()"][2].updates() == 11 + blocks * n
+    n_elem = sum(p.numel() for p in graphs["without"][3].parameters())
+    out(f"weight EMA, {'--encoders 1 parameter set' if encoders else 'head only'} ({n_elem} elements), each form replayed from a "
+        f"graph of its own, {blocks} alternating blocks of {n}:")
+    for name, t in times.items():
+        out(f"  {name:9s}: median {np.median(t):.2f} us per step   blocks {np.round(t, 2).tolist()}   spread {max(t) - min(t):.2f} us")
+    med = {name: float(np.median(t)) for name, t in times.items()}
+    out(f"  with ema / without: {med['with ema'] / med['without']:.3f} of the three launches (by the update launch's bytes at most "
+        f"36 / 28 = {36 / 28:.3f}); update() / without: {med['update()'] / med['without']:.3f} (12 / 28 = {12 / 28:.3f} of the update "
+        "launch alone)")
+    del graphs
+    torch.cuda.empty_cache()
+
+
 def adamw_tail_alone(out, name, params, n=50):
     opt = torch.optim.AdamW(params, lr=1e-4, weight_decay=0.2)
     grads = [torch.randn_like(p) * 0.01 for p in params]
@@ -249,6 +306,7 @@ def main():
     ap.add_argument("--kernels-only", action="store_true", help="50 eager updates of the head's parameters and nothing else")
     ap.add_argument("--skip-encoders", action="store_true")
     ap.add_argument("--guard", action="store_true", help="only: the three launches with the non-finite guard against without")
+    ap.add_argument("--ema", action="store_true", help="only: the three launches with the weight EMA against without, and update()")
     args = ap.parse_args()
     lines = []
 
@@ -258,6 +316,15 @@ def main():
     if args.guard:
         out(f"tools/optim_times.py --guard on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
         guard_cost(out)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    if args.ema:
+        out(f"tools/optim_times.py --ema on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
+        ema_cost(out, encoders=False)
+        if not args.skip_encoders:
+            ema_cost(out, encoders=True, n=20)
         if args.out:
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
