@@ -167,7 +167,22 @@ def get_args():
     p.add_argument("--synthetic_blank", default="", metavar="STEP[:RANK]",
                    help="--synthetic: in global step STEP (1-based) the first video of the batch of rank RANK (default 0) comes "
                         "back the way the reference's loader returns an undecodable one, all zeros with an all-zero mask")
+    p.add_argument("--save_state_every", type=int, default=0, metavar="N",
+                   help="N > 0: after every N-th global step and at the end of every epoch rank 0 writes the whole training state "
+                        "(weights, raw memory-bank ring, noise stream, optimizer with its device counters and guard, EMA; "
+                        "DESIGN.md 6.12) to <output_dir>/training_state.pt, atomically; 0 = off")
+    p.add_argument("--resume", default=None, metavar="PATH|auto",
+                   help="continue training from a training-state file, bit for bit, also in the middle of an epoch and under "
+                        "--hip_graph 1; auto: <output_dir>/training_state.pt when it exists, a fresh start otherwise")
+    p.add_argument("--max_steps", type=int, default=0, metavar="N",
+                   help="N > 0: training stops after global step N, having written the training state (a time-boxed job); 0 = none")
     args = p.parse_args()
+    if args.save_state_every < 0 or args.max_steps < 0:
+        p.error("--save_state_every and --max_steps must be >= 0")
+    if args.resume is not None and not args.do_train:
+        p.error("--resume continues training: it needs --do_train 1")
+    if args.resume is not None and args.init_model:
+        p.error("--resume restores the weights itself: not together with --init_model")
     try:
         blank = [int(v) for v in args.synthetic_blank.split(":")] if args.synthetic_blank else [0, 0]
         args.blank_step, args.blank_rank = blank if len(blank) == 2 else (blank[0], 0)
@@ -558,9 +573,78 @@ class GraphedStep:
         return self.losses
 
 
-def train_epoch(args, model, ddp, data, optimizer, epoch, global_step, ema=None):
+class StateKeeper:
+    """--save_state_every / --max_steps / --resume: writes <output_dir>/training_state.pt on rank 0 and prints
+    every rank's digest line.  Epochs and steps count from 0 here, as in the state's position."""
+
+    def __init__(self, args, model, optimizer, ema):
+        self.args, self.model, self.optimizer, self.ema = args, model, optimizer, ema
+        self.path = os.path.join(args.output_dir, "training_state.pt")
+        self.stopped = False
+
+    def capture(self, epoch, next_step, global_step):
+        from neighborretr_amd import checkpoint
+        return checkpoint.capture_state(self.model, self.optimizer, self.ema,
+                                        position=dict(epoch=epoch, next_step=next_step, global_step=global_step),
+                                        config=checkpoint.config_from_args(self.args),
+                                        host_guard=getattr(self.args, "_host_skips", None))
+
+    def write(self, state):
+        from neighborretr_amd import checkpoint
+        if self.args.rank == 0:
+            checkpoint.save(self.path, state)
+            pos = state["position"]
+            log(self.args, f"training state written: epoch {pos['epoch'] + 1}, next step {pos['next_step'] + 1} "
+                           f"(global step {pos['global_step']}) -> {self.path}")
+
+    def digest_line(self, state, epoch):
+        from neighborretr_amd import checkpoint
+        print(f"rank {self.args.rank} epoch {epoch + 1} training state sha256 {checkpoint.digest(state)[:16]}", flush=True)
+
+    def after_step(self, epoch, i, global_step):
+        """After step i of `epoch`: the N-th step's write, and the stop of --max_steps (state written, digest line) -> stop."""
+        args = self.args
+        stop = bool(args.max_steps) and global_step >= args.max_steps
+        due = bool(args.save_state_every) and global_step % args.save_state_every == 0
+        if stop or (due and args.rank == 0):
+            state = self.capture(epoch, i + 1, global_step)
+            self.write(state)
+            if stop:
+                self.digest_line(state, epoch)
+        self.stopped = stop
+        return stop
+
+    def end_of_epoch(self, epoch, global_step):
+        """After the epoch's evaluation, saved models and EMA pass: position (epoch + 1, 0), so a resume re-runs none of them."""
+        state = self.capture(epoch + 1, 0, global_step)
+        if self.args.save_state_every:
+            self.write(state)
+        self.digest_line(state, epoch)
+
+
+def resume_training(args, state, keeper):
+    """--resume: the loaded state into the run's model, optimizer and EMA on every rank -> its position.  Several ranks compare
+    the digests of what they hold afterwards with one all-gather of the 32 bytes; a difference raises on every rank."""
+    from neighborretr_amd import checkpoint
+    if args.skip_nonfinite and args.optimizer != "bertadam":
+        args._host_skips = dict(skipped=0, consecutive=0, max_consecutive=0, norms=[])
+    pos = checkpoint.restore_state(state, keeper.model, keeper.optimizer, keeper.ema, host_guard=getattr(args, "_host_skips", None))
+    if args.world_size > 1:
+        mine = bytes.fromhex(checkpoint.digest(keeper.capture(**pos)))
+        where = args.device if args.dist_backend == "nccl" else "cpu"
+        got = [torch.empty(32, dtype=torch.uint8, device=where) for _ in range(args.world_size)]
+        dist.all_gather(got, torch.tensor(list(mine), dtype=torch.uint8, device=where))
+        seen = [bytes(g.cpu().tolist()).hex()[:16] for g in got]
+        if len(set(seen)) != 1:
+            raise RuntimeError(f"--resume: the ranks hold different training states after restoring: {seen}")
+    log(args, f"resumed at epoch {pos['epoch'] + 1}, step {pos['next_step'] + 1} (global step {pos['global_step']})")
+    return pos
+
+
+def train_epoch(args, model, ddp, data, optimizer, epoch, global_step, ema=None, start=0, keeper=None):
     """ema: the run's WeightEma.  --optimizer bertadam drives it from its own launches; after an AdamW step that happened it
-    takes its stand-alone update here."""
+    takes its stand-alone update here.  start: the first step of this epoch to run (a resumed run; the memory bank is then the
+    restored one); keeper: the run's StateKeeper, asked after every step."""
     from neighborretr_amd.dist import reduce_losses
     model.train()
     t0 = time.time()
@@ -571,7 +655,7 @@ def train_epoch(args, model, ddp, data, optimizer, epoch, global_step, ema=None)
         args._host_skips = dict(skipped=0, consecutive=0, max_consecutive=0, norms=[])
     bank_steps = -(-int(getattr(model, "mb_batch", 0)) // args.batch_size)        # steps until a batch has left the memory bank
     warned = 0
-    for i in range(len(data)):
+    for i in range(start, len(data)):
         global_step += 1
         text, text_mask, video, video_mask, idx = data.batch(i, args.device)
         if global_step == getattr(args, "blank_step", 0) and args.rank == getattr(args, "blank_rank", 0):
@@ -580,9 +664,17 @@ def train_epoch(args, model, ddp, data, optimizer, epoch, global_step, ema=None)
             video_mask[0] = 0
         if args.hip_graph:
             if graphed is None:
+                # a run resumed inside an epoch captures here, where the uninterrupted run replays: what the capture's warm-up
+                # passes move is put back, so that the loaded state is the state this step starts from
+                kept = None
+                if start > 0:
+                    from neighborretr_amd import checkpoint
+                    kept = checkpoint.volatile_words(model)
                 graphed = args._graphed_step = GraphedStep(model, (text, text_mask, video, video_mask, idx),
                                                            [p for p in model.parameters() if p.requires_grad], args,
                                                            optimizer=optimizer if fused else None)
+                if kept is not None:
+                    checkpoint.reapply_volatile(model, kept)
                 log(args, f"training step replayed as: {graphed.form}")
             losses = graphed.run((text, text_mask, video, video_mask, idx))
             loss = None
@@ -634,7 +726,9 @@ def train_epoch(args, model, ddp, data, optimizer, epoch, global_step, ema=None)
                 warned = stats["consecutive"]
             log(args, f"epoch {epoch} step {i + 1}/{len(data)} loss {red[0]:.4f} centrality {red[1]:.4f} "
                       f"uniform {red[2]:.4f} neighbor {red[3]:.4f} kl {red[4]:.4f}{lr} "
-                      f"({(time.time() - t0) / (i + 1) * 1e3:.1f} ms/step){tail}")
+                      f"({(time.time() - t0) / (i + 1 - start) * 1e3:.1f} ms/step){tail}")
+        if keeper is not None and keeper.after_step(epoch - 1, i, global_step):
+            return global_step
     if guard:                                        # every rank, not only the one that logs: the ranks must agree
         import hashlib
         stats, _ = _guard_report(args, optimizer, fused, 0)
@@ -800,6 +894,17 @@ def main():
     if not args.synthetic:
         raise SystemExit("datasets / CLIP towers are outside this build (SURVEY.md 2.1): run with --synthetic, "
                          "or import neighborretr_amd.modeling.NeighborRetr into the reference's main.py")
+    resume_state = None
+    if args.resume is not None:                             # read (and refused) before anything is built
+        from neighborretr_amd import checkpoint
+        path = os.path.join(args.output_dir, "training_state.pt") if args.resume == "auto" else args.resume
+        if args.resume == "auto" and not os.path.exists(path):
+            log(args, f"--resume auto: no {path}, a fresh start")
+        else:
+            try:
+                resume_state = checkpoint.load(path, config=checkpoint.config_from_args(args))
+            except checkpoint.CheckpointError as err:
+                raise SystemExit(f"--resume: {err}")
     from neighborretr_amd.modeling import NeighborRetr
     model = NeighborRetr(args, precision=args.precision, with_encoders=bool(args.encoders))
     if args.init_model:
@@ -830,15 +935,29 @@ def main():
     os.makedirs(args.output_dir, exist_ok=True)
     global_step = 0
     if args.do_train:
-        for epoch in range(args.epochs):
-            load_memory_bank(args, model, train)
+        keeper, first_epoch, first_step = None, 0, 0
+        if args.save_state_every or args.max_steps or args.resume is not None:
+            keeper = StateKeeper(args, model, optimizer, ema)
+        if resume_state is not None:
+            pos = resume_training(args, resume_state, keeper)
+            first_epoch, first_step, global_step = pos["epoch"], pos["next_step"], pos["global_step"]
+            del resume_state
+        for epoch in range(first_epoch, args.epochs):
+            start = first_step if epoch == first_epoch else 0
+            if start == 0:                                  # (a run resumed inside an epoch goes on with the restored bank)
+                load_memory_bank(args, model, train)
             global_step = train_epoch(args, model, ddp, train, optimizer, epoch + 1, global_step,
-                                      ema=ema if args.optimizer != "bertadam" else None)
+                                      ema=ema if args.optimizer != "bertadam" else None, start=start, keeper=keeper)
+            if keeper is not None and keeper.stopped:
+                log(args, f"--max_steps {args.max_steps}: stopped after global step {global_step}")
+                break
             raw_result = eval_epoch(args, model, test)
             if args.rank == 0 and args.save_model:
                 torch.save(model.state_dict(), os.path.join(args.output_dir, f"pytorch_model.bin.{epoch}"))
             if ema is not None:
                 ema_epoch(args, model, ema, raw_result, test, epoch)
+            if keeper is not None:
+                keeper.end_of_epoch(epoch, global_step)
             clear_memory_bank(model)
     elif args.do_eval:
         with_bank = args.test_norm in ("qbnorm", "qbsinkhorn") or (args.local_scaling != "none" and args.local_scaling_bank) \

@@ -360,6 +360,29 @@ class BertAdam(Optimizer):
         rows = ring[[a & (self.record_ring - 1) for a in range(attempts - n, attempts)]] if n else ring[:0]
         return rows.copy()
 
+    def guard_state_dict(self):
+        """The guard as the device holds it now, raw: {guard: the 48 bytes of NrStepGuard, records: the record ring's bytes,
+        record_ring} with uint8 host tensors (a blocking copy).  state_dict() does not carry them."""
+        self._need_guard("guard_state_dict")
+        dev = self._device_state()
+        return dict(guard=dev["guard"].cpu(), records=dev["ring_records"].cpu(), record_ring=self.record_ring)
+
+    @torch.no_grad()
+    def load_guard_state_dict(self, state_dict):
+        """guard_state_dict()'s value into the existing device guard and record ring (a captured step holds their addresses).
+        The only call that sets them: load_state_dict() leaves them alone."""
+        self._need_guard("load_guard_state_dict")
+        dev = self._device_state()
+        guard, records = state_dict["guard"], state_dict["records"]
+        if int(state_dict["record_ring"]) != self.record_ring:
+            raise ValueError(f"BertAdam.load_guard_state_dict: the records come from a ring of {state_dict['record_ring']}, this "
+                             f"optimizer's has {self.record_ring}")
+        for name, src, dst in (("guard", guard, dev["guard"]), ("records", records, dev["ring_records"])):
+            if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.numel() != dst.numel():
+                raise ValueError(f"BertAdam.load_guard_state_dict: {name} must be a uint8 tensor of {dst.numel()} bytes")
+        dev["guard"].copy_(guard.reshape(-1))
+        dev["ring_records"].copy_(records.reshape(-1))
+
     def _need_guard(self, what):
         if not self.skip_nonfinite:
             raise RuntimeError(f"BertAdam.{what}() belongs to the non-finite guard: build the optimizer with skip_nonfinite=True")
