@@ -136,6 +136,12 @@ int nr_token_weights_fwd_pair(const NrTokenWeightsProblem* a, const NrTokenWeigh
  * when a set does not fit that block (192 % N, H % 256): issue the sets one by one then.  One-pass sets: bit-identical to
  * their single launch; split-bf16 sets: another summation order (~1e-7 relative).                                          */
 int nr_token_weights_fwd_group(const NrTokenWeightsProblem* probs, const int* precs, int n, void* stream);
+/* The launch form of ONE scorer call, from the host alone (no device): block rows *bm (64 / 96 / 128 / 192), hidden units *bn
+ * (128 on 4 waves, 256 on 8) and ring depth *stages (1 or 2) that nr_token_weights_fwd (N_fused = tokens per sample) or
+ * nr_token_logits_fwd (N_fused = 0) will run for n_tok tokens -- the launcher's own picker and ring rule, not a copy.
+ * NR_EUNSUPPORTED exactly where nr_token_weights_fwd returns it (no block holds whole samples, N_fused > 256); NR_EINVAL for
+ * n_tok <= 0, H % 128, an unknown prec, N_fused < 0, n_tok % N_fused, a null pointer.  The outputs are untouched then. */
+int nr_token_scorer_plan(int n_tok, int H, int prec, int N_fused, int* bm, int* bn, int* stages);
 
 /* Fused local_level (modeling.py:499-512): token-token cosine products on MFMA, max-pool over
  * each token axis, weighted sums, (t2v+v2t)/2.  The [A,Bv,Nt,Nv] tensor is never materialised.

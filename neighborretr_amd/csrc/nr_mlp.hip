@@ -271,7 +271,8 @@ int mlp_launch(const NrMlpProblem& q, hipStream_t st, const NrMlpProblem* second
 // block shape (index into `cand`) and workgroup count of one scorer call; -1: none fits
 static const MlpShape nr_mlp_cand[] = {{2, 4, 2}, {3, 4, 2}, {4, 4, 2}, {4, 4, 4}, {6, 4, 4}};
 
-static int nr_mlp_pick(int n_tok, int H, bool x3, const NrMlpSoftmax& sm, long* wg_out) {
+// n_fused: tokens per sample when the softmax is folded into the launch (whole samples per row tile), 0 otherwise
+static int nr_mlp_pick(int n_tok, int H, bool x3, int n_fused, long* wg_out) {
     // candidate block shapes (MI, NI, WC): 64/96/128 x 128 on 4 waves, 128/192 x 256 on 8 waves (one-pass bf16
     // only: the split operands of a 256-wide block do not fit the LDS twice)
     const MlpShape* cand = nr_mlp_cand;
@@ -281,7 +282,7 @@ static int nr_mlp_pick(int n_tok, int H, bool x3, const NrMlpSoftmax& sm, long* 
         const int bm = 32 * cand[c].mi, bn = 16 * cand[c].wc * cand[c].ni;
         if (H % bn) continue;
         if (x3 && cand[c].wc == 4) continue;
-        if (sm.counters && (bm % sm.N) != 0) continue;            // fused softmax: whole samples per row tile
+        if (n_fused && (bm % n_fused) != 0) continue;             // fused softmax: whole samples per row tile
         const long wg = (long)((n_tok + bm - 1) / bm) * (H / bn);
         const long cost = ((wg + 255) / 256) * (bm + bn);
         if (best < 0 || cost < best_cost || (cost == best_cost && wg > best_wg)) { best = c; best_cost = cost; best_wg = wg; }
@@ -290,14 +291,14 @@ static int nr_mlp_pick(int n_tok, int H, bool x3, const NrMlpSoftmax& sm, long* 
     // workgroup, while two of the 128 x 256 block (108) share a CU and hide each other's load phases with a one-deep ring --
     // configs[3], 65536 bank tokens per scorer launch: 485 steps/s with 192 x 256 one-deep, 497 two-deep, 515 with 128 x 256
     // one-deep (tools/ab_c3.sh, A/B in one session)
-    if (best == 4 && best_wg >= 3 * 256 && H % 256 == 0 && !(sm.counters && 128 % sm.N != 0)) {
+    if (best == 4 && best_wg >= 3 * 256 && H % 256 == 0 && !(n_fused && 128 % n_fused != 0)) {
         best = 3;
         best_wg = (long)((n_tok + 127) / 128) * (H / 256);
     }
     if (const char* e = nr_tune_env("NR_MLP_SHAPE")) {          // tuning hook: index into the candidate list
         int c = atoi(e);
         if (c >= 0 && c < 5 && H % (16 * cand[c].wc * cand[c].ni) == 0 && !(x3 && cand[c].wc == 4) &&
-            !(sm.counters && (32 * cand[c].mi) % sm.N != 0)) {
+            !(n_fused && (32 * cand[c].mi) % n_fused != 0)) {
             best = c;
             best_wg = (long)((n_tok + 32 * cand[c].mi - 1) / (32 * cand[c].mi)) * (H / (16 * cand[c].wc * cand[c].ni));
         }
@@ -305,6 +306,17 @@ static int nr_mlp_pick(int n_tok, int H, bool x3, const NrMlpSoftmax& sm, long* 
     if (wg_out) *wg_out = best_wg;
     return best;
 }
+
+// ring depth: workgroups that sit alone on their CU prefetch for themselves (2 stages); crowded grids run 1
+// (the 192 x 256 block holds 142 registers a lane: never two of its 8-wave workgroups on a CU, however crowded the grid --
+// one-stage launches of it ran load and MFMA phases strictly in turn: 150 us for the 65536 bank tokens of configs[3])
+static bool nr_mlp_two_deep(int best, long wg) {
+    bool two = wg < 3 * 256 || (nr_mlp_cand[best].mi == 6 && nr_mlp_cand[best].wc == 4);
+    if (nr_tune_env("NR_MLP_ONE_STAGE")) two = false;          // tuning hook: smallest LDS footprint
+    return two;
+}
+
+static int nr_mlp_fused_n(const NrMlpSoftmax& sm) { return sm.counters ? sm.N : 0; }
 
 static int nr_mlp_check(const NrMlpProblem& q, int prec) {
     if (!q.tok_hi || !q.norm || !q.w1_hi || !q.b1 || !q.w2 || !q.logit_part) return NR_EINVAL;
@@ -323,18 +335,14 @@ static int nr_mlp_go(const NrMlpProblem& q, const NrMlpProblem* second, int prec
     const bool x3 = prec == NR_PREC_BF16X3;
     const MlpShape* cand = nr_mlp_cand;
     long best_wg = 0;
-    const int best = nr_mlp_pick(q.n_tok, q.H, x3, q.sm, &best_wg);
+    const int best = nr_mlp_pick(q.n_tok, q.H, x3, nr_mlp_fused_n(q.sm), &best_wg);
     if (best < 0) return NR_EUNSUPPORTED;
     if (second) {
         long wg_b = 0;
-        if (nr_mlp_pick(second->n_tok, second->H, x3, second->sm, &wg_b) != best || second->d != q.d) return NR_EUNSUPPORTED;
+        if (nr_mlp_pick(second->n_tok, second->H, x3, nr_mlp_fused_n(second->sm), &wg_b) != best || second->d != q.d) return NR_EUNSUPPORTED;
         best_wg += wg_b;
     }
-    // ring depth: workgroups that sit alone on their CU prefetch for themselves (2 stages); crowded grids run 1
-    // (the 192 x 256 block holds 142 registers a lane: never two of its 8-wave workgroups on a CU, however crowded the grid --
-    // one-stage launches of it ran load and MFMA phases strictly in turn: 150 us for the 65536 bank tokens of configs[3])
-    bool two = best_wg < 3 * 256 || (cand[best].mi == 6 && cand[best].wc == 4);
-    if (nr_tune_env("NR_MLP_ONE_STAGE")) two = false;          // tuning hook: smallest LDS footprint
+    const bool two = nr_mlp_two_deep(best, best_wg);
 #define NR_MLP_GO(MI_, NI_, WC_)                                                                                              \
     if (cand[best].mi == MI_ && cand[best].ni == NI_ && cand[best].wc == WC_) {                                               \
         if (x3) {                                                                                                             \
@@ -376,6 +384,22 @@ extern "C" int nr_token_weights_fwd(const uint16_t* tok_hi, const uint16_t* tok_
     if (n_counters < (n_tok + 63) / 64) return NR_EINVAL;           // the smallest row tile is 64 tokens
     NrMlpSoftmax sm{counters, b2, mask, N, w, logits};
     return nr_token_logits_go(tok_hi, tok_lo, norm, (int)n_tok, d, w1_hi, w1_lo, b1, w2, H, prec, logit_part, stream, sm);
+}
+
+// Which launch form nr_mlp_go runs for ONE scorer call (host only, no device): block rows x hidden units and the ring depth.
+// n_fused: tokens per sample of an nr_token_weights_fwd call, 0 for nr_token_logits_fwd.  Same picker, same ring rule.
+extern "C" int nr_token_scorer_plan(int n_tok, int H, int prec, int n_fused, int* bm, int* bn, int* stages) {
+    if (!bm || !bn || !stages || n_tok <= 0 || H <= 0 || (H % 128) != 0 || n_fused < 0) return NR_EINVAL;
+    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3) return NR_EINVAL;
+    if (n_fused > 0 && (n_tok % n_fused) != 0) return NR_EINVAL;
+    if (n_fused > 256) return NR_EUNSUPPORTED;
+    long wg = 0;
+    const int best = nr_mlp_pick(n_tok, H, prec == NR_PREC_BF16X3, n_fused, &wg);
+    if (best < 0) return NR_EUNSUPPORTED;
+    *bm = 32 * nr_mlp_cand[best].mi;
+    *bn = 16 * nr_mlp_cand[best].wc * nr_mlp_cand[best].ni;
+    *stages = nr_mlp_two_deep(best, wg) ? 2 : 1;
+    return NR_OK;
 }
 
 // Two nr_token_weights_fwd calls of one precision in ONE launch (the step's text and video tokens).  NR_EUNSUPPORTED when the

@@ -175,6 +175,7 @@ _SIGNATURES = {
     "nr_token_mlp_bwd_hidden": ([_P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "nr_token_weights_fwd_pair": ([ctypes.POINTER(TokenWeightsProblem), ctypes.POINTER(TokenWeightsProblem), _I, _P], _I),
     "nr_token_weights_fwd_group": ([ctypes.POINTER(TokenWeightsProblem), ctypes.POINTER(ctypes.c_int), _I, _P], _I),
+    "nr_token_scorer_plan": ([_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)], _I),
     "nr_token_weights_fwd": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P], _I),
     "nr_local_level_tiles": ([_I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)], _I),
     "nr_local_level_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
@@ -405,6 +406,18 @@ def local_level_tiles(A, Nt, Bv, Nv, prec=PREC_BF16):
     r, c = _I(0), _I(0)
     _check("nr_local_level_tiles", lib().nr_local_level_tiles(A, Nt, Bv, Nv, int(prec), ctypes.byref(r), ctypes.byref(c)))
     return r.value, c.value
+
+
+def token_scorer_plan(n_tok, H, prec, N_fused=0):
+    """(block rows, hidden units per block, ring depth) of one scorer launch (nr_token_scorer_plan; host only).  N_fused: tokens
+    per sample for the fused nr_token_weights_fwd, 0 for nr_token_logits_fwd.  None where nr_token_weights_fwd returns
+    NR_EUNSUPPORTED (ops.token_weights then runs the two launches); raises on bad arguments."""
+    bm, bn, st = _I(0), _I(0), _I(0)
+    rc = lib().nr_token_scorer_plan(int(n_tok), int(H), int(prec), int(N_fused), ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(st))
+    if rc == NR_EUNSUPPORTED:
+        return None
+    _check("nr_token_scorer_plan", rc)
+    return bm.value, bn.value, st.value
 
 
 def local_level_group_kind(A, Nt, Bv, Nv, d, prec):

@@ -143,10 +143,10 @@ def token_weights(prep, w1_hi, w1_lo, b1, w2, b2, mask, n_samples, N, prec, want
     return token_softmax(parts, b2, mask, n_samples, N, want_logits)
 
 
-def token_weights_pair(calls, prec):
+def token_weights_pair(calls, prec, want_logits=False):
     """Two token_weights calls of one precision in ONE launch (nr_token_weights_fwd_pair; bit-identical to the single calls).
-    calls: two tuples (prep, w1_hi, w1_lo, b1, w2, b2, mask, n_samples, N).  -> [(w, None), (w, None)]; falls back to two
-    launches when the two do not run the same block shape."""
+    calls: two tuples (prep, w1_hi, w1_lo, b1, w2, b2, mask, n_samples, N).  -> [(w, logits or None), (w, logits or None)]; falls
+    back to two launches when the two do not run the same block shape."""
     import ctypes
     dev = calls[0][0].hi.device
     probs, outs, keep = [], [], []
@@ -164,10 +164,11 @@ def token_weights_pair(calls, prec):
         q.w1_hi, q.w1_lo = hip.ptr(w1_hi), hip.ptr(w1_lo, allow_none=True)
         q.b1, q.w2, q.b2 = hip.ptr(b1, torch.float32), hip.ptr(w2, torch.float32), hip.ptr(b2, torch.float32)
         q.mask, q.logit_part, q.counters = hip.ptr(m, allow_none=True), hip.ptr(parts), hip.ptr(counters)
-        q.w, q.logits = hip.ptr(w), None
+        logits = torch.empty((n_samples, N), dtype=torch.float32, device=dev) if want_logits else None
+        q.w, q.logits = hip.ptr(w), hip.ptr(logits, allow_none=True)
         q.n_samples, q.N, q.d, q.H, q.n_counters = int(n_samples), int(N), int(prep.d), int(H), counters.numel()
         probs.append(q)
-        outs.append((w, None))
+        outs.append((w, logits))
         keep += [parts, m]
     if probs is not None:
         hip.N_CALLS += 1
@@ -177,13 +178,13 @@ def token_weights_pair(calls, prec):
         if rc != hip.NR_EUNSUPPORTED:
             hip._check("nr_token_weights_fwd_pair", rc)
         hip.N_CALLS -= 1
-    return [token_weights(*c, prec) for c in calls]
+    return [token_weights(*c, prec, want_logits) for c in calls]
 
 
-def token_weights_group(calls, precs):
+def token_weights_group(calls, precs, want_logits=False):
     """Up to four token_weights calls, each in its own precision, in ONE launch (nr_token_weights_fwd_group: 192 x 256 blocks,
     split-bf16 sets as three accumulated passes).  calls: tuples (prep, w1_hi, w1_lo, b1, w2, b2, mask, n_samples, N); precs: one
-    hip.PREC_* per call.  -> [(w, None), ...], or None when a set does not fit the grouped form (nothing launched: the caller
+    hip.PREC_* per call.  -> [(w, logits or None), ...], or None when a set does not fit the grouped form (nothing launched: the caller
     issues the calls one by one)."""
     import ctypes
     if not FUSE_TOKEN_SOFTMAX or not 0 < len(calls) <= 4:
@@ -203,9 +204,10 @@ def token_weights_group(calls, precs):
         q.w1_hi, q.w1_lo = hip.ptr(w1_hi), hip.ptr(w1_lo, allow_none=True)
         q.b1, q.w2, q.b2 = hip.ptr(b1, torch.float32), hip.ptr(w2, torch.float32), hip.ptr(b2, torch.float32)
         q.mask, q.logit_part, q.counters = hip.ptr(m, allow_none=True), hip.ptr(parts), hip.ptr(counters)
-        q.w, q.logits = hip.ptr(w), None
+        logits = torch.empty((n_samples, N), dtype=torch.float32, device=dev) if want_logits else None
+        q.w, q.logits = hip.ptr(w), hip.ptr(logits, allow_none=True)
         q.n_samples, q.N, q.d, q.H, q.n_counters = int(n_samples), int(N), int(prep.d), int(H), counters.numel()
-        outs.append((w, None))
+        outs.append((w, logits))
         keep += [parts, m]
     pa = (ctypes.c_int * len(calls))(*[int(p) for p in precs])
     hip.N_CALLS += 1

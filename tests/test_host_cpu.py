@@ -193,6 +193,45 @@ def test_tile_query_no_gpu_needed():
         hip.local_level_tiles(4, 200, 4, 12)                         # > 128 tokens per sample: unsupported
 
 
+def test_token_scorer_plan_no_gpu_needed():
+    """nr_token_scorer_plan (host only): the launch form of every row of scorer_ref.FORMS -- the table tests/test_scorer_gpu.py
+    walks --, the two shapes of test_token_weights, and the refusals: NR_EUNSUPPORTED exactly where nr_token_weights_fwd returns
+    it, NR_EINVAL for bad arguments with the outputs untouched."""
+    import scorer_ref as R
+    prec = {"bf16": hip.PREC_BF16, "x3": hip.PREC_BF16X3}
+    seen = set()
+    for call, precs, n, N, form in R.FORMS:
+        for p in precs:
+            if call == "fused":
+                assert hip.token_scorer_plan(n * N, 1024, prec[p], N) == form, (call, p, n, N)
+            else:
+                assert hip.token_scorer_plan(n * N, 1024, prec[p], N) is None, (call, p, n, N)
+                assert hip.token_scorer_plan(n * N, 1024, prec[p], 0) == form, (call, p, n, N)
+            seen.add((p,) + form)
+    # every block of the family on both ring depths where a release build reaches it
+    for form in ((64, 128, 2), (96, 128, 2), (128, 128, 2), (96, 128, 1), (128, 128, 1)):
+        assert ("x3",) + form in seen, form
+    for form in ((64, 128, 2), (96, 128, 2), (128, 128, 2), (128, 128, 1), (128, 256, 2), (128, 256, 1), (192, 256, 2)):
+        assert ("bf16",) + form in seen, form
+    for p in prec.values():
+        # test_token_weights issues the two launches (N_fused = 0: 64-row blocks); ops.token_weights fuses the same sets on 96 rows
+        assert hip.token_scorer_plan(16 * 24, 1024, p, 0) == (64, 128, 2) and hip.token_scorer_plan(128 * 12, 1024, p, 0) == (64, 128, 2)
+        assert hip.token_scorer_plan(16 * 24, 1024, p, 24) == (96, 128, 2) and hip.token_scorer_plan(128 * 12, 1024, p, 12) == (96, 128, 2)
+        assert hip.token_scorer_plan(17 * 24, 128, p, 24) == (96, 128, 2)          # H = 128 admits only the 128-wide blocks
+        assert hip.token_scorer_plan(257 * 24, 128, p, 24)[1] == 128
+        assert hip.token_scorer_plan(2 * 257, 1024, p, 257) is None                 # N > 256
+    assert hip.token_scorer_plan(257 * 24, 1152, hip.PREC_BF16, 24) == (96, 128, 2)   # H % 256: no 8-wave block
+    lib = hip.lib()
+    out = [ctypes.c_int(-7) for _ in range(3)]
+    ref = [ctypes.byref(o) for o in out]
+    for args in ((0, 1024, hip.PREC_BF16, 0), (10, 1000, hip.PREC_BF16, 0), (10, 1024, 9, 0), (10, 1024, hip.PREC_BF16, 3),
+                 (10, 1024, hip.PREC_BF16, -1), (10, 0, hip.PREC_BF16, 0)):
+        assert lib.nr_token_scorer_plan(*args, *ref) == hip.NR_EINVAL, args
+    assert lib.nr_token_scorer_plan(24, 1024, hip.PREC_BF16, 24, None, ref[1], ref[2]) == hip.NR_EINVAL
+    assert lib.nr_token_scorer_plan(9 * 20, 1024, hip.PREC_BF16, 20, *ref) == hip.NR_EUNSUPPORTED
+    assert [o.value for o in out] == [-7, -7, -7]
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_product_path_fails_loudly_without_gpu():
     from neighborretr_amd import ops

@@ -54,6 +54,9 @@ def test_token_weights(prec, tol):
                                (x["mb_feat_v"], x["mb_mask_v"], "video_weight_fc")):
         n, N, _ = feat.shape
         prep = ops.prepare_tokens(feat.to(DEV), mask.to(DEV))
+        # the form this test is about: the two launches of _tw (no fused softmax) on 64 x 128 blocks, two-deep ring; every other
+        # form is held to an fp64 reference in tests/test_scorer_gpu.py
+        assert hip.token_scorer_plan(n * N, 1024, prec, 0) == (64, 128, 2), (n, N)
         w, logits = _tw(prep, mask.to(DEV), Pg, prefix, n, N, prec)
         w_ref = O.token_weights(feat, mask, P, prefix)
         assert maxdiff(w, w_ref) < tol
