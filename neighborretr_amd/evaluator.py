@@ -551,24 +551,32 @@ def _video_units(ranks, ends):
     return ranks[ranks >= 0], kept[np.asarray(ends, dtype=np.int64) - 1] - 1, "low"
 
 
+def _dev32(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+
+
+def _rank_bootstrap(units, other, boot, seed, dev):
+    """(stats, paired): the ops.bootstrap_rank_stats rows of `units` = (entries, unit_end, median) and, with `other`, of both from
+    ONE launch (the same draws) next to the paired summary of units minus other; paired is None without other."""
+    n_boot, _, level = boot
+    rankings = tuple(units[:2]) + (() if other is None else tuple(other[:2]))
+    stats = ops.bootstrap_rank_stats(*(_dev32(x, dev) for x in rankings), cuts=BOOTSTRAP_CUTS, seed=seed, b0=0, n_boot=n_boot)
+    stats = stats.cpu().numpy()
+    if other is None:
+        return stats, None
+    paired = RetrievalMetrics.paired_bootstrap_summary(stats[:, 0], stats[:, 1], BOOTSTRAP_CUTS, units[0], other[0], level, units[2])
+    return stats, dict(paired, seed=seed)
+
+
 def _bootstrap_direction(units, boot, seed, dev, raw_units=None):
     """{"bootstrap": summary of `units`} and, with raw_units, "bootstrap_vs_raw": the paired summary of units minus raw_units from ONE
     launch (the same draws); summaries carry the units they resampled ("entries", "unit_end")."""
-    n_boot, _, level = boot
     entries, unit_end, median = units
-
-    def dev32(a):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-    args = [dev32(entries), dev32(unit_end)]
-    if raw_units is not None:
-        args += [dev32(raw_units[0]), dev32(raw_units[1])]
-    stats = ops.bootstrap_rank_stats(*args, cuts=BOOTSTRAP_CUTS, seed=seed, b0=0, n_boot=n_boot).cpu().numpy()
-    out = {"bootstrap": RetrievalMetrics.bootstrap_summary(stats[:, 0], BOOTSTRAP_CUTS, entries, level, median)}
+    stats, paired = _rank_bootstrap(units, raw_units, boot, seed, dev)
+    out = {"bootstrap": RetrievalMetrics.bootstrap_summary(stats[:, 0], BOOTSTRAP_CUTS, entries, boot[2], median)}
     out["bootstrap"].update(seed=seed, entries=np.asarray(entries, dtype=np.int64), unit_end=np.asarray(unit_end, dtype=np.int64))
-    if raw_units is not None:
-        out["bootstrap_vs_raw"] = RetrievalMetrics.paired_bootstrap_summary(stats[:, 0], stats[:, 1], BOOTSTRAP_CUTS, entries,
-                                                                           raw_units[0], level, median)
-        out["bootstrap_vs_raw"]["seed"] = seed
+    if paired is not None:
+        out["bootstrap_vs_raw"] = paired
     return out
 
 
@@ -772,16 +780,22 @@ def _pair_ranks_from_slab(T_slab, V_slab, n_rows, n_cols, W, rank, ends):
     return rt, rv, (rt >= 0) & (rv >= 0)
 
 
+def _column_bootstrap(columns, other, boot, seed, dev):
+    """(sums, paired): the ops.bootstrap_unit_sums rows of the IR `columns` and, with `other`, of both rankings' columns from ONE
+    launch next to the paired summary of columns minus other; paired is None without other."""
+    n_boot, _, level = boot
+    both = columns if other is None else np.concatenate([columns, other], axis=1)
+    sums = ops.bootstrap_unit_sums(torch.from_numpy(np.ascontiguousarray(both)).to(dev), seed=seed, b0=0, n_boot=n_boot).cpu().numpy()
+    return sums, None if other is None else dict(RetrievalMetrics.ir_paired_bootstrap_summary(sums, columns, other, level), seed=seed)
+
+
 def _ir_bootstrap(columns, boot, seed, dev, raw_columns=None):
     """{"bootstrap": summary of `columns`} and, with raw_columns, "bootstrap_vs_raw": both rankings' columns in ONE launch."""
-    n_boot, _, level = boot
-    both = columns if raw_columns is None else np.concatenate([columns, raw_columns], axis=1)
-    sums = ops.bootstrap_unit_sums(torch.from_numpy(np.ascontiguousarray(both)).to(dev), seed=seed, b0=0, n_boot=n_boot).cpu().numpy()
-    out = {"bootstrap": RetrievalMetrics.ir_bootstrap_summary(sums[:, :columns.shape[1]], columns, level)}
+    sums, paired = _column_bootstrap(columns, raw_columns, boot, seed, dev)
+    out = {"bootstrap": RetrievalMetrics.ir_bootstrap_summary(sums[:, :columns.shape[1]], columns, boot[2])}
     out["bootstrap"].update(seed=seed, columns=columns)
-    if raw_columns is not None:
-        out["bootstrap_vs_raw"] = RetrievalMetrics.ir_paired_bootstrap_summary(sums, columns, raw_columns, level)
-        out["bootstrap_vs_raw"]["seed"] = seed
+    if paired is not None:
+        out["bootstrap_vs_raw"] = paired
     return out
 
 
@@ -842,10 +856,6 @@ def _units_entry(units):
     return {"entries": np.asarray(entries, dtype=np.int64), "unit_end": np.asarray(unit_end, dtype=np.int64), "median": median}
 
 
-def _dev32(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-
-
 def _check_comparable(a, b, what="permutation test"):
     """Refuses two dictionaries whose "units" (and, where both carry "ir", whose IR "columns") do not pair up."""
     for name, m in (("a", a), ("b", b)):
@@ -888,20 +898,10 @@ def _compare_direction(a, b, side, perm, boot, dev):
     if ir:
         out["ir"] = {"permutation": _permutation_of_columns(a["ir"]["columns"], b["ir"]["columns"], n_perm, seed + side, dev)}
     if boot:
-        n_boot, bseed, level = boot
-        ua, ub = a["units"], b["units"]
-        stats = ops.bootstrap_rank_stats(_dev32(ua["entries"], dev), _dev32(ua["unit_end"], dev), _dev32(ub["entries"], dev),
-                                         _dev32(ub["unit_end"], dev), cuts=BOOTSTRAP_CUTS, seed=bseed + side, b0=0,
-                                         n_boot=n_boot).cpu().numpy()
-        out["bootstrap"] = RetrievalMetrics.paired_bootstrap_summary(stats[:, 0], stats[:, 1], BOOTSTRAP_CUTS, ua["entries"],
-                                                                     ub["entries"], level, ua["median"])
-        out["bootstrap"]["seed"] = bseed + side
+        ua, ub = ((u["entries"], u["unit_end"], u["median"]) for u in (a["units"], b["units"]))
+        out["bootstrap"] = _rank_bootstrap(ua, ub, boot, boot[1] + side, dev)[1]
         if ir:
-            ca, cb = a["ir"]["columns"], b["ir"]["columns"]
-            both = torch.from_numpy(np.ascontiguousarray(np.concatenate([ca, cb], axis=1))).to(dev)
-            sums = ops.bootstrap_unit_sums(both, seed=bseed + side, b0=0, n_boot=n_boot).cpu().numpy()
-            out["ir"]["bootstrap"] = RetrievalMetrics.ir_paired_bootstrap_summary(sums, ca, cb, level)
-            out["ir"]["bootstrap"]["seed"] = bseed + side
+            out["ir"]["bootstrap"] = _column_bootstrap(a["ir"]["columns"], b["ir"]["columns"], boot, boot[1] + side, dev)[1]
     return out
 
 

@@ -3,6 +3,7 @@
 Each function allocates its outputs with torch (device memory plumbing only), enqueues the HIP
 kernel on torch's current stream and returns without synchronising.
 """
+import ctypes
 import math
 from collections import namedtuple
 
@@ -147,7 +148,6 @@ def token_weights_pair(calls, prec, want_logits=False):
     """Two token_weights calls of one precision in ONE launch (nr_token_weights_fwd_pair; bit-identical to the single calls).
     calls: two tuples (prep, w1_hi, w1_lo, b1, w2, b2, mask, n_samples, N).  -> [(w, logits or None), (w, logits or None)]; falls
     back to two launches when the two do not run the same block shape."""
-    import ctypes
     dev = calls[0][0].hi.device
     probs, outs, keep = [], [], []
     for prep, w1_hi, w1_lo, b1, w2, b2, mask, n_samples, N in calls:
@@ -186,7 +186,6 @@ def token_weights_group(calls, precs, want_logits=False):
     split-bf16 sets as three accumulated passes).  calls: tuples (prep, w1_hi, w1_lo, b1, w2, b2, mask, n_samples, N); precs: one
     hip.PREC_* per call.  -> [(w, logits or None), ...], or None when a set does not fit the grouped form (nothing launched: the caller
     issues the calls one by one)."""
-    import ctypes
     if not FUSE_TOKEN_SOFTMAX or not 0 < len(calls) <= 4:
         return None
     dev = calls[0][0].hi.device
@@ -736,7 +735,6 @@ def mask_piece(mask):
 def pack_shard(tensors, packed, offsets, kinds=None):
     """nr_pack_shard(_convert): the (contiguous GPU) tensors' bytes at `offsets` inside the uint8 buffer `packed`; a piece of
     kind 1 / 2 (mask_piece) is converted to u8 on the way and takes one byte per ELEMENT."""
-    import ctypes
     n = len(tensors)
     for t in tensors:
         hip.ptr(t)
@@ -752,7 +750,6 @@ def pack_shard(tensors, packed, offsets, kinds=None):
 
 def copy_group(dsts, srcs):
     """nr_copy_group: dsts[k] <- srcs[k] (contiguous GPU tensors of equal size and dtype, at most 12) in one launch."""
-    import ctypes
     n = len(dsts)
     for d_, s_ in zip(dsts, srcs):
         hip.ptr(d_)
@@ -765,7 +762,6 @@ def copy_group(dsts, srcs):
 
 def unpack_gathered(gathered, world, record_bytes, nbytes, offsets, outs, u8_to_f32):
     """nr_unpack_gathered: [world, record_bytes] uint8 -> the rank-major output tensors `outs`."""
-    import ctypes
     n = len(outs)
     for t in outs:
         hip.ptr(t)
@@ -839,7 +835,6 @@ def step_prologue(mask0, mask1, logit_scale, rng_state, n_noise, ring=None):
 def bank_ring_push(banks, batches, head_new, head_dev=None):
     """Ring-buffer push of several bank tensors in one launch (nr_bank_ring_push).  head_dev: int32 [1] device
     tensor holding the head (overrides head_new)."""
-    import ctypes
     n = len(banks)
     cap, n_new = banks[0].shape[0], batches[0].shape[0]
     bs = [b.contiguous() for b in batches]
@@ -1341,6 +1336,34 @@ def _boot_ranking(ranks, unit_end, which, dev=None, U=None):
     return ranks, unit_end, E
 
 
+def _resample_range(seed, first, count, names):
+    """The checked integers (seed, first, count) of a resampling call; names = what the last two are called."""
+    for name, v in (("seed", seed), (names[0], first), (names[1], count)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    seed, first, count = int(seed), int(first), int(count)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must lie in [0, 2^64), got {seed}")
+    if first < 0 or count < 0 or first + count > (1 << 31) - 1:
+        raise ValueError(f"{names[0]} and {names[1]} must be >= 0 with {names[0]} + {names[1]} <= 2^31 - 1, got {first} and {count}")
+    return seed, first, count
+
+
+def _resample_values(values, name):
+    """The checked contiguous [U, Q] int64 values of a unit-sum call: on the GPU, U and Q in range, no sum can overflow."""
+    if not torch.is_tensor(values) or values.dtype != torch.int64 or values.dim() != 2:
+        raise ValueError(f"{name} must be a 2-D int64 tensor [U, Q]")
+    if not values.is_cuda:
+        raise ValueError(f"{name} must be on the GPU (no CPU fallback)")
+    U, Q = values.shape
+    if not 1 <= U <= hip.BOOT_MAX_UNITS or not 1 <= Q <= hip.BOOT_MAX_COLS:
+        raise ValueError(f"{name} must be [U, Q] with U in [1, 2^24] and Q in [1, {hip.BOOT_MAX_COLS}], got {tuple(values.shape)}")
+    largest = max(int(values.max()), -int(values.min()))
+    if U * largest >= hip.BOOT_SUM_LIMIT:
+        raise ValueError(f"{name}: U max|value| = {U} x {largest} reaches 2^62: a resample's sum could overflow")
+    return values.contiguous()
+
+
 def bootstrap_rank_stats(ranks_a, unit_end_a, ranks_b=None, unit_end_b=None, cuts=(1, 5, 10, 50), seed=0, b0=0, n_boot=1000):
     """int64 [n_boot, V, 4 + K] on the device (nr_bootstrap_rank_stats): for resamples b0 .. b0 + n_boot - 1 of the U units drawn
     with replacement and ranking v (V = 2 with ranks_b / unit_end_b, paired: the same draws), over the entries of the drawn units:
@@ -1350,14 +1373,7 @@ def bootstrap_rank_stats(ranks_a, unit_end_a, ranks_b=None, unit_end_b=None, cut
     cuts = _boot_cuts(cuts)
     if (ranks_b is None) != (unit_end_b is None):
         raise ValueError("ranks_b and unit_end_b come together")
-    for name, v in (("seed", seed), ("b0", b0), ("n_boot", n_boot)):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"{name} must be an integer, got {v!r}")
-    seed, b0, n_boot = int(seed), int(b0), int(n_boot)
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must lie in [0, 2^64), got {seed}")
-    if b0 < 0 or n_boot < 0 or b0 + n_boot > (1 << 31) - 1:
-        raise ValueError(f"b0 and n_boot must be >= 0 with b0 + n_boot <= 2^31 - 1, got {b0} and {n_boot}")
+    seed, b0, n_boot = _resample_range(seed, b0, n_boot, ("b0", "n_boot"))
     ra, ea, E_a = _boot_ranking(ranks_a, unit_end_a, "a")
     U = ea.numel()
     rb = eb = None
@@ -1368,7 +1384,6 @@ def bootstrap_rank_stats(ranks_a, unit_end_a, ranks_b=None, unit_end_b=None, cut
     K = len(cuts)
     out = torch.empty((n_boot, V, 4 + K), dtype=torch.int64, device=ra.device)
     if n_boot:
-        import ctypes
         hip.call("nr_bootstrap_rank_stats", hip.ptr(ra), hip.ptr(ea), E_a, hip.ptr(rb, allow_none=True), hip.ptr(eb, allow_none=True),
                  E_b, U, (ctypes.c_int32 * K)(*cuts), K, ctypes.c_uint64(seed), b0, n_boot, hip.ptr(out), hip.stream_ptr())
     return out
@@ -1412,43 +1427,13 @@ def bootstrap_unit_sums(values, seed=0, b0=0, n_boot=1000):
     """int64 [n_boot, Q] on the device (nr_bootstrap_unit_sums): out[i, q] = the sum of values[u, q] over the U units u that resample
     b0 + i draws with replacement -- the draws of bootstrap_rank_stats for the same (seed, b, U).  values [U, Q] int64 on the
     device, U in [1, 2^24], Q in [1, 16], U max|value| < 2^62 (no sum can overflow)."""
-    if not torch.is_tensor(values) or values.dtype != torch.int64 or values.dim() != 2:
-        raise ValueError("values must be a 2-D int64 tensor [U, Q]")
-    if not values.is_cuda:
-        raise ValueError("values must be on the GPU (no CPU fallback)")
-    for name, v in (("seed", seed), ("b0", b0), ("n_boot", n_boot)):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"{name} must be an integer, got {v!r}")
-    seed, b0, n_boot = int(seed), int(b0), int(n_boot)
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must lie in [0, 2^64), got {seed}")
-    if b0 < 0 or n_boot < 0 or b0 + n_boot > (1 << 31) - 1:
-        raise ValueError(f"b0 and n_boot must be >= 0 with b0 + n_boot <= 2^31 - 1, got {b0} and {n_boot}")
-    values = values.contiguous()
+    values = _resample_values(values, "values")
+    seed, b0, n_boot = _resample_range(seed, b0, n_boot, ("b0", "n_boot"))
     U, Q = values.shape
-    if not 1 <= U <= hip.BOOT_MAX_UNITS or not 1 <= Q <= hip.BOOT_MAX_COLS:
-        raise ValueError(f"values must be [U, Q] with U in [1, 2^24] and Q in [1, {hip.BOOT_MAX_COLS}], got {tuple(values.shape)}")
-    largest = max(int(values.max()), -int(values.min()))
-    if U * largest >= hip.BOOT_SUM_LIMIT:
-        raise ValueError(f"U max|value| = {U} x {largest} reaches 2^62: a resample's sum could overflow")
     out = torch.empty((n_boot, Q), dtype=torch.int64, device=values.device)
     if n_boot:
-        import ctypes
         hip.call("nr_bootstrap_unit_sums", hip.ptr(values), U, Q, ctypes.c_uint64(seed), b0, n_boot, hip.ptr(out), hip.stream_ptr())
     return out
-
-
-def _resample_range(seed, first, count, names):
-    """The checked integers (seed, first, count) of a resampling call; names = what the last two are called."""
-    for name, v in (("seed", seed), (names[0], first), (names[1], count)):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"{name} must be an integer, got {v!r}")
-    seed, first, count = int(seed), int(first), int(count)
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must lie in [0, 2^64), got {seed}")
-    if first < 0 or count < 0 or first + count > (1 << 31) - 1:
-        raise ValueError(f"{names[0]} and {names[1]} must be >= 0 with {names[0]} + {names[1]} <= 2^31 - 1, got {first} and {count}")
-    return seed, first, count
 
 
 def permtest_rank_stats(ranks_a, unit_end_a, ranks_b, unit_end_b, cuts=(1, 5, 10, 50), seed=0, p0=0, n_perm=1000):
@@ -1465,7 +1450,6 @@ def permtest_rank_stats(ranks_a, unit_end_a, ranks_b, unit_end_b, cuts=(1, 5, 10
     K = len(cuts)
     out = torch.empty((n_perm, 2, 4 + K), dtype=torch.int64, device=ra.device)
     if n_perm:
-        import ctypes
         hip.call("nr_permtest_rank_stats", hip.ptr(ra), hip.ptr(ea), E_a, hip.ptr(rb), hip.ptr(eb), E_b, U, (ctypes.c_int32 * K)(*cuts),
                  K, ctypes.c_uint64(seed), p0, n_perm, hip.ptr(out), hip.stream_ptr())
     return out
@@ -1475,26 +1459,14 @@ def permtest_unit_sums(values_a, values_b, seed=0, p0=0, n_perm=1000):
     """int64 [n_perm, Q] on the device (nr_permtest_unit_sums): out[i, q] = the sum over the units u of values_b[u, q] where the swap
     bit s(p0 + i, u) of permtest_rank_stats is 1 and of values_a[u, q] where it is 0: side X; side Y is the two inputs' totals minus
     it.  values_a, values_b [U, Q] int64 on one device, U in [1, 2^24], Q in [1, 16], U max|value| < 2^62 for either."""
-    for name, v in (("values_a", values_a), ("values_b", values_b)):
-        if not torch.is_tensor(v) or v.dtype != torch.int64 or v.dim() != 2:
-            raise ValueError(f"{name} must be a 2-D int64 tensor [U, Q]")
-        if not v.is_cuda:
-            raise ValueError(f"{name} must be on the GPU (no CPU fallback)")
+    values_a, values_b = _resample_values(values_a, "values_a"), _resample_values(values_b, "values_b")
     if values_a.shape != values_b.shape or values_a.device != values_b.device:
         raise ValueError(f"values_a and values_b must have one shape and one device, got {tuple(values_a.shape)} and "
                          f"{tuple(values_b.shape)}")
     seed, p0, n_perm = _resample_range(seed, p0, n_perm, ("p0", "n_perm"))
-    values_a, values_b = values_a.contiguous(), values_b.contiguous()
     U, Q = values_a.shape
-    if not 1 <= U <= hip.BOOT_MAX_UNITS or not 1 <= Q <= hip.BOOT_MAX_COLS:
-        raise ValueError(f"values must be [U, Q] with U in [1, 2^24] and Q in [1, {hip.BOOT_MAX_COLS}], got {tuple(values_a.shape)}")
-    for name, v in (("values_a", values_a), ("values_b", values_b)):
-        largest = max(int(v.max()), -int(v.min()))
-        if U * largest >= hip.BOOT_SUM_LIMIT:
-            raise ValueError(f"{name}: U max|value| = {U} x {largest} reaches 2^62: a side's sum could overflow")
     out = torch.empty((n_perm, Q), dtype=torch.int64, device=values_a.device)
     if n_perm:
-        import ctypes
         hip.call("nr_permtest_unit_sums", hip.ptr(values_a), hip.ptr(values_b), U, Q, ctypes.c_uint64(seed), p0, n_perm, hip.ptr(out),
                  hip.stream_ptr())
     return out
@@ -1528,7 +1500,6 @@ def bertadam_plan(entries, groups):
     """Host-only check of a BertAdam table before its upload (nr_bertadam_plan): `entries` a ctypes array of hip.OptimTensor,
     `groups` one of hip.OptimGroup.  Writes every entry's chunk0 -> the number of chunks; raises on a null / misaligned pointer,
     a negative count, a group index out of range or a bad schedule id."""
-    import ctypes
     n_chunks = ctypes.c_int(0)
     hip._check("nr_bertadam_plan", hip.lib().nr_bertadam_plan(entries, len(entries), groups, len(groups), ctypes.byref(n_chunks)))
     return int(n_chunks.value)
@@ -1542,7 +1513,6 @@ def bertadam_step(groups_dev, n_groups, table_dev, n_tensors, n_chunks, workspac
     """The three launches of the multi-tensor BertAdam update (nr_bertadam_step) on the current stream.  groups_dev / table_dev:
     uint8 device tensors holding the uploaded hip.OptimGroup / hip.OptimTensor arrays that bertadam_plan checked (the table
     starts `table_offset` bytes into table_dev); workspace: uint8, bertadam_workspace_bytes(n_tensors, n_chunks) or more."""
-    import ctypes
     if workspace.numel() < bertadam_workspace_bytes(n_tensors, n_chunks):
         raise hip.NrHipError("bertadam_step: workspace too small")
     gmn = -1.0 if global_max_norm is None else float(global_max_norm)
@@ -1557,7 +1527,6 @@ def bertadam_step_guarded(groups_dev, n_groups, table_dev, n_tensors, n_chunks, 
     leaves p, m, v and the step counters as they were.  guard: uint8 device tensor holding one hip.StepGuard (zeroed by the
     caller, last_skipped = -1); ring: uint8 device tensor of n_ring hip.StepRecord, n_ring a power of two in [1, 4096]; losses:
     None or a contiguous float32 device tensor of at most 8 values, copied into the step's record when the launches execute."""
-    import ctypes
     if workspace.numel() < bertadam_workspace_bytes(n_tensors, n_chunks):
         raise hip.NrHipError("bertadam_step_guarded: workspace too small")
     rec = ctypes.sizeof(hip.StepRecord)
@@ -1577,7 +1546,6 @@ def bertadam_step_ema(groups_dev, n_groups, table_dev, n_tensors, n_chunks, work
     """bertadam_step / bertadam_step_guarded (guard and ring given) with the weight EMA inside (nr_bertadam_step_ema).
     shadows_dev: uint8 device tensor holding, `shadows_offset` bytes in, n_tensors 8-byte pointers parallel to the table (0: that
     tensor is not averaged); state: uint8 device tensor holding one hip.EmaState."""
-    import ctypes
     if workspace.numel() < bertadam_workspace_bytes(n_tensors, n_chunks):
         raise hip.NrHipError("bertadam_step_ema: workspace too small")
     if state.numel() < ctypes.sizeof(hip.EmaState) or shadows_dev.numel() < int(shadows_offset) + 8 * int(n_tensors):
@@ -1604,7 +1572,6 @@ def ema_plan(entries, state):
     """Host-only check of a weight-EMA table and state before their upload (nr_ema_plan): `entries` a ctypes array of
     hip.EmaTensor, `state` a hip.EmaState.  Writes every entry's chunk0 -> the number of chunks; raises on a null / misaligned
     pointer, a negative count or a decay outside [0, 1)."""
-    import ctypes
     n_chunks = ctypes.c_int(0)
     hip._check("nr_ema_plan", hip.lib().nr_ema_plan(entries, len(entries), ctypes.byref(state), ctypes.byref(n_chunks)))
     return int(n_chunks.value)
@@ -1613,7 +1580,6 @@ def ema_plan(entries, state):
 def ema_update(table_dev, n_tensors, n_chunks, state):
     """One stand-alone update of every shadow of the uploaded hip.EmaTensor table (nr_ema_update: two launches on the current
     stream); state: uint8 device tensor holding one hip.EmaState."""
-    import ctypes
     if state.numel() < ctypes.sizeof(hip.EmaState) or table_dev.numel() < int(n_tensors) * ctypes.sizeof(hip.EmaTensor):
         raise hip.NrHipError("ema_update: state / table do not have the size of NrEmaState / n_tensors NrEmaTensor")
     hip.call("nr_ema_update", hip.ptr(table_dev, torch.uint8), int(n_tensors), int(n_chunks), hip.ptr(state, torch.uint8),
@@ -1622,7 +1588,6 @@ def ema_update(table_dev, n_tensors, n_chunks, state):
 
 def ema_swap(table_dev, n_tensors, n_chunks):
     """Exchanges the contents of every (parameter, shadow) pair of the uploaded hip.EmaTensor table in place (nr_ema_swap)."""
-    import ctypes
     if table_dev.numel() < int(n_tensors) * ctypes.sizeof(hip.EmaTensor):
         raise hip.NrHipError("ema_swap: the table does not hold n_tensors NrEmaTensor")
     hip.call("nr_ema_swap", hip.ptr(table_dev, torch.uint8), int(n_tensors), int(n_chunks), hip.stream_ptr())

@@ -65,6 +65,13 @@ def _cases():
     c["large_seed"] = dict(a=_random_ranking(rng, 257, 5000), seed=(1 << 40) + 3, n_boot=3)
     c["largest_seed_late_b0"] = dict(a=_random_ranking(rng, 70, 90), seed=(1 << 64) - 1, b0=(1 << 31) - 4, n_boot=3)
     c["long_units"] = dict(a=_random_ranking(rng, 20, 2000, (0, 90)), b=_random_ranking(rng, 20, 2000, (30, 31)), n_boot=3)
+    # the second ranking's select reuses the first one's LDS (hist, wave_tot, pick): both take the successor pass, and a one-pass
+    # select follows a three-pass one and the reverse
+    c["paired_both_need_the_successor"] = dict(a=(np.arange(6) * 1000, np.arange(6)), b=(np.arange(6) * 1000 + 500, np.arange(6)),
+                                               n_boot=130)
+    three, one = _random_ranking(rng, 257, 1 << 30), _random_ranking(rng, 257, 40)
+    c["paired_one_pass_after_three"] = dict(a=three, b=one, n_boot=130)
+    c["paired_three_passes_after_one"] = dict(a=one, b=three, n_boot=130)
     return c
 
 
@@ -88,6 +95,8 @@ def test_kernel_equals_the_restatement_bit_for_bit(name):
         assert (got[:, 0, 2] < got[:, 0, 3]).any() and (got[:, 0, 2] == got[:, 0, 3]).any()
     if name == "n_odd":
         assert (got[:, 0, 2] == got[:, 0, 3]).all()
+    if name == "paired_both_need_the_successor":
+        assert all((got[:, v, 2] < got[:, v, 3]).any() for v in range(2))
 
 
 def test_any_split_of_the_resamples_and_of_the_rankings_gives_the_same_integers():
