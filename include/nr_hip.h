@@ -962,6 +962,29 @@ int nr_permtest_rank_stats(const int32_t* ranks_a, const int32_t* unit_end_a, in
 int nr_permtest_unit_sums(const int64_t* values_a, const int64_t* values_b, int U, int Q, uint64_t seed, int p0, int n_perm,
                           int64_t* out, void* stream);
 
+/* Paired permutation test of hubness (DESIGN.md "Permutation test of hubness"): two rankings A and B as top-k lists idx_a, idx_b
+ * [n_lists, k] int32 over the same queries and one gallery of n_gallery items, exactly as nr_slab_topk_rows / nr_topk_merge write them
+ * (absent slots -1; indices outside [0, n_gallery) are not counted; a list holds an item at most once); gt_begin / gt_end [n_lists]: the
+ * ground-truth gallery range of every list (nr_topk_occurrences's convention, one pair of arrays for both rankings); unit_end [U] int32
+ * = index of the LAST list of unit u (nr_bootstrap_rank_stats's convention: non-decreasing, the unit before unit 0 ends at -1, a unit
+ * may be empty, unit_end[U-1] = n_lists - 1); occ_ab / good_ab [n_gallery] int32 = the sums over A and B of nr_topk_occurrences's occ
+ * and good.  With exactly the swap bits s(p, u) of nr_permtest_rank_stats, side X takes unit u's lists from A when s = 0 and from B
+ * when s = 1, side Y the other ranking's.  With N[j] = the side's lists that hold j and GN[j] = those whose range holds j,
+ *   out [n_perm, 2 (X, Y), 9] int64, exact integers:  S1 = sum N, S2 = sum N^2, S3 = sum N^3, anti = #{N = 0}, hubs = #{N G > 2 S1},
+ *   hub_occ = sum of N over the hubs, bad_hubs = #{hub and N - GN > GN}, good = sum GN, max N;   X + Y = A + B in S1 and good.
+ * One workgroup of 256 threads per permutation: side X's counters in LDS by integer LDS atomics, one 32-bit word per item (N low,
+ * GN high: n_lists < 65 536), side Y as occ_ab - N_X; a wave reads consecutive words of idx, the unit of a word found by shuffles and
+ * its swap bit recomputed; two sweeps over the items; int64 reductions by wave shuffles and through LDS.  Dynamic LDS 4 n_gallery + 576
+ * bytes (above 64 KB the kernel's limit is raised first).  No global atomics, no float atomics, no scratch, no hand-off between
+ * workgroups: the result depends on (seed, p, inputs) alone, whatever the grid and the split over p0.  The kernel stays in bounds
+ * whatever unit_end and idx hold; the caller checks them.
+ * NR_EINVAL before any launch: U outside [1, 2^24], k outside [1, 128], n_lists < 0, n_gallery < 1, p0 < 0, n_perm < 0,
+ * p0 + n_perm > 2^31 - 1, a null pointer.  NR_EUNSUPPORTED before any launch: n_gallery > 32 768 or n_lists >= 65 536.
+ * n_perm = 0: NR_OK, no launch. */
+int nr_permtest_hubness(const int32_t* idx_a, const int32_t* idx_b, int n_lists, int k, const int32_t* unit_end, int U, int n_gallery,
+                        const int32_t* gt_begin, const int32_t* gt_end, const int32_t* occ_ab, const int32_t* good_ab, uint64_t seed,
+                        int p0, int n_perm, int64_t* out, void* stream);
+
 /* Multi-tensor BertAdam step (models/optimization.py:76-211 with the trainer's clip and clamp around it, trainer.py:104-119;
  * DESIGN.md "BertAdam in the captured step").  fp32 tensors only.  Per step, for every table entry t with group q:
  *   c    = min(1, global_max_norm / (sqrt(sum_t ||g_t||^2) + 1e-6))             (global_max_norm <= 0: c = 1)

@@ -140,6 +140,10 @@ def get_args():
                    help="--do_eval with --permutation N: the test set is scored again with the same architecture loaded from PATH, and "
                         "'model - compared' lines give the paired permutation test (with --bootstrap the paired interval too) of "
                         "this model against it")
+    p.add_argument("--hubness_test", type=int, default=0, choices=[0, 1],
+                   help="1, with --hubness_k K and --permutation N: the paired permutation test of the hubness figures (skewness, "
+                        "hubs, bad hubs, anti-hubs, ...) from the relabelled top-K lists on the GPU, for a correction against raw, "
+                        "with --compare_model and for the EMA: every difference with its two-sided p-value (DESIGN.md 6.13); 0 = off")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -218,6 +222,8 @@ def get_args():
     if args.permutation and not (corrected or args.compare_model or args.ema_decay):
         p.error("--permutation needs a correction (--test_norm, --local_scaling, --mutual_proximity), --compare_model or "
                 "--ema_decay: there is nothing to compare")
+    if args.hubness_test and not (args.hubness_k > 0 and args.permutation > 0):
+        p.error("--hubness_test needs --hubness_k > 0 and --permutation > 0")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
         raise ValueError("--batch_size must divide over the ranks (args_parser.py:149-165)")
     return args
@@ -806,12 +812,16 @@ def eval_epoch(args, model, test, tag=""):
                 log(args, RetrievalMetrics.format_bootstrap(m["bootstrap_vs_raw"], prefix=f"{side} {tag} - raw "))
 
     def log_permutation(nt, nv, tag):
-        """The paired permutation test of a correction against raw: one line per direction, and one for its IR metrics."""
+        """The paired permutation test of a correction against raw: one line per direction, one for its IR metrics and, with
+        --hubness_test, one for its hubness."""
         for side, m in (("text->video", nt), ("video->text", nv)):
             if "permutation_vs_raw" in m:
                 log(args, RetrievalMetrics.format_permutation(m["permutation_vs_raw"], prefix=f"{side} {tag} - raw "))
             if "permutation_vs_raw" in m.get("ir", {}):
                 log(args, RetrievalMetrics.format_permutation(m["ir"]["permutation_vs_raw"], prefix=f"{side} {tag} - raw "))
+            if "permutation_vs_raw" in m.get("hubness", {}):
+                log(args, RetrievalMetrics.format_hubness_permutation(m["hubness"]["permutation_vs_raw"], m["hubness"]["k"],
+                                                                      prefix=f"{side} {tag} - raw: "))
     model.eval()
     dev = args.device
     mine = rank_sample_indices(test.n, args.world_size, args.rank)     # equal counts on every rank (padded like DistributedSampler)
@@ -879,6 +889,9 @@ def _log_comparison(args, cmp, what, versus):
             log(args, RetrievalMetrics.format_permutation(c["ir"]["permutation"], prefix=prefix, versus=versus))
             if "bootstrap" in c["ir"]:
                 log(args, RetrievalMetrics.format_ir_bootstrap(c["ir"]["bootstrap"], prefix=prefix, versus=versus))
+        if "hubness" in c:
+            log(args, RetrievalMetrics.format_hubness_permutation(c["hubness"]["permutation"], c["hubness"]["k"], prefix=prefix,
+                                                                  versus=versus))
     for side, c in zip(("text->video", "video->text"), cmp):
         lines(c, f"{what} {side} ")
         for key in CORRECTION_KEYS:

@@ -9,21 +9,14 @@
 // swap bits are counter-based: every pass recomputes them, nothing is stored per permutation.  One workgroup per permutation.  Where
 // the bootstrap gathers (position t reads a DRAWN unit), here position u reads unit u of one of the two rankings: the threads stride
 // over u, so `unit_end` and the entries are read coalesced -- the one structural gain over nr_bootstrap.hip, and why the two entry
-// walks stay apart.  This file holds the swap rule with its salt, the walk over a thread's entries of one side, the kernels' LDS and
-// orchestration (pass 0 serves both sides behind one barrier, then one select per side) and the entry points; pass 0, the radix
-// select of the order statistics and the sums of per-unit columns are the resampling engine's (nr_resample.h), shared with
-// nr_bootstrap.hip.  No global atomics, no scratch, no hand-off between workgroups: the result is a function of (seed, p, inputs)
+// walks stay apart.  This file holds the walk over a thread's entries of one side, the kernels' LDS and orchestration (pass 0 serves
+// both sides behind one barrier, then one select per side) and the entry points; the swap rule with its salt (shared with
+// nr_hubperm.hip), pass 0, the radix select of the order statistics and the sums of per-unit columns are the resampling engine's
+// (nr_resample.h), shared with nr_bootstrap.hip.  No global atomics, no scratch, no hand-off between workgroups: the result is a function of (seed, p, inputs)
 // alone, the same for any grid and any split of the permutations over calls.
 #include "nr_common.h"
 #include "nr_resample.h"
 #include "../../include/nr_hip.h"
-
-#define NR_PERM_SALT 0x7065726D74657374ull
-
-// s(p, u); base = (seed ^ salt) + ((p << 32) + 1) * golden
-__device__ __forceinline__ int nr_perm_swap(uint64_t base, int u) {
-    return (int)(nr_boot_mix(base + (uint64_t)(uint32_t)u * NR_BOOT_GOLDEN) >> 63);
-}
 
 // f(r) for every entry r of `side` (0: X, 1: Y) that this thread owns: the entries of unit u = tid, tid + 256, ... of the ranking
 // the swap bit gives that side

@@ -1,5 +1,5 @@
-// The resampling engine of nr_bootstrap.hip and nr_permtest.hip: the workgroup shape, the limits, the descriptor of one ranking,
-// SplitMix64's output function, what the entry points check alike, and the three device templates both files instantiate -- pass 0
+// The resampling engine of nr_bootstrap.hip, nr_permtest.hip and nr_hubperm.hip: the workgroup shape, the limits, the descriptor of one ranking,
+// SplitMix64's output function, the swap rule of the permutation tests, what the entry points check alike, and the three device templates both files instantiate -- pass 0
 // (n, sum, hits, the largest rank), the radix select of the two middle order statistics, and the sums of per-unit columns.  A file
 // brings its resampling rule as a callable: `entries(f)` calls f(r) for every rank r the calling thread owns, `row(t)` is the row
 // of values that unit position t reads.  Every thread of the workgroup calls a template with the same multiset of entries spread
@@ -57,6 +57,13 @@ __device__ __forceinline__ uint64_t nr_boot_mix(uint64_t z) {
 // the state of this workgroup's resample first + blockIdx.x: position t of it mixes base + t * golden
 __device__ __forceinline__ uint64_t nr_resample_base(uint64_t seed, uint32_t first) {
     return seed + ((((uint64_t)first + blockIdx.x) << 32) + 1ull) * NR_BOOT_GOLDEN;
+}
+
+// the swap bit s(p, u) of the paired permutation tests (nr_permtest.hip, nr_hubperm.hip); base = nr_resample_base(seed ^ salt, p0):
+// (seed ^ salt) + ((p << 32) + 1) * golden.  The salt keeps the stream apart from the bootstrap's draws at equal seeds.
+#define NR_PERM_SALT 0x7065726D74657374ull
+__device__ __forceinline__ int nr_perm_swap(uint64_t base, int u) {
+    return (int)(nr_boot_mix(base + (uint64_t)(uint32_t)u * NR_BOOT_GOLDEN) >> 63);
 }
 
 // entries [lo, hi] of unit u, clamped to the ranking's extent

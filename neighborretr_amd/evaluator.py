@@ -217,8 +217,27 @@ def _topk_from_slab(S_slab, n_rows, n_cols, k, W, rank):
     return ri, rv, ci, cv
 
 
-def _row_hubness(S_slab, n_rows, n_cols, k, W, rank, ends):
-    """Hubness of the row (text -> video) lists: each rank counts its rows, one int32 all-reduce."""
+def _lists_entry(idx, unit_end, gt_begin, gt_end):
+    """What a "hubness" entry carries of its top-k lists under "lists" (hubness_test): the lists, their resampling units and their
+    ground-truth ranges, as NumPy arrays."""
+    return {"idx": idx.cpu().numpy().astype(np.int32), "unit_end": np.asarray(unit_end, dtype=np.int64),
+            "gt_begin": gt_begin.cpu().numpy().astype(np.int32), "gt_end": gt_end.cpu().numpy().astype(np.int32)}
+
+
+def _gathered_row_lists(ri, n_rows, W, rank):
+    """Every rank's row lists [n_rows, k] int32 from this rank's ri: the indices travel transposed, as in _topk_from_slab."""
+    if W == 1:
+        return ri
+    r0, r1 = slab_bounds(n_rows, W, rank)
+    k = ri.shape[1]
+    mine = torch.zeros((k, -(-n_rows // W)), dtype=torch.int32, device=ri.device)
+    mine[:, :r1 - r0] = ri.T
+    return _gathered_rows(mine, n_rows, W).T.contiguous()
+
+
+def _row_hubness(S_slab, n_rows, n_cols, k, W, rank, ends, lists=False):
+    """Hubness of the row (text -> video) lists: each rank counts its rows, one int32 all-reduce.  lists: the entry also carries
+    every rank's row lists (one more all-gather); their unit is the query, in a multi-sentence set the video."""
     r0, r1 = slab_bounds(n_rows, W, rank)
     rb, re_, _, _ = _ground_truth(n_rows, n_cols, ends, S_slab.device)
     ri, _ = _slab_row_lists(S_slab, k, n_cols)
@@ -226,20 +245,28 @@ def _row_hubness(S_slab, n_rows, n_cols, k, W, rank, ends):
     if W > 1:
         comm.all_reduce(occ_t)                                        # the ranks' row counts -> the whole matrix's
     occ_t = occ_t.cpu().numpy()
-    return RetrievalMetrics.hubness_from_occurrences(occ_t[0], occ_t[1], k, n_rows)
+    hub = RetrievalMetrics.hubness_from_occurrences(occ_t[0], occ_t[1], k, n_rows)
+    if lists:
+        unit_end = np.arange(n_rows) if ends is None else np.asarray(ends, dtype=np.int64) - 1
+        hub["lists"] = _lists_entry(_gathered_row_lists(ri, n_rows, W, rank), unit_end, rb, re_)
+    return hub
 
 
-def _col_hubness(S_slab, n_rows, n_cols, k, W, rank, ends):
-    """Hubness of the column (video -> text) lists: partial lists, one all-gather, merge (_column_lists)."""
+def _col_hubness(S_slab, n_rows, n_cols, k, W, rank, ends, lists=False):
+    """Hubness of the column (video -> text) lists: partial lists, one all-gather, merge (_column_lists).  lists: the entry also
+    carries them (complete on every rank already); their unit is the video."""
     _, _, cb, ce = _ground_truth(n_rows, n_cols, ends, S_slab.device)
     ci, _ = _column_lists(S_slab, n_rows, n_cols, k, W, rank)
     occ_v = torch.stack(ops.topk_occurrences(ci, n_rows, cb, ce)).cpu().numpy()
-    return RetrievalMetrics.hubness_from_occurrences(occ_v[0], occ_v[1], k, n_cols)
+    hub = RetrievalMetrics.hubness_from_occurrences(occ_v[0], occ_v[1], k, n_cols)
+    if lists:
+        hub["lists"] = _lists_entry(ci, np.arange(n_cols), cb, ce)
+    return hub
 
 
-def _hubness_from_slab(S_slab, n_rows, n_cols, k, W, rank, ends):
-    return (_row_hubness(S_slab, n_rows, n_cols, k, W, rank, ends),
-            _col_hubness(S_slab, n_rows, n_cols, k, W, rank, ends))
+def _hubness_from_slab(S_slab, n_rows, n_cols, k, W, rank, ends, lists=False):
+    return (_row_hubness(S_slab, n_rows, n_cols, k, W, rank, ends, lists),
+            _col_hubness(S_slab, n_rows, n_cols, k, W, rank, ends, lists))
 
 
 def _check_hubness_k(hubness_k):
@@ -501,17 +528,17 @@ def _metrics_and_units(T_slab, V_slab, n_rows, n_cols, W, rank, ends):
     return t2v, RetrievalMetrics.metrics_from_ranks(video_units[0]), (_video_units(ranks, ends), video_units)
 
 
-def _metrics_from_normalised(T_slab, V_slab, n_rows, n_cols, W, rank, ends, hubness_k, units=None):
-    """(t2v, v2t) of _metrics_and_units, and with hubness_k the hubness of T's row lists and V's column lists.  units: a list
-    that receives the two directions' resampling units."""
+def _metrics_from_normalised(T_slab, V_slab, n_rows, n_cols, W, rank, ends, hubness_k, units=None, lists=False):
+    """(t2v, v2t) of _metrics_and_units, and with hubness_k the hubness of T's row lists and V's column lists (lists: each entry
+    with its "lists").  units: a list that receives the two directions' resampling units."""
     t2v, v2t, u = _metrics_and_units(T_slab, V_slab, n_rows, n_cols, W, rank, ends)
     if units is not None:
         units.extend(u)
     if hubness_k and V_slab is T_slab:
-        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(T_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(T_slab, n_rows, n_cols, hubness_k, W, rank, ends, lists)
     elif hubness_k:
-        t2v["hubness"] = _row_hubness(T_slab, n_rows, n_cols, hubness_k, W, rank, ends)
-        v2t["hubness"] = _col_hubness(V_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+        t2v["hubness"] = _row_hubness(T_slab, n_rows, n_cols, hubness_k, W, rank, ends, lists)
+        v2t["hubness"] = _col_hubness(V_slab, n_rows, n_cols, hubness_k, W, rank, ends, lists)
     return t2v, v2t
 
 
@@ -872,6 +899,45 @@ def _check_comparable(a, b, what="permutation test"):
         ca, cb = np.asarray(a["ir"]["columns"]), np.asarray(b["ir"]["columns"])
         if ca.shape != cb.shape or ca.ndim != 2 or ca.shape[0] != len(ua["unit_end"]):
             raise ValueError(f"{what}: the two rankings' IR columns are {ca.shape} and {cb.shape} over {len(ua['unit_end'])} units")
+    if _has_lists(a) and _has_lists(b):
+        ha, hb = a["hubness"], b["hubness"]
+        la, lb = ha["lists"], hb["lists"]
+        if ha["k"] != hb["k"] or la["idx"].shape != lb["idx"].shape:
+            raise ValueError(f"{what}: the two rankings' top-k lists are {la['idx'].shape} (k = {ha['k']}) and {lb['idx'].shape} "
+                             f"(k = {hb['k']})")
+        if ha["n_gallery"] != hb["n_gallery"]:
+            raise ValueError(f"{what}: the two rankings' galleries hold {ha['n_gallery']} and {hb['n_gallery']} items")
+        if any(not np.array_equal(la[key], lb[key]) for key in ("unit_end", "gt_begin", "gt_end")):
+            raise ValueError(f"{what}: the two rankings' top-k lists have different units or ground-truth ranges")
+
+
+def _has_lists(m):
+    return "hubness" in m and "lists" in m["hubness"]
+
+
+def _check_hubness_test(hubness_test, hubness_k=0, perm=None, n_rows=None, n_cols=None):
+    """hubness_test as a bool (--hubness_test {0,1}); with it hubness_k and permutation must be set and, once the sizes are known,
+    both directions' galleries must fit nr_permtest_hubness (the limit of the lists lies above that of the gallery)."""
+    if isinstance(hubness_test, (bool, np.bool_)) or (isinstance(hubness_test, (int, np.integer)) and int(hubness_test) in (0, 1)):
+        hubness_test = bool(hubness_test)
+    else:
+        raise ValueError(f"hubness_test must be 0 or 1, got {hubness_test!r}")
+    if hubness_test and (not hubness_k or perm is None):
+        raise ValueError("hubness_test needs hubness_k > 0 (the top-k lists it relabels) and permutation > 0 (how many relabellings)")
+    if hubness_test and n_rows is not None:
+        if max(n_rows, n_cols) > ops.hip.HUBPERM_MAX_GALLERY:
+            raise ValueError(f"hubness_test: a gallery of {max(n_rows, n_cols)} items is above the limit of {ops.hip.HUBPERM_MAX_GALLERY}")
+    return hubness_test
+
+
+def _hubness_permutation(hub, other, n_perm, seed, dev):
+    """RetrievalMetrics.hubness_permutation_summary of the "hubness" entry `hub` minus `other` (both with "lists" over the same
+    units): the two rankings' occurrence counts and one launch of the relabellings."""
+    la, lb = hub["lists"], other["lists"]
+    stats = ops.permtest_hubness(_dev32(la["idx"], dev), _dev32(lb["idx"], dev), _dev32(la["unit_end"], dev), hub["n_gallery"],
+                                 _dev32(la["gt_begin"], dev), _dev32(la["gt_end"], dev), seed=seed, p0=0, n_perm=n_perm).cpu().numpy()
+    moments = (RetrievalMetrics.hubness_moments(h["occurrence"], h["good_occurrence"]) for h in (hub, other))
+    return RetrievalMetrics.hubness_permutation_summary(stats, *moments, hub["n_gallery"], seed)
 
 
 def _permutation_of_units(units, other, n_perm, seed, dev):
@@ -897,6 +963,8 @@ def _compare_direction(a, b, side, perm, boot, dev):
     ir = "ir" in a and "ir" in b
     if ir:
         out["ir"] = {"permutation": _permutation_of_columns(a["ir"]["columns"], b["ir"]["columns"], n_perm, seed + side, dev)}
+    if _has_lists(a) and _has_lists(b):
+        out["hubness"] = {"k": a["hubness"]["k"], "permutation": _hubness_permutation(a["hubness"], b["hubness"], n_perm, seed + side, dev)}
     if boot:
         ua, ub = ((u["entries"], u["unit_end"], u["median"]) for u in (a["units"], b["units"]))
         out["bootstrap"] = _rank_bootstrap(ua, ub, boot, boot[1] + side, dev)[1]
@@ -910,7 +978,8 @@ def compare_evaluations(a, b, permutation, permutation_seed=0, bootstrap=0, boot
     sharded_evaluation calls with permutation > 0 (two checkpoints, or two settings, scored on the SAME test set).  ->
     (text->video, video->text) comparison dictionaries of "a minus b": "permutation" (RetrievalMetrics.permutation_summary; seed for
     text->video, seed + 1 for video->text); with bootstrap > 0 "bootstrap" (paired_bootstrap_summary on the draws of the bootstrap);
-    the same two under "ir" when both results carry "ir", and all of it under a correction's key when both carry the same one.
+    the same two under "ir" when both results carry "ir", ["hubness"]["permutation"] (hubness_permutation_summary) when both carry
+    their top-k lists (hubness_test), and all of it under a correction's key when both carry the same one.
     ValueError when the units, the median kind or the column layout of the two results differ."""
     perm = _check_permutation(permutation, permutation_seed)
     if perm is None:
@@ -1022,7 +1091,7 @@ def _corrected_entry(metrics, correction, info, side):
 
 def sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, correction=None, hubness_k=0, cut_off_points=None,
                        chunk=256, querybank=None, bootstrap=0, bootstrap_seed=0, bootstrap_level=0.95, ir=False, permutation=0,
-                       permutation_seed=0):
+                       permutation_seed=0, hubness_test=False):
     """-> (text->video, video->text) metric dictionaries, identical on every rank, from ONE scoring of this rank's slab: R@K as
     RetrievalMetrics.compute_metrics(S) / (S.T) would give them (cut_off_points: the multi-sentence metrics, see
     sharded_multi_sentence_metrics).  hubness_k: each with a "hubness" entry (sharded_hubness).  ir: an "ir" entry (DESIGN.md
@@ -1032,11 +1101,15 @@ def sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args
     querybank: (text_feat, text_mask, video_feat, video_mask) for a correction that needs one; None: the model's memory bank.
     permutation > 0 (DESIGN.md "Paired permutation tests"): every dictionary, the correction's too, also carries its resampling
     "units" (entries, unit_end, median) and its "ir" entry its "columns" -- what compare_evaluations reads --, and the correction's
-    dictionary and its "ir" entry gain "permutation_vs_raw", the paired permutation test of corrected minus raw."""
+    dictionary and its "ir" entry gain "permutation_vs_raw", the paired permutation test of corrected minus raw.
+    hubness_test (DESIGN.md "Permutation test of hubness"; needs hubness_k > 0 and permutation > 0): every "hubness" entry, the
+    correction's too, also carries its top-k "lists" (idx, unit_end, gt_begin, gt_end; the row lists of a sharded run cost one more
+    all-gather), and the correction's "hubness" entry gains "permutation_vs_raw", the test of corrected minus raw hubness."""
     boot = _check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level)
     perm = _check_permutation(permutation, permutation_seed)
     ir = _check_ir(ir)
     hubness_k = _check_hubness_k(hubness_k)
+    hubness_test = _check_hubness_test(hubness_test, hubness_k, perm, text_feat.shape[0], video_feat.shape[0])
     if correction is not None and correction.needs_bank:
         _querybank(model, querybank, text_feat.device)                 # an empty bank fails before any scoring
     slab = _eval_slab(model, text_feat, video_feat, text_mask, video_mask, args, cut_off_points, chunk)
@@ -1044,7 +1117,7 @@ def sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args
     dev = S_slab.device
     t2v, v2t, raw_units = _metrics_and_units(S_slab, S_slab, n_rows, n_cols, W, rank, ends)
     if hubness_k:
-        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends)
+        t2v["hubness"], v2t["hubness"] = _hubness_from_slab(S_slab, n_rows, n_cols, hubness_k, W, rank, ends, hubness_test)
     raw_columns = _add_ir(t2v, v2t, S_slab, S_slab, n_rows, n_cols, W, rank, ends, boot) if ir else None
     _add_bootstrap(t2v, v2t, raw_units, boot, dev)
     if perm:
@@ -1054,12 +1127,15 @@ def sharded_evaluation(model, text_feat, video_feat, text_mask, video_mask, args
     T, V, info = _apply_correction(model, text_feat, video_feat, text_mask, video_mask, slab, correction, querybank, chunk)
     del S_slab, slab                       # the raw slab, the largest buffer of the evaluation, goes before the corrected metrics
     units = []
-    nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k, units)
+    nt, nv = _metrics_from_normalised(T, V, n_rows, n_cols, W, rank, ends, hubness_k, units, hubness_test)
     _add_bootstrap(nt, nv, units, boot, dev, raw_units)
     columns = _add_ir(nt, nv, T, V, n_rows, n_cols, W, rank, ends, boot, raw_columns) if ir else None
     if perm:
         _carry_units(nt, nv, units, columns)
         _add_permutation(nt, nv, units, raw_units, perm, dev, columns, raw_columns)
+    if hubness_test:
+        for side, (m, raw) in enumerate(((nt, t2v), (nv, v2t))):
+            m["hubness"]["permutation_vs_raw"] = _hubness_permutation(m["hubness"], raw["hubness"], perm[0], perm[1] + side, dev)
     t2v[correction.key] = _corrected_entry(nt, correction, info, 0)
     v2t[correction.key] = _corrected_entry(nv, correction, info, 1)
     return t2v, v2t
@@ -1203,8 +1279,8 @@ def sharded_metrics_with_mutual_proximity(model, text_feat, video_feat, text_mas
 
 def correction_from_args(args, model):
     """What the command-line flags ask of the evaluation -> (correction or None, the keyword arguments of sharded_evaluation:
-    hubness_k, the bootstrap triple, ir and, when asked for, permutation and its seed), everything checked before any work: the
-    values, that at most one correction is chosen, that a permutation test has something to compare (a correction,
+    hubness_k, the bootstrap triple, ir and, when asked for, permutation with its seed and hubness_test), everything checked before
+    any work: the values, that at most one correction is chosen, that a permutation test has something to compare (a correction,
     args.compare_model, or the weight average of args.ema_decay), and that a correction that needs a querybank finds the model's memory bank filled."""
     kw = dict(bootstrap=getattr(args, "bootstrap", 0) or 0, bootstrap_seed=getattr(args, "bootstrap_seed", 0) or 0,
               bootstrap_level=getattr(args, "bootstrap_level", 0.95))
@@ -1233,6 +1309,8 @@ def correction_from_args(args, model):
             raise ValueError("permutation needs a correction (test_norm, local_scaling, mutual_proximity) or compare_model or "
                              "ema_decay: there is nothing to compare")
         kw.update(permutation=perm[0], permutation_seed=perm[1])
+    if _check_hubness_test(getattr(args, "hubness_test", 0) or 0, kw["hubness_k"], perm):
+        kw["hubness_test"] = True
     if correction is not None and correction.needs_bank:
         _querybank(model, None, model.mb_feat_t.device)         # checked where it lies: nothing is copied
     return correction, kw

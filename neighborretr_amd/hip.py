@@ -283,6 +283,7 @@ _SIGNATURES = {
     "nr_bootstrap_unit_sums": ([_P, _I, _I, ctypes.c_uint64, _I, _I, _P, _P], _I),
     "nr_permtest_rank_stats": ([_P, _P, _I, _P, _P, _I, _I, _P, _I, ctypes.c_uint64, _I, _I, _P, _P], _I),
     "nr_permtest_unit_sums": ([_P, _P, _I, _I, ctypes.c_uint64, _I, _I, _P, _P], _I),
+    "nr_permtest_hubness": ([_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, ctypes.c_uint64, _I, _I, _P, _P], _I),
     "nr_bertadam_plan": ([ctypes.POINTER(OptimTensor), _I, ctypes.POINTER(OptimGroup), _I, ctypes.POINTER(_I)], _I),
     "nr_bertadam_workspace_bytes": ([_I, _I], _Z),
     "nr_bertadam_step": ([_P, _I, _I, _P, _I, _F, _P, _P], _I),
@@ -299,6 +300,7 @@ MP_LINE_MAX = 1 << 23                        # a mutual-proximity reference line
 BOOT_MAX_UNITS, BOOT_MAX_CUTS, BOOT_RANK_LIMIT = 1 << 24, 8, 1 << 30      # nr_bootstrap_rank_stats: U, K and the ranks' bound
 BOOT_MAX_COLS, BOOT_SUM_LIMIT = 16, 1 << 62  # nr_bootstrap_unit_sums: Q and the bound of U max|value|
 PERM_SALT = 0x7065726D74657374                # nr_permtest_*: xor-ed into the seed of the swap bits; U, K, Q and the bounds are BOOT_*
+HUBPERM_MAX_GALLERY, HUBPERM_MAX_LISTS = 32768, 65535      # nr_permtest_hubness: 4 G bytes of LDS, and N in 16 bits of a counter word
 GUARD_MAX_LOSSES, GUARD_MAX_RING = 8, 4096   # nr_bertadam_step_guarded: n_losses and n_ring (a power of two)
 SCHEDULE_IDS = {"warmup_cosine": 0, "warmup_constant": 1, "warmup_linear": 2}      # NR_SCHEDULE_*
 

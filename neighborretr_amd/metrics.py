@@ -503,6 +503,92 @@ class RetrievalMetrics:
         if self.logger is not None:
             self.logger.info(self.format_permutation(summary, prefix, versus))
 
+    # ---- paired permutation test of hubness (DESIGN.md "Permutation test of hubness") ---------------------------------------------------
+    HUBNESS_TEST_METRICS = ("skewness", "anti_hub_pct", "hub_pct", "bad_hub_pct", "hub_occurrence_pct", "good_occurrence_pct",
+                            "max_occurrence")
+    HUBNESS_TEST_LABELS = {"skewness": "skew", "anti_hub_pct": "anti-hubs", "hub_pct": "hubs", "bad_hub_pct": "bad hubs",
+                           "hub_occurrence_pct": "hub occurrence", "good_occurrence_pct": "good occurrence", "max_occurrence": "max N_k"}
+
+    @staticmethod
+    def hubness_moments(occ, good):
+        """int64 [9], the integers of ops.permtest_hubness for un-permuted k-occurrence counts occ = N and good = GN over the gallery:
+        S1 = sum N, S2 = sum N^2, S3 = sum N^3, #{N = 0}, hubs = #{N G > 2 S1}, the sum of N over the hubs, #{hub and N - GN > GN},
+        sum GN, max N."""
+        occ = np.asarray(occ, dtype=np.int64).reshape(-1)
+        good = np.asarray(good, dtype=np.int64).reshape(-1)
+        if occ.shape != good.shape or occ.size == 0:
+            raise ValueError("occ and good must be non-empty and of one length")
+        s1 = int(occ.sum())
+        hubs = occ * occ.size > 2 * s1
+        return np.asarray([s1, int(np.sum(occ ** 2)), int(np.sum(occ ** 3)), int(np.sum(occ == 0)), int(np.sum(hubs)),
+                           int(np.sum(occ[hubs])), int(np.sum(hubs & (occ - good > good))), int(good.sum()), int(occ.max())],
+                          dtype=np.int64)
+
+    @staticmethod
+    def _hubness_skewness(m, G):
+        """fp64 skewness of rows (S1, S2, S3, ...) of Python ints (object arrays): float(c) / (float(a) sqrt(float(a))) with
+        a = G S2 - S1^2 and c = G^2 S3 - 3 G S1 S2 + 2 S1^3 taken exactly; 0.0 where a = 0."""
+        s1, s2, s3 = m[..., 0], m[..., 1], m[..., 2]
+        a = np.asarray(G * s2 - s1 * s1, dtype=object)
+        c = np.asarray(G * G * s3 - 3 * G * s1 * s2 + 2 * s1 * s1 * s1, dtype=object)
+        a, c = a.astype(np.float64), c.astype(np.float64)                      # float() of every exact integer: rounded once
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(a != 0, c / (a * np.sqrt(a)), 0.0)
+
+    @staticmethod
+    def _hubness_ratios(m, G):
+        """{metric: (numerator, denominator)} of the six rational figures of rows of the nine integers (object arrays)."""
+        one = 1 + 0 * m[..., 0]
+        return {"anti_hub_pct": (100 * m[..., 3], G * one), "hub_pct": (100 * m[..., 4], G * one), "bad_hub_pct": (100 * m[..., 6], G * one),
+                "hub_occurrence_pct": (100 * m[..., 5], m[..., 0]), "good_occurrence_pct": (100 * m[..., 7], m[..., 0]),
+                "max_occurrence": (m[..., 8], one)}
+
+    @staticmethod
+    def hubness_permutation_summary(stats, moments_a, moments_b, n_gallery, seed=0):
+        """Paired permutation (randomisation) test of the hubness of "ranking A minus ranking B": stats [n_perm, 2, 9] int64
+        (ops.permtest_hubness: the sides X, Y of every relabelling), moments_a / moments_b = hubness_moments of the un-permuted A / B
+        over the gallery of n_gallery items.  Per side: skewness (the formula of _hubness_skewness), anti_hub_pct = 100 anti / G,
+        hub_pct, bad_hub_pct likewise, hub_occurrence_pct = 100 hub_occ / S1, good_occurrence_pct = 100 good / S1, max_occurrence.
+        d_p = m(X_p) - m(Y_p), d_0 = m(A) - m(B); permutations with an empty side (S1 = 0) are dropped (n_empty).  -> {"n_perm",
+        "n_empty", "kept", "seed", and per metric "diff", "p_two", "p_ge", "p_le" as permutation_summary}.  The six rational figures
+        are compared on cross-multiplied Python integers; skewness is irrational and is compared in fp64: equal integers give equal
+        doubles, and the mirror image of a relabelling gives exactly -d."""
+        stats = np.asarray(stats.cpu() if torch.is_tensor(stats) else stats, dtype=np.int64)
+        ma, mb = (np.asarray(m, dtype=np.int64).reshape(-1).astype(object) for m in (moments_a, moments_b))
+        if stats.ndim != 3 or stats.shape[1:] != (2, 9) or ma.shape != (9,) or mb.shape != (9,):
+            raise ValueError(f"stats must be [n_perm, 2, 9] and both moments [9], got {stats.shape}, {ma.shape} and {mb.shape}")
+        G = int(n_gallery)
+        if G < 1:
+            raise ValueError(f"n_gallery must be positive, got {n_gallery!r}")
+        keep = (stats[:, 0, 0] > 0) & (stats[:, 1, 0] > 0)
+        kept = int(np.sum(keep))
+        out = {"n_perm": int(len(stats)), "n_empty": int(np.sum(~keep)), "kept": kept, "seed": int(seed)}
+        x, y = stats[keep, 0].astype(object), stats[keep, 1].astype(object)
+        rx, ry = RetrievalMetrics._hubness_ratios(x, G), RetrievalMetrics._hubness_ratios(y, G)
+        if ma[0] == 0 or mb[0] == 0:
+            out["skewness"] = {"diff": float("nan"), "p_two": float("nan"), "p_ge": float("nan"), "p_le": float("nan")}
+            return RetrievalMetrics._permutation_p_values(out, rx, ry, None, None, keep)
+        d0 = float(RetrievalMetrics._hubness_skewness(ma, G) - RetrievalMetrics._hubness_skewness(mb, G))
+        d = RetrievalMetrics._hubness_skewness(x, G) - RetrievalMetrics._hubness_skewness(y, G) if kept else np.zeros((0,))
+        two, ge, le = int(np.sum(np.abs(d) >= abs(d0))), int(np.sum(d >= d0)), int(np.sum(d <= d0))
+        out["skewness"] = {"diff": d0, "p_two": (1 + two) / (1 + kept), "p_ge": (1 + ge) / (1 + kept), "p_le": (1 + le) / (1 + kept)}
+        return RetrievalMetrics._permutation_p_values(out, rx, ry, RetrievalMetrics._hubness_ratios(ma, G),
+                                                      RetrievalMetrics._hubness_ratios(mb, G), keep)
+
+    @staticmethod
+    def format_hubness_permutation(summary, k, prefix="", versus="raw"):
+        """One line: every hubness figure's signed difference and its two-sided p-value."""
+        parts = [f"{RetrievalMetrics.HUBNESS_TEST_LABELS[n]} {summary[n]['diff']:+.2f} p={summary[n]['p_two']:.4f}"
+                 for n in RetrievalMetrics.HUBNESS_TEST_METRICS]
+        tail = f" (paired permutation test vs {versus}, {summary['n_perm']} permutations"
+        tail += f", {summary['n_empty']} empty)" if summary["n_empty"] else ")"
+        return f"{prefix}Hubness@{int(k)}: " + " - ".join(parts) + tail
+
+    def log_hubness_permutation(self, summary, k, prefix="", versus="raw"):
+        """One line per direction, in the style of log_permutation (silent without a logger)."""
+        if self.logger is not None:
+            self.logger.info(self.format_hubness_permutation(summary, k, prefix, versus))
+
     def print_metrics(self, metrics, prefix=""):
         msg = (f"{prefix}R@1: {metrics['R1']:.1f} - R@5: {metrics['R5']:.1f} - R@10: {metrics['R10']:.1f} - "
                f"R@50: {metrics.get('R50', 0.0):.1f} - Median R: {metrics['MR']:.1f} - Mean R: {metrics['MeanR']:.1f}")

@@ -1472,6 +1472,54 @@ def permtest_unit_sums(values_a, values_b, seed=0, p0=0, n_perm=1000):
     return out
 
 
+def permtest_hubness(idx_a, idx_b, unit_end, n_gallery, gt_begin, gt_end, seed=0, p0=0, n_perm=1000):
+    """int64 [n_perm, 2, 9] on the device (nr_permtest_hubness): for permutations p0 .. p0 + n_perm - 1 and the sides X, Y of the
+    relabelling -- X takes unit u's top-k lists from ranking a when the swap bit s(p, u) of permtest_rank_stats is 0 and from b when
+    it is 1, Y the other ranking's -- the integers S1, S2, S3 (power sums of the k-occurrence counts N over the gallery), #{N = 0},
+    #{N G > 2 S1}, the sum of N over those hubs, #{hub and N - GN > GN}, sum GN and max N.  idx_a, idx_b [n_lists, k] int32 as
+    slab_topk_rows / topk_merge write them; unit_end [U] int32 = the index of the last list of unit u (non-decreasing, from -1, ends
+    at n_lists - 1; checked on the device: ValueError); gt_begin / gt_end [n_lists] int32 as for topk_occurrences.  At most
+    32 768 gallery items and 65 535 lists.  The result depends on (seed, p, inputs) alone."""
+    tensors = (("idx_a", idx_a, 2), ("idx_b", idx_b, 2), ("unit_end", unit_end, 1), ("gt_begin", gt_begin, 1), ("gt_end", gt_end, 1))
+    for name, t, dim in tensors:
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != dim:
+            raise ValueError(f"{name} must be a {dim}-D int32 tensor")
+        if not t.is_cuda or t.device != idx_a.device:
+            raise ValueError(f"{name} must be on the GPU, on one device with the other operands (no CPU fallback)")
+    if idx_a.shape != idx_b.shape:
+        raise ValueError(f"idx_a and idx_b must have one shape, got {tuple(idx_a.shape)} and {tuple(idx_b.shape)}")
+    n_lists, k = idx_a.shape
+    k = _check_k(k)
+    if isinstance(n_gallery, bool) or int(n_gallery) != n_gallery or int(n_gallery) < 1:
+        raise ValueError(f"n_gallery must be a positive integer, got {n_gallery!r}")
+    n_gallery = int(n_gallery)
+    if n_gallery > hip.HUBPERM_MAX_GALLERY:
+        raise ValueError(f"n_gallery = {n_gallery} is above the {hip.HUBPERM_MAX_GALLERY} items whose counters one workgroup's LDS holds")
+    if n_lists > hip.HUBPERM_MAX_LISTS:
+        raise ValueError(f"{n_lists} lists are above the limit of {hip.HUBPERM_MAX_LISTS}: a counter keeps N in 16 bits")
+    if gt_begin.shape != (n_lists,) or gt_end.shape != (n_lists,):
+        raise ValueError("gt_begin / gt_end must have one entry per list")
+    seed, p0, n_perm = _resample_range(seed, p0, n_perm, ("p0", "n_perm"))
+    U = unit_end.numel()
+    if not 1 <= U <= hip.BOOT_MAX_UNITS:
+        raise ValueError(f"unit_end must hold 1 to 2^24 units, got {U}")
+    ends = unit_end.to(torch.int64)
+    if int(torch.diff(ends, prepend=ends.new_full((1,), -1)).min()) < 0 or int(ends[-1]) != n_lists - 1:
+        raise ValueError(f"unit_end must be non-decreasing from -1 and end at n_lists - 1 = {n_lists - 1}")
+    idx_a, idx_b, unit_end, gt_begin, gt_end = (t.contiguous() for t in (idx_a, idx_b, unit_end, gt_begin, gt_end))
+    out = torch.empty((n_perm, 2, 9), dtype=torch.int64, device=idx_a.device)
+    if not n_perm:
+        return out
+    occ_a, good_a = topk_occurrences(idx_a, n_gallery, gt_begin, gt_end)
+    occ_b, good_b = topk_occurrences(idx_b, n_gallery, gt_begin, gt_end)
+    occ_ab, good_ab = occ_a + occ_b, good_a + good_b
+    if n_lists == 0:
+        idx_a = idx_b = gt_begin = gt_end = torch.zeros((1,), dtype=torch.int32, device=out.device)      # never read: pointers for the entry point
+    hip.call("nr_permtest_hubness", hip.ptr(idx_a), hip.ptr(idx_b), n_lists, k, hip.ptr(unit_end), U, n_gallery, hip.ptr(gt_begin),
+             hip.ptr(gt_end), hip.ptr(occ_ab), hip.ptr(good_ab), ctypes.c_uint64(seed), p0, n_perm, hip.ptr(out), hip.stream_ptr())
+    return out
+
+
 def linear_x3(x, w, bias=None, residual=None):
     """Y = X W^T (+ bias) (+ residual) on the split-bf16 MFMA tile engine (nr_linear_x3): x [M,K], w [N,K] fp32, K padded to
     a multiple of 64 with zeros.  ~fp32-grade products (3 bf16 passes); used for the clustering GEMMs and for the

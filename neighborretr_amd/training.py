@@ -208,12 +208,15 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
                     tracker.log_bootstrap(m["bootstrap_vs_raw"], prefix=f"{side} {tag} - raw: ")
 
         def log_permutation(nt, nv, tag):
-            """The paired permutation test of a correction against raw: one line per direction, and one for its IR metrics."""
+            """The paired permutation test of a correction against raw: one line per direction, one for its IR metrics and, with
+            hubness_test, one for its hubness."""
             for side, m in (("Text-to-Video", nt), ("Video-to-Text", nv)):
                 if "permutation_vs_raw" in m:
                     tracker.log_permutation(m["permutation_vs_raw"], prefix=f"{side} {tag} - raw: ")
                 if "permutation_vs_raw" in m.get("ir", {}):
                     tracker.log_permutation(m["ir"]["permutation_vs_raw"], prefix=f"{side} {tag} - raw: ")
+                if "permutation_vs_raw" in m.get("hubness", {}):
+                    tracker.log_hubness_permutation(m["hubness"]["permutation_vs_raw"], m["hubness"]["k"], prefix=f"{side} {tag} - raw: ")
 
         def log_ir(nt, nv, tag=""):
             """The IR line of each direction (MRR, mAP, nDCG@10, R-Prec) and its interval lines."""
