@@ -441,7 +441,31 @@ __global__ __launch_bounds__(256) void nr_row_losses_bwd_kernel(NrRowArgs a, con
     nr_wave_argmax(mxc, imxc);
 
     const float rs = 1.0f / (r.max_s - r.min_s), rc = 1.0f / (r.max_c - r.min_c);
-    // neighbour: dz_j = p_j * (-1/ps) * (e_j - pe);  dadj_j = T * dz_j
+    // neighbour: the row term is L = -N / D,  N = sum_j p_j e_j + e_i,  D = sum_j p_j + 1,  e = log_softmax_E(s),  p = softmax(T adj);
+    //   g_j = dL/dp_j = -(e_j - N/D) / D,   dz_j = p_j * (g_j - sum_k p_k g_k) = -p_j * ((e_j - N/D) - q) / D,   dadj_j = T * dz_j,
+    //   q = sum_k p_k (e_k - N/D)  summed from the very terms it is subtracted from.
+    // e is centred by N/D BEFORE the softmax backward: sum_j dz_j = q (1 - sum_j p_j), and sum_j p_j is 1 only to rounding.  Uncentred
+    // (e_j - sum_k p_k e_k, e about -log|E|) that residue was 60 times larger; min-max normalisation turns it into the whole of
+    // d_c's error, whose columns sum B rows that cancel (1e-3 of max|d_c| at B = 1025, tests/test_rowloss_gpu.py).
+    const float nd = (pe + (r.s_ii - r.lse_e)) / psum;
+    float q = 0.f;
+#pragma unroll
+    for (int e = 0; e < NE; ++e)
+        if (r.sel[e]) q += r.posw(e) * ((r.s[e] - r.lse_e) - nd);
+    q = nr_wave_sum(q);
+    // K >= B: the diagonal's adjusted similarity sits in the softmax's denominator (NrRowState::stats) although its weight is
+    // overwritten by 1 (g_i = 0): p_d is its softmax weight, the p_j sum to 1 - p_d and dz_i = p_d * q / D.
+    const bool diag_in = a.K >= B;
+    float pd = 0.f;
+    if (diag_in) {
+#pragma unroll
+        for (int e = 0; e < NE; ++e)
+            if (r.valid[e] && e * 64 + lane == row) {
+                float adj = (r.s[e] - r.min_s) * rs - (r.c[e] - r.min_c) * rc;
+                pd = expf(adj * r.T - r.amax) / r.asum;
+            }
+        pd = nr_wave_sum(pd);
+    }
     float Dmin_s = 0.f, Dmax_s = 0.f, Dmin_c = 0.f, Dmax_c = 0.f;
     float dadj[NE];
 #pragma unroll
@@ -449,13 +473,15 @@ __global__ __launch_bounds__(256) void nr_row_losses_bwd_kernel(NrRowArgs a, con
         dadj[e] = 0.f;
         if (r.valid[e] && r.sel[e]) {
             float p = r.posw(e);
-            float ej = r.s[e] - r.lse_e;
-            dadj[e] = r.T * p * (-1.0f / psum) * (ej - pe);
+            float ej = (r.s[e] - r.lse_e) - nd;
+            dadj[e] = r.T * p * (-1.0f / psum) * (ej - q);
             float ns = (r.s[e] - r.min_s) * rs, nc = (r.c[e] - r.min_c) * rc;
             Dmin_s += dadj[e] * rs * (ns - 1.0f);
             Dmax_s -= dadj[e] * ns * rs;
             Dmin_c += dadj[e] * rc * (1.0f - nc);
             Dmax_c += dadj[e] * nc * rc;
+        } else if (diag_in && r.valid[e] && e * 64 + lane == row) {
+            dadj[e] = r.T * pd * q / psum;          // (the rest set is empty: nothing takes the min / max gradients)
         }
     }
     Dmin_s = nr_wave_sum(Dmin_s); Dmax_s = nr_wave_sum(Dmax_s);
@@ -487,7 +513,7 @@ __global__ __launch_bounds__(256) void nr_row_losses_bwd_kernel(NrRowArgs a, con
             float wk = diag ? 1.0f : r.posw(e);
             dn += expf(r.s[e] - r.lse_e) - wk / psum;
         }
-        if (r.sel[e]) {
+        if (r.sel[e] || (diag && diag_in)) {
             dn += rs * dadj[e];
             dc -= rc * dadj[e];
         }
