@@ -157,6 +157,20 @@ int nr_local_level_fwd(const uint16_t* t_hi, const uint16_t* t_lo, const uint16_
                        int prec, int out_mode, float* out, uint8_t* arg_v, uint8_t* arg_t,
                        float* pmax, float* qmax, void* stream);
 
+/* Fused local_level (modeling.py:483-514) of CANDIDATE LISTS: the token-level score of chosen (query, gallery item) pairs
+ * instead of a whole rectangle -- the second stage of two-stage retrieval.  No counterpart in the reference, which scores
+ * every pair (evaluator.py:21-63).
+ *   q_hi/lo [n_q*Nq,d], g_hi/lo [n_g*Ng,d] prepared tokens (nr_prepare_tokens; lo: split-bf16 only); w_q [n_q*Nq], w_g [n_g*Ng]
+ *   token weights; cand [n_q,C] int32; out [n_q,C] f32: out[i,c] = 0.5 (sum_t w_q max_v + sum_v w_g max_t) of query i and
+ *   item cand[i,c].  The formula is symmetric: queries may be texts or videos.  An entry of cand outside [0, n_g) (the
+ *   padding -1 included) gives -inf and is never dereferenced; duplicates are allowed; a fully masked query or item gives
+ *   exactly 0.  The score of a pair does not depend on its position in the list or on C (identical pairs: identical bits).
+ * NR_EINVAL: a null pointer, a count <= 0, d % 64 != 0, C outside [1, 128], an unknown prec, split-bf16 without lo.
+ * NR_EUNSUPPORTED: Nq or Ng > 128, d > 1024.  Both before any launch.                                                  */
+int nr_local_level_cand(const uint16_t* q_hi, const uint16_t* q_lo, const uint16_t* g_hi, const uint16_t* g_lo,
+                        const float* w_q, const float* w_g, int n_q, int Nq, int n_g, int Ng, int d, int prec,
+                        const int32_t* cand, int C, float* out, void* stream);
+
 /* Several fused local_level products of ONE step in a single grid (modeling.py:499-512 is called three times per step:
  * batch x batch, :283-287, and the two memory-bank products of until_module.py:170-185): every product as
  * nr_local_level_fwd would compute it, without arg-max outputs, outputs in the same layout.  A CU picks up the next

@@ -144,6 +144,10 @@ def get_args():
                    help="1, with --hubness_k K and --permutation N: the paired permutation test of the hubness figures (skewness, "
                         "hubs, bad hubs, anti-hubs, ...) from the relabelled top-K lists on the GPU, for a correction against raw, "
                         "with --compare_model and for the EMA: every difference with its two-sided p-value (DESIGN.md 6.13); 0 = off")
+    p.add_argument("--rerank_top", type=int, default=0, metavar="C",
+                   help="two-stage retrieval after the exhaustive evaluation: a pooled single-vector prefilter picks C candidates "
+                        "per query, the token-level score re-ranks those only; logs R@K and the candidate recall per direction "
+                        "(DESIGN.md 6.14); 1..128; 0 = off")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -222,6 +226,8 @@ def get_args():
     if args.permutation and not (corrected or args.compare_model or args.ema_decay):
         p.error("--permutation needs a correction (--test_norm, --local_scaling, --mutual_proximity), --compare_model or "
                 "--ema_decay: there is nothing to compare")
+    if not 0 <= args.rerank_top <= 128:
+        p.error("--rerank_top must lie in [0, 128] (0 = off)")
     if args.hubness_test and not (args.hubness_k > 0 and args.permutation > 0):
         p.error("--hubness_test needs --hubness_k > 0 and --permutation > 0")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
@@ -785,9 +791,11 @@ def eval_epoch(args, model, test, tag=""):
     they are the inputs), one packed all-gather + index scatter restores dataset order (evaluator.py:173-189), rank r
     computes rows [r N/W, (r+1) N/W) of the N x N similarity and the rank counts of its slab on the GPU, three small
     collectives complete them."""
-    from neighborretr_amd.evaluator import correction_from_args, gather_eval_features, rank_sample_indices, sharded_evaluation
+    from neighborretr_amd.evaluator import (correction_from_args, gather_eval_features, rank_sample_indices, rerank_top_from_args,
+                                            sharded_evaluation, two_stage_evaluation, two_stage_label)
     from neighborretr_amd.metrics import RetrievalMetrics
     correction, extras = correction_from_args(args, model)     # every flag checked before any work
+    rerank_top = rerank_top_from_args(args)
     hubness_k = extras["hubness_k"]
     log = _tagged_log(tag)
 
@@ -852,6 +860,15 @@ def eval_epoch(args, model, test, tag=""):
             log(args, RetrievalMetrics.format_hubness(nv["hubness"], prefix=f"video->text {tag} "))
         if "marginal_err" in nt:
             log(args, f"{tag} marginal error {nt['marginal_err']:.3e} / {nv['marginal_err']:.3e}")
+    if rerank_top:                                          # two-stage retrieval next to the exhaustive figures, never instead of them
+        torch.cuda.synchronize()
+        tic = time.time()
+        t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, t, v, tm.float(), vm.float(), args, rerank_top)
+        toc = time.time()
+        tag = two_stage_label(rerank_top)
+        log(args, RetrievalMetrics.format_two_stage(t2v["two_stage"], prefix=f"text->video {tag} "))
+        log(args, RetrievalMetrics.format_two_stage(v2t["two_stage"], prefix=f"video->text {tag} "))
+        log(args, f"{tag} wall time {toc - tic:.2f}s")
     return t2v, v2t
 
 

@@ -139,12 +139,25 @@ struct NrGemmTile {
         run_impl<true>(a_hi, a_lo, a_row0, a_rows, b_hi, b_lo, b_row0, b_rows, K, smem, 0, false, conv_n);
     }
 
-    template <bool CONV3>
+    // Operand B GATHERED by a list of items (nr_sim_cand.hip): tile row r of B is token r % gat_n of item gat_idx[r / gat_n],
+    // i.e. row gat_idx[r / gat_n] * gat_n + r % gat_n of b_hi / b_lo, for the gat_cnt list entries the tile holds.  A row
+    // whose list entry does not exist (r / gat_n >= gat_cnt) or lies outside [0, gat_items) reads the zero row: such an
+    // entry never forms an address.  K <= 1024 (the zero row's length).
+    __device__ __forceinline__ void run_gather(const uint16_t* __restrict__ a_hi, const uint16_t* __restrict__ a_lo,
+                                               int a_row0, int a_rows,
+                                               const uint16_t* __restrict__ b_hi, const uint16_t* __restrict__ b_lo,
+                                               const int32_t* __restrict__ gat_idx, int gat_cnt, int gat_n, int gat_items,
+                                               int K, char* smem) {
+        run_impl<false, true>(a_hi, a_lo, a_row0, a_rows, b_hi, b_lo, 0, 0, K, smem, 0, false, 0, 0, gat_idx, gat_cnt, gat_n, gat_items);
+    }
+
+    template <bool CONV3, bool GATHER = false>
     __device__ __forceinline__ void run_impl(const uint16_t* __restrict__ a_hi, const uint16_t* __restrict__ a_lo,
                                              int a_row0, int a_rows,
                                              const uint16_t* __restrict__ b_hi, const uint16_t* __restrict__ b_lo,
                                              int b_row0, int b_rows, int K, char* smem, int rot, bool dma_front, int conv_n,
-                                             int ld = 0) {
+                                             int ld = 0, const int32_t* __restrict__ gat_idx = nullptr, int gat_cnt = 0,
+                                             int gat_n = 1, int gat_items = 0) {
         static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0, "tile rows must split evenly over the waves");
         // ld: row pitch of BOTH operands in elements when they are K-slices of wider matrices (0: the rows are K long)
         const int LD = ld > 0 ? ld : K;
@@ -184,9 +197,18 @@ struct NrGemmTile {
         for (int i = 0; i < PB; ++i) {
             int r = (wave + NW * i) * 8 + (lane >> 3);
             int kc = (lane & 7) ^ row_key<TPS_B, NI>(r);
-            int gr = min(b_row0 + r, b_rows - 1);
-            gb_h[i] = reinterpret_cast<const char*>(b_hi + (size_t)gr * LD + kc * 8);
-            if constexpr (X3) gb_l[i] = reinterpret_cast<const char*>(b_lo + (size_t)gr * LD + kc * 8);
+            if constexpr (GATHER) {
+                const int slot = r / gat_n, tok = r - slot * gat_n;
+                const int item = slot < gat_cnt ? gat_idx[slot] : -1;
+                const bool on = item >= 0 && item < gat_items;
+                const size_t o = ((size_t)(on ? item : 0) * gat_n + tok) * LD + kc * 8;
+                gb_h[i] = reinterpret_cast<const char*>(on ? b_hi + o : nr_zero_row + kc * 8);
+                if constexpr (X3) gb_l[i] = reinterpret_cast<const char*>(on ? b_lo + o : nr_zero_row + kc * 8);
+            } else {
+                int gr = min(b_row0 + r, b_rows - 1);
+                gb_h[i] = reinterpret_cast<const char*>(b_hi + (size_t)gr * LD + kc * 8);
+                if constexpr (X3) gb_l[i] = reinterpret_cast<const char*>(b_lo + (size_t)gr * LD + kc * 8);
+            }
         }
         const int KT_ = K / BK;
         // DMA instruction `idx` (0 .. DMA_PER_STAGE-1) of slice kt: A pieces first (hi, then lo), then B pieces

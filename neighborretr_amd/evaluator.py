@@ -1314,3 +1314,139 @@ def correction_from_args(args, model):
     if correction is not None and correction.needs_bank:
         _querybank(model, None, model.mb_feat_t.device)         # checked where it lies: nothing is copied
     return correction, kw
+
+
+# ---- two-stage retrieval: pooled prefilter, gathered token re-ranking (DESIGN.md "Two-stage retrieval") ----------------------------
+# Rank r searches the queries slab_bounds(n_queries, W, r) of each direction against a GalleryIndex every rank prepares in full
+# (search.py); the [n, C] candidate lists and their fine scores are gathered like the top-k lists (_gathered_rows: indices and
+# score bits, transposed), one collective per direction, and every rank counts the same numbers on the host.  No n x N buffer.
+
+RERANK_CUTS = (1, 5, 10, 50)
+
+
+def two_stage_label(n_candidates):
+    """The tag of the log lines of the two-stage metrics: "[two-stage C=64]"."""
+    return f"[two-stage C={int(n_candidates)}]"
+
+
+def rerank_top_from_args(args):
+    """args.rerank_top as an int: 0 (off) or 1..128, checked before any work."""
+    from .search import check_candidates
+    top = getattr(args, "rerank_top", 0)
+    top = 0 if top is None else top
+    try:
+        return check_candidates(top, allow_zero=True)
+    except ValueError:
+        raise ValueError(f"rerank_top must be an integer in [0, 128] (0 = off), got {top!r}") from None
+
+
+def two_stage_counts(cand, fine, gt):
+    """(found [n] bool, greater [n], equal [n] int64) of candidate lists cand [n, C] (-1 = absent) with scores fine [n, C] and one
+    ground-truth item gt[i] per query: whether gt[i] is a candidate, how many candidates score above it and how many equal it
+    (itself included); 0 where it is not found."""
+    cand, fine, gt = np.asarray(cand), np.asarray(fine), np.asarray(gt).reshape(-1, 1)
+    hit = (cand == gt) & (cand >= 0)
+    found = hit.any(1)
+    own = np.where(found, np.where(hit, fine, -np.inf).max(1), np.nan)[:, None]
+    valid = cand >= 0
+    greater = (valid & (fine > own)).sum(1).astype(np.int64)
+    equal = (valid & (fine == own)).sum(1).astype(np.int64)
+    return found, np.where(found, greater, 0), np.where(found, equal, 0)
+
+
+def two_stage_metrics(found, greater, equal, n_candidates):
+    """The dictionary of one direction from its per-query counts: R@K over all queries (a missed query fails at every K; None
+    where K > C), cand_recall, n_candidates, cols (the ranks of the found queries, ranks_from_counts) and, when every query was
+    found, MR / MedianR / MeanR."""
+    found = np.asarray(found, dtype=bool)
+    ind = RetrievalMetrics.ranks_from_counts(np.asarray(greater)[found], np.asarray(equal)[found])
+    return _two_stage_dict(ind, int((~found).sum()), len(found), n_candidates)
+
+
+def _two_stage_dict(ind, n_missed, n_queries, C):
+    total = len(ind) + n_missed
+    m = {f"R{K}": (float(np.sum(ind < K)) * 100 / total if K <= C and total else None) for K in RERANK_CUTS}
+    m["cand_recall"] = float(n_queries - n_missed) * 100 / n_queries if n_queries else 0.0
+    m["n_candidates"] = int(C)
+    m["cols"] = [int(i) for i in ind]
+    if n_missed == 0 and len(ind):
+        m["MR"] = m["MedianR"] = float(np.median(ind)) + 1
+        m["MeanR"] = float(np.mean(ind)) + 1
+    return m
+
+
+def two_stage_multi_sentence_metrics(cand_t, fine_t, cand_v, fine_v, ends, n_candidates):
+    """(t2v, v2t) of a multi-sentence set; ends[g] = one past the last sentence of video g.  t2v: sentence s is ranked among its
+    candidate videos, its own video's rank = the candidates scoring above it plus the equal ones at lower indices (the stable
+    order of the exhaustive rule; the lists are in ascending index).  v2t: video j's candidate sentences are reduced to group
+    scores (the maximum per video group); found = group j has a candidate; greater / equal count the groups present."""
+    ends = np.asarray(ends, dtype=np.int64)
+    cand_t, fine_t, cand_v, fine_v = (np.asarray(a) for a in (cand_t, fine_t, cand_v, fine_v))
+    C = int(n_candidates)
+    Ns, V = cand_t.shape[0], cand_v.shape[0]
+    group = np.searchsorted(ends, np.arange(Ns), side="right")
+    hit = (cand_t == group[:, None]) & (cand_t >= 0)
+    found = hit.any(1)
+    own = np.where(found, np.where(hit, fine_t, -np.inf).max(1), np.nan)[:, None]
+    valid = cand_t >= 0
+    ranks = (valid & (fine_t > own)).sum(1) + (valid & (fine_t == own) & (cand_t < group[:, None])).sum(1)
+    ranks = ranks[found].astype(np.int64)
+    t2v = {f"R{K}": (float(np.sum(ranks < K)) * 100 / Ns if K <= C else None) for K in RERANK_CUTS}
+    t2v.update(cand_recall=float(found.sum()) * 100 / Ns, n_candidates=C, cols=[int(r) for r in ranks])
+    if found.all():
+        t2v["MedianR"] = t2v["MR"] = float(np.sort(ranks + 1)[(len(ranks) - 1) // 2])       # torch.median: the lower middle element
+        t2v["MeanR"] = float(np.mean(ranks + 1))
+        t2v["Std_Rank"] = float(np.std(ranks + 1))
+    f_v, g_v, e_v = np.zeros(V, dtype=bool), np.zeros(V, dtype=np.int64), np.zeros(V, dtype=np.int64)
+    for j in range(V):
+        ok = cand_v[j] >= 0
+        gmax = np.full(V, -np.inf)
+        present = np.zeros(V, dtype=bool)
+        gj = np.searchsorted(ends, cand_v[j][ok], side="right")
+        np.maximum.at(gmax, gj, fine_v[j][ok])
+        present[gj] = True
+        if present[j]:
+            f_v[j], g_v[j], e_v[j] = True, int((present & (gmax > gmax[j])).sum()), int((present & (gmax == gmax[j])).sum())
+    return t2v, two_stage_metrics(f_v, g_v, e_v, C)
+
+
+def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk):
+    """(cand [n, C] int32, fine [n, C] fp32) as NumPy arrays, the same on every rank: this rank's queries searched, one gather."""
+    n = q_feat.shape[0]
+    r0, r1 = slab_bounds(n, W, rank)
+    cand, fine = index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk)
+    if W > 1:
+        mine = torch.zeros((2 * C, -(-n // W)), dtype=torch.int32, device=cand.device)
+        mine[:C, :r1 - r0], mine[C:, :r1 - r0] = cand.T, fine.view(torch.int32).T
+        rows = _gathered_rows(mine, n, W)
+        cand, fine = rows[:C].T.contiguous(), rows[C:].T.contiguous().view(torch.float32)
+    return cand.cpu().numpy(), fine.cpu().numpy()
+
+
+def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, n_candidates, cut_off_points=None, chunk=256):
+    """-> (t2v, v2t) of two-stage retrieval with n_candidates (1..128) candidates per query, identical on every rank: R1 / R5 /
+    R10 / R50 (None where K > C), cand_recall (percent of the queries whose ground truth is among their candidates),
+    n_candidates, cols, and MR / MedianR / MeanR only when every query was found.  Every argument is checked before any work."""
+    from .search import GalleryIndex, check_candidates, check_chunk
+    C, chunk = check_candidates(n_candidates), check_chunk(chunk)
+    for feat, mask, what in ((text_feat, text_mask, "text"), (video_feat, video_mask, "video")):
+        if not torch.is_tensor(feat) or feat.dim() != 3 or not torch.is_tensor(mask) or tuple(mask.shape) != tuple(feat.shape[:2]):
+            raise ValueError(f"{what} features must be [n, tokens, d] with a mask [n, tokens]")
+    n_rows, n_cols = text_feat.shape[0], video_feat.shape[0]
+    if n_rows < 1 or n_cols < 1:
+        raise ValueError("two-stage evaluation needs at least one text and one video")
+    if cut_off_points is None:
+        if n_cols != n_rows:
+            raise ValueError("single-sentence retrieval: one text per video expected")
+        ends = None
+    else:
+        ends = _group_ends(cut_off_points, n_rows, n_cols)
+    W = _world(args)
+    rank = comm.get_rank() if W > 1 else 0
+    text_mask, video_mask = text_mask.float(), video_mask.float()
+    cand_t, fine_t = _two_stage_lists(GalleryIndex(model, video_feat, video_mask, "video"), text_feat, text_mask, C, W, rank, chunk)
+    cand_v, fine_v = _two_stage_lists(GalleryIndex(model, text_feat, text_mask, "text"), video_feat, video_mask, C, W, rank, chunk)
+    if ends is not None:
+        return two_stage_multi_sentence_metrics(cand_t, fine_t, cand_v, fine_v, ends, C)
+    gt = np.arange(n_rows)
+    return (two_stage_metrics(*two_stage_counts(cand_t, fine_t, gt), C), two_stage_metrics(*two_stage_counts(cand_v, fine_v, gt), C))

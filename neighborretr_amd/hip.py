@@ -179,6 +179,7 @@ _SIGNATURES = {
     "nr_token_weights_fwd": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P], _I),
     "nr_local_level_tiles": ([_I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)], _I),
     "nr_local_level_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
+    "nr_local_level_cand": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P], _I),
     "nr_local_level_group_kind": ([_I, _I, _I, _I, _I, _I], _I),
     "nr_local_level_group": ([_I, ctypes.POINTER(LocalLevelProblem), _P], _I),
     "nr_reduce_parts": ([_P, _I, _I, _F, _P, _P], _I),

@@ -128,6 +128,14 @@ class RetrievalMetrics:
         }
 
     @staticmethod
+    def format_two_stage(m, prefix=""):
+        """One line of a two-stage direction (evaluator.two_stage_evaluation): R@K where K <= C, the candidate recall and, when
+        every query was found, MedR."""
+        recalls = " ".join(f"R@{K} {m[f'R{K}']:.1f}" for K in (1, 5, 10, 50) if m.get(f"R{K}") is not None)
+        line = f"{prefix}{recalls} - candidate recall {m['cand_recall']:.1f}%"
+        return line + (f" - MedR {m['MR']:.1f}" if "MR" in m else "")
+
+    @staticmethod
     def format_hubness(hub, prefix=""):
         return (f"{prefix}Hubness@{hub['k']}: skew {hub['skewness']:.2f} - hubs {hub['hub_pct']:.1f}% - "
                f"hub occurrence {hub['hub_occurrence_pct']:.1f}% - bad hubs {hub['bad_hub_pct']:.1f}% - "

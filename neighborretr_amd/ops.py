@@ -244,6 +244,24 @@ def local_level(prep_t, prep_v, w_t, w_v, A, Nt, Bv, Nv, prec=hip.PREC_BF16, out
     return out, ((arg_v, arg_t, pmax, qmax) if want_arg else None)
 
 
+def local_level_cand(prep_q, prep_g, w_q, w_g, n_q, Nq, n_g, Ng, cand, prec=hip.PREC_BF16X3):
+    """out [n_q, C] fp32: the local_level score of query i and gallery item cand[i, c] (nr_local_level_cand); cand [n_q, C]
+    int32, 1 <= C <= 128.  Entries outside [0, n_g), the padding -1 included, give -inf."""
+    if prep_q.n_tok != n_q * Nq or prep_g.n_tok != n_g * Ng:
+        raise ValueError("prepared token counts do not match n_q*Nq / n_g*Ng")
+    if prep_q.d != prep_g.d:
+        raise ValueError("queries and gallery must have the same feature width")
+    if cand.dim() != 2 or cand.shape[0] != n_q:
+        raise ValueError(f"cand must be [n_q, C] = [{n_q}, C], got {tuple(cand.shape)}")
+    C = int(cand.shape[1])
+    out = torch.empty((n_q, C), dtype=torch.float32, device=prep_q.hi.device)
+    hip.call("nr_local_level_cand", hip.ptr(prep_q.hi), hip.ptr(prep_q.lo, allow_none=True), hip.ptr(prep_g.hi),
+             hip.ptr(prep_g.lo, allow_none=True), hip.ptr(w_q, torch.float32), hip.ptr(w_g, torch.float32),
+             int(n_q), int(Nq), int(n_g), int(Ng), prep_q.d, int(prec), hip.ptr(cand, torch.int32), C, hip.ptr(out),
+             hip.stream_ptr())
+    return out
+
+
 def local_level_group(problems):
     """Several loss-only products of one step: [(prep_t, prep_v, w_t, w_v, A, Nt, Bv, Nv, prec, out_mode), ...] -> list of
     outputs as local_level(...)[0] would return them.  One grid for all of them (nr_local_level_group) when every product

@@ -1,0 +1,170 @@
+"""Two-stage retrieval: a pooled single-vector prefilter picks C candidates per query, the fused token-level score
+(nr_local_level_cand) re-ranks those candidates only.
+
+The reference has no such path: it scores every (text, video) pair (training/evaluator.py:21-63).  Here a gallery is
+prepared ONCE (GalleryIndex: bf16 hi/lo tokens, token weights, pooled vectors) and searched by any number of query batches.
+
+  coarse score   p_q . p_g,   p(x) = normalize(sum_tok w[tok] x^[tok])   -- the fine score with both max-pools relaxed to
+                 weighted means; x^ = the normalised, masked tokens, w = the scorer weights of the fine stage
+  candidates     the top C of every coarse row (ops.slab_topk_rows: score descending, ties by lower index), then sorted by
+                 ascending gallery index, so that position order equals index order
+  fine score     ops.local_level_cand on the split-bf16 plan, for the candidates only
+  result         the top k of the fine scores, ties by lower gallery index
+
+The coarse scores are computed in row chunks ([chunk, N], dropped after use): nothing of size n x N is ever allocated.  Every
+step is deterministic per element (pointwise torch ops, this library's own kernels), so a query's list and scores do not depend
+on the chunk size or on which other queries share its batch.
+"""
+import torch
+
+from . import head, hip, ops
+
+MAX_CANDIDATES = 128                      # nr_local_level_cand: C <= 128 (= hip.TOPK_MAX, the longest top-k list)
+_SCORER = {"video": "video_weight_fc", "text": "text_weight_fc"}
+
+
+def check_candidates(n_candidates, allow_zero=False):
+    """n_candidates as an int in [1, 128] (allow_zero: 0 = the exhaustive path)."""
+    lo = 0 if allow_zero else 1
+    if isinstance(n_candidates, bool) or not isinstance(n_candidates, int) or not lo <= n_candidates <= MAX_CANDIDATES:
+        raise ValueError(f"n_candidates must be an integer in [{lo}, {MAX_CANDIDATES}], got {n_candidates!r}")
+    return int(n_candidates)
+
+
+def check_chunk(chunk):
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"chunk must be an integer >= 1, got {chunk!r}")
+    return int(chunk)
+
+
+def _check_tokens(feat, mask, what):
+    if not torch.is_tensor(feat) or feat.dim() != 3:
+        raise ValueError(f"{what} features must be a [n, tokens, d] tensor")
+    if not torch.is_tensor(mask) or mask.dim() != 2 or tuple(mask.shape) != tuple(feat.shape[:2]):
+        raise ValueError(f"{what} mask must be [n, tokens] = {tuple(feat.shape[:2])}")
+
+
+def pooled_vectors(feat, mask, norm, w):
+    """p [n, d] fp32 = normalize(sum_tok w[tok] x^[tok]); norm [n * tokens] = the token norms nr_prepare_tokens wrote.  A fully
+    masked item gives the zero vector.  Pointwise ops and one prepare launch (the norm): the same bits for any batch."""
+    n, n_tok, d = feat.shape
+    m = mask.float()
+    coef = torch.where(m > 0, w.view(n, n_tok), torch.zeros_like(m)) / norm.view(n, n_tok)
+    u = torch.zeros((n, d), dtype=torch.float32, device=feat.device)
+    for t in range(n_tok):
+        u.addcmul_(feat[:, t, :], coef[:, t:t + 1])
+    if n == 0:
+        return u
+    return u / ops.prepare_tokens(u, None, want_lo=False).norm[:, None]
+
+
+class _Side:
+    """One prepared token set: split-bf16 tokens, scorer weights, pooled vectors."""
+
+    def __init__(self, model, feat, mask, side):
+        feat = feat.float().contiguous()
+        mask = mask.float().contiguous()
+        self.n, self.n_tok, self.d = feat.shape
+        if self.n:
+            self.prep = ops.prepare_tokens(feat, mask, want_lo=True)
+            self.w, _ = head.token_weights(self.prep, mask, model.scorer_weights(_SCORER[side]), self.n, self.n_tok, hip.PREC_BF16X3)
+            self.pooled = pooled_vectors(feat, mask, self.prep.norm, self.w)
+        else:
+            self.prep = self.w = None
+            self.pooled = torch.zeros((0, self.d), dtype=torch.float32, device=feat.device)
+
+
+class GalleryIndex:
+    """A gallery prepared once for two-stage search.  side="video": the items are videos, the queries texts; side="text":
+    the items are texts, the queries videos (the fine score is symmetric in its two sides)."""
+
+    def __init__(self, model, feat, mask, side="video"):
+        if side not in _SCORER:
+            raise ValueError(f"side must be 'video' or 'text', got {side!r}")
+        _check_tokens(feat, mask, "gallery")
+        if feat.shape[0] < 1:
+            raise ValueError("the gallery is empty")
+        self.model = model
+        self.side = side
+        self.query_side = "text" if side == "video" else "video"
+        self.feat, self.mask = feat, mask
+        with torch.no_grad():
+            self.items = _Side(model, feat, mask, side)
+
+    def __len__(self):
+        return self.items.n
+
+    def _check_queries(self, q_feat, q_mask):
+        _check_tokens(q_feat, q_mask, "query")
+        if q_feat.shape[2] != self.items.d:
+            raise ValueError(f"queries are {q_feat.shape[2]} wide, the gallery {self.items.d}")
+        if q_feat.device != self.feat.device:
+            raise ValueError("queries and gallery must be on the same device")
+
+    def coarse_scores(self, pooled_q):
+        """[n_q, N] fp32 cosines of pooled query vectors against the gallery's (nr_gemm_nt_f32: exact fp32 products, one
+        fixed summation order per element)."""
+        return ops.gemm_nt_f32(pooled_q, self.items.pooled)
+
+    def candidates(self, q_feat, q_mask, n_candidates, chunk=256):
+        """(cand [n, C] int32, fine [n, C] fp32): every query's C candidates in ascending gallery index (padded with -1 when
+        the gallery has fewer than C items) and their fine scores (-inf at the padding)."""
+        C, chunk = check_candidates(n_candidates), check_chunk(chunk)
+        self._check_queries(q_feat, q_mask)
+        dev = q_feat.device
+        n = q_feat.shape[0]
+        cand = torch.empty((n, C), dtype=torch.int32, device=dev)
+        if n == 0:
+            return cand, torch.empty((n, C), dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            q = _Side(self.model, q_feat, q_mask, self.query_side)
+            big = torch.iinfo(torch.int32).max
+            for lo in range(0, n, chunk):
+                ci, _ = ops.slab_topk_rows(self.coarse_scores(q.pooled[lo:lo + chunk].contiguous()), C)
+                ci = torch.where(ci < 0, torch.full_like(ci, big), ci).sort(dim=1).values       # ascending index, padding last
+                cand[lo:lo + chunk] = torch.where(ci == big, torch.full_like(ci, -1), ci)
+            g = self.items
+            fine = ops.local_level_cand(q.prep, g.prep, q.w, g.w, n, q.n_tok, g.n, g.n_tok, cand, hip.PREC_BF16X3)
+        return cand, fine
+
+    def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False):
+        """-> (idx [n, k] int32, val [n, k] fp32): the top k of every query, fine score descending, ties by lower gallery index,
+        padded with -1 / -inf when the gallery has fewer than k items.  1 <= k <= n_candidates <= 128; n_candidates = 0 scores
+        every pair (the exhaustive path: the evaluator's slab similarity and ops.slab_topk_rows).  return_candidates: also the
+        candidate lists and their fine scores, (idx, val, cand, fine)."""
+        C, chunk = check_candidates(n_candidates, allow_zero=True), check_chunk(chunk)
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > (C or hip.TOPK_MAX):
+            raise ValueError(f"k must be an integer in [1, {C or hip.TOPK_MAX}] (1 <= k <= n_candidates), got {k!r}")
+        self._check_queries(q_feat, q_mask)
+        if C == 0:
+            if return_candidates:
+                raise ValueError("the exhaustive path (n_candidates = 0) has no candidate lists")
+            return self._exhaustive(q_feat, q_mask, k, chunk)
+        cand, fine = self.candidates(q_feat, q_mask, C, chunk)
+        idx, val = rerank(cand, fine, k)
+        return (idx, val, cand, fine) if return_candidates else (idx, val)
+
+    def _exhaustive(self, q_feat, q_mask, k, chunk):
+        from .evaluator import _slab_similarity
+        n = q_feat.shape[0]
+        if self.side == "video":
+            S = _slab_similarity(self.model, q_feat, self.feat, q_mask, self.mask, 0, n, chunk)
+        else:
+            S = _slab_similarity(self.model, self.feat, q_feat, self.mask, q_mask, 0, len(self), chunk).T.contiguous()
+        if n == 0:
+            return (torch.empty((0, k), dtype=torch.int32, device=S.device), torch.empty((0, k), dtype=torch.float32, device=S.device))
+        return ops.slab_topk_rows(S, k)
+
+
+def rerank(cand, fine, k):
+    """The top k of candidate lists in ascending index order: (idx [n, k] int32, val [n, k] fp32), fine score descending, ties by
+    lower position = lower gallery index; absent slots -1 / -inf."""
+    n = cand.shape[0]
+    if n == 0:
+        return (torch.empty((0, k), dtype=torch.int32, device=cand.device), torch.empty((0, k), dtype=torch.float32, device=cand.device))
+    pos, val = ops.slab_topk_rows(fine, k)
+    idx = torch.gather(cand, 1, pos.clamp(min=0).long())
+    gone = (pos < 0) | (idx < 0)
+    idx = torch.where(gone, torch.full_like(idx, -1), idx)
+    val = torch.where(gone, torch.full_like(val, float("-inf")), val)
+    return idx, val

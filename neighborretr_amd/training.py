@@ -161,8 +161,10 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
     (rank r: rows [r N/W, (r+1) N/W)).  Multi-sentence sets (`dataset.multi_sentence_per_video`): every rank walks the whole
     loader, as in the reference (:114-131), keeps the video of each group's last sentence (:137-149), and the
     sentence x video matrix is again scored in row slabs.  Both go through evaluator.sharded_evaluation."""
-    from .evaluator import correction_from_args, dataset_order, gather_eval_features, sharded_evaluation
+    from .evaluator import (correction_from_args, dataset_order, gather_eval_features, rerank_top_from_args, sharded_evaluation,
+                            two_stage_evaluation, two_stage_label)
     correction, extras = correction_from_args(args, _unwrap(model))        # every flag checked before any work
+    rerank_top = rerank_top_from_args(args)
     hubness_k = extras["hubness_k"]
     logger = getattr(args, "logger", None)
     tracker = RetrievalMetrics(logger=logger)
@@ -188,11 +190,17 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
                 tf, vf, tm, vm = dataset_order(tf, vf, ind, tm, vm)
         toc1 = time.time()
         t2v, v2t = sharded_evaluation(model, tf, vf, tm.float(), vm.float(), args, correction, cut_off_points=cut_off_points, **extras)
-    toc2 = time.time()
+        toc2 = time.time()
+        if rerank_top:                                     # two-stage retrieval next to the exhaustive figures, never instead of them
+            t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, tf, vf, tm.float(), vm.float(), args, rerank_top,
+                                                                      cut_off_points=cut_off_points)
+        toc3 = time.time()
     if is_main_process() and logger is not None:
         logger.info("Evaluation timing breakdown:")
         logger.info(f"  - Feature extraction: {toc1 - tic:.2f}s")
         logger.info(f"  - Similarity + metrics: {toc2 - toc1:.2f}s")
+        if rerank_top:
+            logger.info(f"  - Two-stage retrieval {two_stage_label(rerank_top)}: {toc3 - toc2:.2f}s")
         logger.info("=" * 80)
         logger.info("EVALUATION RESULTS" + (f" [{tag}]" if tag else ""))
         logger.info("=" * 80)
@@ -241,6 +249,10 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
             if hubness_k:
                 tracker.log_hubness(nt["hubness"], prefix=f"Text-to-Video {tag} ")
                 tracker.log_hubness(nv["hubness"], prefix=f"Video-to-Text {tag} ")
+        if rerank_top:
+            tag = two_stage_label(rerank_top)
+            logger.info(RetrievalMetrics.format_two_stage(t2v["two_stage"], prefix=f"Text-to-Video {tag}: "))
+            logger.info(RetrievalMetrics.format_two_stage(v2t["two_stage"], prefix=f"Video-to-Text {tag}: "))
     return t2v, v2t
 
 
