@@ -265,7 +265,11 @@ int nr_ctm_back(const float* dist, const float* smax, const float* mask, const f
  * three taps side by side (tap k multiplies x[n+k-1]), q.weight [C,C], kv.weight [2C,C], proj.weight [C,C].
  * mask may be NULL (stage 1); conv_bias / q_bias / kv_bias may be NULL; assign (int64 [n_samples,N]) may
  * be NULL.  workspace: nr_ctm_stage_workspace_bytes(n_samples, N, C, cnum) bytes, 256-byte aligned,
- * private to the problem.  out [n_samples, cnum, C] f32.  N <= 64, C == 64*heads <= 1024.              */
+ * private to the problem.  out [n_samples, cnum, C] f32.
+ * Shapes, checked per problem before anything is launched (NR_EINVAL before NR_EUNSUPPORTED): NR_EINVAL for a NULL required
+ * pointer, a count <= 0, k or cnum > N, and -- after every problem passed -- x_hi without x_lo; NR_EUNSUPPORTED for N > 64,
+ * C % 128 != 0, C > 1024, C != 64 * heads, cnum * C/128 > 192 and N * C * 4 > 150 KB.  What is launched for the shapes that
+ * pass is decided once per call by one host function; nr_ctm_stage_plan (below) returns that decision without a device.  */
 #define NR_CTM_MAX_GROUP 4
 typedef struct NrCtmStageDesc {
     int32_t n_samples, N, C, k, cnum, heads;
@@ -305,6 +309,42 @@ int nr_ctm_stage_fwd(const NrCtmStageDesc* problems, int n_problems, void* strea
  * the launches of an independent branch, because the graph starts its nodes in capture order.            */
 #define NR_CTM_STAGE_LAUNCHES 7
 int nr_ctm_stage_fwd_range(const NrCtmStageDesc* problems, int n_problems, int first, int last, void* stream);
+/* What nr_ctm_stage_fwd_range will launch for these problems, from the host alone (no device, no HIP call): the plan the stage
+ * itself launches from, not a copy -- every call validates, plans once and then issues the launches [first, last) of that one
+ * plan, so a stage driven whole, launch by launch or in two halves runs the same kernels.  Reads the scalar fields of the
+ * descriptors and whether mask, x_hi and x_lo are NULL; no other pointer is looked at or required.  NR_EINVAL / NR_EUNSUPPORTED
+ * exactly where nr_ctm_stage_fwd_range returns them for shapes (plan is untouched then):
+ *   NR_EINVAL        no problems or more than NR_CTM_MAX_GROUP, a count <= 0, k or cnum > N, x_hi without x_lo, plan NULL
+ *   NR_EUNSUPPORTED  N > 64, C % 128, C > 1024, C != 64 * heads, cnum * C/128 > 192 merge jobs, N * C * 4 > 150 KB of LDS
+ * plan: NR_CTM_PLAN_WORDS integers.  Every launch is a grid of `..._GRID` workgroups of `..._THREADS` threads with `..._LDS`
+ * bytes of dynamic LDS (`..._ATTR`: the launch first raises the kernel's dynamic-LDS limit to that size).                  */
+#define NR_CTM_PLAN_WORDS 24
+enum {
+    NR_CTM_PLAN_SAMPLES = 0,       /* samples of all problems: the grid of launches 2 and 3 and of the whole-sample attention    */
+    NR_CTM_PLAN_START = 1,         /* [NR_CTM_MAX_GROUP] first sample of every problem (SAMPLES past the last problem)           */
+    NR_CTM_PLAN_SPLIT_GRID = 5,    /* launch 0; 0 = no launch (every problem brings x_hi / x_lo)                                 */
+    NR_CTM_PLAN_FUSABLE = 6,       /* no problem carries a mask                                                                  */
+    NR_CTM_PLAN_FORM = 7,          /* 1 / 2: first or second form of the front and back bodies (second: every C = 512, cnum <= 16) */
+    NR_CTM_PLAN_FRONT_THREADS = 8, /* launch 2: the front half alone, or front + back in one kernel when BACK is ..._BACK_NONE    */
+    NR_CTM_PLAN_FRONT_LDS = 9,
+    NR_CTM_PLAN_FRONT_ATTR = 10,
+    NR_CTM_PLAN_BACK = 11,         /* launch 3: NR_CTM_BACK_*                                                                    */
+    NR_CTM_PLAN_BACK_FORM = 12,    /* 0 first form; 4 / 16 second form with accumulators for that many clusters                  */
+    NR_CTM_PLAN_BACK_THREADS = 13,
+    NR_CTM_PLAN_BACK_LDS = 14,     /* of a back workgroup (beside the kv GEMM the grid takes the larger of this and the tile ring) */
+    NR_CTM_PLAN_BACK_USE_LDS = 15, /* the back half keeps the sample's token rows in LDS                                         */
+    NR_CTM_PLAN_BACK_ATTR = 16,
+    NR_CTM_PLAN_KV_LAUNCH = 17,    /* 3: the kv GEMM rides beside the back half; 4: with the q GEMM                               */
+    NR_CTM_PLAN_ATTN_FORM = 18,    /* launch 5: NR_CTM_ATTN_*                                                                    */
+    NR_CTM_PLAN_ATTN_GRID = 19,
+    NR_CTM_PLAN_ATTN_THREADS = 20,
+    NR_CTM_PLAN_ATTN_LDS = 21,
+    NR_CTM_PLAN_ATTN_USE_LDS = 22, /* whole-sample form: k | v rows in LDS                                                       */
+    NR_CTM_PLAN_ATTN_ATTR = 23
+};
+enum { NR_CTM_BACK_NONE = 0, NR_CTM_BACK_ALONE = 1, NR_CTM_BACK_BESIDE_KV = 2 };
+enum { NR_CTM_ATTN_WHOLE = 0, NR_CTM_ATTN_HEADS = 1 };      /* a workgroup per sample / per (sample, pair of heads) */
+int nr_ctm_stage_plan(const NrCtmStageDesc* problems, int n_problems, int32_t* plan);
 
 /* As nr_ctm_stage_workspace_layout, plus the split-bf16 operands the forward GEMMs read and the backward's weight-gradient
  * GEMMs need again: [8] kvn_hi [9] kvn_lo  [n*N, C]  norm1(xn);  [10] qn_hi [11] qn_lo  [n*cnum, C]  norm1(merged);

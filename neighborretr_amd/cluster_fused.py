@@ -1,12 +1,17 @@
-"""No-grad forward of the token-clustering stage on fused HIP kernels + library GEMMs.
+"""The token-clustering stage (CTM + TCBlock) on HIP kernels: same arithmetic as neighborretr_amd/cluster.py (and the
+reference's cluster.py:670-965), whose ~45 ATen launches per stage and modality stay the traced fallback.
 
-Same arithmetic as neighborretr_amd/cluster.py (and the reference's cluster.py:670-965); used when no
-gradient is required (loss-only forward, evaluation), where the ~45 ATen launches of one
-CTM + TCBlock stage collapse to 8:
-    nr_shift_concat -> GEMM(+residual) -> nr_ctm_front -> nr_ctm_back
-    -> GEMM q, GEMM kv -> nr_tc_attention -> GEMM proj (+residual+bias)
-The training path keeps the autograd-traced torch ops of cluster.py.
+What the step runs -- the GROUPED stage, text and video in the same seven launches (nr_ctm_stage_fwd; csrc/nr_ctm_group.hip):
+    split -> conv GEMM (+x) -> front -> back (+ kv GEMM) -> q (+ kv) GEMM -> attention -> proj GEMM (+merged +bias)
+    grouped_stages_supported   the one gate for its widths and token counts: the library's own planner (hip.ctm_stage_plan)
+    ctm_stage_group            no-grad forward: whole, launch by launch (stepwise=) or in two halves around an exchange=
+    cluster_stages_train       the same forward as an autograd node (ClusterStagesFn) with the hand-derived backward
+    build_stage_weights        the bf16 pairs of the stages' weights the GEMMs read, one split launch for all stale ones
+The ONE-PROBLEM chain -- ctm_stage_fused: nr_shift_concat -> GEMM -> nr_ctm_front -> nr_ctm_back -> GEMM q, kv ->
+nr_tc_attention -> GEMM proj, eight launches per modality -- is what modeling._merge_one runs (it takes C % 64) and the
+independent implementation tests/test_kernels_gpu.py holds the grouped stage against.
 """
+import functools
 import math
 
 import torch
@@ -215,6 +220,23 @@ def _workspace_views(ws, B, N, C, cnum):
         else:
             out[name] = ws[int(o): int(o) + 2 * n].view(torch.int16).view(shape)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def grouped_stages_supported(Nt, Nv, C, heads, k=(3, 3, 3, 3)):
+    """Whether the grouped stage (ctm_stage_group, cluster_stages_train) takes the model's four stage shapes: text and video
+    tokens [*, Nt, C] / [*, Nv, C] through stage 0 (masked) and stage 1 (no mask, fed the bf16 pair of stage 0's output), token
+    counts as modeling._token_counts, k of the four CTM modules in the order (text0, video0, text1, video1).  THE gate for the
+    width and token-count arithmetic of every caller of the grouped stage: it asks the library's own planner
+    (hip.ctm_stage_plan, host only) instead of repeating its limits.  False where the library answers NR_EUNSUPPORTED; raises
+    where it answers NR_EINVAL (fewer tokens than k reach a stage: the reference raises there too).  Memoised on its arguments:
+    a step pays a dictionary lookup."""
+    from .modeling import NeighborRetr
+    (t0, t1), (v0, v1) = NeighborRetr._token_counts(Nt, Nv)
+    # (n_samples, N, C, k, cnum, heads, masked, paired): support does not depend on the number of samples
+    stage0 = [(1, Nt, C, k[0], t0, heads, True, False), (1, Nv, C, k[1], v0, heads, True, False)]
+    stage1 = [(1, t0, C, k[2], t1, heads, False, True), (1, v0, C, k[3], v1, heads, False, True)]
+    return hip.ctm_stage_plan(stage0) is not None and hip.ctm_stage_plan(stage1) is not None
 
 
 def ctm_stage_group(problems, cache, stepwise=False, want_assign=False, want_saved=False, exchange=None):

@@ -194,291 +194,370 @@ extern "C" int nr_ctm_stage_workspace_layout2(int n_samples, int N, int C, int c
     return NR_OK;
 }
 
+// ---- the stage: validate, carve, plan once, launch [first, last) of the plan ----------------------------------------
+namespace {
+// Every check of a call that needs no device, in the order their statuses are reported: per problem NR_EINVAL before
+// NR_EUNSUPPORTED.  pointers = false (nr_ctm_stage_plan): only the scalars, and x_hi / x_lo only as "given or not".
+int validate(const NrCtmStageDesc* d, int n, bool pointers) {
+    if (!d || n <= 0 || n > NR_CTM_MAX_GROUP) return NR_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        const NrCtmStageDesc& s = d[i];
+        if (pointers && (!s.x || !s.noise || !s.wconv_hi || !s.wconv_lo || !s.ln_w || !s.ln_b || !s.sc_w || !s.sc_b || !s.n1_w || !s.n1_b ||
+                         !s.wq_hi || !s.wq_lo || !s.wkv_hi || !s.wkv_lo || !s.wp_hi || !s.wp_lo || !s.proj_bias || !s.workspace || !s.out))
+            return NR_EINVAL;
+        if (s.n_samples <= 0 || s.N <= 0 || s.k <= 0 || s.k > s.N || s.cnum <= 0 || s.cnum > s.N || s.heads <= 0) return NR_EINVAL;
+        if (s.N > 64 || s.C <= 0 || (s.C % 128) != 0 || s.C > 1024 || s.C != s.heads * 64) return NR_EUNSUPPORTED;
+        if (s.cnum * (s.C / 128) > 16 * BK_MAXJ) return NR_EUNSUPPORTED;
+        if ((size_t)s.N * s.C * sizeof(float) > 150 * 1024) return NR_EUNSUPPORTED;      // the front half keeps a sample's rows in LDS
+    }
+    for (int i = 0; i < n; ++i)
+        if ((d[i].x_hi == nullptr) != (d[i].x_lo == nullptr)) return NR_EINVAL;
+    return NR_OK;
+}
+
+// What the seven launches of one call have to agree on, decided once (plan_stage) from the validated shapes alone.
+struct StagePlan {
+    int samples, start[NR_CTM_MAX_GROUP + 1];   // one workgroup per sample in launches 2 and 3: first sample of every problem
+    int split_grid;                             // launch 0: 0 = every problem brings x_hi / x_lo, nothing to launch
+    bool fusable;                               // no problem carries a mask
+    int form;                                   // 1 / 2: first or second form of the two bodies (nr_ctm_bodies.h)
+    bool small, few;                            // every C <= 512 (register budget); a handful of tokens per sample
+    int front_threads;                          // launch 2: front alone, or front + back in one kernel when back == NR_CTM_BACK_NONE
+    size_t front_lds;
+    bool front_attr;
+    int back, back_form, back_threads, back_use_lds;       // launch 3 (NR_CTM_BACK_*)
+    size_t back_lds;
+    bool back_attr;
+    int kv_launch;                              // 3: the kv GEMM rides beside the back half; 4: with the q GEMM
+    int attn_form, attn_grid, attn_threads, attn_use_lds;  // launch 5 (NR_CTM_ATTN_*)
+    size_t attn_lds;
+    bool attn_attr;
+};
+
+int shift_blocks(const NrCtmStageDesc& s) { return (s.n_samples * s.N + NR_SHIFT_ROWS - 1) / NR_SHIFT_ROWS; }
+int attn_blocks(const NrCtmStageDesc& s, int form) { return s.n_samples * (form == NR_CTM_ATTN_HEADS ? s.heads / NR_ATTN_HG : 1); }
+
+// Pure host arithmetic: no HIP call, no launch range.  The tuning hooks (NR_TUNE builds only, tools/ab_attn.sh) are read here
+// and nowhere else in this file.
+StagePlan plan_stage(const NrCtmStageDesc* d, int n) {
+    StagePlan p{};
+    const bool kv_apart = nr_tune_env("NR_KV_APART") != nullptr, v1 = nr_tune_env("NR_CTM_V1") != nullptr;
+    const bool attn_whole = nr_tune_env("NR_ATTN_WHOLE") != nullptr;
+    const char* te = nr_tune_env("NR_CTM_THREADS");
+    const bool threads512 = te && atoi(te) == 512;
+    p.fusable = p.small = true;
+    bool c512 = true, n8 = true, few1 = true, rows256 = true, heads_even = true;
+    int maxc = 0, maxn = 0, jobs_max = 0;       // jobs: (head, query) pairs of a sample's attention
+    size_t rows_lds = 0, front2_lds = 0, kv_lds = 0, kv_heads_lds = 0;       // largest problem's, bytes
+    auto upto = [](size_t& m, size_t v) { m = v > m ? v : m; };
+    for (int i = 0; i < n; ++i) {
+        const NrCtmStageDesc& s = d[i];
+        p.start[i] = p.samples;
+        p.samples += s.n_samples;
+        if (!s.x_hi) p.split_grid += shift_blocks(s);
+        p.fusable = p.fusable && s.mask == nullptr;
+        p.small = p.small && s.C <= 512;
+        c512 = c512 && s.C == 512;
+        n8 = n8 && s.N <= 8;
+        few1 = few1 && s.N <= 8 && s.cnum * (s.C / 128) <= 4 * BK_MAXJ;
+        rows256 = rows256 && (s.N * s.C) % 256 == 0;
+        heads_even = heads_even && s.heads % NR_ATTN_HG == 0;
+        maxc = s.cnum > maxc ? s.cnum : maxc;
+        maxn = s.N > maxn ? s.N : maxn;
+        jobs_max = s.heads * s.cnum > jobs_max ? s.heads * s.cnum : jobs_max;
+        upto(rows_lds, (size_t)s.N * s.C * sizeof(float));
+        upto(front2_lds, nr_ctm_front2_lds_floats(s.N, s.C) * sizeof(float));
+        upto(kv_lds, (size_t)s.N * (2 * s.C + 4) * sizeof(float));
+        upto(kv_heads_lds, (size_t)s.N * (2 * 64 * NR_ATTN_HG + 4) * sizeof(float));
+    }
+    for (int i = n; i <= NR_CTM_MAX_GROUP; ++i) p.start[i] = p.samples;
+
+    // The second form of the two bodies: every problem 512 channels wide (the model's width), at most 16 clusters.  Its back half
+    // keeps 4 cluster accumulators and a 32-entry distance row per token in registers, or 16 and 64.  NR_CTM_V1=1 keeps the first.
+    p.form = (!v1 && c512 && maxc <= 16) ? 2 : 1;
+    p.back_form = p.form == 1 ? 0 : (maxc <= 4 && maxn <= 32) ? 4 : 16;
+    // Front and back are ONE launch when no problem carries a mask (stage 1 of the step); with a mask the back half needs the
+    // maximum distance over ALL samples.  First form, C > 512: sixteen channels per lane of seven per-channel vectors do not fit
+    // the 128 registers a 1024-thread workgroup leaves a lane (48 spilled registers, round 3) -- 512-thread workgroups, never fused.
+    const bool fused = p.fusable && (p.form == 2 || p.small);
+    // a handful of tokens per sample (stage 1 of the step): 256-thread workgroups for the fused kernel
+    p.few = p.form == 2 ? (maxc <= 4 && n8) : (p.small && few1);
+    if (p.form == 2) {
+        p.front_threads = (fused && p.few) ? 256 : 512;
+        p.front_lds = front2_lds;
+        p.front_attr = p.front_lds > 40 * 1024;
+    } else {
+        p.front_threads = (fused && p.few) ? 256 : p.small ? CF_THREADS : 512;
+        p.front_lds = rows_lds;
+        p.front_attr = p.front_lds > 64 * 1024;
+    }
+
+    // Launch 3: the back half when it is a launch of its own, with the token rows of a sample in LDS when they fit (second form:
+    // while two workgroups still share a CU).  The kv projection needs the front launch alone, like the back half, so it rides in
+    // that launch where nr_linear.h takes the pair, and launch 4 is the q projection alone.  NR_KV_APART=1: never.
+    p.kv_launch = 4;
+    if (fused) {
+        p.back = NR_CTM_BACK_NONE;
+        p.back_form = 0;
+    } else {
+        p.back_use_lds = p.form == 2 ? rows_lds <= 56 * 1024 : (rows256 && rows_lds <= 96 * 1024);
+        p.back_lds = p.back_use_lds ? rows_lds : 0;
+        bool beside = !p.fusable && p.small && !kv_apart;
+        for (int i = 0; i < n; ++i) beside = beside && nr_linear_beside_back_fits(d[i].C, true, d[i].N, d[i].C, d[i].cnum, p.back_form);
+        p.back = beside ? NR_CTM_BACK_BESIDE_KV : NR_CTM_BACK_ALONE;
+        p.back_threads = (beside || p.form == 2 || threads512) ? 512 : BK_THREADS;
+        p.back_attr = !beside && p.back_lds > 40 * 1024;
+        if (beside) p.kv_launch = 3;
+    }
+
+    // Launch 5.  More than a wave's worth of (head, query) jobs per pair of heads: a 256-thread workgroup per (sample, pair of
+    // heads) with only those heads' k | v columns in LDS -- several share a CU, and 64-token samples get their k | v rows into LDS
+    // at all.  Otherwise one workgroup per sample with up to 128 KB of k | v rows: a wave per job, 8 waves when that covers them.
+    // NR_ATTN_WHOLE=1 keeps the whole-sample form (A/B hook).
+    if (jobs_max > 8 && !attn_whole && heads_even && kv_heads_lds <= 72 * 1024) {
+        p.attn_form = NR_CTM_ATTN_HEADS;
+        p.attn_threads = 256;
+        p.attn_use_lds = 1;
+        p.attn_lds = kv_heads_lds;
+    } else {
+        p.attn_form = NR_CTM_ATTN_WHOLE;
+        p.attn_threads = (jobs_max <= 8 || threads512) ? 512 : 1024;
+        p.attn_use_lds = kv_lds <= 128 * 1024;
+        p.attn_lds = p.attn_use_lds ? kv_lds : 0;
+    }
+    p.attn_attr = p.attn_lds > 64 * 1024;
+    for (int i = 0; i < n; ++i) p.attn_grid += attn_blocks(d[i], p.attn_form);
+    return p;
+}
+
+int raise_lds(const void* kernel, size_t lds) { return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
+
+// ---- the argument groups ----
+void kv_problems(const NrCtmStageDesc* d, const StageBuffers* w, int n, NrLinearArgs* p) {
+    for (int i = 0; i < n; ++i)
+        p[i] = NrLinearArgs{w[i].kvn_hi, w[i].kvn_lo, d[i].wkv_hi, d[i].wkv_lo, d[i].kv_bias, nullptr, w[i].kv, d[i].n_samples * d[i].N, 2 * d[i].C, d[i].C};
+}
+
+NrGroupOf<NrCtmFrontArgs> front_args(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan& p) {
+    NrGroupOf<NrCtmFrontArgs> g;
+    g.n = n;
+    for (int i = 0; i <= NR_CTM_MAX_GROUP; ++i) g.start[i] = p.start[i];
+    for (int i = 0; i < n; ++i) {
+        const NrCtmStageDesc& s = d[i];
+        g.p[i] = NrCtmFrontArgs{w[i].y, s.mask, s.ln_w, s.ln_b, s.sc_w, s.sc_b, s.n1_w, s.n1_b, s.eps_ctm, 1.0f / sqrtf((float)s.C),
+                                s.N, s.C, w[i].xn, nullptr, w[i].score, w[i].tokw, w[i].dist, w[i].smax, w[i].kvn_hi, w[i].kvn_lo};
+    }
+    return g;
+}
+
+NrGroupOf<NrCtmBackArgs> back_args(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan& p) {
+    NrGroupOf<NrCtmBackArgs> g;
+    g.n = n;
+    for (int i = 0; i <= NR_CTM_MAX_GROUP; ++i) g.start[i] = p.start[i];
+    for (int i = 0; i < n; ++i) {
+        const NrCtmStageDesc& s = d[i];
+        g.p[i] = NrCtmBackArgs{w[i].dist, w[i].smax, s.mask, s.noise, w[i].xn, w[i].tokw, s.n1_w, s.n1_b, s.proj_bias,
+                               s.n_samples, s.N, s.C, s.k, s.cnum, s.eps_n1, nullptr, w[i].merged_pb, nullptr, s.assign,
+                               w[i].qn_hi, w[i].qn_lo};
+    }
+    return g;
+}
+
+NrGroupOf<NrAttnArgs> attn_args(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan& p) {
+    NrGroupOf<NrAttnArgs> g;
+    g.n = n;
+    int blocks = 0;                          // (start[] counts WORKGROUPS: samples, or (sample, pair of heads))
+    for (int i = 0; i < n; ++i) {
+        const NrCtmStageDesc& s = d[i];
+        g.p[i] = NrAttnArgs{w[i].q, w[i].kv, w[i].score, s.N, s.C, s.cnum, s.heads, 1.0f / sqrtf(64.0f), nullptr, w[i].att_hi, w[i].att_lo};
+        g.start[i] = blocks;
+        blocks += attn_blocks(s, p.attn_form);
+    }
+    for (int i = n; i <= NR_CTM_MAX_GROUP; ++i) g.start[i] = blocks;
+    return g;
+}
+
+// ---- the seven launches, by launch index ----
+// 0. the token rows as bf16 pairs [rows, C] -- for the problems that do not bring them along (x_hi / x_lo: written by the
+//    previous stage's proj GEMM).  The k=3 convolution reads its neighbour rows in place: no shifted copy.
+int launch_split(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan& p, hipStream_t st) {
+    if (p.split_grid == 0) return NR_OK;
+    NrGroupOf<NrShiftArgs> g;
+    g.n = 0;
+    int total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (d[i].x_hi) continue;
+        g.p[g.n] = NrShiftArgs{d[i].x, d[i].n_samples * d[i].N, d[i].C, w[i].cat_hi, w[i].cat_lo, 1};       // (N = all rows: see the kernel)
+        g.start[g.n++] = total;
+        total += shift_blocks(d[i]);
+    }
+    for (int i = g.n; i <= NR_CTM_MAX_GROUP; ++i) g.start[i] = total;
+    hipLaunchKernelGGL(nr_group_shift_kernel, dim3(total), dim3(256), 0, st, g);
+    NR_LAUNCH_CHECK();
+    return NR_OK;
+}
+
+// 1. y = x + conv(x)  (k=3 convolution as a [B*N, 3C] x [3C, C] product whose A operand is read in place)
+int launch_conv(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan&, hipStream_t st) {
+    NrLinearArgs p[NR_CTM_MAX_GROUP];
+    for (int i = 0; i < n; ++i) {
+        p[i] = NrLinearArgs{d[i].x_hi ? d[i].x_hi : w[i].cat_hi, d[i].x_hi ? d[i].x_lo : w[i].cat_lo, d[i].wconv_hi, d[i].wconv_lo,
+                            d[i].conv_bias, d[i].x, w[i].y, d[i].n_samples * d[i].N, d[i].C, 3 * d[i].C};
+        p[i].conv_n = d[i].N;
+    }
+    return nr_linear_group_launch(p, n, st, true);
+}
+
+// 2. front (LayerNorm, score, exp, norm1, pairwise distances) -- and, fused, back (launch 3 is empty then)
+int launch_front(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan& p, hipStream_t st) {
+    const NrGroupOf<NrCtmFrontArgs> gf = front_args(d, w, n, p);
+    const NrGroupOf<NrCtmBackArgs> gb = back_args(d, w, n, p);
+    const bool fused = p.back == NR_CTM_BACK_NONE;
+    const dim3 grid(p.samples), block(p.front_threads);
+    const size_t lds = p.front_lds;
+    const void* k = p.form == 2 ? (!fused  ? (const void*)nr_group_front2_kernel<2, 512>
+                                   : p.few ? (const void*)nr_group_front_back2_kernel<2, 256, 4, 8>
+                                           : (const void*)nr_group_front_back2_kernel<2, 512, 16, 64>)
+                    : fused     ? (p.few ? (const void*)nr_group_front_back_kernel<8, 256> : (const void*)nr_group_front_back_kernel<8>)
+                    : p.small   ? (const void*)nr_group_front_kernel<8>
+                                : (const void*)nr_group_front_kernel<CF_MAX_CPL, 512>;
+    int rc;
+    if (p.front_attr && (rc = raise_lds(k, lds)) != NR_OK) return rc;
+    if (p.form == 2) {
+        if (!fused) hipLaunchKernelGGL((nr_group_front2_kernel<2, 512>), grid, block, lds, st, gf);
+        else if (p.few) hipLaunchKernelGGL((nr_group_front_back2_kernel<2, 256, 4, 8>), grid, block, lds, st, gf, gb);
+        else hipLaunchKernelGGL((nr_group_front_back2_kernel<2, 512, 16, 64>), grid, block, lds, st, gf, gb);
+    } else if (fused) {
+        if (p.few) hipLaunchKernelGGL((nr_group_front_back_kernel<8, 256>), grid, block, lds, st, gf, gb);
+        else hipLaunchKernelGGL(nr_group_front_back_kernel<8>, grid, block, lds, st, gf, gb);
+    } else {
+        if (p.small) hipLaunchKernelGGL(nr_group_front_kernel<8>, grid, block, lds, st, gf);
+        else hipLaunchKernelGGL((nr_group_front_kernel<CF_MAX_CPL, 512>), grid, block, lds, st, gf);
+    }
+    NR_LAUNCH_CHECK();
+    return NR_OK;
+}
+
+// 3. back (DPC-KNN assignment, weighted cluster means, norm1) as a launch of its own, the kv projection beside it where it fits
+int launch_back(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan& p, hipStream_t st) {
+    if (p.back == NR_CTM_BACK_NONE) return NR_OK;
+    const NrGroupOf<NrCtmBackArgs> gb = back_args(d, w, n, p);
+    const size_t lds = p.back_lds;
+    const int use_lds = p.back_use_lds;
+    int rc;
+    if (p.back == NR_CTM_BACK_BESIDE_KV) {
+        NrLinearArgs kv[NR_CTM_MAX_GROUP];
+        kv_problems(d, w, n, kv);
+        rc = nr_linear_group_launch_beside_back(kv, n, gb, lds, use_lds, p.back_form, st);
+        return rc == NR_EUNSUPPORTED ? NR_EINVAL : rc;      // planned with the launch's own predicate: a refusal is a bug here
+    }
+    const dim3 grid(p.samples), block(p.back_threads);
+    const void* k = p.back_form == 4    ? (const void*)nr_group_back2_kernel<512, 4, 1>
+                    : p.back_form == 16 ? (const void*)nr_group_back2_kernel<512, 16, 1>
+#ifdef NR_TUNE
+                    : p.back_threads == 512 ? (const void*)nr_group_back_kernel<512>
+#endif
+                                        : (const void*)nr_group_back_kernel<BK_THREADS>;
+    if (p.back_attr && (rc = raise_lds(k, lds)) != NR_OK) return rc;
+    if (p.back_form == 4) hipLaunchKernelGGL((nr_group_back2_kernel<512, 4, 1>), grid, block, lds, st, gb, use_lds);
+    else if (p.back_form == 16) hipLaunchKernelGGL((nr_group_back2_kernel<512, 16, 1>), grid, block, lds, st, gb, use_lds);
+#ifdef NR_TUNE
+    else if (p.back_threads == 512) hipLaunchKernelGGL(nr_group_back_kernel<512>, grid, block, lds, st, gb, use_lds);
+#endif
+    else hipLaunchKernelGGL(nr_group_back_kernel<BK_THREADS>, grid, block, lds, st, gb, use_lds);
+    NR_LAUNCH_CHECK();
+    return NR_OK;
+}
+
+// 4. q = norm1(merged) Wq^T (+b), and kv = norm1(xn) Wkv^T (+b) unless it rode in launch 3: one grouped launch
+int launch_qkv(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan& p, hipStream_t st) {
+    NrLinearArgs lp[2 * NR_CTM_MAX_GROUP];
+    int np = 0;
+    if (p.kv_launch == 4) {
+        kv_problems(d, w, n, lp);
+        np = n;
+    }
+    for (int i = 0; i < n; ++i) {
+        const NrCtmStageDesc& s = d[i];
+        lp[np++] = NrLinearArgs{w[i].qn_hi, w[i].qn_lo, s.wq_hi, s.wq_lo, s.q_bias, nullptr, w[i].q, s.n_samples * s.cnum, s.C, s.C};
+    }
+    return nr_linear_group_launch(lp, np, st);
+}
+
+// 5. score-biased attention of the merged tokens over the un-merged ones
+int launch_attention(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan& p, hipStream_t st) {
+    const NrGroupOf<NrAttnArgs> g = attn_args(d, w, n, p);
+    const dim3 grid(p.attn_grid), block(p.attn_threads);
+    const bool by_heads = p.attn_form == NR_CTM_ATTN_HEADS;
+    int rc;
+    if (p.attn_attr && (rc = raise_lds(by_heads ? (const void*)nr_group_attention_heads_kernel : (const void*)nr_group_attention_kernel, p.attn_lds)) != NR_OK)
+        return rc;
+    if (by_heads) hipLaunchKernelGGL(nr_group_attention_heads_kernel, grid, block, p.attn_lds, st, g);
+    else hipLaunchKernelGGL(nr_group_attention_kernel, grid, block, p.attn_lds, st, g, p.attn_use_lds);
+    NR_LAUNCH_CHECK();
+    return NR_OK;
+}
+
+// 6. out = merged + proj(att) + proj.bias
+int launch_proj(const NrCtmStageDesc* d, const StageBuffers* w, int n, const StagePlan&, hipStream_t st) {
+    NrLinearArgs p[NR_CTM_MAX_GROUP];
+    for (int i = 0; i < n; ++i) {
+        p[i] = NrLinearArgs{w[i].att_hi, w[i].att_lo, d[i].wp_hi, d[i].wp_lo, nullptr, w[i].merged_pb, d[i].out,
+                            d[i].n_samples * d[i].cnum, d[i].C, d[i].C};
+        p[i].out_hi = d[i].out_hi;              // optional: the output also as a bf16 pair (the next stage's x_hi / x_lo)
+        p[i].out_lo = d[i].out_lo;
+    }
+    return nr_linear_group_launch(p, n, st);
+}
+
+using StageLaunch = int (*)(const NrCtmStageDesc*, const StageBuffers*, int, const StagePlan&, hipStream_t);
+constexpr StageLaunch stage_launches[NR_CTM_STAGE_LAUNCHES] = {launch_split, launch_conv,      launch_front, launch_back,
+                                                               launch_qkv,   launch_attention, launch_proj};
+}  // namespace
+
+extern "C" int nr_ctm_stage_plan(const NrCtmStageDesc* d, int n, int32_t* plan) {
+    if (!plan) return NR_EINVAL;
+    const int rc = validate(d, n, false);
+    if (rc != NR_OK) return rc;
+    const StagePlan p = plan_stage(d, n);
+    plan[NR_CTM_PLAN_SAMPLES] = p.samples;
+    for (int i = 0; i < NR_CTM_MAX_GROUP; ++i) plan[NR_CTM_PLAN_START + i] = p.start[i];
+    plan[NR_CTM_PLAN_SPLIT_GRID] = p.split_grid;
+    plan[NR_CTM_PLAN_FUSABLE] = p.fusable;
+    plan[NR_CTM_PLAN_FORM] = p.form;
+    plan[NR_CTM_PLAN_FRONT_THREADS] = p.front_threads;
+    plan[NR_CTM_PLAN_FRONT_LDS] = (int32_t)p.front_lds;
+    plan[NR_CTM_PLAN_FRONT_ATTR] = p.front_attr;
+    plan[NR_CTM_PLAN_BACK] = p.back;
+    plan[NR_CTM_PLAN_BACK_FORM] = p.back_form;
+    plan[NR_CTM_PLAN_BACK_THREADS] = p.back_threads;
+    plan[NR_CTM_PLAN_BACK_LDS] = (int32_t)p.back_lds;
+    plan[NR_CTM_PLAN_BACK_USE_LDS] = p.back_use_lds;
+    plan[NR_CTM_PLAN_BACK_ATTR] = p.back_attr;
+    plan[NR_CTM_PLAN_KV_LAUNCH] = p.kv_launch;
+    plan[NR_CTM_PLAN_ATTN_FORM] = p.attn_form;
+    plan[NR_CTM_PLAN_ATTN_GRID] = p.attn_grid;
+    plan[NR_CTM_PLAN_ATTN_THREADS] = p.attn_threads;
+    plan[NR_CTM_PLAN_ATTN_LDS] = (int32_t)p.attn_lds;
+    plan[NR_CTM_PLAN_ATTN_USE_LDS] = p.attn_use_lds;
+    plan[NR_CTM_PLAN_ATTN_ATTR] = p.attn_attr;
+    return NR_OK;
+}
+
 extern "C" int nr_ctm_stage_fwd(const NrCtmStageDesc* d, int n, void* stream) {
     return nr_ctm_stage_fwd_range(d, n, 0, NR_CTM_STAGE_LAUNCHES, stream);
 }
 
 // launches [first, last) of the stage's seven: lets the host interleave them with other work in capture order
 extern "C" int nr_ctm_stage_fwd_range(const NrCtmStageDesc* d, int n, int first, int last, void* stream) {
-    if (!d || n <= 0 || n > NR_CTM_MAX_GROUP || first < 0 || last > NR_CTM_STAGE_LAUNCHES || first >= last) return NR_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+    if (first < 0 || last > NR_CTM_STAGE_LAUNCHES || first >= last) return NR_EINVAL;
+    int rc = validate(d, n, true);
+    if (rc != NR_OK) return rc;
     StageBuffers w[NR_CTM_MAX_GROUP];
-    size_t front_lds = 0;
-    for (int i = 0; i < n; ++i) {
-        const NrCtmStageDesc& s = d[i];
-        if (!s.x || !s.noise || !s.wconv_hi || !s.wconv_lo || !s.ln_w || !s.ln_b || !s.sc_w || !s.sc_b || !s.n1_w || !s.n1_b ||
-            !s.wq_hi || !s.wq_lo || !s.wkv_hi || !s.wkv_lo || !s.wp_hi || !s.wp_lo || !s.proj_bias || !s.workspace || !s.out)
-            return NR_EINVAL;
-        if (s.n_samples <= 0 || s.N <= 0 || s.k <= 0 || s.k > s.N || s.cnum <= 0 || s.cnum > s.N || s.heads <= 0) return NR_EINVAL;
-        if (s.N > 64 || s.C <= 0 || (s.C % 128) != 0 || s.C > 1024 || s.C != s.heads * 64) return NR_EUNSUPPORTED;
-        if (s.cnum * (s.C / 128) > 16 * BK_MAXJ) return NR_EUNSUPPORTED;
-        w[i] = carve(s.workspace, s.n_samples, s.N, s.C, s.cnum);
-        size_t lds = (size_t)s.N * s.C * sizeof(float);
-        if (lds > 150 * 1024) return NR_EUNSUPPORTED;
-        front_lds = lds > front_lds ? lds : front_lds;
-    }
-    int rc;
-    // 1. the token rows as bf16 pairs [rows, C] -- for the problems that do not bring them along (x_hi / x_lo: written by
-    //    the previous stage's proj GEMM).  The k=3 convolution reads its neighbour rows in place: no shifted copy.
-    bool all_split = true;
-    for (int i = 0; i < n; ++i) {
-        if ((d[i].x_hi == nullptr) != (d[i].x_lo == nullptr)) return NR_EINVAL;
-        all_split = all_split && d[i].x_hi != nullptr;
-    }
-    if (first <= 0 && 0 < last && !all_split) {
-        NrGroupOf<NrShiftArgs> g;
-        g.n = 0;
-        int total = 0;
-        for (int i = 0; i < n; ++i) {
-            if (d[i].x_hi) continue;
-            const int rows = d[i].n_samples * d[i].N;
-            g.p[g.n] = NrShiftArgs{d[i].x, rows, d[i].C, w[i].cat_hi, w[i].cat_lo, 1};       // (N = all rows: see the kernel)
-            g.start[g.n++] = total;
-            total += (rows + NR_SHIFT_ROWS - 1) / NR_SHIFT_ROWS;
-        }
-        for (int i = g.n; i <= NR_CTM_MAX_GROUP; ++i) g.start[i] = total;
-        hipLaunchKernelGGL(nr_group_shift_kernel, dim3(total), dim3(256), 0, st, g);
-        NR_LAUNCH_CHECK();
-    }
-    // 2. y = x + conv(x)  (k=3 convolution as a [B*N, 3C] x [3C, C] product whose A operand is read in place)
-    if (first <= 1 && 1 < last) {
-        NrLinearArgs p[NR_CTM_MAX_GROUP];
-        for (int i = 0; i < n; ++i) {
-            p[i] = NrLinearArgs{d[i].x_hi ? d[i].x_hi : w[i].cat_hi, d[i].x_hi ? d[i].x_lo : w[i].cat_lo, d[i].wconv_hi, d[i].wconv_lo,
-                                d[i].conv_bias, d[i].x, w[i].y, d[i].n_samples * d[i].N, d[i].C, 3 * d[i].C};
-            p[i].conv_n = d[i].N;
-        }
-        if ((rc = nr_linear_group_launch(p, n, st, true)) != NR_OK) return rc;
-    }
-    // 3 + 4. front (LayerNorm, score, exp, norm1, pairwise distances) and back (DPC-KNN assignment, weighted cluster
-    //        means, norm1).  Two launches when a problem carries a mask (the back half then needs the maximum
-    //        distance over ALL samples); ONE when none does (stage 1 of the step): launch index 2 runs both, index 3
-    //        is empty.
-    bool fusable = true;
-    for (int i = 0; i < n; ++i) fusable = fusable && d[i].mask == nullptr;
-    bool small_c = true;                     // (`small` below: registers sized for C <= 512 unless a problem is wider)
-    for (int i = 0; i < n; ++i) small_c = small_c && d[i].C <= 512;
-    // Stages whose back half is a launch of its own (a mask: the back half needs the maximum distance over all samples): the kv
-    // projection rides in that launch (launch 3), launch 4 is the q projection alone.  NR_KV_APART=1 (tuning builds): as before.
-    bool kv_beside_back = !(fusable && small_c) && small_c && !nr_tune_env("NR_KV_APART");
-    for (int i = 0; i < n; ++i) kv_beside_back = kv_beside_back && d[i].cnum * (d[i].C / 128) <= 8 * BK_MAXJ;
-    if ((first <= 2 && 2 < last) || (first <= 3 && 3 < last)) {
-        NrGroupOf<NrCtmFrontArgs> gf;
-        NrGroupOf<NrCtmBackArgs> gb;
-        gf.n = gb.n = n;
-        int total = 0;
-        for (int i = 0; i < n; ++i) {
-            const NrCtmStageDesc& s = d[i];
-            gf.p[i] = NrCtmFrontArgs{w[i].y, s.mask, s.ln_w, s.ln_b, s.sc_w, s.sc_b, s.n1_w, s.n1_b, s.eps_ctm, 1.0f / sqrtf((float)s.C),
-                                     s.N, s.C, w[i].xn, nullptr, w[i].score, w[i].tokw, w[i].dist, w[i].smax, w[i].kvn_hi, w[i].kvn_lo};
-            gb.p[i] = NrCtmBackArgs{w[i].dist, w[i].smax, s.mask, s.noise, w[i].xn, w[i].tokw, s.n1_w, s.n1_b, s.proj_bias,
-                                    s.n_samples, s.N, s.C, s.k, s.cnum, s.eps_n1, nullptr, w[i].merged_pb, nullptr, s.assign,
-                                    w[i].qn_hi, w[i].qn_lo};
-            gf.start[i] = gb.start[i] = total;
-            total += s.n_samples;
-        }
-        for (int i = n; i <= NR_CTM_MAX_GROUP; ++i) gf.start[i] = gb.start[i] = total;
-        bool small = true;                   // registers sized for C <= 512 unless a problem is wider
-        for (int i = 0; i < n; ++i) small = small && d[i].C <= 512;
-        // The second form of the two bodies (nr_ctm_bodies.h): every problem 512 channels wide (the model's width), at most 16
-        // clusters.  NR_CTM_V1=1 (tuning builds) keeps the first form.
-        bool v2 = !nr_tune_env("NR_CTM_V1");
-        int maxc = 0, maxn = 0;
-        size_t lds2 = 0;
-        for (int i = 0; i < n; ++i) {
-            v2 = v2 && d[i].C == 512 && d[i].cnum <= 16;
-            maxc = d[i].cnum > maxc ? d[i].cnum : maxc;
-            maxn = d[i].N > maxn ? d[i].N : maxn;
-            const size_t need = nr_ctm_front2_lds_floats(d[i].N, d[i].C) * sizeof(float);
-            lds2 = need > lds2 ? need : lds2;
-        }
-        // the back half's registers: 4 cluster accumulators and a 32-entry distance row per token, or 16 and 64
-        const int back_form = (maxc <= 4 && maxn <= 32) ? 4 : 16;
-        if (v2 && first <= 2 && 2 < last) {
-            bool few = maxc <= 4;                // a handful of tokens per sample (stage 1 of the step): 256-thread workgroups
-            for (int i = 0; i < n; ++i) few = few && d[i].N <= 8;
-            const void* k = !fusable ? (const void*)nr_group_front2_kernel<2, 512>
-                            : few    ? (const void*)nr_group_front_back2_kernel<2, 256, 4, 8>
-                                     : (const void*)nr_group_front_back2_kernel<2, 512, 16, 64>;
-            if (lds2 > 40 * 1024) {
-                hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                if (e != hipSuccess) return (int)e;
-            }
-            if (!fusable) hipLaunchKernelGGL((nr_group_front2_kernel<2, 512>), dim3(total), dim3(512), lds2, st, gf);
-            else if (few) hipLaunchKernelGGL((nr_group_front_back2_kernel<2, 256, 4, 8>), dim3(total), dim3(256), lds2, st, gf, gb);
-            else hipLaunchKernelGGL((nr_group_front_back2_kernel<2, 512, 16, 64>), dim3(total), dim3(512), lds2, st, gf, gb);
-            NR_LAUNCH_CHECK();
-        }
-        if (v2 && first <= 3 && 3 < last && !fusable) {
-            size_t lds = 0;                      // token rows of the largest problem: in LDS when two workgroups still fit a CU
-            for (int i = 0; i < n; ++i) {
-                size_t need = (size_t)d[i].N * d[i].C * sizeof(float);
-                lds = need > lds ? need : lds;
-            }
-            const int use_lds = lds <= 56 * 1024;
-            if (!use_lds) lds = 0;
-            if (kv_beside_back) {
-                // the kv projections need the front launch alone, like the back half: one grid carries both (nr_linear.h)
-                NrLinearArgs p[NR_CTM_MAX_GROUP];
-                for (int i = 0; i < n; ++i) {
-                    const NrCtmStageDesc& s = d[i];
-                    p[i] = NrLinearArgs{w[i].kvn_hi, w[i].kvn_lo, s.wkv_hi, s.wkv_lo, s.kv_bias, nullptr, w[i].kv, s.n_samples * s.N, 2 * s.C, s.C};
-                }
-                rc = nr_linear_group_launch_beside_back(p, n, gb, lds, use_lds, back_form, st);
-                if (rc != NR_OK) return rc;
-            } else {
-                const void* k = back_form == 4 ? (const void*)nr_group_back2_kernel<512, 4, 1> : (const void*)nr_group_back2_kernel<512, 16, 1>;
-                if (lds > 40 * 1024) {
-                    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    if (e != hipSuccess) return (int)e;
-                }
-                if (back_form == 4) hipLaunchKernelGGL((nr_group_back2_kernel<512, 4, 1>), dim3(total), dim3(512), lds, st, gb, use_lds);
-                else hipLaunchKernelGGL((nr_group_back2_kernel<512, 16, 1>), dim3(total), dim3(512), lds, st, gb, use_lds);
-                NR_LAUNCH_CHECK();
-            }
-        }
-        if (!v2 && first <= 2 && 2 < last) {
-            bool few = small;                    // a handful of tokens per sample (stage 1 of the step): 256-thread workgroups
-            for (int i = 0; i < n; ++i) few = few && d[i].N <= 8 && d[i].cnum * (d[i].C / 128) <= 4 * BK_MAXJ;
-            if (fusable && few) {
-                hipLaunchKernelGGL((nr_group_front_back_kernel<8, 256>), dim3(total), dim3(256), front_lds, st, gf, gb);
-            } else if (fusable && small) {
-                const void* k = (const void*)nr_group_front_back_kernel<8>;
-                if (front_lds > 64 * 1024) {
-                    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)front_lds);
-                    if (e != hipSuccess) return (int)e;
-                }
-                hipLaunchKernelGGL(nr_group_front_back_kernel<8>, dim3(total), dim3(CF_THREADS), front_lds, st, gf, gb);
-            } else {
-                // C > 512: sixteen channels per lane of seven per-channel vectors do not fit the 128 registers a 1024-thread
-                // workgroup leaves a lane (48 spilled registers, round 3) -- 512-thread workgroups, and never the fused
-                // front + back form (the back launch below runs on its own)
-                if (front_lds > 64 * 1024) {
-                    hipError_t e = hipFuncSetAttribute(small ? (const void*)nr_group_front_kernel<8> : (const void*)nr_group_front_kernel<CF_MAX_CPL, 512>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)front_lds);
-                    if (e != hipSuccess) return (int)e;
-                }
-                if (small) hipLaunchKernelGGL(nr_group_front_kernel<8>, dim3(total), dim3(CF_THREADS), front_lds, st, gf);
-                else hipLaunchKernelGGL((nr_group_front_kernel<CF_MAX_CPL, 512>), dim3(total), dim3(512), front_lds, st, gf);
-            }
-            NR_LAUNCH_CHECK();
-        }
-        if (!v2 && first <= 3 && 3 < last && !(fusable && small)) {
-            size_t lds = 0;                      // token rows of the largest problem, if every problem's rows fit
-            bool fits = true;
-            for (int i = 0; i < n; ++i) {
-                size_t need = (size_t)d[i].N * d[i].C * sizeof(float);
-                lds = need > lds ? need : lds;
-                fits = fits && (d[i].N * d[i].C) % 256 == 0;
-            }
-            const int use_lds = fits && lds <= 96 * 1024;
-            if (!use_lds) lds = 0;
-            if (kv_beside_back) {
-                // the kv projections need the front launch alone, like the back half: one grid carries both (nr_linear.h)
-                NrLinearArgs p[NR_CTM_MAX_GROUP];
-                for (int i = 0; i < n; ++i) {
-                    const NrCtmStageDesc& s = d[i];
-                    p[i] = NrLinearArgs{w[i].kvn_hi, w[i].kvn_lo, s.wkv_hi, s.wkv_lo, s.kv_bias, nullptr, w[i].kv, s.n_samples * s.N, 2 * s.C, s.C};
-                }
-                rc = nr_linear_group_launch_beside_back(p, n, gb, lds, use_lds, 0, st);
-                if (rc != NR_OK) return rc;
-            } else {
-            if (lds > 40 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void*)nr_group_back_kernel<BK_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-#ifdef NR_TUNE
-                if (e == hipSuccess) e = hipFuncSetAttribute((const void*)nr_group_back_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-#endif
-                if (e != hipSuccess) return (int)e;
-            }
-#ifdef NR_TUNE
-            const char* te = nr_tune_env("NR_CTM_THREADS");
-            if (te && atoi(te) == 512) hipLaunchKernelGGL(nr_group_back_kernel<512>, dim3(total), dim3(512), lds, st, gb, use_lds);
-            else
-#endif
-            hipLaunchKernelGGL(nr_group_back_kernel<BK_THREADS>, dim3(total), dim3(BK_THREADS), lds, st, gb, use_lds);
-            NR_LAUNCH_CHECK();
-            }
-        }
-    }
-    // 5. q = norm1(merged) Wq^T (+b), kv = norm1(xn) Wkv^T (+b): 2n problems, one launch
-    if (first <= 4 && 4 < last) {
-        NrLinearArgs p[2 * NR_CTM_MAX_GROUP];
-        int np = 0;
-        for (int i = 0; i < n && !kv_beside_back; ++i) {
-            const NrCtmStageDesc& s = d[i];
-            p[np++] = NrLinearArgs{w[i].kvn_hi, w[i].kvn_lo, s.wkv_hi, s.wkv_lo, s.kv_bias, nullptr, w[i].kv, s.n_samples * s.N, 2 * s.C, s.C};
-        }
-        for (int i = 0; i < n; ++i) {
-            const NrCtmStageDesc& s = d[i];
-            p[np++] = NrLinearArgs{w[i].qn_hi, w[i].qn_lo, s.wq_hi, s.wq_lo, s.q_bias, nullptr, w[i].q, s.n_samples * s.cnum, s.C, s.C};
-        }
-        if ((rc = nr_linear_group_launch(p, np, st)) != NR_OK) return rc;
-    }
-    // 6. score-biased attention of the merged tokens over the un-merged ones
-    if (first <= 5 && 5 < last) {
-        NrGroupOf<NrAttnArgs> g;
-        g.n = n;
-        int total = 0;
-        for (int i = 0; i < n; ++i) {
-            const NrCtmStageDesc& s = d[i];
-            g.p[i] = NrAttnArgs{w[i].q, w[i].kv, w[i].score, s.N, s.C, s.cnum, s.heads, 1.0f / sqrtf(64.0f), nullptr, w[i].att_hi, w[i].att_lo};
-            g.start[i] = total;
-            total += s.n_samples;
-        }
-        for (int i = n; i <= NR_CTM_MAX_GROUP; ++i) g.start[i] = total;
-        size_t lds = 0;                      // k|v rows of the largest problem, if every problem's rows fit
-        for (int i = 0; i < n; ++i) {
-            size_t need = (size_t)d[i].N * (2 * d[i].C + 4) * sizeof(float);
-            lds = need > lds ? need : lds;
-        }
-        const int use_lds = lds <= 128 * 1024;
-        if (!use_lds) lds = 0;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)nr_group_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        int jobs_max = 0;                    // (head, query) jobs per sample: one wave each, 8 waves when that covers them
-        for (int i = 0; i < n; ++i) jobs_max = d[i].heads * d[i].cnum > jobs_max ? d[i].heads * d[i].cnum : jobs_max;
-        // More than a wave's worth of jobs per pair of heads: a 256-thread workgroup per (sample, pair of heads) with only those
-        // heads' k | v columns in LDS -- several share a CU (the whole-sample form: one 1024-thread workgroup with up to 128 KB),
-        // and 64-token samples get their k | v rows into LDS at all.  NR_ATTN_WHOLE=1 keeps the whole-sample form (A/B hook).
-        bool by_heads = jobs_max > 8 && !nr_tune_env("NR_ATTN_WHOLE");
-        size_t lds_h = 0;
-        for (int i = 0; i < n; ++i) {
-            by_heads = by_heads && d[i].heads % NR_ATTN_HG == 0;
-            size_t need = (size_t)d[i].N * (2 * 64 * NR_ATTN_HG + 4) * sizeof(float);
-            lds_h = need > lds_h ? need : lds_h;
-        }
-        if (by_heads && lds_h <= 72 * 1024) {
-            int blocks = 0;
-            for (int i = 0; i < n; ++i) {
-                g.start[i] = blocks;
-                blocks += d[i].n_samples * (d[i].heads / NR_ATTN_HG);
-            }
-            for (int i = n; i <= NR_CTM_MAX_GROUP; ++i) g.start[i] = blocks;
-            if (lds_h > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void*)nr_group_attention_heads_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);
-                if (e != hipSuccess) return (int)e;
-            }
-            hipLaunchKernelGGL(nr_group_attention_heads_kernel, dim3(blocks), dim3(256), lds_h, st, g);
-            NR_LAUNCH_CHECK();
-        } else {
-            const char* te = nr_tune_env("NR_CTM_THREADS");
-            hipLaunchKernelGGL(nr_group_attention_kernel, dim3(total), dim3((jobs_max <= 8 || (te && atoi(te) == 512)) ? 512 : 1024), lds, st, g,
-                               use_lds);
-            NR_LAUNCH_CHECK();
-        }
-    }
-    // 7. out = merged + proj(att) + proj.bias
-    if (first <= 6 && 6 < last) {
-        NrLinearArgs p[NR_CTM_MAX_GROUP];
-        for (int i = 0; i < n; ++i) {
-            p[i] = NrLinearArgs{w[i].att_hi, w[i].att_lo, d[i].wp_hi, d[i].wp_lo, nullptr, w[i].merged_pb, d[i].out,
-                                d[i].n_samples * d[i].cnum, d[i].C, d[i].C};
-            p[i].out_hi = d[i].out_hi;              // optional: the output also as a bf16 pair (the next stage's x_hi / x_lo)
-            p[i].out_lo = d[i].out_lo;
-        }
-        if ((rc = nr_linear_group_launch(p, n, st)) != NR_OK) return rc;
-    }
+    for (int i = 0; i < n; ++i) w[i] = carve(d[i].workspace, d[i].n_samples, d[i].N, d[i].C, d[i].cnum);
+    const StagePlan p = plan_stage(d, n);
+    for (int i = first; i < last; ++i)
+        if ((rc = stage_launches[i](d, w, n, p, (hipStream_t)stream)) != NR_OK) return rc;
     return NR_OK;
 }
+

@@ -3,6 +3,7 @@
 // runs its text and video problems side by side (nr_ctm_group.hip).
 #pragma once
 #include "nr_common.h"
+#include "nr_ctm_bodies.h"
 
 struct NrLinearArgs {
     const uint16_t *x_hi, *x_lo, *w_hi, *w_lo;
@@ -30,9 +31,18 @@ int nr_linear_group_launch(const NrLinearArgs* probs, int n_probs, hipStream_t s
 // so the two run beside each other instead of one behind the other (the back half is a latency chain on a few waves per
 // sample, the GEMM tiles are LDS-DMA bound: they share CUs well).  gb: the back problems (start[] = first workgroup of each,
 // start[NR_CTM_MAX_GROUP] = their total); back_lds: dynamic LDS of a back workgroup when use_lds.  Tile shape fixed: 64 x 128
-// on 8 waves, one-deep ring.  NR_EUNSUPPORTED when a problem does not fit that form (the caller then launches the two apart).
-struct NrCtmBackArgs;
-template <typename A> struct NrGroupOf;
+// on 8 waves, one-deep ring.  probs[i] rides beside gb.p[i] (n_probs == gb.n).
 // back_form: 0 = nr_ctm_back_body (first form); 4 / 16 = nr_ctm_back_body2 with accumulators for that many clusters (C = 512).
+//
+// nr_linear_beside_back_fits: whether ONE projection (inner dimension K; plain: no conv_n, no ld, no out_hi / out_lo) and the
+// back problem beside it (N tokens, C channels, cnum clusters) fit that grid in form back_form.  The clustering stage asks it
+// while it PLANS (nr_ctm_group.hip: plan_stage) and launches the two apart where the answer is no; the launch checks its own
+// arguments with the same function and returns NR_EUNSUPPORTED, launching nothing, where it is no -- after planning that cannot
+// happen, and the stage reports it as an internal error.
+inline bool nr_linear_beside_back_fits(int K, bool plain, int N, int C, int cnum, int back_form) {
+    if ((K % 64) != 0 || !plain || N > 64) return false;
+    // first form: the 8-wave body spreads cnum * C/128 merge jobs over 8 waves; second form: C = 512, cnum <= back_form
+    return back_form == 0 ? cnum * (C / 128) <= 8 * BK_MAXJ : (C == 512 && cnum <= back_form);
+}
 int nr_linear_group_launch_beside_back(const NrLinearArgs* probs, int n_probs, const NrGroupOf<NrCtmBackArgs>& gb, size_t back_lds,
                                        int use_lds, int back_form, hipStream_t stream);

@@ -115,25 +115,21 @@ int nr_linear_group_launch_beside_back(const NrLinearArgs* probs, int n, const N
                                        int back_form, hipStream_t st) {
     constexpr int MI = 2, NI = 2, STAGES = 1, WC = 4;
     using Tile = NrGemmTile<MI, NI, true, 16, 16, STAGES, WC>;
-    if (!probs || n <= 0 || n > NR_LINEAR_MAX_GROUP) return NR_EINVAL;
+    if (!probs || n <= 0 || n > NR_LINEAR_MAX_GROUP || n != gb.n) return NR_EINVAL;
+    if (back_form != 0 && back_form != 4 && back_form != 16) return NR_EINVAL;
     NrLinearGroup g;
     g.n = n;
     int total = 0;
     for (int i = 0; i < n; ++i) {
         const NrLinearArgs& a = probs[i];
         if (!a.x_hi || !a.x_lo || !a.w_hi || !a.w_lo || !a.out || a.M <= 0 || a.N <= 0 || a.K <= 0) return NR_EINVAL;
-        if ((a.K % 64) != 0 || a.conv_n != 0 || a.ld != 0 || a.out_hi || a.out_lo) return NR_EUNSUPPORTED;
+        if (!nr_linear_beside_back_fits(a.K, a.conv_n == 0 && a.ld == 0 && !a.out_hi && !a.out_lo, gb.p[i].N, gb.p[i].C, gb.p[i].cnum, back_form))
+            return NR_EUNSUPPORTED;
         g.p[i] = a;
         g.tile_start[i] = total;
         total += ((a.M + Tile::BM - 1) / Tile::BM) * ((a.N + Tile::BN - 1) / Tile::BN);
     }
     for (int i = n; i <= NR_LINEAR_MAX_GROUP; ++i) g.tile_start[i] = total;
-    if (back_form != 0 && back_form != 4 && back_form != 16) return NR_EINVAL;
-    for (int i = 0; i < gb.n; ++i) {
-        if (gb.p[i].N > 64) return NR_EUNSUPPORTED;
-        // first form: the 8-wave body spreads cnum * C/128 merge jobs over 8 waves; second form: C = 512, cnum <= back_form
-        if (back_form == 0 ? gb.p[i].cnum * (gb.p[i].C / 128) > 8 * BK_MAXJ : (gb.p[i].C != 512 || gb.p[i].cnum > back_form)) return NR_EUNSUPPORTED;
-    }
     const int n_back = gb.start[NR_CTM_MAX_GROUP], n_back_pad = (n_back + 7) & ~7;
     size_t lds = Tile::RING_BYTES;
     if (use_lds && back_lds > lds) lds = back_lds;

@@ -157,6 +157,14 @@ SIM_BWD_GROUP_MAX, POOLW_GROUP_MAX = 4, 8
 LOCAL_LEVEL_GROUP_MAX = 4
 CTM_MAX_GROUP = 4
 CTM_STAGE_LAUNCHES = 7
+# nr_ctm_stage_plan: the words of a plan (NR_CTM_PLAN_* of include/nr_hip.h; "start" is CTM_MAX_GROUP words long)
+CTM_PLAN_WORDS = 24
+CTM_PLAN = {name: i for i, name in enumerate(
+    ("samples", "start", None, None, None, "split_grid", "fusable", "form", "front_threads", "front_lds", "front_attr", "back",
+     "back_form", "back_threads", "back_lds", "back_use_lds", "back_attr", "kv_launch", "attn_form", "attn_grid", "attn_threads",
+     "attn_lds", "attn_use_lds", "attn_attr")) if name}
+CTM_BACK_NONE, CTM_BACK_ALONE, CTM_BACK_BESIDE_KV = 0, 1, 2
+CTM_ATTN_WHOLE, CTM_ATTN_HEADS = 0, 1
 
 _SIGNATURES = {
     "nr_version": ([], _I),
@@ -206,6 +214,7 @@ _SIGNATURES = {
     "nr_ctm_mid_bwd": ([_I, ctypes.POINTER(CtmMidBwdDesc), _P], _I),
     "nr_ctm_stage_fwd": ([ctypes.POINTER(CtmStageDesc), _I, _P], _I),
     "nr_ctm_stage_fwd_range": ([ctypes.POINTER(CtmStageDesc), _I, _I, _I, _P], _I),
+    "nr_ctm_stage_plan": ([ctypes.POINTER(CtmStageDesc), _I, ctypes.POINTER(ctypes.c_int32)], _I),
     "nr_sinkhorn_workspace_bytes": ([_I], _Z),
     "nr_sinkhorn_cooperative_ok": ([_I], _I),
     "nr_sinkhorn_cooperative_gate": ([_I, _I, _I, _I], _I),
@@ -421,6 +430,26 @@ def token_scorer_plan(n_tok, H, prec, N_fused=0):
         return None
     _check("nr_token_scorer_plan", rc)
     return bm.value, bn.value, st.value
+
+
+def ctm_stage_plan(problems):
+    """The plan words (tuple of CTM_PLAN_WORDS ints, indexed by CTM_PLAN) of one grouped clustering stage (nr_ctm_stage_plan; host
+    only).  problems: a CtmStageDesc array, or a list of (n_samples, N, C, k, cnum, heads, masked, paired) -- the plan reads the
+    scalars and whether mask / x_hi / x_lo are given, nothing else.  None where nr_ctm_stage_fwd returns NR_EUNSUPPORTED for the
+    shapes (the caller takes its other path); raises on bad arguments."""
+    if not isinstance(problems, ctypes.Array):
+        descs = (CtmStageDesc * len(problems))()
+        for d, (n_samples, N, C, k, cnum, heads, masked, paired) in zip(descs, problems):
+            d.n_samples, d.N, d.C, d.k, d.cnum, d.heads = int(n_samples), int(N), int(C), int(k), int(cnum), int(heads)
+            d.mask = 1 if masked else None                  # (never dereferenced: given or not)
+            d.x_hi = d.x_lo = 1 if paired else None
+        problems = descs
+    words = (ctypes.c_int32 * CTM_PLAN_WORDS)()
+    rc = lib().nr_ctm_stage_plan(problems, len(problems), words)
+    if rc == NR_EUNSUPPORTED:
+        return None
+    _check("nr_ctm_stage_plan", rc)
+    return tuple(words)
 
 
 def local_level_group_kind(A, Nt, Bv, Nv, d, prec):

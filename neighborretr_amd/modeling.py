@@ -719,7 +719,8 @@ class NeighborRetr(nn.Module):
                                              mb_mask_t, mb_mask_v, hp, logit_scale, comm.get_rank(), world, noise)
             return losses[0], losses[1], losses[2], losses[3], losses[4]
         if (shard_now and not torch.is_grad_enabled()
-                and self._can_fuse_clustering(text_feat, mods) and self._can_fuse_clustering(video_feat, mods)):
+                and self._can_fuse_clustering(text_feat, mods) and self._can_fuse_clustering(video_feat, mods)
+                and self._grouped_stages_supported(text_feat, video_feat)):
             from . import comm
             # The clustering is sharded by samples too: every rank clusters ITS b samples and the [b, c, d] global tokens are
             # all-gathered.  Its masked stage fills distances with the maximum over the WHOLE gathered batch
@@ -743,7 +744,8 @@ class NeighborRetr(nn.Module):
                                                **self._global_scorers(text_feat, video_feat))
             return losses[0], losses[1], losses[2], losses[3], losses[4]
         if (text_feat.is_cuda and self.use_side_streams and self.group_clustering and not torch.is_grad_enabled()
-                and self._can_fuse_clustering(text_feat, mods) and self._can_fuse_clustering(video_feat, mods)):
+                and self._can_fuse_clustering(text_feat, mods) and self._can_fuse_clustering(video_feat, mods)
+                and self._grouped_stages_supported(text_feat, video_feat)):
             # loss-only step: the text and video clustering advance together inside grouped launches on THIS
             # stream (the critical path); the local branch runs beside them on a side stream, the two bank
             # chains beside the Sinkhorn solve (head.head_forward).
@@ -752,7 +754,7 @@ class NeighborRetr(nn.Module):
             self._join_global = self._merge_grouped_steps(text_feat, video_feat, text_mask, video_mask, nz)
         elif (text_feat.is_cuda and self.fuse_clustering and torch.is_grad_enabled()
               and (self.fused_training_clustering is None or self.fused_training_clustering)
-              and text_feat.shape[1] <= 64 and video_feat.shape[1] <= 64 and text_feat.shape[2] % 128 == 0):
+              and self._grouped_stages_supported(text_feat, video_feat)):
             # training step: the clustering forward on the grouped HIP kernels, the backward hand-derived from what they
             # leave in their workspaces (cluster_fused.ClusterStagesFn, cluster_backward.stage_backward)
             from .cluster_fused import build_stage_weights, cluster_stages_train, route_on_this_stream, stage_params
@@ -983,8 +985,18 @@ class NeighborRetr(nn.Module):
         t = blk0(ctm0({"x": feat, "mask": mask.detach()}, noise0))
         return blk1(ctm1(t, noise1))["x"]
 
+    def _grouped_stages_supported(self, text_feat, video_feat):
+        """Whether the GROUPED stage (ctm_stage_group / cluster_stages_train) takes these token counts and this width: the
+        library's planner answers (cluster_fused.grouped_stages_supported, memoised).  Shapes only -- flags, gradients, device
+        and streams are the caller's conditions."""
+        from .cluster_fused import grouped_stages_supported
+        ks = tuple(int(getattr(self, n).k) for n in ("text_ctm0", "video_ctm0", "text_ctm1", "video_ctm1"))
+        return grouped_stages_supported(text_feat.shape[1], video_feat.shape[1], text_feat.shape[2],
+                                        int(self.text_block0.attn.num_heads), ks)
+
     def _can_fuse_clustering(self, feat, mods):
-        """Fused forward kernels when no gradient is wanted; autograd-traced torch ops otherwise."""
+        """The ONE-PROBLEM fused forward (ctm_stage_fused, which takes C % 64) when no gradient is wanted; autograd-traced torch
+        ops otherwise.  The grouped stage has its own shape gate: _grouped_stages_supported."""
         if not (feat.is_cuda and self.fuse_clustering and feat.shape[1] <= 64 and feat.shape[2] % 64 == 0):
             return False
         if not torch.is_grad_enabled():

@@ -298,7 +298,7 @@ def sharded_training_losses(model, text_feat, video_feat, text_mask, video_mask,
     # differentiable all-gather: d gt of a rank's samples = the sum of every rank's W dL_r / d gt, so the clustering
     # parameters receive W x (the contribution of this rank's samples) and DDP's mean over the ranks is the full gradient.
     # `model.shard_clustering = False`: the replicated form (every rank differentiates the whole clustering).
-    if model.shard_clustering and text_feat.is_cuda and text_feat.shape[1] <= 64 and video_feat.shape[1] <= 64 and d % 128 == 0:
+    if model.shard_clustering and text_feat.is_cuda and model._grouped_stages_supported(text_feat, video_feat):
         gt_l, gv_l = model._merge_sharded(text_feat, video_feat, text_mask, video_mask, noise or {}, rank, world)
         if gt_l.shape[1] != 1 or gv_l.shape[1] != 1:
             raise RuntimeError("the sharded training loss covers one global token per sample (until_module.py:321)")

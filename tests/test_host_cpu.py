@@ -232,6 +232,82 @@ def test_token_scorer_plan_no_gpu_needed():
     assert [o.value for o in out] == [-7, -7, -7]
 
 
+def _ctm_problems(shapes):
+    """ctm_plan_ref's (n_samples, N, C, cnum, masked, paired) -> the tuples hip.ctm_stage_plan takes."""
+    return [(B, N, C, min(5, N), cnum, C // 64, m, p) for B, N, C, cnum, m, p in shapes]
+
+
+def test_ctm_stage_plan_no_gpu_needed():
+    """nr_ctm_stage_plan (host only): EVERY row of ctm_plan_ref.ROWS -- plans read off a launch trace of the code before the
+    planner existed, refused shapes with their status --, every other refusal with its status and the output untouched, and
+    that the plan of two problems does not depend on their order except for the per-problem offsets."""
+    import ctm_plan_ref as R
+    P = hip.CTM_PLAN
+    assert len(R.ROWS) > 2900
+    for shapes, want in R.ROWS:
+        got = hip.ctm_stage_plan(_ctm_problems(shapes))
+        assert (hip.NR_EUNSUPPORTED if got is None else got) == want, (shapes, got, want)
+        if got is not None and len(shapes) == 2:
+            swapped = hip.ctm_stage_plan(_ctm_problems(shapes[::-1]))
+            lo, hi = P["start"], P["start"] + hip.CTM_MAX_GROUP
+            assert swapped[:lo] == got[:lo] and swapped[hi:] == got[hi:], shapes
+            assert swapped[lo:hi] == (0, shapes[1][0]) + (got[P["samples"]],) * 2, shapes
+    # the model's stage 0 at B = 128 by name: second form of the bodies, back (form 4) beside the kv GEMM, attention by heads
+    plan = hip.ctm_stage_plan(_ctm_problems(((128, 24, 512, 4, 1, 0), (128, 12, 512, 3, 1, 0))))
+    assert [plan[P[k]] for k in ("samples", "split_grid", "form", "front_threads", "front_lds", "front_attr")] == [256, 576, 2, 512, 51968, 1]
+    assert [plan[P[k]] for k in ("back", "back_form", "back_lds", "back_use_lds", "kv_launch")] == [hip.CTM_BACK_BESIDE_KV, 4, 49152, 1, 3]
+    assert [plan[P[k]] for k in ("attn_form", "attn_grid", "attn_threads", "attn_lds", "attn_attr")] == [hip.CTM_ATTN_HEADS, 1024, 256, 24960, 0]
+    # refusals, with the statuses the stage itself returned for them in the same trace; the output stays untouched
+    lib = hip.lib()
+    words = (ctypes.c_int32 * hip.CTM_PLAN_WORDS)(*([-7] * hip.CTM_PLAN_WORDS))
+
+    def status(probs, n=None, **fields):
+        descs = (hip.CtmStageDesc * max(len(probs), 5))()
+        for d, (B, N, C, k, cnum, heads, m, p) in zip(descs, probs):
+            d.n_samples, d.N, d.C, d.k, d.cnum, d.heads = B, N, C, k, cnum, heads
+            d.mask, d.x_hi, d.x_lo = (1 if m else None), (1 if p else None), (1 if p else None)
+        for name, v in fields.items():
+            setattr(descs[0], name, v)
+        return lib.nr_ctm_stage_plan(descs, len(probs) if n is None else n, words)
+    ok = (3, 24, 512, 5, 4, 8, 1, 0)
+    assert status([ok]) == 0 and words[0] == 3
+    for i in range(hip.CTM_PLAN_WORDS):
+        words[i] = -7
+    cases = {"n=0": status([ok], n=0), "n=5": status([ok] * 5), "k>N": status([ok], k=25), "cnum>N": status([ok], cnum=25),
+             "heads=0": status([ok], heads=0), "x_hi without x_lo": status([ok], x_hi=1), "C=192": status([(3, 24, 192, 5, 4, 3, 1, 0)]),
+             "C=512 heads=4": status([ok], heads=4), "C=1152": status([(3, 24, 1152, 5, 4, 18, 1, 0)]),
+             "N=65": status([(3, 65, 512, 5, 4, 8, 1, 0)]), "N=64 C=640": status([(3, 64, 640, 5, 4, 10, 1, 0)]),
+             "N=64 cnum=64 C=512": status([(3, 64, 512, 5, 64, 8, 1, 0)]), "second of two C=192": status([ok, (3, 24, 192, 5, 4, 3, 1, 0)])}
+    # the launch range is checked before anything touches a device: these two answer on a CPU as well
+    descs = (hip.CtmStageDesc * 1)()
+    cases["first>=last"] = lib.nr_ctm_stage_fwd_range(descs, 1, 3, 3, None)
+    cases["last>7"] = lib.nr_ctm_stage_fwd_range(descs, 1, 0, 8, None)
+    assert cases == R.REFUSALS
+    assert list(words) == [-7] * hip.CTM_PLAN_WORDS
+    assert lib.nr_ctm_stage_plan(None, 1, words) == hip.NR_EINVAL and status([ok]) == 0
+    assert lib.nr_ctm_stage_plan((hip.CtmStageDesc * 1)(), 1, None) == hip.NR_EINVAL
+    assert hip.ctm_stage_plan(_ctm_problems(((3, 24, 192, 4, 1, 0),))) is None
+    with pytest.raises(hip.NrHipError):
+        hip.ctm_stage_plan([(3, 2, 512, 3, 1, 8, 0, 1)])               # k > N
+
+
+def test_grouped_stages_supported_is_the_library_answer():
+    """cluster_fused.grouped_stages_supported: the one shape gate of the grouped stage's callers, answered by the planner."""
+    from neighborretr_amd.cluster_fused import grouped_stages_supported as ok
+    assert ok(24, 12, 512, 8) is True and ok(64, 64, 512, 8) is True
+    assert ok(24, 12, 192, 3) is False           # C % 128: the one-problem path takes this width, the grouped stage does not
+    assert ok(24, 12, 64, 1) is False
+    assert ok(64, 64, 640, 10) is False          # 64 tokens x 640 channels: the front half's rows exceed 150 KB of LDS
+    assert ok(65, 12, 512, 8) is False
+    with pytest.raises(hip.NrHipError):
+        ok(6, 12, 512, 8)                        # one text token reaches stage 1, k = 3 (the reference raises there as well)
+    m = modeling.NeighborRetr(modeling.default_config())
+    x = problem(1, 4, 24, 12, 8)
+    assert m._grouped_stages_supported(x["text_feat"], x["video_feat"]) is True
+    hits = ok.cache_info().hits
+    assert m._grouped_stages_supported(x["text_feat"], x["video_feat"]) is True and ok.cache_info().hits == hits + 1      # memoised
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_product_path_fails_loudly_without_gpu():
     from neighborretr_amd import ops

@@ -442,6 +442,53 @@ def test_grouped_clustering_stage_equals_the_per_modality_path(B, Nt, Nv):
         assert maxdiff(a, b) < 2e-5 * max(1.0, float(b.abs().max()))
 
 
+@pytest.mark.parametrize("B,Nt,Nv", [(4, 24, 12), (2, 64, 64)])
+def test_grouped_stage_gives_the_same_bits_however_it_is_driven(B, Nt, Nv):
+    """The three ways cluster_fused drives nr_ctm_stage_fwd_range -- the whole stage, launch by launch (stepwise=True) and in two
+    halves around an exchange that changes nothing -- launch from ONE plan: outputs, cluster ids and everything a backward pass
+    reads from the workspaces are the same bits, stage 0 (masked) chained into stage 1.  (2, 64, 64): the back half in its
+    16-cluster form, token rows that do not fit its LDS."""
+    from neighborretr_amd import modeling, synth
+    from neighborretr_amd.cluster_fused import ctm_stage_group
+    m = modeling.NeighborRetr(modeling.default_config())
+    m.load_state_dict(params(), strict=False)
+    m = m.to(DEV).eval()
+    prob = {k: torch.from_numpy(v).to(DEV) for k, v in synth.make_problem(77, B, Nt, Nv, 8).items()}
+    nz = {k: torch.from_numpy(v).to(DEV) for k, v in synth.make_noise(77, B, Nt, Nv).items()}
+    tm, vm = prob["text_mask"].float(), prob["video_mask"].float()
+    if Nt == 64:
+        P = hip.CTM_PLAN
+        plan = hip.ctm_stage_plan([(B, 64, 512, 3, 11, 8, True, False), (B, 64, 512, 3, 16, 8, True, False)])
+        assert (plan[P["back_form"]], plan[P["back_use_lds"]]) == (16, 0)
+
+    def two_stages(**how):
+        cache, res = {}, []
+        t, v = prob["text_feat"], prob["video_feat"]
+        for s, (mt, mv) in enumerate(((tm, vm), (None, None))):
+            ret = ctm_stage_group([(f"t{s}", t, mt, getattr(m, f"text_ctm{s}"), getattr(m, f"text_block{s}"), nz[f"t{s}"]),
+                                   (f"v{s}", v, mv, getattr(m, f"video_ctm{s}"), getattr(m, f"video_block{s}"), nz[f"v{s}"])],
+                                  cache, want_saved=True, **how)
+            if how.get("stepwise"):
+                (t, v), steps, saved = ret
+                assert sum(1 for _ in steps) == hip.CTM_STAGE_LAUNCHES
+            else:
+                (t, v), saved = ret
+            res.append(((t, v), saved))
+        torch.cuda.synchronize()
+        return res
+    with torch.no_grad():
+        whole = two_stages()
+        others = {"stepwise": two_stages(stepwise=True), "halves": two_stages(exchange=lambda smax: None)}
+    for how, got in others.items():
+        for s, ((outs_w, saved_w), (outs_g, saved_g)) in enumerate(zip(whole, got)):
+            for i in range(2):
+                assert torch.equal(outs_w[i], outs_g[i]), (how, s, i)
+                assert torch.equal(saved_w[i]["assign"], saved_g[i]["assign"]), (how, s, i)
+                assert saved_w[i].keys() == saved_g[i].keys()
+                for name, ref in saved_w[i].items():
+                    assert (ref is None and saved_g[i][name] is None) or torch.equal(ref, saved_g[i][name]), (how, s, i, name)
+
+
 def test_step_prologue_masks_scale_and_noise():
     g = torch.Generator().manual_seed(0)
     m0 = (torch.rand(128, 24, generator=g) > 0.3).long().to(DEV)
