@@ -157,6 +157,36 @@ int nr_local_level_fwd(const uint16_t* t_hi, const uint16_t* t_lo, const uint16_
                        int prec, int out_mode, float* out, uint8_t* arg_v, uint8_t* arg_t,
                        float* pmax, float* qmax, void* stream);
 
+/* The launch form of ONE nr_local_level_fwd call, from the host alone (no device, no launch): NR_LLP_WORDS ints computed by the
+ * launcher's own selection, tile grid, ring rule and LDS budget, not by a copy of them.
+ *   [NR_LLP_KERNEL]     NR_LLP_KERNEL_LDS (nr_sim.hip: the block goes through the LDS) or NR_LLP_KERNEL_REG (nr_sim_reg.hip)
+ *   [NR_LLP_BLOCK_ROWS], [NR_LLP_BLOCK_COLS]   the MFMA block in tokens;  [NR_LLP_WAVES]  4 or 8
+ *   [NR_LLP_STAGES]     ring depth;  [NR_LLP_KLOOP]  NR_KLOOP_PLAIN, NR_KLOOP_PP (ping-pong) or NR_KLOOP_PP3 (split-bf16 as three
+ *                       accumulated passes through the ping-pong loop of the one-pass tile)
+ *   [NR_LLP_TEXTS], [NR_LLP_VIDEOS]   whole texts x videos per block: the tiling nr_local_level_tiles reports
+ *   [NR_LLP_GRID_COLS], [NR_LLP_GRID_ROWS]   blocks along the videos / the texts
+ *   [NR_LLP_PAIR_LANES] LDS kernel: lanes per pair in its last phase (1 .. 64); 0 for the register kernel
+ * NR_EINVAL / NR_EUNSUPPORTED exactly where nr_local_level_fwd returns them for these arguments (pointer checks aside);
+ * `words` is untouched then. */
+#define NR_LLP_KERNEL 0
+#define NR_LLP_BLOCK_ROWS 1
+#define NR_LLP_BLOCK_COLS 2
+#define NR_LLP_WAVES 3
+#define NR_LLP_STAGES 4
+#define NR_LLP_KLOOP 5
+#define NR_LLP_TEXTS 6
+#define NR_LLP_VIDEOS 7
+#define NR_LLP_GRID_COLS 8
+#define NR_LLP_GRID_ROWS 9
+#define NR_LLP_PAIR_LANES 10
+#define NR_LLP_WORDS 11
+#define NR_LLP_KERNEL_LDS 0
+#define NR_LLP_KERNEL_REG 1
+#define NR_KLOOP_PLAIN 0
+#define NR_KLOOP_PP 1
+#define NR_KLOOP_PP3 2
+int nr_local_level_plan(int A, int Nt, int Bv, int Nv, int d, int prec, int32_t* words);
+
 /* Fused local_level (modeling.py:483-514) of CANDIDATE LISTS: the token-level score of chosen (query, gallery item) pairs
  * instead of a whole rectangle -- the second stage of two-stage retrieval.  No counterpart in the reference, which scores
  * every pair (evaluator.py:21-63).

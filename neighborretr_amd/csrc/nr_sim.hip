@@ -189,6 +189,8 @@ int nr_sim_reg_dispatch(const uint16_t* t_hi, const uint16_t* t_lo, const uint16
                         const float* w_t, const float* w_v, int A, int Nt, int Bv, int Nv, int d, int prec, int out_mode,
                         float* out, uint8_t* arg_v, uint8_t* arg_t, float* pmax, float* qmax, hipStream_t st);
 extern "C" int nr_sim_reg_tile(int A, int Nt, int Bv, int Nv, int prec, int* TA, int* TB);
+int nr_sim_reg_describe(int A, int Nt, int Bv, int Nv, int d, int prec, int32_t* w);
+static int nr_sim_generic_setup(NrSimArgs& a, int prec, int* mi_out, int* ni_out, size_t* lds_out);
 
 static bool nr_sim_force_generic() {
     const char* e = nr_tune_env("NR_SIM_GENERIC");
@@ -260,16 +262,38 @@ extern "C" int nr_local_level_fwd(const uint16_t* t_hi, const uint16_t* t_lo, co
             if (rc != NR_EUNSUPPORTED) return rc;
         }
     }
+    NrSimArgs a;
+    a.t_hi = t_hi; a.t_lo = t_lo; a.v_hi = v_hi; a.v_lo = v_lo;
+    a.w_t = w_t; a.w_v = w_v; a.out = out; a.arg_v = arg_v; a.arg_t = arg_t; a.pmax = pmax; a.qmax = qmax;
+    a.A = A; a.Nt = Nt; a.Bv = Bv; a.Nv = Nv; a.K = d; a.out_mode = out_mode;
+    int mi = 0, ni = 0;
+    size_t lds = 0;
+    if (int rc = nr_sim_generic_setup(a, prec, &mi, &ni, &lds)) return rc;
+
+    dim3 grid((Bv + a.TB - 1) / a.TB, (A + a.TA - 1) / a.TA);
+    hipStream_t st = (hipStream_t)stream;
+    const bool x3 = prec == NR_PREC_BF16X3;
+#define NR_SIM_CASE(M_, N_)                                                       \
+    if (mi == M_ && ni == N_)                                                     \
+        return x3 ? nr_sim_launch<M_, N_, true>(a, grid, lds, st) : nr_sim_launch<M_, N_, false>(a, grid, lds, st);
+    NR_SIM_CASE(2, 2) NR_SIM_CASE(2, 3) NR_SIM_CASE(2, 4)
+    NR_SIM_CASE(3, 2) NR_SIM_CASE(3, 3) NR_SIM_CASE(3, 4)
+    NR_SIM_CASE(4, 2) NR_SIM_CASE(4, 3) NR_SIM_CASE(4, 4)
+#undef NR_SIM_CASE
+    return NR_EUNSUPPORTED;
+}
+
+// The LDS kernel's launch parameters for a.A / Nt / Bv / Nv: block extents (*mi, *ni sub-tile counts), texts x videos per
+// block, lanes per pair, LDS layout and size.  NR_EUNSUPPORTED: more than 128 tokens per sample, or over the LDS budget.
+// Read by nr_local_level_fwd and by nr_local_level_plan.
+static int nr_sim_generic_setup(NrSimArgs& a, int prec, int* mi_out, int* ni_out, size_t* lds_out) {
+    const int A = a.A, Nt = a.Nt, Bv = a.Bv, Nv = a.Nv;
     int mi = 0, ni = 0;
     int TA = nr_pick_extent(Nt, &mi), TB = nr_pick_extent(Nv, &ni);
     if (TA == 0 || TB == 0) return NR_EUNSUPPORTED;
     if (TA > A) TA = A;
     if (TB > Bv) TB = Bv;
-
-    NrSimArgs a;
-    a.t_hi = t_hi; a.t_lo = t_lo; a.v_hi = v_hi; a.v_lo = v_lo;
-    a.w_t = w_t; a.w_v = w_v; a.out = out; a.arg_v = arg_v; a.arg_t = arg_t; a.pmax = pmax; a.qmax = qmax;
-    a.A = A; a.Nt = Nt; a.Bv = Bv; a.Nv = Nv; a.K = d; a.TA = TA; a.TB = TB; a.out_mode = out_mode;
+    a.TA = TA; a.TB = TB;
     const int BM = 32 * mi, BN = 32 * ni;
     a.ldc = BN + 4;
     int npair = TA * TB;
@@ -289,16 +313,39 @@ extern "C" int nr_local_level_fwd(const uint16_t* t_hi, const uint16_t* t_lo, co
     a.off_wt = (int)(base + pw + qw + sp);
     size_t lds = base + pw + qw + sp + (size_t)(BM + BN) * 4;
     if (lds > 160 * 1024) return NR_EUNSUPPORTED;
+    *mi_out = mi;
+    *ni_out = ni;
+    *lds_out = lds;
+    return NR_OK;
+}
 
-    dim3 grid((Bv + TB - 1) / TB, (A + TA - 1) / TA);
-    hipStream_t st = (hipStream_t)stream;
-    const bool x3 = prec == NR_PREC_BF16X3;
-#define NR_SIM_CASE(M_, N_)                                                       \
-    if (mi == M_ && ni == N_)                                                     \
-        return x3 ? nr_sim_launch<M_, N_, true>(a, grid, lds, st) : nr_sim_launch<M_, N_, false>(a, grid, lds, st);
-    NR_SIM_CASE(2, 2) NR_SIM_CASE(2, 3) NR_SIM_CASE(2, 4)
-    NR_SIM_CASE(3, 2) NR_SIM_CASE(3, 3) NR_SIM_CASE(3, 4)
-    NR_SIM_CASE(4, 2) NR_SIM_CASE(4, 3) NR_SIM_CASE(4, 4)
-#undef NR_SIM_CASE
-    return NR_EUNSUPPORTED;
+extern "C" int nr_local_level_plan(int A, int Nt, int Bv, int Nv, int d, int prec, int32_t* words) {
+    if (!words) return NR_EINVAL;
+    if (A <= 0 || Bv <= 0 || Nt <= 0 || Nv <= 0 || d <= 0 || (d % 64) != 0) return NR_EINVAL;
+    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3) return NR_EINVAL;
+    if (Nt > 255 || Nv > 255) return NR_EUNSUPPORTED;
+    int32_t w[NR_LLP_WORDS];
+    int rc = nr_sim_force_generic() ? NR_EUNSUPPORTED : nr_sim_reg_describe(A, Nt, Bv, Nv, d, prec, w);
+    if (rc == NR_EUNSUPPORTED) {          // as in nr_local_level_fwd: what the register kernel does not take runs the LDS kernel
+        NrSimArgs a{};
+        a.A = A; a.Nt = Nt; a.Bv = Bv; a.Nv = Nv; a.K = d;
+        int mi = 0, ni = 0;
+        size_t lds = 0;
+        rc = nr_sim_generic_setup(a, prec, &mi, &ni, &lds);
+        if (rc) return rc;
+        w[NR_LLP_KERNEL] = NR_LLP_KERNEL_LDS;
+        w[NR_LLP_BLOCK_ROWS] = 32 * mi;
+        w[NR_LLP_BLOCK_COLS] = 32 * ni;
+        w[NR_LLP_WAVES] = 4;
+        w[NR_LLP_STAGES] = NrGemmTile<2, 2, false>::RING_BYTES / NrGemmTile<2, 2, false>::STAGE_BYTES;      // the kernel's Tile: the engine's default ring, run()
+        w[NR_LLP_KLOOP] = NR_KLOOP_PLAIN;
+        w[NR_LLP_TEXTS] = a.TA;
+        w[NR_LLP_VIDEOS] = a.TB;
+        w[NR_LLP_GRID_COLS] = (Bv + a.TB - 1) / a.TB;
+        w[NR_LLP_GRID_ROWS] = (A + a.TA - 1) / a.TA;
+        w[NR_LLP_PAIR_LANES] = a.J;
+    }
+    if (rc) return rc;
+    for (int i = 0; i < NR_LLP_WORDS; ++i) words[i] = w[i];
+    return NR_OK;
 }

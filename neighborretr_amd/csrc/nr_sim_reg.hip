@@ -549,37 +549,58 @@ static void nr_sim_reg_plan(NrSimRegArgs& a) {
     a.dma_front = 0;
 }
 
-template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int WC = 2>
-static int nr_sim_reg_launch(NrSimRegArgs& a, hipStream_t st) {
-    nr_sim_reg_plan<MI, NI, TPS, FPS, WC>(a);
-    if (const char* e = nr_tune_env("NR_SIM_DMA_FRONT")) a.dma_front = atoi(e);
-    if (const char* e = nr_tune_env("NR_SIM_ROT")) {          // tuning hook: "XxY" K-slice rotation per slot column / row
-        int rx = 0, ry = 0;
-        if (sscanf(e, "%dx%d", &rx, &ry) == 2) { a.rot_x = rx; a.rot_y = ry; }
-    }
+// Ring depth and K loop of a block shape that chooses them by rule (nr_sim_reg_launch; the plan call reads the same function):
+// stages 1 / 2 (3: a -DNR_TUNE hook), loop NR_KLOOP_PLAIN or NR_KLOOP_PP.
+struct NrSimRing {
+    int stages, kloop;
+};
+template <int MI, int NI, bool X3, int WC>
+static NrSimRing nr_sim_reg_ring(long n_workgroups, int K) {
     // 192 x 192 blocks (8 waves, one workgroup per CU): nobody else hides their DMA latency, so they run the
     // 2-deep ring -- except split-bf16, whose two stages (196 KB) exceed the LDS
     constexpr bool big = WC == 4;
     constexpr bool mid = WC == 2 && MI * NI >= 18;          // 96 x 192 split-bf16: 144 KB for two stages, one workgroup per CU
     // 96 x 192 split-bf16 on 2 x 4 waves (48 x 48 per wave): the two-stage ring fits (144 KB) -> ping-pong K loop
+    if constexpr (big && X3 && MI * NI == 9) return {2, NR_KLOOP_PP};
+    else if constexpr (big && X3) return {1, NR_KLOOP_PLAIN};
+    else if constexpr (big) {          // (8-wave one-pass blocks always prefetch for themselves: no one-stage form of them)
+#ifdef NR_TUNE
+        if constexpr (NI == 3) {          // 192 x 192: three stages fit (144 KB)
+            const char* e3 = nr_tune_env("NR_SIM_STAGES");
+            if (e3 && atoi(e3) == 3) return {3, NR_KLOOP_PLAIN};
+        }
+#endif
+        // 8-wave blocks on the two-stage ring: ping-pong K loop (NrGemmTile::run_pp); NR_SIM_PP=0 = the plain loop (A/B)
+        const char* e = nr_tune_env("NR_SIM_PP");
+        return {2, (!(e && atoi(e) == 0) && K >= 128) ? NR_KLOOP_PP : NR_KLOOP_PLAIN};
+    } else return {mid ? 2 : nr_pick_stages(n_workgroups), NR_KLOOP_PLAIN};
+}
+
+template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int WC = 2>
+static int nr_sim_reg_launch(NrSimRegArgs& a, hipStream_t st) {
+    nr_sim_reg_plan<MI, NI, TPS, FPS, WC>(a);
+    const NrSimRing ring = nr_sim_reg_ring<MI, NI, X3, WC>((long)a.ntx * a.nty, a.K);
+    if (const char* e = nr_tune_env("NR_SIM_DMA_FRONT")) a.dma_front = atoi(e);
+    if (const char* e = nr_tune_env("NR_SIM_ROT")) {          // tuning hook: "XxY" K-slice rotation per slot column / row
+        int rx = 0, ry = 0;
+        if (sscanf(e, "%dx%d", &rx, &ry) == 2) { a.rot_x = rx; a.rot_y = ry; }
+    }
+    // which of the forms exist for a block shape is decided at compile time, exactly as nr_sim_reg_ring decides it
+    constexpr bool big = WC == 4;
     if constexpr (big && X3 && MI * NI == 9) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 2, WC, true>(a, st);
     else {
-    if constexpr (!(big && !X3)) {          // (8-wave one-pass blocks always prefetch for themselves: no one-stage form of them)
-        const bool one_stage = big ? X3 : (mid ? false : nr_pick_stages((long)a.ntx * a.nty) == 1);
-        if (one_stage) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 1, WC>(a, st);
+    if constexpr (!(big && !X3)) {
+        if (ring.stages == 1) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 1, WC>(a, st);
     }
     if constexpr (big && X3) return NR_EUNSUPPORTED;
     else {
 #ifdef NR_TUNE
-        if constexpr (big && NI == 3) {          // 192 x 192: three stages fit (144 KB)
-            const char* e = nr_tune_env("NR_SIM_STAGES");
-            if (e && atoi(e) == 3) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 3, WC>(a, st);
+        if constexpr (big && NI == 3) {
+            if (ring.stages == 3) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 3, WC>(a, st);
         }
 #endif
         if constexpr (big) {
-            // 8-wave blocks on the two-stage ring: ping-pong K loop (NrGemmTile::run_pp); NR_SIM_PP=0 = the plain loop (A/B)
-            const char* e = nr_tune_env("NR_SIM_PP");
-            if (!(e && atoi(e) == 0) && a.K >= 128) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 2, WC, true>(a, st);
+            if (ring.kloop == NR_KLOOP_PP) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 2, WC, true>(a, st);
         }
         return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 2, WC>(a, st);
     }
@@ -638,57 +659,115 @@ extern "C" int nr_sim_reg_tile(int A, int Nt, int Bv, int Nv, int prec, int* TA,
     return 1;
 }
 
+// ---- which block shape a product runs: ONE selection, read by the launch and by the plan call -------------------------
+// A block shape as a type.  MODE: which precisions it is built for, and how its ring and K loop are chosen.
+enum { NR_CFG_BOTH, NR_CFG_SPLIT, NR_CFG_ONE_PASS,      // ring / loop by nr_sim_reg_ring; both tiles, the split tile only, the one-pass tile only
+       NR_CFG_PASSES };                                 // two-deep ring, ping-pong loop on the ONE-PASS tile; split-bf16 = three accumulated passes
+template <int MI_, int NI_, int TPS_, int FPS_, int WC_, int MODE_, int RT_ = 1>
+struct NrSimRegCfg {
+    static constexpr int MI = MI_, NI = NI_, TPS = TPS_, FPS = FPS_, WC = WC_, MODE = MODE_, RT = RT_;
+};
+enum { NR_SEL_NONE, NR_SEL_256x256, NR_SEL_128x256, NR_SEL_96x192_W8, NR_SEL_96x192_W4, NR_SEL_192x384_PASSES, NR_SEL_192x384,
+       NR_SEL_192x192, NR_SEL_24x12, NR_SEL_64x64, NR_SEL_24x64, NR_SEL_64x12 };
+
+static int nr_sim_reg_select(int A, int Nt, int Bv, int Nv, int d, int prec) {
+    if (!nr_sim_reg_tile(A, Nt, Bv, Nv, prec, nullptr, nullptr)) return NR_SEL_NONE;
+    const bool x3 = prec == NR_PREC_BF16X3;
+    const int big = nr_sim_reg_big(A, Nt, Bv, Nv, prec);
+    if (big == 5) return NR_SEL_256x256;     // 64 x 64 tokens, 256 x 256 blocks on 2 x 4 waves
+    if (big == 4) return NR_SEL_128x256;     // 64 x 64 tokens, 128 x 256 blocks on 2 x 4 waves
+    if (big == 3) {                          // split-bf16, 96 x 192 blocks (4 texts x 16 videos), 2-deep ring
+        // 2 x 4 waves of 48 x 48 on the ping-pong K loop (13.7 -> 13.2 us at B = 128); NR_SIM_X3PP=0: the 2 x 2-wave form (A/B)
+        const char* e = nr_tune_env("NR_SIM_X3PP");
+        return (!(e && atoi(e) == 0) && d >= 128) ? NR_SEL_96x192_W8 : NR_SEL_96x192_W4;
+    }
+    // 192 x 384 blocks; split-bf16: three accumulated passes on the one-pass blocks, at EVERY d -- the ping-pong loop is valid
+    // from one K slice on, and nr_sim_reg_tile, which takes no d, reports these blocks' tiling for the sum modes
+    if (big == 2) return x3 ? NR_SEL_192x384_PASSES : NR_SEL_192x384;
+    if (big) return NR_SEL_192x192;          // 24 x 12 tokens, 192 x 192 blocks on 2 x 4 waves
+    if (Nt == 24 && Nv == 12) return NR_SEL_24x12;      // 24 text tokens x 12 frames (MSR-VTT)
+    if (Nt == 64 && Nv == 64) return NR_SEL_64x64;      // ActivityNet
+    if (Nt == 24 && Nv == 64) return NR_SEL_24x64;
+    if (Nt == 64 && Nv == 12) return NR_SEL_64x12;
+    return NR_SEL_NONE;
+}
+
+template <typename F>
+static int nr_sim_reg_visit(int sel, F&& f) {
+    switch (sel) {
+    case NR_SEL_256x256: return f(NrSimRegCfg<8, 4, 16, 16, 4, NR_CFG_PASSES, 2>{});
+    case NR_SEL_128x256: return f(NrSimRegCfg<4, 4, 16, 16, 4, NR_CFG_BOTH>{});
+    case NR_SEL_96x192_W8: return f(NrSimRegCfg<3, 3, 8, 4, 4, NR_CFG_SPLIT>{});
+    case NR_SEL_96x192_W4: return f(NrSimRegCfg<3, 6, 8, 2, 2, NR_CFG_SPLIT>{});
+    case NR_SEL_192x384_PASSES: return f(NrSimRegCfg<6, 6, 4, 2, 4, NR_CFG_PASSES>{});
+    case NR_SEL_192x384: return f(NrSimRegCfg<6, 6, 4, 2, 4, NR_CFG_ONE_PASS>{});
+    case NR_SEL_192x192: return f(NrSimRegCfg<6, 3, 4, 4, 4, NR_CFG_BOTH>{});
+    case NR_SEL_24x12: return f(NrSimRegCfg<3, 3, 8, 4, 2, NR_CFG_BOTH>{});
+    case NR_SEL_64x64: return f(NrSimRegCfg<4, 4, 16, 16, 2, NR_CFG_BOTH>{});
+    case NR_SEL_24x64: return f(NrSimRegCfg<3, 4, 8, 16, 2, NR_CFG_BOTH>{});
+    case NR_SEL_64x12: return f(NrSimRegCfg<4, 3, 16, 4, 2, NR_CFG_BOTH>{});
+    }
+    return NR_EUNSUPPORTED;
+}
+
 // returns NR_EUNSUPPORTED when the shape is not covered (the caller falls back to nr_sim.hip)
 int nr_sim_reg_dispatch(const uint16_t* t_hi, const uint16_t* t_lo, const uint16_t* v_hi, const uint16_t* v_lo,
                         const float* w_t, const float* w_v, int A, int Nt, int Bv, int Nv, int d, int prec, int out_mode,
                         float* out, uint8_t* arg_v, uint8_t* arg_t, float* pmax, float* qmax, hipStream_t st) {
-    if (!nr_sim_reg_tile(A, Nt, Bv, Nv, prec, nullptr, nullptr)) return NR_EUNSUPPORTED;
     NrSimRegArgs a{t_hi, t_lo, v_hi, v_lo, w_t, w_v, out, arg_v, arg_t, pmax, qmax, A, Bv, d, out_mode};
     const bool x3 = prec == NR_PREC_BF16X3, args = arg_v != nullptr;
-#define NR_REG_CASE(MI_, TPS_, NI_, FPS_)                                                              \
-    if (Nt == MI_ * TPS_ && Nv == NI_ * FPS_) {                                                        \
-        if (x3) return args ? nr_sim_reg_launch<MI_, NI_, TPS_, FPS_, true, true>(a, st)               \
-                            : nr_sim_reg_launch<MI_, NI_, TPS_, FPS_, true, false>(a, st);             \
-        return args ? nr_sim_reg_launch<MI_, NI_, TPS_, FPS_, false, true>(a, st)                      \
-                    : nr_sim_reg_launch<MI_, NI_, TPS_, FPS_, false, false>(a, st);                    \
-    }
-    if (nr_sim_reg_big(A, Nt, Bv, Nv, prec) == 5) {     // 64 x 64 tokens, 256 x 256 blocks on 2 x 4 waves
-        nr_sim_reg_plan<8, 4, 16, 16, 4, 2>(a);
-        if (x3)       // split-bf16 as three accumulated passes on the one-pass tile
-            return args ? nr_sim_reg_launch_s<8, 4, 16, 16, false, true, 2, 4, true, 2, true>(a, st)
-                        : nr_sim_reg_launch_s<8, 4, 16, 16, false, false, 2, 4, true, 2, true>(a, st);
-        return args ? nr_sim_reg_launch_s<8, 4, 16, 16, false, true, 2, 4, true, 2>(a, st)
-                    : nr_sim_reg_launch_s<8, 4, 16, 16, false, false, 2, 4, true, 2>(a, st);
-    }
-    if (nr_sim_reg_big(A, Nt, Bv, Nv, prec) == 4) {     // 64 x 64 tokens, 128 x 256 blocks on 2 x 4 waves
-        if (x3) return args ? nr_sim_reg_launch<4, 4, 16, 16, true, true, 4>(a, st) : nr_sim_reg_launch<4, 4, 16, 16, true, false, 4>(a, st);
-        return args ? nr_sim_reg_launch<4, 4, 16, 16, false, true, 4>(a, st) : nr_sim_reg_launch<4, 4, 16, 16, false, false, 4>(a, st);
-    }
-    if (nr_sim_reg_big(A, Nt, Bv, Nv, prec) == 3) {     // split-bf16, 96 x 192 blocks (4 texts x 16 videos), 2-deep ring
-        // 2 x 4 waves of 48 x 48 on the ping-pong K loop (13.7 -> 13.2 us at B = 128); NR_SIM_X3PP=0: the 2 x 2-wave form (A/B)
-        if (const char* e = nr_tune_env("NR_SIM_X3PP"); !(e && atoi(e) == 0) && d >= 128)
-            return args ? nr_sim_reg_launch<3, 3, 8, 4, true, true, 4>(a, st) : nr_sim_reg_launch<3, 3, 8, 4, true, false, 4>(a, st);
-        return args ? nr_sim_reg_launch<3, 6, 8, 2, true, true, 2>(a, st) : nr_sim_reg_launch<3, 6, 8, 2, true, false, 2>(a, st);
-    }
-    if (nr_sim_reg_big(A, Nt, Bv, Nv, prec) == 2 && x3) {     // ... split-bf16: three accumulated passes on the one-pass blocks
-        if (d < 128) return NR_EUNSUPPORTED;
-        nr_sim_reg_plan<6, 6, 4, 2, 4>(a);
-        return args ? nr_sim_reg_launch_s<6, 6, 4, 2, false, true, 2, 4, true, 1, true>(a, st)
-                    : nr_sim_reg_launch_s<6, 6, 4, 2, false, false, 2, 4, true, 1, true>(a, st);
-    }
-    if (nr_sim_reg_big(A, Nt, Bv, Nv, prec) == 2) {     // 24 x 12 tokens, 192 x 384 blocks on 2 x 4 waves
-        return args ? nr_sim_reg_launch<6, 6, 4, 2, false, true, 4>(a, st) : nr_sim_reg_launch<6, 6, 4, 2, false, false, 4>(a, st);
-    }
-    if (nr_sim_reg_big(A, Nt, Bv, Nv, prec)) {     // 24 x 12 tokens, 192 x 192 blocks on 2 x 4 waves
-        if (x3) return args ? nr_sim_reg_launch<6, 3, 4, 4, true, true, 4>(a, st) : nr_sim_reg_launch<6, 3, 4, 4, true, false, 4>(a, st);
-        return args ? nr_sim_reg_launch<6, 3, 4, 4, false, true, 4>(a, st) : nr_sim_reg_launch<6, 3, 4, 4, false, false, 4>(a, st);
-    }
-    NR_REG_CASE(3, 8, 3, 4)      // 24 text tokens x 12 frames (MSR-VTT)
-    NR_REG_CASE(4, 16, 4, 16)    // 64 x 64 (ActivityNet)
-    NR_REG_CASE(3, 8, 4, 16)     // 24 x 64
-    NR_REG_CASE(4, 16, 3, 4)     // 64 x 12
-#undef NR_REG_CASE
-    return NR_EUNSUPPORTED;
+    return nr_sim_reg_visit(nr_sim_reg_select(A, Nt, Bv, Nv, d, prec), [&](auto c) -> int {
+        using C = decltype(c);
+        constexpr int MI = C::MI, NI = C::NI, TPS = C::TPS, FPS = C::FPS, WC = C::WC, RT = C::RT;
+        if constexpr (C::MODE == NR_CFG_PASSES) {
+            nr_sim_reg_plan<MI, NI, TPS, FPS, WC, RT>(a);
+            if (x3)       // split-bf16 as three accumulated passes on the one-pass tile
+                return args ? nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, true, 2, WC, true, RT, true>(a, st)
+                            : nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, false, 2, WC, true, RT, true>(a, st);
+            return args ? nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, true, 2, WC, true, RT>(a, st)
+                        : nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, false, 2, WC, true, RT>(a, st);
+        } else {
+            static_assert(RT == 1, "two texts per wave strip: only on the fixed ping-pong form");
+            if constexpr (C::MODE != NR_CFG_ONE_PASS)
+                if (x3) return args ? nr_sim_reg_launch<MI, NI, TPS, FPS, true, true, WC>(a, st)
+                                    : nr_sim_reg_launch<MI, NI, TPS, FPS, true, false, WC>(a, st);
+            if constexpr (C::MODE != NR_CFG_SPLIT)
+                if (!x3) return args ? nr_sim_reg_launch<MI, NI, TPS, FPS, false, true, WC>(a, st)
+                                     : nr_sim_reg_launch<MI, NI, TPS, FPS, false, false, WC>(a, st);
+            return NR_EUNSUPPORTED;
+        }
+    });
+}
+
+// What nr_sim_reg_dispatch launches for these arguments, from the same selection, tile grid and ring rule: the words of
+// nr_local_level_plan (include/nr_hip.h).  NR_EUNSUPPORTED: the register kernel does not take the shape.
+int nr_sim_reg_describe(int A, int Nt, int Bv, int Nv, int d, int prec, int32_t* w) {
+    const bool x3 = prec == NR_PREC_BF16X3;
+    return nr_sim_reg_visit(nr_sim_reg_select(A, Nt, Bv, Nv, d, prec), [&](auto c) -> int {
+        using C = decltype(c);
+        constexpr int MI = C::MI, NI = C::NI, TPS = C::TPS, FPS = C::FPS, WC = C::WC, RT = C::RT;
+        NrSimRegArgs a{};
+        a.A = A; a.Bv = Bv; a.K = d;
+        nr_sim_reg_plan<MI, NI, TPS, FPS, WC, RT>(a);
+        NrSimRing ring{2, x3 ? NR_KLOOP_PP3 : NR_KLOOP_PP};          // NR_CFG_PASSES: one form per precision
+        if constexpr (C::MODE != NR_CFG_PASSES) {
+            if ((x3 && C::MODE == NR_CFG_ONE_PASS) || (!x3 && C::MODE == NR_CFG_SPLIT)) return NR_EUNSUPPORTED;
+            const long n_wg = (long)a.ntx * a.nty;
+            ring = x3 ? nr_sim_reg_ring<MI, NI, true, WC>(n_wg, d) : nr_sim_reg_ring<MI, NI, false, WC>(n_wg, d);
+        }
+        w[NR_LLP_KERNEL] = NR_LLP_KERNEL_REG;
+        w[NR_LLP_BLOCK_ROWS] = 32 * MI;
+        w[NR_LLP_BLOCK_COLS] = 16 * WC * NI;
+        w[NR_LLP_WAVES] = 2 * WC;
+        w[NR_LLP_STAGES] = ring.stages;
+        w[NR_LLP_KLOOP] = ring.kloop;
+        w[NR_LLP_TEXTS] = 2 * RT * (16 / TPS);
+        w[NR_LLP_VIDEOS] = WC * (16 / FPS);
+        w[NR_LLP_GRID_COLS] = a.ntx;
+        w[NR_LLP_GRID_ROWS] = a.nty;
+        w[NR_LLP_PAIR_LANES] = 0;
+        return NR_OK;
+    });
 }
 
 // ---- grouped launch (see nr_sim_group_kernel) -------------------------------------------------------------------------

@@ -186,6 +186,7 @@ _SIGNATURES = {
     "nr_token_scorer_plan": ([_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)], _I),
     "nr_token_weights_fwd": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P], _I),
     "nr_local_level_tiles": ([_I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)], _I),
+    "nr_local_level_plan": ([_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32)], _I),
     "nr_local_level_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "nr_local_level_cand": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P], _I),
     "nr_local_level_group_kind": ([_I, _I, _I, _I, _I, _I], _I),
@@ -418,6 +419,24 @@ def local_level_tiles(A, Nt, Bv, Nv, prec=PREC_BF16):
     r, c = _I(0), _I(0)
     _check("nr_local_level_tiles", lib().nr_local_level_tiles(A, Nt, Bv, Nv, int(prec), ctypes.byref(r), ctypes.byref(c)))
     return r.value, c.value
+
+
+LLP_WORDS = 11                               # NR_LLP_WORDS
+LLP_KERNELS = ("lds", "reg")                 # NR_LLP_KERNEL_*
+LLP_KLOOPS = ("plain", "pp", "pp3")          # NR_KLOOP_*
+
+
+def local_level_plan(A, Nt, Bv, Nv, d, prec):
+    """What one nr_local_level_fwd call launches (nr_local_level_plan; host only): (kernel "lds" / "reg", block rows, block columns,
+    waves, ring depth, K loop "plain" / "pp" / "pp3", texts per block, videos per block, grid columns, grid rows, lanes per pair of
+    the LDS kernel or 0).  None where nr_local_level_fwd returns NR_EUNSUPPORTED; raises on bad arguments."""
+    words = (ctypes.c_int32 * LLP_WORDS)()
+    rc = lib().nr_local_level_plan(int(A), int(Nt), int(Bv), int(Nv), int(d), int(prec), words)
+    if rc == NR_EUNSUPPORTED:
+        return None
+    _check("nr_local_level_plan", rc)
+    w = tuple(words)
+    return (LLP_KERNELS[w[0]],) + w[1:5] + (LLP_KLOOPS[w[5]],) + w[6:]
 
 
 def token_scorer_plan(n_tok, H, prec, N_fused=0):

@@ -109,8 +109,11 @@ SHAPES = [
 
 @pytest.fixture(params=[0, 1], ids=["auto", "lds-epilogue"])
 def sim_variant(request, monkeypatch):
-    """0: let the library pick (register epilogue for 24/64-token shapes); 1: force the generic LDS
-    epilogue of nr_sim.hip (NR_SIM_GENERIC is read by the host entry point on every call)."""
+    """0: let the library pick (register epilogue for 24/64-token shapes); 1: set NR_SIM_GENERIC=1, which forces the generic LDS
+    epilogue of nr_sim.hip ONLY in a -DNR_TUNE build: the host entry point reads it through nr_tune_env, and that returns
+    nullptr in a release build (csrc/nr_common.h), so in the build the suite tests both parameter values run the same code --
+    the library's own choice.  The LDS epilogue is reached there through the token counts the register kernel does not own
+    (three of SHAPES); every instance of it is held to fp64 in tests/test_simfwd_gpu.py."""
     monkeypatch.setenv("NR_SIM_GENERIC", str(request.param))
     return request.param
 
