@@ -880,6 +880,27 @@ int nr_hubnorm_combine(int P, const float* parts, int L, float* stats, float* ls
 int nr_hubnorm_apply(const float* S, int n, int L, float beta, int mode, const float* col_norm, const int32_t* row_gate,
                      float* T, const float* row_norm, const int32_t* col_gate, float* V, void* stream);
 
+/* Query-bank normalisation and re-ranking of CANDIDATE LISTS: the search-time stage of IS / QB-Norm on two-stage retrieval
+ * (DESIGN.md "Query-bank normalisation of two-stage retrieval").  The reference has no such path: it has neither candidate
+ * lists nor a test-time normalisation.  One launch; fine / cand [n, C] as nr_local_level_cand reads and writes them (the
+ * lists in ascending gallery index, so position order is index order); norm [n_gallery] f32 or null, active [n_gallery] int32
+ * or null: the gallery's normalisers and activation set, computed once from a query bank.  Per query i:
+ *   present   slot p is present iff 0 <= cand[i,p] < n_gallery; an absent slot never forms an address into norm / active,
+ *             its out_corr is -inf and it is never selected;
+ *   top-1     the present slot with the largest non-NaN fine, ties by lower position, -0.0 == +0.0 (nr_slab_topk_rows' order);
+ *   gate      0 when norm is null; 1 when norm is given and active is null (every query); with active: 1 iff a top-1 exists
+ *             and active[cand[i,top1]] != 0;
+ *   corr      gate = 1: fl(fl(beta fine[i,p]) - norm[cand[i,p]]), no fused multiply-add (NR_HUBNORM_IS); gate = 0: fine[i,p];
+ *   output    the top k of corr over the present non-NaN slots, value descending, ties by lower position:
+ *             out_idx [n,k] = cand[...], out_val [n,k] = corr[...], missing entries -1 / -inf.
+ * out_corr [n,C] and out_gate [n] may be null.  Integer comparisons order the list, no atomics: bitwise reproducible, and a
+ * query's output depends on its own line only.
+ * NR_EINVAL before any launch: fine, cand, out_idx or out_val null; n, n_gallery or k <= 0; C outside [1, 128]; k > C; active
+ * without norm; norm with a beta that is not finite and > 0.                                                            */
+int nr_cand_norm_rerank(const float* fine, const int32_t* cand, int n, int C, int n_gallery, const float* norm,
+                        const int32_t* active, float beta, int k, int32_t* out_idx, float* out_val, float* out_corr,
+                        int32_t* out_gate, void* stream);
+
 /* Test-time Sinkhorn normalisation (DESIGN.md "Test-time Sinkhorn normalisation"): the log-domain iteration of the reference's
  * uniform regularisation (until_module.py:223-266; :248-250 is the order of the two half-steps) on a test similarity slab
  * S [n, L] instead of the batch's logits.  a[i,j] = fl(beta S[i,j]), beta finite and > 0; log_mu [n], log_nu [L]: the log

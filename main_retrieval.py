@@ -148,6 +148,12 @@ def get_args():
                    help="two-stage retrieval after the exhaustive evaluation: a pooled single-vector prefilter picks C candidates "
                         "per query, the token-level score re-ranks those only; logs R@K and the candidate recall per direction "
                         "(DESIGN.md 6.14); 1..128; 0 = off")
+    p.add_argument("--rerank_norm", default="none", choices=["none", "is", "qbnorm"],
+                   help="with --rerank_top C: the candidate scores are also normalised against the memory bank as querybank -- is "
+                        "(every query) or qbnorm (the queries whose top-1 candidate is in the bank's activation set) -- with "
+                        "--test_norm_beta and --qb_k; the statistics are computed once per gallery, one fused launch normalises "
+                        "and re-ranks the lists; logs R@K, candidate recall and the gated share per direction and, with "
+                        "--hubness_k K <= C, the hubness of the two-stage lists before and after (DESIGN.md 6.15); none = off")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -228,6 +234,8 @@ def get_args():
                 "--ema_decay: there is nothing to compare")
     if not 0 <= args.rerank_top <= 128:
         p.error("--rerank_top must lie in [0, 128] (0 = off)")
+    if args.rerank_norm != "none" and args.rerank_top < 1:
+        p.error("--rerank_norm normalises candidate lists: it needs --rerank_top >= 1")
     if args.hubness_test and not (args.hubness_k > 0 and args.permutation > 0):
         p.error("--hubness_test needs --hubness_k > 0 and --permutation > 0")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
@@ -791,11 +799,12 @@ def eval_epoch(args, model, test, tag=""):
     they are the inputs), one packed all-gather + index scatter restores dataset order (evaluator.py:173-189), rank r
     computes rows [r N/W, (r+1) N/W) of the N x N similarity and the rank counts of its slab on the GPU, three small
     collectives complete them."""
-    from neighborretr_amd.evaluator import (correction_from_args, gather_eval_features, rank_sample_indices, rerank_top_from_args,
-                                            sharded_evaluation, two_stage_evaluation, two_stage_label)
+    from neighborretr_amd.evaluator import (correction_from_args, gather_eval_features, rank_sample_indices, rerank_norm_from_args,
+                                            rerank_top_from_args, sharded_evaluation, two_stage_evaluation, two_stage_label)
     from neighborretr_amd.metrics import RetrievalMetrics
     correction, extras = correction_from_args(args, model)     # every flag checked before any work
     rerank_top = rerank_top_from_args(args)
+    rerank_norm = rerank_norm_from_args(args, model)
     hubness_k = extras["hubness_k"]
     log = _tagged_log(tag)
 
@@ -863,11 +872,12 @@ def eval_epoch(args, model, test, tag=""):
     if rerank_top:                                          # two-stage retrieval next to the exhaustive figures, never instead of them
         torch.cuda.synchronize()
         tic = time.time()
-        t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, t, v, tm.float(), vm.float(), args, rerank_top)
+        norm_kw = {} if rerank_norm is None else dict(rerank_norm, hubness_k=min(hubness_k, rerank_top))
+        t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, t, v, tm.float(), vm.float(), args, rerank_top, **norm_kw)
         toc = time.time()
         tag = two_stage_label(rerank_top)
-        log(args, RetrievalMetrics.format_two_stage(t2v["two_stage"], prefix=f"text->video {tag} "))
-        log(args, RetrievalMetrics.format_two_stage(v2t["two_stage"], prefix=f"video->text {tag} "))
+        for line in RetrievalMetrics.two_stage_lines(t2v["two_stage"], v2t["two_stage"], tag, ("text->video", "video->text"), " "):
+            log(args, line)
         log(args, f"{tag} wall time {toc - tic:.2f}s")
     return t2v, v2t
 
@@ -991,8 +1001,8 @@ def main():
             clear_memory_bank(model)
     elif args.do_eval:
         with_bank = args.test_norm in ("qbnorm", "qbsinkhorn") or (args.local_scaling != "none" and args.local_scaling_bank) \
-            or (args.mutual_proximity != "none" and args.mutual_proximity_bank)
-        if with_bank:                                       # the querybank: the memory bank of the training set
+            or (args.mutual_proximity != "none" and args.mutual_proximity_bank) or args.rerank_norm != "none"
+        if with_bank:                                      # the querybank: the memory bank of the training set
             load_memory_bank(args, model, train)
         result = eval_epoch(args, model, test)
         if with_bank:

@@ -1410,25 +1410,75 @@ def two_stage_multi_sentence_metrics(cand_t, fine_t, cand_v, fine_v, ends, n_can
     return t2v, two_stage_metrics(f_v, g_v, e_v, C)
 
 
-def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk):
-    """(cand [n, C] int32, fine [n, C] fp32) as NumPy arrays, the same on every rank: this rank's queries searched, one gather."""
+def two_stage_norm_label(n_candidates, mode, beta, qb_k=1):
+    """The tag of the log lines of the normalised two-stage metrics: "[two-stage C=64 QB-Norm b=20 k=1]", "[two-stage C=64 IS b=20]"."""
+    tail = f" k={int(qb_k)}" if mode == "qbnorm" else ""
+    return f"[two-stage C={int(n_candidates)} {TEST_NORM_LABELS[mode]} b={beta:g}{tail}]"
+
+
+def rerank_norm_from_args(args, model):
+    """args.rerank_norm -> None or the keyword arguments of two_stage_evaluation (norm, beta, qb_k), checked before any work: the
+    mode, that rerank_top asks for candidates, beta (test_norm_beta), qb_k and that the model's memory bank is filled."""
+    from .search import check_norm
+    mode = getattr(args, "rerank_norm", None) or "none"
+    if mode == "none":
+        return None
+    try:
+        check_norm(mode)
+    except ValueError:
+        raise ValueError(f"rerank_norm must be 'is' or 'qbnorm', got {mode!r}") from None
+    if rerank_top_from_args(args) < 1:
+        raise ValueError("rerank_norm normalises candidate lists: it needs rerank_top >= 1")
+    kw = dict(norm=mode, beta=ops._check_beta(getattr(args, "test_norm_beta", 20.0)), qb_k=ops._check_k(getattr(args, "qb_k", 1)))
+    _querybank(model, None, model.mb_feat_t.device)             # checked where it lies: nothing is copied
+    return kw
+
+
+def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None):
+    """(cand [n, C] int32, fine [n, C] fp32) on the device, the same on every rank: this rank's queries searched, one gather.
+    norm: (cand, fine, corr [n, C] fp32, gate [n] int32), all four in that one gather."""
     n = q_feat.shape[0]
     r0, r1 = slab_bounds(n, W, rank)
-    cand, fine = index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk)
+    out = index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk) if norm is None else \
+        index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk, norm=norm)
     if W > 1:
-        mine = torch.zeros((2 * C, -(-n // W)), dtype=torch.int32, device=cand.device)
-        mine[:C, :r1 - r0], mine[C:, :r1 - r0] = cand.T, fine.view(torch.int32).T
+        blocks = [out[0].T, out[1].view(torch.int32).T] + ([out[2].view(torch.int32).T, out[3][None]] if norm is not None else [])
+        mine = torch.zeros((sum(b.shape[0] for b in blocks), -(-n // W)), dtype=torch.int32, device=out[0].device)
+        mine[:, :r1 - r0] = torch.cat(blocks, 0)
         rows = _gathered_rows(mine, n, W)
-        cand, fine = rows[:C].T.contiguous(), rows[C:].T.contiguous().view(torch.float32)
-    return cand.cpu().numpy(), fine.cpu().numpy()
+        out = (rows[:C].T.contiguous(), rows[C:2 * C].T.contiguous().view(torch.float32))
+        if norm is not None:
+            out += (rows[2 * C:3 * C].T.contiguous().view(torch.float32), rows[3 * C].contiguous())
+    return out
 
 
-def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, n_candidates, cut_off_points=None, chunk=256):
+def _two_stage_hubness(cand, score, K, n_gallery, gt_begin, gt_end):
+    """Hubness of the top-K lists of gathered candidate scores (the same on every rank): nr_cand_norm_rerank without a
+    normaliser orders them, nr_topk_occurrences counts them."""
+    idx, _, _, _ = ops.cand_norm_rerank(score, cand, n_gallery, K, want_corr=False)
+    occ = torch.stack(ops.topk_occurrences(idx, n_gallery, gt_begin, gt_end)).cpu().numpy()
+    return RetrievalMetrics.hubness_from_occurrences(occ[0], occ[1], K, cand.shape[0])
+
+
+def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, n_candidates, cut_off_points=None, chunk=256,
+                         norm=None, beta=20.0, qb_k=1, querybank=None, hubness_k=0):
     """-> (t2v, v2t) of two-stage retrieval with n_candidates (1..128) candidates per query, identical on every rank: R1 / R5 /
     R10 / R50 (None where K > C), cand_recall (percent of the queries whose ground truth is among their candidates),
-    n_candidates, cols, and MR / MedianR / MeanR only when every query was found.  Every argument is checked before any work."""
-    from .search import GalleryIndex, check_candidates, check_chunk
+    n_candidates, cols, and MR / MedianR / MeanR only when every query was found.  Every argument is checked before any work.
+
+    norm "is" | "qbnorm" (DESIGN.md 6.15): the candidate scores are also normalised against a querybank (`querybank` as in
+    sharded_evaluation, None: the model's memory bank; the video index takes its texts, the text index its videos) with
+    inverse temperature beta and, for qbnorm, the activation lists' length qb_k.  Each direction gains ["normalised"]: the same
+    fields computed from the corrected scores, `gated` (percent of the queries normalised) and `label`.  hubness_k = K, 1 <= K
+    <= n_candidates: the raw and the normalised dictionary each gain ["hubness"] of the top-K of their candidate scores."""
+    from .search import GalleryIndex, check_candidates, check_chunk, check_norm
     C, chunk = check_candidates(n_candidates), check_chunk(chunk)
+    norm = check_norm(norm)
+    hubness_k = _check_hubness_k(hubness_k)
+    if hubness_k > C:
+        raise ValueError(f"hubness_k must lie in [1, n_candidates = {C}], got {hubness_k}")
+    if norm is not None:
+        beta, qb_k = ops._check_beta(beta), ops._check_k(qb_k)
     for feat, mask, what in ((text_feat, text_mask, "text"), (video_feat, video_mask, "video")):
         if not torch.is_tensor(feat) or feat.dim() != 3 or not torch.is_tensor(mask) or tuple(mask.shape) != tuple(feat.shape[:2]):
             raise ValueError(f"{what} features must be [n, tokens, d] with a mask [n, tokens]")
@@ -1441,12 +1491,40 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
         ends = None
     else:
         ends = _group_ends(cut_off_points, n_rows, n_cols)
+    bank = _querybank(model, querybank, text_feat.device) if norm is not None else None
     W = _world(args)
     rank = comm.get_rank() if W > 1 else 0
     text_mask, video_mask = text_mask.float(), video_mask.float()
-    cand_t, fine_t = _two_stage_lists(GalleryIndex(model, video_feat, video_mask, "video"), text_feat, text_mask, C, W, rank, chunk)
-    cand_v, fine_v = _two_stage_lists(GalleryIndex(model, text_feat, text_mask, "text"), video_feat, video_mask, C, W, rank, chunk)
-    if ends is not None:
-        return two_stage_multi_sentence_metrics(cand_t, fine_t, cand_v, fine_v, ends, C)
-    gt = np.arange(n_rows)
-    return (two_stage_metrics(*two_stage_counts(cand_t, fine_t, gt), C), two_stage_metrics(*two_stage_counts(cand_v, fine_v, gt), C))
+    index_v, index_t = GalleryIndex(model, video_feat, video_mask, "video"), GalleryIndex(model, text_feat, text_mask, "text")
+    if bank is not None:
+        index_v.attach_querybank(bank[0], bank[1], beta, qb_k, chunk)
+        index_t.attach_querybank(bank[2], bank[3], beta, qb_k, chunk)
+    lists_t = _two_stage_lists(index_v, text_feat, text_mask, C, W, rank, chunk, norm)
+    lists_v = _two_stage_lists(index_t, video_feat, video_mask, C, W, rank, chunk, norm)
+    cand_t, cand_v = lists_t[0].cpu().numpy(), lists_v[0].cpu().numpy()
+
+    def metrics(score_t, score_v):
+        score_t, score_v = score_t.cpu().numpy(), score_v.cpu().numpy()
+        if ends is not None:
+            return two_stage_multi_sentence_metrics(cand_t, score_t, cand_v, score_v, ends, C)
+        gt = np.arange(n_rows)
+        return (two_stage_metrics(*two_stage_counts(cand_t, score_t, gt), C), two_stage_metrics(*two_stage_counts(cand_v, score_v, gt), C))
+
+    def add_hubness(m_t, m_v, score_t, score_v):
+        rb, re_, cb, ce = _ground_truth(n_rows, n_cols, ends, score_t.device)
+        m_t["hubness"] = _two_stage_hubness(lists_t[0], score_t, hubness_k, n_cols, rb, re_)
+        m_v["hubness"] = _two_stage_hubness(lists_v[0], score_v, hubness_k, n_rows, cb, ce)
+
+    t2v, v2t = metrics(lists_t[1], lists_v[1])
+    if hubness_k:
+        add_hubness(t2v, v2t, lists_t[1], lists_v[1])
+    if norm is not None:
+        nt, nv = metrics(lists_t[2], lists_v[2])
+        if hubness_k:
+            add_hubness(nt, nv, lists_t[2], lists_v[2])
+        label = two_stage_norm_label(C, norm, beta, qb_k)
+        for m, n, gate, raw in ((nt, n_rows, lists_t[3], t2v), (nv, n_cols, lists_v[3], v2t)):
+            m["gated"] = float(int(gate.sum())) * 100 / n
+            m["label"] = label
+            raw["normalised"] = m
+    return t2v, v2t

@@ -274,6 +274,7 @@ _SIGNATURES = {
     "nr_hubnorm_col_stats": ([_P, _I, _I, _F, _P, _P, _P], _I),
     "nr_hubnorm_combine": ([_I, _P, _I, _P, _P, _P], _I),
     "nr_hubnorm_apply": ([_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P], _I),
+    "nr_cand_norm_rerank": ([_P, _P, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _P], _I),
     "nr_sinknorm_row": ([_P, _I, _I, _F, _P, _P, _P, _P], _I),
     "nr_sinknorm_col_stats": ([_P, _I, _I, _F, _P, _P, _P, _P], _I),
     "nr_sinknorm_finish_cols": ([_I, _P, _I, _P, _P, _P], _I),

@@ -133,7 +133,25 @@ class RetrievalMetrics:
         every query was found, MedR."""
         recalls = " ".join(f"R@{K} {m[f'R{K}']:.1f}" for K in (1, 5, 10, 50) if m.get(f"R{K}") is not None)
         line = f"{prefix}{recalls} - candidate recall {m['cand_recall']:.1f}%"
-        return line + (f" - MedR {m['MR']:.1f}" if "MR" in m else "")
+        line += f" - MedR {m['MR']:.1f}" if "MR" in m else ""
+        return line + (f" - normalised {m['gated']:.1f}% of the queries" if "gated" in m else "")
+
+    @staticmethod
+    def two_stage_lines(t2v, v2t, tag, sides=("Text-to-Video", "Video-to-Text"), sep=": "):
+        """The log lines of evaluator.two_stage_evaluation: one per direction tagged `tag`; with a query-bank normalisation one
+        more per direction tagged with its label ("[two-stage C=64 QB-Norm b=20 k=1]", with the gated share); with hubness, the
+        line of each dictionary's top-K lists after it."""
+        lines = []
+        for pick in (lambda m: m, lambda m: m.get("normalised")):
+            for side, raw in zip(sides, (t2v, v2t)):
+                m = pick(raw)
+                if m is None:
+                    continue
+                label = m.get("label", tag)
+                lines.append(RetrievalMetrics.format_two_stage(m, prefix=f"{side} {label}{sep}"))
+                if "hubness" in m:
+                    lines.append(RetrievalMetrics.format_hubness(m["hubness"], prefix=f"{side} {label} "))
+        return lines
 
     @staticmethod
     def format_hubness(hub, prefix=""):

@@ -1063,6 +1063,40 @@ def hubnorm_apply(S, beta, mode, col_norm=None, row_gate=None, row_norm=None, co
     return T, V
 
 
+def cand_norm_rerank(fine, cand, n_gallery, k, norm=None, active=None, beta=20.0, want_corr=True):
+    """(idx [n, k] int32, val [n, k] fp32, corr [n, C] fp32 or None, gate [n] int32) of candidate lists cand [n, C] int32 (ascending
+    gallery index, entries outside [0, n_gallery) absent) with fine scores fine [n, C], in one launch (nr_cand_norm_rerank).
+    norm [n_gallery] fp32: the gallery's normalisers, active [n_gallery] int32: the activation set.  norm None: gate 0, corr =
+    fine -- search.rerank; active None: every query takes corr = fl(fl(beta fine) - norm[cand]) (mode "is"); with active only
+    the queries whose top-1 candidate is active (mode "qbnorm").  idx / val: the top k of corr, ties by lower position, -1 / -inf
+    where the line has fewer than k present non-NaN slots.  1 <= k <= C <= 128."""
+    if fine.dim() != 2 or cand.dim() != 2 or fine.shape != cand.shape:
+        raise ValueError(f"fine and cand must both be [n, C], got {tuple(fine.shape)} and {tuple(cand.shape)}")
+    n, C = cand.shape
+    n_gallery, k = int(n_gallery), _check_k(k)
+    if not 1 <= C <= hip.TOPK_MAX or k > C:
+        raise ValueError(f"1 <= k <= C <= {hip.TOPK_MAX} expected, got k = {k}, C = {C}")
+    if n_gallery < 1:
+        raise ValueError("the gallery is empty")
+    if active is not None and norm is None:
+        raise ValueError("an activation set needs the normalisers")
+    beta = _check_beta(beta) if norm is not None else 0.0
+    dev = fine.device
+    for x, dtype, what in ((norm, torch.float32, "norm"), (active, torch.int32, "active")):
+        if x is not None and (x.dtype != dtype or x.shape != (n_gallery,) or x.device != dev):
+            raise ValueError(f"{what} must be a {dtype} vector of {n_gallery} entries on {dev}")
+    fine, cand = _f32(fine).contiguous(), cand.contiguous()
+    idx = torch.empty((n, k), dtype=torch.int32, device=dev)
+    val = torch.empty((n, k), dtype=torch.float32, device=dev)
+    corr = torch.empty((n, C), dtype=torch.float32, device=dev) if want_corr else None
+    gate = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n:
+        p = lambda x: hip.ptr(None if x is None else x.contiguous(), allow_none=True)        # noqa: E731
+        hip.call("nr_cand_norm_rerank", hip.ptr(fine), hip.ptr(cand, torch.int32), n, C, n_gallery, p(norm), p(active), beta, k,
+                 hip.ptr(idx), hip.ptr(val), p(corr), hip.ptr(gate), hip.stream_ptr())
+    return idx, val, corr, gate
+
+
 def _sink_vec(x, size, what):
     if x.dtype != torch.float32 or x.shape != (size,) or not x.is_contiguous():
         raise ValueError(f"{what} must be a contiguous fp32 vector of {size} entries, got {x.dtype} {tuple(x.shape)}")

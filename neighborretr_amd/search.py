@@ -14,6 +14,10 @@ prepared ONCE (GalleryIndex: bf16 hi/lo tokens, token weights, pooled vectors) a
 The coarse scores are computed in row chunks ([chunk, N], dropped after use): nothing of size n x N is ever allocated.  Every
 step is deterministic per element (pointwise torch ops, this library's own kernels), so a query's list and scores do not depend
 on the chunk size or on which other queries share its batch.
+
+Query-bank normalisation: `attach_querybank` computes, once per gallery, every item's normaliser and the activation
+set from a bank of training queries; `candidates` / `search` with norm="is" | "qbnorm" then correct every query's candidate scores and
+re-rank them in one launch (nr_cand_norm_rerank).  Without the argument nothing changes.
 """
 import torch
 
@@ -21,6 +25,7 @@ from . import head, hip, ops
 
 MAX_CANDIDATES = 128                      # nr_local_level_cand: C <= 128 (= hip.TOPK_MAX, the longest top-k list)
 _SCORER = {"video": "video_weight_fc", "text": "text_weight_fc"}
+NORM_MODES = ("is", "qbnorm")             # query-bank normalisation of the candidate scores
 
 
 def check_candidates(n_candidates, allow_zero=False):
@@ -35,6 +40,13 @@ def check_chunk(chunk):
     if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
         raise ValueError(f"chunk must be an integer >= 1, got {chunk!r}")
     return int(chunk)
+
+
+def check_norm(norm):
+    """norm as None, "is" or "qbnorm" ("dsl" needs the query's whole row of scores: the evaluator's exhaustive path has it)."""
+    if norm is not None and norm not in NORM_MODES:
+        raise ValueError(f"norm must be None or one of {NORM_MODES}, got {norm!r}")
+    return norm
 
 
 def _check_tokens(feat, mask, what):
@@ -90,9 +102,57 @@ class GalleryIndex:
         self.feat, self.mask = feat, mask
         with torch.no_grad():
             self.items = _Side(model, feat, mask, side)
+        self.norm = self.active = self.norm_beta = self.qb_k = None
+        self.n_bank = 0
 
     def __len__(self):
         return self.items.n
+
+    def attach_querybank(self, bank_feat, bank_mask, beta=20.0, qb_k=1, chunk=256):
+        """The gallery's query-bank statistics, computed once -> self.  The bank holds items of
+        `self.query_side` (texts for a video gallery, videos for a text gallery), [M, tokens, d] with a mask [M, tokens].
+        Stores norm [N] fp32 (item j's normaliser: the log-sum-exp of beta x its scores against the M bank items), active [N]
+        int32 (1 iff j is in the top-qb_k list of some bank item), norm_beta, qb_k and n_bank: the definitions of DESIGN.md 6.2
+        in the evaluator's orientation (texts are rows), so at one rank these are the bits of the exhaustive `qbnorm`.
+        Every argument is checked before any work.
+
+        The bank product (bank x gallery similarity, 4 M N bytes: 41 MB at M = 512, N = 20 000) is scored once, whole, and
+        dropped.  The statistics are never chunked over bank items: merging (max, sum) pairs is not associative bit for bit,
+        so `norm` would depend on the chunk size (`chunk` only bounds the rows of one similarity launch)."""
+        _check_tokens(bank_feat, bank_mask, "querybank")
+        if bank_feat.shape[0] < 1:
+            raise ValueError("the querybank is empty")
+        if bank_feat.shape[2] != self.items.d:
+            raise ValueError(f"the querybank is {bank_feat.shape[2]} wide, the gallery {self.items.d}")
+        if bank_feat.device != self.feat.device or bank_mask.device != self.feat.device:
+            raise ValueError("querybank and gallery must be on the same device")
+        beta, qb_k, chunk = ops._check_beta(beta), ops._check_k(qb_k), check_chunk(chunk)
+        from .evaluator import _slab_similarity
+        N, M = len(self), bank_feat.shape[0]
+        bank_feat, bank_mask, feat, mask = bank_feat.float(), bank_mask.float(), self.feat.float(), self.mask.float()
+        with torch.no_grad():
+            if self.side == "video":
+                Q = _slab_similarity(self.model, bank_feat, feat, bank_mask, mask, 0, M, chunk)          # Qt [M, N]
+                norm = ops.hubnorm_combine(ops.hubnorm_col_stats(Q, beta)[None])
+                lists, _ = ops.slab_topk_rows(Q, qb_k)
+            else:
+                Q = _slab_similarity(self.model, feat, bank_feat, mask, bank_mask, 0, N, chunk)          # Qv [N, M]
+                norm = ops.hubnorm_row_lse(Q, beta)
+                lists, _ = ops.slab_topk_cols(Q, 0, qb_k)
+            none = torch.zeros((M,), dtype=torch.int32, device=Q.device)
+            occ, _ = ops.topk_occurrences(lists, N, none, none)
+            self.norm, self.active = norm, (occ > 0).to(torch.int32)
+        self.norm_beta, self.qb_k, self.n_bank = beta, qb_k, M
+        return self
+
+    def _check_norm(self, norm, n_candidates=None):
+        if check_norm(norm) is None:
+            return None
+        if self.norm is None:
+            raise ValueError(f"norm={norm!r} needs the gallery's query-bank statistics: call attach_querybank(...) first")
+        if n_candidates == 0:
+            raise ValueError("norm acts on candidate lists: the exhaustive path (n_candidates = 0) has the evaluator's corrections")
+        return norm
 
     def _check_queries(self, q_feat, q_mask):
         _check_tokens(q_feat, q_mask, "query")
@@ -106,9 +166,14 @@ class GalleryIndex:
         fixed summation order per element)."""
         return ops.gemm_nt_f32(pooled_q, self.items.pooled)
 
-    def candidates(self, q_feat, q_mask, n_candidates, chunk=256):
+    def candidates(self, q_feat, q_mask, n_candidates, chunk=256, norm=None):
         """(cand [n, C] int32, fine [n, C] fp32): every query's C candidates in ascending gallery index (padded with -1 when
-        the gallery has fewer than C items) and their fine scores (-inf at the padding)."""
+        the gallery has fewer than C items) and their fine scores (-inf at the padding).  norm "is" | "qbnorm" (after
+        attach_querybank): (cand, fine, corr [n, C] fp32, gate [n] int32), the corrected scores and which queries were normalised
+        ("is": all of them; "qbnorm": those whose top-1 candidate is in the activation set)."""
+        norm = self._check_norm(norm)
+        if norm is not None:
+            return self._normalised(q_feat, q_mask, 1, n_candidates, chunk, norm)[2:]
         C, chunk = check_candidates(n_candidates), check_chunk(chunk)
         self._check_queries(q_feat, q_mask)
         dev = q_feat.device
@@ -127,15 +192,27 @@ class GalleryIndex:
             fine = ops.local_level_cand(q.prep, g.prep, q.w, g.w, n, q.n_tok, g.n, g.n_tok, cand, hip.PREC_BF16X3)
         return cand, fine
 
-    def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False):
+    def _normalised(self, q_feat, q_mask, k, n_candidates, chunk, norm):
+        """(idx, val, cand, fine, corr, gate): the candidates and their fine scores, then nr_cand_norm_rerank in one launch."""
+        cand, fine = self.candidates(q_feat, q_mask, n_candidates, chunk)
+        idx, val, corr, gate = ops.cand_norm_rerank(fine, cand, len(self), k, norm=self.norm,
+                                                    active=self.active if norm == "qbnorm" else None, beta=self.norm_beta)
+        return idx, val, cand, fine, corr, gate
+
+    def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False, norm=None):
         """-> (idx [n, k] int32, val [n, k] fp32): the top k of every query, fine score descending, ties by lower gallery index,
         padded with -1 / -inf when the gallery has fewer than k items.  1 <= k <= n_candidates <= 128; n_candidates = 0 scores
         every pair (the exhaustive path: the evaluator's slab similarity and ops.slab_topk_rows).  return_candidates: also the
-        candidate lists and their fine scores, (idx, val, cand, fine)."""
+        candidate lists and their fine scores, (idx, val, cand, fine).  norm "is" | "qbnorm" (after attach_querybank): the
+        order and val are those of the corrected scores; with return_candidates (idx, val, cand, fine, gate)."""
         C, chunk = check_candidates(n_candidates, allow_zero=True), check_chunk(chunk)
         if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > (C or hip.TOPK_MAX):
             raise ValueError(f"k must be an integer in [1, {C or hip.TOPK_MAX}] (1 <= k <= n_candidates), got {k!r}")
+        norm = self._check_norm(norm, C)
         self._check_queries(q_feat, q_mask)
+        if norm is not None:
+            idx, val, cand, fine, _, gate = self._normalised(q_feat, q_mask, k, C, chunk, norm)
+            return (idx, val, cand, fine, gate) if return_candidates else (idx, val)
         if C == 0:
             if return_candidates:
                 raise ValueError("the exhaustive path (n_candidates = 0) has no candidate lists")

@@ -161,10 +161,11 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
     (rank r: rows [r N/W, (r+1) N/W)).  Multi-sentence sets (`dataset.multi_sentence_per_video`): every rank walks the whole
     loader, as in the reference (:114-131), keeps the video of each group's last sentence (:137-149), and the
     sentence x video matrix is again scored in row slabs.  Both go through evaluator.sharded_evaluation."""
-    from .evaluator import (correction_from_args, dataset_order, gather_eval_features, rerank_top_from_args, sharded_evaluation,
-                            two_stage_evaluation, two_stage_label)
+    from .evaluator import (correction_from_args, dataset_order, gather_eval_features, rerank_norm_from_args, rerank_top_from_args,
+                            sharded_evaluation, two_stage_evaluation, two_stage_label)
     correction, extras = correction_from_args(args, _unwrap(model))        # every flag checked before any work
     rerank_top = rerank_top_from_args(args)
+    rerank_norm = rerank_norm_from_args(args, _unwrap(model))
     hubness_k = extras["hubness_k"]
     logger = getattr(args, "logger", None)
     tracker = RetrievalMetrics(logger=logger)
@@ -192,8 +193,9 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
         t2v, v2t = sharded_evaluation(model, tf, vf, tm.float(), vm.float(), args, correction, cut_off_points=cut_off_points, **extras)
         toc2 = time.time()
         if rerank_top:                                     # two-stage retrieval next to the exhaustive figures, never instead of them
+            norm_kw = {} if rerank_norm is None else dict(rerank_norm, hubness_k=min(hubness_k, rerank_top))
             t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, tf, vf, tm.float(), vm.float(), args, rerank_top,
-                                                                      cut_off_points=cut_off_points)
+                                                                      cut_off_points=cut_off_points, **norm_kw)
         toc3 = time.time()
     if is_main_process() and logger is not None:
         logger.info("Evaluation timing breakdown:")
@@ -250,9 +252,8 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
                 tracker.log_hubness(nt["hubness"], prefix=f"Text-to-Video {tag} ")
                 tracker.log_hubness(nv["hubness"], prefix=f"Video-to-Text {tag} ")
         if rerank_top:
-            tag = two_stage_label(rerank_top)
-            logger.info(RetrievalMetrics.format_two_stage(t2v["two_stage"], prefix=f"Text-to-Video {tag}: "))
-            logger.info(RetrievalMetrics.format_two_stage(v2t["two_stage"], prefix=f"Video-to-Text {tag}: "))
+            for line in RetrievalMetrics.two_stage_lines(t2v["two_stage"], v2t["two_stage"], two_stage_label(rerank_top)):
+                logger.info(line)
     return t2v, v2t
 
 
