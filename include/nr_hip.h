@@ -31,6 +31,15 @@ extern "C" {
 /* precision of the MFMA contractions */
 #define NR_PREC_BF16 0   /* one bf16 pass (training path)                                   */
 #define NR_PREC_BF16X3 1 /* split-bf16, 3 passes: ~fp32 products (eval / rank-parity path)  */
+/* (2 is not a contraction precision: it is the host-level mixed plan, neighborretr_amd/head.py PREC_MIXED) */
+#define NR_PREC_F16 3    /* one fp16 pass (v_mfma_f32_16x16x32_f16): the `hi` operand pointers hold IEEE fp16 planes (11 significand
+                          * bits; the operands are normalised tokens, |x| <= 1, and scorer weights), the `lo` pointers are ignored and
+                          * may be NULL.  Accepted by nr_local_level_fwd / nr_local_level_plan (the register kernel's one-pass forms,
+                          * picked exactly as NR_PREC_BF16, on the blocks built for it: 96 x 96 at 24 x 12 tokens, 192 x 384, 256 x 256
+                          * at 64 x 64 tokens; NR_EUNSUPPORTED, nothing launched, for every other block and where the shape would run
+                          * the LDS kernel -- the plan call answers the same), nr_token_logits_fwd / nr_token_weights_fwd / nr_token_weights_fwd_pair / nr_token_scorer_plan
+                          * (as one bf16 pass; nr_token_weights_fwd_group refuses it: NR_EUNSUPPORTED, nothing written).  Every
+                          * other entry point with a `prec` argument still returns NR_EINVAL for it (ABI 5: an added value).   */
 
 /* what nr_local_level_fwd writes */
 #define NR_OUT_FULL 0   /* S[A,Bv]                                                          */
@@ -69,8 +78,19 @@ int nr_prepare_tokens_pair(const float* x0, const float* mask0, int n_tok0, uint
                            float* colsum_part0, const float* x1, const float* mask1, int n_tok1, uint16_t* hi1, uint16_t* lo1,
                            float* norm1, float* colsum_part1, int d, int normalize, void* stream);
 
+/* nr_prepare_tokens / nr_prepare_tokens_pair that ALSO write an fp16 plane f16 [n_tok,d] of the same normalised, masked values
+ * (fp32 -> fp16, nearest even), the operand of the NR_PREC_F16 contractions, in the same pass.  f16 may be NULL (then the call is
+ * the plain one); hi, norm and the column sums do not depend on it.  (Additions of ABI 5.) */
+int nr_prepare_tokens_f16(const float* x, const float* mask, int n_tok, int d, int normalize, uint16_t* hi, uint16_t* lo,
+                          uint16_t* f16, float* norm, float* colsum_part, void* stream);
+int nr_prepare_tokens_pair_f16(const float* x0, const float* mask0, int n_tok0, uint16_t* hi0, uint16_t* lo0, uint16_t* f16_0,
+                               float* norm0, float* colsum_part0, const float* x1, const float* mask1, int n_tok1, uint16_t* hi1,
+                               uint16_t* lo1, uint16_t* f16_1, float* norm1, float* colsum_part1, int d, int normalize, void* stream);
+
 /* plain f32 -> bf16 hi/lo split (MLP weight matrices). */
 int nr_split_bf16(const float* x, size_t n, uint16_t* hi, uint16_t* lo, void* stream);
+/* plain f32 -> fp16 (nearest even): the NR_PREC_F16 image of a scorer's W1.  (Addition of ABI 5.) */
+int nr_split_f16(const float* x, size_t n, uint16_t* f16, void* stream);
 
 /* Token-weight MLP, Linear(d,H)+ReLU+Linear(H,1), on the prepared tokens (modeling.py:148-153,
  * called at :485 and :490).  logit_part[p, tok] holds the contribution of hidden units

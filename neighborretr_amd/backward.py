@@ -88,6 +88,9 @@ def _mlp_backward_hip(jobs):
     Returns [(dW1 [H,d], db1 [H], dW2 [1,H], db2 [1], dX [n_0, d]), ...]."""
     from .cluster_backward_hip import _colsum_group, _linear_group
     from .cluster_fused import split_group
+    from .head import backward_prec
+    # (a set whose forward ran one fp16 pass: the split-bf16 rules of the batch side -- the backward reads the bf16 pair)
+    jobs = [dict(job, sets=[(prep, feat, dl, backward_prec(prec)) for prep, feat, dl, prec in job["sets"]]) for job in jobs]
     J = []
     items = []
     for job in jobs:
@@ -241,7 +244,7 @@ class HeadLossFn(torch.autograd.Function):
                                        bank_streams=model._bank_streams(text_feat.device),
                                        **model._global_scorers(text_feat, video_feat))
         ctx.sv, ctx.hp, ctx.exact = sv, dict(hp), prec == hip.PREC_BF16X3
-        ctx.model, ctx.plan = model, head.precision_plan(prec)
+        ctx.model, ctx.plan = model, head.backward_plan(prec)
         ctx.masks = (text_mask, video_mask)
         ctx.shapes = (text_feat.shape, video_feat.shape, mb_feat_t.shape, mb_feat_v.shape, gt.shape, gv.shape)
         sv["gt2"], sv["gv2"] = sv["gt2"].reshape(-1, sv["gt2"].shape[-1]), sv["gv2"].reshape(-1, sv["gv2"].shape[-1])
@@ -439,7 +442,7 @@ class HeadLocalFn(torch.autograd.Function):
                                        bank_streams=model._bank_streams(text_feat.device),
                                        **extra, **model._global_scorers(text_feat, video_feat))
         ctx.sv, ctx.exact = sv, prec == hip.PREC_BF16X3
-        ctx.model, ctx.plan = model, head.precision_plan(prec)
+        ctx.model, ctx.plan = model, head.backward_plan(prec)
         ctx.masks = (text_mask, video_mask)
         ctx.shapes = (text_feat.shape, video_feat.shape, mb_feat_t.shape, mb_feat_v.shape, sv["gt2"].shape, sv["gv2"].shape)
         sv["gt2"], sv["gv2"] = sv["gt2"].reshape(-1, sv["gt2"].shape[-1]), sv["gv2"].reshape(-1, sv["gv2"].shape[-1])

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef __attribute__((ext_vector_type(8))) short short8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
@@ -48,6 +49,9 @@ static inline const char* nr_tune_env(const char*) { return nullptr; }
         hipError_t e__ = hipGetLastError();            \
         if (e__ != hipSuccess) return (int)e__;        \
     } while (0)
+
+// fp32 -> fp16 bits, round to nearest even (v_cvt_f16_f32; fp16 subnormals are produced, values past 65504 become inf)
+__device__ __forceinline__ uint16_t nr_f2h(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
 
 // round-to-nearest-even f32 -> bf16 bits: the plain cast, which hipcc lowers to v_cvt_pk_bf16_f32 on gfx950 (one instruction
 // where the integer form -- u += 0x7FFF + ((u >> 16) & 1) -- took five; the same bits for every finite input, and a NaN

@@ -65,8 +65,12 @@ typedef const __attribute__((address_space(1))) void* nr_glb_ptr_t;
 constexpr int nr_pick_stages(long n_workgroups) { return n_workgroups >= 512 ? 1 : 2; }
 
 // WC = waves along the columns: the workgroup is 2 x WC waves (256 threads at WC = 2, 512 at WC = 4).
-template <int MI, int NI, bool X3, int TPS_A = 16, int TPS_B = 16, int STAGES = 2, int WC = 2>
+// F16 (one-pass tiles only): the operand planes hold IEEE fp16 instead of bf16 -- 11 significand bits where bf16 has 8 -- and
+// the products run on v_mfma_f32_16x16x32_f16: same rate, same 2-byte elements, same fragment layout (8 per lane), so
+// staging, ring, swizzle and K loops are the bf16 ones and only the MFMA instruction differs.
+template <int MI, int NI, bool X3, int TPS_A = 16, int TPS_B = 16, int STAGES = 2, int WC = 2, bool F16 = false>
 struct NrGemmTile {
+    static_assert(!(F16 && X3), "fp16 planes: one pass (the split is a bf16 scheme)");
     static constexpr int NW = 2 * WC;                  // waves per workgroup
     static constexpr int BM = 32 * MI;
     static constexpr int BN = 16 * WC * NI;
@@ -80,6 +84,12 @@ struct NrGemmTile {
     static constexpr int DMA_PER_STAGE = (PA + PB) * (X3 ? 2 : 1);   // per wave
 
     f32x4_t acc[MI][NI];
+
+    // one 16 x 16 x 32 product of two fragments in the tile's element type
+    __device__ static __forceinline__ f32x4_t mfma(bf16x8_t a, bf16x8_t b, f32x4_t c) {
+        if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+        else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
 
     // Fragment row `f` (0..15) of sub-tile `m` of a wave strip -> row of the strip in memory order.
     // TPS = 16: identity.  TPS = 8 / 4: the strip holds 16/TPS samples of MI*TPS tokens each and a
@@ -321,7 +331,7 @@ struct NrGemmTile {
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_l[m], fb_h[n], acc[m][n], 0, 0, 0);
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_h[m], fb_l[n], acc[m][n], 0, 0, 0);
                     }
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_h[m], fb_h[n], acc[m][n], 0, 0, 0);
+                    acc[m][n] = mfma(fa_h[m], fb_h[n], acc[m][n]);
                     if constexpr (STAGES > 1) {
                         // the DMA instructions go out between the MFMA groups of the FIRST HALF of the slice: apart
                         // enough not to stall the matrix pipe, early enough to have landed when the slice ends
@@ -544,7 +554,7 @@ struct NrGemmTile {
                     acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_l[m], fb_h[n], acc[m][n], 0, 0, 0);
                     acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_h[m], fb_l[n], acc[m][n], 0, 0, 0);
                 }
-                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_h[m], fb_h[n], acc[m][n], 0, 0, 0);
+                acc[m][n] = mfma(fa_h[m], fb_h[n], acc[m][n]);
                 if constexpr (g == (MI * NI) / 3) mid();
             });
             if constexpr (NR_PP_PRIO == 1) __builtin_amdgcn_s_setprio(0);

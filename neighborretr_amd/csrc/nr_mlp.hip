@@ -51,7 +51,8 @@ struct NrMlpProblem {
 // ACC3 (one-pass ring only): the split-bf16 product as THREE accumulated passes over K through the ping-pong loop
 // (NrGemmTile::run_pp3: Ah Bh, then Ah Bl, then Al Bh) -- what lets split-bf16 token sets share a grid, a block shape and an
 // LDS footprint with one-pass sets (nr_mlp_group_kernel)
-template <int MI, int NI, int WC, bool X3, int STAGES, bool ACC3 = false>
+// F16 (one-pass forms): tok_hi / w1_hi are fp16 planes (NR_PREC_F16); same blocks, ring and epilogue
+template <int MI, int NI, int WC, bool X3, int STAGES, bool ACC3 = false, bool F16 = false>
 __device__ __forceinline__ void nr_mlp_body(const NrMlpProblem& q, const int wg, char* smem) {
     const uint16_t* __restrict__ tok_hi = q.tok_hi;
     const uint16_t* __restrict__ tok_lo = q.tok_lo;
@@ -63,7 +64,8 @@ __device__ __forceinline__ void nr_mlp_body(const NrMlpProblem& q, const int wg,
     const float* __restrict__ w2 = q.w2;
     float* __restrict__ logit_part = q.logit_part;
     const NrMlpSoftmax& sm = q.sm;
-    using Tile = NrGemmTile<MI, NI, X3, 16, 16, STAGES, WC>;
+    static_assert(!F16 || (!X3 && !ACC3), "fp16 planes: one pass");
+    using Tile = NrGemmTile<MI, NI, X3, 16, 16, STAGES, WC, F16>;
     constexpr int BM = Tile::BM, BN = Tile::BN;
     constexpr int WCOLS = 16 * NI;                 // hidden units per wave
     constexpr int WPP = 128 / WCOLS;               // waves per 128-unit part
@@ -189,21 +191,21 @@ __device__ __forceinline__ void nr_mlp_body(const NrMlpProblem& q, const int wg,
     if (tid == 0) __hip_atomic_store(&sm.counters[by], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int MI, int NI, int WC, bool X3, int STAGES>
+template <int MI, int NI, int WC, bool X3, int STAGES, bool F16 = false>
 __global__ __launch_bounds__(128 * WC) void nr_mlp_kernel(NrMlpProblem q) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    nr_mlp_body<MI, NI, WC, X3, STAGES>(q, blockIdx.x, smem);
+    nr_mlp_body<MI, NI, WC, X3, STAGES, false, F16>(q, blockIdx.x, smem);
 }
 
 // TWO scorer calls of one block shape in one grid (the step's text and video tokens): workgroups [0, grid_a) take `a`, the
 // rest `b`.  Pays from a few workgroups per CU on -- configs[3] (512 + 512 workgroups) 517 -> 530 steps/s, configs[2] 424 -> 427;
 // at configs[1] (256 + 128, one per CU with a two-deep ring) the two launches one after the other are FASTER (3725 vs 3605
 // steps/s, also with a one-deep ring for the pair): the host pairs only large token sets (head.PAIR_BATCH_SCORERS_FROM).
-template <int MI, int NI, int WC, bool X3, int STAGES>
+template <int MI, int NI, int WC, bool X3, int STAGES, bool F16 = false>
 __global__ __launch_bounds__(128 * WC) void nr_mlp_pair_kernel(NrMlpProblem a, NrMlpProblem b, int grid_a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.x < grid_a) nr_mlp_body<MI, NI, WC, X3, STAGES>(a, blockIdx.x, smem);
-    else nr_mlp_body<MI, NI, WC, X3, STAGES>(b, (int)blockIdx.x - grid_a, smem);
+    if ((int)blockIdx.x < grid_a) nr_mlp_body<MI, NI, WC, X3, STAGES, false, F16>(a, blockIdx.x, smem);
+    else nr_mlp_body<MI, NI, WC, X3, STAGES, false, F16>(b, (int)blockIdx.x - grid_a, smem);
 }
 
 // ---- ALL scorer calls of a step in one grid ---------------------------------------------------------------------------------
@@ -234,9 +236,9 @@ __global__ __launch_bounds__(512) void nr_mlp_group_kernel(NrMlpGroup g) {
 namespace {
 struct MlpShape { int mi, ni, wc; };
 
-template <int MI, int NI, int WC, bool X3, int STAGES>
+template <int MI, int NI, int WC, bool X3, int STAGES, bool F16 = false>
 int mlp_launch(const NrMlpProblem& q, hipStream_t st, const NrMlpProblem* second = nullptr) {
-    using Tile = NrGemmTile<MI, NI, X3, 16, 16, STAGES, WC>;
+    using Tile = NrGemmTile<MI, NI, X3, 16, 16, STAGES, WC, F16>;
     size_t lds = Tile::RING_BYTES;
     const size_t epi = 8192 + 16;                                 // sPart (<= 3 KiB) + the last-block flag at 8192
     static_assert((size_t)WC * Tile::BM * sizeof(float) <= 8192, "the flag sits behind sPart");
@@ -246,7 +248,7 @@ int mlp_launch(const NrMlpProblem& q, hipStream_t st, const NrMlpProblem* second
         // (pairs pay only for crowded grids -- a one-deep ring on 4-wave blocks: the other forms are not built)
         if constexpr (!(WC == 2 && STAGES == 1)) return NR_EUNSUPPORTED;
         else {
-        auto kern = nr_mlp_pair_kernel<MI, NI, WC, X3, STAGES>;
+        auto kern = nr_mlp_pair_kernel<MI, NI, WC, X3, STAGES, F16>;
         if (lds > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return (int)e;
@@ -257,7 +259,7 @@ int mlp_launch(const NrMlpProblem& q, hipStream_t st, const NrMlpProblem* second
         return NR_OK;
         }
     }
-    auto kern = nr_mlp_kernel<MI, NI, WC, X3, STAGES>;
+    auto kern = nr_mlp_kernel<MI, NI, WC, X3, STAGES, F16>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
@@ -321,7 +323,7 @@ static int nr_mlp_fused_n(const NrMlpSoftmax& sm) { return sm.counters ? sm.N : 
 static int nr_mlp_check(const NrMlpProblem& q, int prec) {
     if (!q.tok_hi || !q.norm || !q.w1_hi || !q.b1 || !q.w2 || !q.logit_part) return NR_EINVAL;
     if (q.n_tok <= 0 || q.d <= 0 || (q.d % 64) != 0 || q.H <= 0 || (q.H % 128) != 0) return NR_EINVAL;
-    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3) return NR_EINVAL;
+    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3 && prec != NR_PREC_F16) return NR_EINVAL;
     if (prec == NR_PREC_BF16X3 && (!q.tok_lo || !q.w1_lo)) return NR_EINVAL;
     return NR_OK;
 }
@@ -332,7 +334,7 @@ static int nr_mlp_go(const NrMlpProblem& q, const NrMlpProblem* second, int prec
     if (rc == NR_OK && second) rc = nr_mlp_check(*second, prec);
     if (rc != NR_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool x3 = prec == NR_PREC_BF16X3;
+    const bool x3 = prec == NR_PREC_BF16X3, f16 = prec == NR_PREC_F16;      // (fp16 planes: picked as one bf16 pass is)
     const MlpShape* cand = nr_mlp_cand;
     long best_wg = 0;
     const int best = nr_mlp_pick(q.n_tok, q.H, x3, nr_mlp_fused_n(q.sm), &best_wg);
@@ -349,6 +351,8 @@ static int nr_mlp_go(const NrMlpProblem& q, const NrMlpProblem* second, int prec
             if constexpr (WC_ == 2) {                                                                                         \
                 return two ? mlp_launch<MI_, NI_, WC_, true, 2>(q, st, second) : mlp_launch<MI_, NI_, WC_, true, 1>(q, st, second); \
             }                                                                                                                 \
+        } else if (f16) {                                                                                                     \
+            return two ? mlp_launch<MI_, NI_, WC_, false, 2, true>(q, st, second) : mlp_launch<MI_, NI_, WC_, false, 1, true>(q, st, second); \
         } else {                                                                                                              \
             return two ? mlp_launch<MI_, NI_, WC_, false, 2>(q, st, second) : mlp_launch<MI_, NI_, WC_, false, 1>(q, st, second);   \
         }                                                                                                                     \
@@ -390,7 +394,7 @@ extern "C" int nr_token_weights_fwd(const uint16_t* tok_hi, const uint16_t* tok_
 // n_fused: tokens per sample of an nr_token_weights_fwd call, 0 for nr_token_logits_fwd.  Same picker, same ring rule.
 extern "C" int nr_token_scorer_plan(int n_tok, int H, int prec, int n_fused, int* bm, int* bn, int* stages) {
     if (!bm || !bn || !stages || n_tok <= 0 || H <= 0 || (H % 128) != 0 || n_fused < 0) return NR_EINVAL;
-    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3) return NR_EINVAL;
+    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3 && prec != NR_PREC_F16) return NR_EINVAL;
     if (n_fused > 0 && (n_tok % n_fused) != 0) return NR_EINVAL;
     if (n_fused > 256) return NR_EUNSUPPORTED;
     long wg = 0;
@@ -447,6 +451,7 @@ extern "C" int nr_token_weights_fwd_group(const NrTokenWeightsProblem* probs, co
                        NrMlpSoftmax{t.counters, t.b2, t.mask, t.N, t.w, t.logits}};
         int rc = nr_mlp_check(q, prec);
         if (rc != NR_OK) return rc;
+        if (prec == NR_PREC_F16) return NR_EUNSUPPORTED;          // no fp16 form of the grouped grid
         for (int j2 = 0; j2 < j; ++j2)
             if (g.p[j2].sm.counters == t.counters) return NR_EINVAL;      // (the problems' row tiles count separately)
         g.p[j] = q;

@@ -23,7 +23,8 @@ template <int CH>   // CH = d / 256 float4 chunks per lane
 __device__ __forceinline__ void nr_prepare_body(const float* __restrict__ x, const float* __restrict__ mask,
                                                 int n_tok, int d, int normalize, uint16_t* __restrict__ hi,
                                                 uint16_t* __restrict__ lo, float* __restrict__ norm_out,
-                                                float* __restrict__ colsum_part, const int bid, const int nblocks) {
+                                                float* __restrict__ colsum_part, const int bid, const int nblocks,
+                                                uint16_t* __restrict__ f16 = nullptr) {
     __shared__ float s_col[4][CH * 256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float csum[CH][4];
@@ -81,6 +82,12 @@ __device__ __forceinline__ void nr_prepare_body(const float* __restrict__ x, con
                     uint2 pl = make_uint2((uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16));
                     *reinterpret_cast<uint2*>(lo + o) = pl;
                 }
+                if (f16) {      // the same masked value rounded to fp16 (nearest even, subnormals kept): the NR_PREC_F16 operand plane
+                    uint16_t q[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) q[e] = nr_f2h((v[i][c][e] * inv) * mk[i]);
+                    *reinterpret_cast<uint2*>(f16 + o) = make_uint2((uint32_t)q[0] | ((uint32_t)q[1] << 16), (uint32_t)q[2] | ((uint32_t)q[3] << 16));
+                }
             }
         }
     }
@@ -99,8 +106,8 @@ template <int CH>
 __global__ __launch_bounds__(256) void nr_prepare_kernel(const float* __restrict__ x, const float* __restrict__ mask,
                                                          int n_tok, int d, int normalize, uint16_t* __restrict__ hi,
                                                          uint16_t* __restrict__ lo, float* __restrict__ norm_out,
-                                                         float* __restrict__ colsum_part) {
-    nr_prepare_body<CH>(x, mask, n_tok, d, normalize, hi, lo, norm_out, colsum_part, blockIdx.x, gridDim.x);
+                                                         float* __restrict__ colsum_part, uint16_t* __restrict__ f16) {
+    nr_prepare_body<CH>(x, mask, n_tok, d, normalize, hi, lo, norm_out, colsum_part, blockIdx.x, gridDim.x, f16);
 }
 
 // Two tensors (the batch's text and video tokens) in ONE launch: workgroups [0, nb0) take the first, the rest the second.
@@ -109,17 +116,24 @@ struct NrPrepareOne {
     int n_tok;
     uint16_t *hi, *lo;
     float *norm, *colsum_part;
+    uint16_t* f16;       // fp16 plane or nullptr
 };
 template <int CH>
 __global__ __launch_bounds__(256) void nr_prepare_pair_kernel(NrPrepareOne a, NrPrepareOne b, int d, int normalize, int nb0) {
     const bool second = (int)blockIdx.x >= nb0;
     const NrPrepareOne& p = second ? b : a;
     nr_prepare_body<CH>(p.x, p.mask, p.n_tok, d, normalize, p.hi, p.lo, p.norm, p.colsum_part, second ? blockIdx.x - nb0 : blockIdx.x,
-                        second ? gridDim.x - nb0 : nb0);
+                        second ? gridDim.x - nb0 : nb0, p.f16);
 }
 
 extern "C" int nr_prepare_tokens(const float* x, const float* mask, int n_tok, int d, int normalize, uint16_t* hi,
                                  uint16_t* lo, float* norm, float* colsum_part, void* stream) {
+    return nr_prepare_tokens_f16(x, mask, n_tok, d, normalize, hi, lo, nullptr, norm, colsum_part, stream);
+}
+
+// nr_prepare_tokens that also writes the fp16 plane of the same values (f16 may be NULL: then it IS nr_prepare_tokens)
+extern "C" int nr_prepare_tokens_f16(const float* x, const float* mask, int n_tok, int d, int normalize, uint16_t* hi,
+                                     uint16_t* lo, uint16_t* f16, float* norm, float* colsum_part, void* stream) {
     if (!x || !hi || n_tok <= 0 || d <= 0) return NR_EINVAL;
     if ((d % 256) != 0 || d / 256 > NR_PREP_MAX_CHUNKS) return NR_EUNSUPPORTED;
     // column sums wanted: one partial per workgroup, so few workgroups (the batch tensors are small);
@@ -131,10 +145,10 @@ extern "C" int nr_prepare_tokens(const float* x, const float* mask, int n_tok, i
     }
     hipStream_t st = (hipStream_t)stream;
     switch (d / 256) {
-        case 1: hipLaunchKernelGGL(nr_prepare_kernel<1>, dim3(grid), dim3(256), 0, st, x, mask, n_tok, d, normalize, hi, lo, norm, colsum_part); break;
-        case 2: hipLaunchKernelGGL(nr_prepare_kernel<2>, dim3(grid), dim3(256), 0, st, x, mask, n_tok, d, normalize, hi, lo, norm, colsum_part); break;
-        case 3: hipLaunchKernelGGL(nr_prepare_kernel<3>, dim3(grid), dim3(256), 0, st, x, mask, n_tok, d, normalize, hi, lo, norm, colsum_part); break;
-        default: hipLaunchKernelGGL(nr_prepare_kernel<4>, dim3(grid), dim3(256), 0, st, x, mask, n_tok, d, normalize, hi, lo, norm, colsum_part); break;
+        case 1: hipLaunchKernelGGL(nr_prepare_kernel<1>, dim3(grid), dim3(256), 0, st, x, mask, n_tok, d, normalize, hi, lo, norm, colsum_part, f16); break;
+        case 2: hipLaunchKernelGGL(nr_prepare_kernel<2>, dim3(grid), dim3(256), 0, st, x, mask, n_tok, d, normalize, hi, lo, norm, colsum_part, f16); break;
+        case 3: hipLaunchKernelGGL(nr_prepare_kernel<3>, dim3(grid), dim3(256), 0, st, x, mask, n_tok, d, normalize, hi, lo, norm, colsum_part, f16); break;
+        default: hipLaunchKernelGGL(nr_prepare_kernel<4>, dim3(grid), dim3(256), 0, st, x, mask, n_tok, d, normalize, hi, lo, norm, colsum_part, f16); break;
     }
     NR_LAUNCH_CHECK();
     return NR_OK;
@@ -143,6 +157,14 @@ extern "C" int nr_prepare_tokens(const float* x, const float* mask, int n_tok, i
 extern "C" int nr_prepare_tokens_pair(const float* x0, const float* mask0, int n_tok0, uint16_t* hi0, uint16_t* lo0, float* norm0,
                                       float* colsum_part0, const float* x1, const float* mask1, int n_tok1, uint16_t* hi1,
                                       uint16_t* lo1, float* norm1, float* colsum_part1, int d, int normalize, void* stream) {
+    return nr_prepare_tokens_pair_f16(x0, mask0, n_tok0, hi0, lo0, nullptr, norm0, colsum_part0, x1, mask1, n_tok1, hi1, lo1, nullptr,
+                                      norm1, colsum_part1, d, normalize, stream);
+}
+
+extern "C" int nr_prepare_tokens_pair_f16(const float* x0, const float* mask0, int n_tok0, uint16_t* hi0, uint16_t* lo0, uint16_t* f16_0,
+                                          float* norm0, float* colsum_part0, const float* x1, const float* mask1, int n_tok1,
+                                          uint16_t* hi1, uint16_t* lo1, uint16_t* f16_1, float* norm1, float* colsum_part1, int d,
+                                          int normalize, void* stream) {
     if (!x0 || !hi0 || !x1 || !hi1 || n_tok0 <= 0 || n_tok1 <= 0 || d <= 0) return NR_EINVAL;
     if ((d % 256) != 0 || d / 256 > NR_PREP_MAX_CHUNKS) return NR_EUNSUPPORTED;
     auto blocks = [](int n_tok, const float* cs) {
@@ -151,7 +173,7 @@ extern "C" int nr_prepare_tokens_pair(const float* x0, const float* mask0, int n
         return g > NR_PREP_MAX_GRID ? NR_PREP_MAX_GRID : g;
     };
     const int nb0 = blocks(n_tok0, colsum_part0), nb1 = blocks(n_tok1, colsum_part1);
-    NrPrepareOne a{x0, mask0, n_tok0, hi0, lo0, norm0, colsum_part0}, b{x1, mask1, n_tok1, hi1, lo1, norm1, colsum_part1};
+    NrPrepareOne a{x0, mask0, n_tok0, hi0, lo0, norm0, colsum_part0, f16_0}, b{x1, mask1, n_tok1, hi1, lo1, norm1, colsum_part1, f16_1};
     hipStream_t st = (hipStream_t)stream;
     switch (d / 256) {
         case 1: hipLaunchKernelGGL(nr_prepare_pair_kernel<1>, dim3(nb0 + nb1), dim3(256), 0, st, a, b, d, normalize, nb0); break;
@@ -178,6 +200,20 @@ extern "C" int nr_split_bf16(const float* x, size_t n, uint16_t* hi, uint16_t* l
     size_t blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(nr_split_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, n, hi, lo);
+    NR_LAUNCH_CHECK();
+    return NR_OK;
+}
+
+// plain f32 -> fp16 (nearest even): the NR_PREC_F16 image of a scorer's W1, beside nr_split_bf16's halves
+__global__ __launch_bounds__(256) void nr_split_f16_kernel(const float* __restrict__ x, size_t n, uint16_t* __restrict__ f16) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) f16[i] = nr_f2h(x[i]);
+}
+
+extern "C" int nr_split_f16(const float* x, size_t n, uint16_t* f16, void* stream) {
+    if (!x || !f16 || n == 0) return NR_EINVAL;
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(nr_split_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, n, f16);
     NR_LAUNCH_CHECK();
     return NR_OK;
 }

@@ -248,7 +248,7 @@ extern "C" int nr_local_level_fwd(const uint16_t* t_hi, const uint16_t* t_lo, co
                                   uint8_t* arg_t, float* pmax, float* qmax, void* stream) {
     if (!t_hi || !v_hi || !w_t || !w_v || !out) return NR_EINVAL;
     if (A <= 0 || Bv <= 0 || Nt <= 0 || Nv <= 0 || d <= 0 || (d % 64) != 0) return NR_EINVAL;
-    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3) return NR_EINVAL;
+    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3 && prec != NR_PREC_F16) return NR_EINVAL;
     if (prec == NR_PREC_BF16X3 && (!t_lo || !v_lo)) return NR_EINVAL;
     if (out_mode < 0 || out_mode > 2) return NR_EINVAL;
     if ((arg_v || arg_t || pmax || qmax) && !(arg_v && arg_t && pmax && qmax)) return NR_EINVAL;
@@ -262,6 +262,7 @@ extern "C" int nr_local_level_fwd(const uint16_t* t_hi, const uint16_t* t_lo, co
             if (rc != NR_EUNSUPPORTED) return rc;
         }
     }
+    if (prec == NR_PREC_F16) return NR_EUNSUPPORTED;      // fp16 planes: only the register kernel's one-pass forms are built
     NrSimArgs a;
     a.t_hi = t_hi; a.t_lo = t_lo; a.v_hi = v_hi; a.v_lo = v_lo;
     a.w_t = w_t; a.w_v = w_v; a.out = out; a.arg_v = arg_v; a.arg_t = arg_t; a.pmax = pmax; a.qmax = qmax;
@@ -322,10 +323,11 @@ static int nr_sim_generic_setup(NrSimArgs& a, int prec, int* mi_out, int* ni_out
 extern "C" int nr_local_level_plan(int A, int Nt, int Bv, int Nv, int d, int prec, int32_t* words) {
     if (!words) return NR_EINVAL;
     if (A <= 0 || Bv <= 0 || Nt <= 0 || Nv <= 0 || d <= 0 || (d % 64) != 0) return NR_EINVAL;
-    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3) return NR_EINVAL;
+    if (prec != NR_PREC_BF16 && prec != NR_PREC_BF16X3 && prec != NR_PREC_F16) return NR_EINVAL;
     if (Nt > 255 || Nv > 255) return NR_EUNSUPPORTED;
     int32_t w[NR_LLP_WORDS];
     int rc = nr_sim_force_generic() ? NR_EUNSUPPORTED : nr_sim_reg_describe(A, Nt, Bv, Nv, d, prec, w);
+    if (rc == NR_EUNSUPPORTED && prec == NR_PREC_F16) return rc;      // no fp16 form of the LDS kernel
     if (rc == NR_EUNSUPPORTED) {          // as in nr_local_level_fwd: what the register kernel does not take runs the LDS kernel
         NrSimArgs a{};
         a.A = A; a.Nt = Nt; a.Bv = Bv; a.Nv = Nv; a.K = d;

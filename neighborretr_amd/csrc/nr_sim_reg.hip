@@ -75,10 +75,11 @@ __device__ __forceinline__ float nr_lanes_sum(float v) {
 // RT > 1 (TPS = 16 only: the strip is in memory order): a wave strip of 16*MI rows holds RT texts one behind the other, text
 // rt in sub-tiles [rt*MI/RT, (rt+1)*MI/RT) -- twice the rows per wave for the same columns, i.e. the operand bytes per MFMA of
 // the 192 x 384 blocks at 64 x 64 tokens: 256 x 256 blocks = 4 texts x 4 videos on 2 x 4 waves of 128 x 64 (MI, NI = 8, 4).
-template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int STAGES, int WC, bool PP = false, int RT = 1, bool P3 = false>
+template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int STAGES, int WC, bool PP = false, int RT = 1, bool P3 = false, bool F16 = false>
 __device__ __forceinline__ void nr_sim_reg_body(const NrSimRegArgs& p, const int bid, char* smem) {
     static_assert(!P3 || (PP && !X3), "three accumulated passes run on the one-pass tile's ping-pong loop");
-    using Tile = NrGemmTile<MI, NI, X3, TPS, FPS, STAGES, WC>;
+    static_assert(!F16 || (!X3 && !P3), "fp16 planes: one pass");
+    using Tile = NrGemmTile<MI, NI, X3, TPS, FPS, STAGES, WC, F16>;
     static_assert(MI % RT == 0 && (RT == 1 || TPS == 16), "texts stacked in a wave strip: whole sub-tiles each, strip in memory order");
     constexpr int MIE = MI / RT;                      // sub-tiles per text
     constexpr int Nt = MIE * TPS, Nv = NI * FPS;
@@ -337,10 +338,10 @@ __device__ __forceinline__ void nr_sim_reg_body(const NrSimRegArgs& p, const int
     }
 }
 
-template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int STAGES, int WC, bool PP = false, int RT = 1, bool P3 = false>
+template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int STAGES, int WC, bool PP = false, int RT = 1, bool P3 = false, bool F16 = false>
 __global__ __launch_bounds__(128 * WC) void nr_sim_reg_kernel(NrSimRegArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    nr_sim_reg_body<MI, NI, TPS, FPS, X3, ARGS, STAGES, WC, PP, RT, P3>(p, blockIdx.x, smem);
+    nr_sim_reg_body<MI, NI, TPS, FPS, X3, ARGS, STAGES, WC, PP, RT, P3, F16>(p, blockIdx.x, smem);
 }
 
 // ---- two chained tiles per workgroup (the step's two bank products) ---------------------------------------------------
@@ -506,10 +507,10 @@ __global__ __launch_bounds__(512) void nr_sim_group_kernel(NrSimGroup g) {
     else nr_sim_reg_body<3, 3, 8, 4, true, false, 2, 4, true>(g.p[k], b - g.first[k], smem);
 }
 
-template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int STAGES, int WC, bool PP = false, int RT = 1, bool P3 = false>
+template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int STAGES, int WC, bool PP = false, int RT = 1, bool P3 = false, bool F16 = false>
 static int nr_sim_reg_launch_s(NrSimRegArgs& a, hipStream_t st) {
-    using Tile = NrGemmTile<MI, NI, X3, TPS, FPS, STAGES, WC>;
-    auto kern = nr_sim_reg_kernel<MI, NI, TPS, FPS, X3, ARGS, STAGES, WC, PP, RT, P3>;
+    using Tile = NrGemmTile<MI, NI, X3, TPS, FPS, STAGES, WC, F16>;
+    auto kern = nr_sim_reg_kernel<MI, NI, TPS, FPS, X3, ARGS, STAGES, WC, PP, RT, P3, F16>;
     size_t lds = Tile::RING_BYTES;
     if constexpr (MI * NI >= 32)          // the block's token weights, parked behind the ring (LATE_W in the kernel)
         lds += sizeof(float) * (2 * (16 / TPS) * MI * TPS + WC * (16 / FPS) * NI * FPS);
@@ -576,8 +577,10 @@ static NrSimRing nr_sim_reg_ring(long n_workgroups, int K) {
     } else return {mid ? 2 : nr_pick_stages(n_workgroups), NR_KLOOP_PLAIN};
 }
 
-template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int WC = 2>
+// F16: the one-pass forms on fp16 planes (NR_PREC_F16) -- the rules below pick among them exactly as for one bf16 pass
+template <int MI, int NI, int TPS, int FPS, bool X3, bool ARGS, int WC = 2, bool F16 = false>
 static int nr_sim_reg_launch(NrSimRegArgs& a, hipStream_t st) {
+    static_assert(!(F16 && X3), "fp16 planes: one pass");
     nr_sim_reg_plan<MI, NI, TPS, FPS, WC>(a);
     const NrSimRing ring = nr_sim_reg_ring<MI, NI, X3, WC>((long)a.ntx * a.nty, a.K);
     if (const char* e = nr_tune_env("NR_SIM_DMA_FRONT")) a.dma_front = atoi(e);
@@ -590,19 +593,19 @@ static int nr_sim_reg_launch(NrSimRegArgs& a, hipStream_t st) {
     if constexpr (big && X3 && MI * NI == 9) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 2, WC, true>(a, st);
     else {
     if constexpr (!(big && !X3)) {
-        if (ring.stages == 1) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 1, WC>(a, st);
+        if (ring.stages == 1) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 1, WC, false, 1, false, F16>(a, st);
     }
     if constexpr (big && X3) return NR_EUNSUPPORTED;
     else {
 #ifdef NR_TUNE
         if constexpr (big && NI == 3) {
-            if (ring.stages == 3) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 3, WC>(a, st);
+            if (ring.stages == 3) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 3, WC, false, 1, false, F16>(a, st);
         }
 #endif
         if constexpr (big) {
-            if (ring.kloop == NR_KLOOP_PP) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 2, WC, true>(a, st);
+            if (ring.kloop == NR_KLOOP_PP) return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 2, WC, true, 1, false, F16>(a, st);
         }
-        return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 2, WC>(a, st);
+        return nr_sim_reg_launch_s<MI, NI, TPS, FPS, X3, ARGS, 2, WC, false, 1, false, F16>(a, st);
     }
     }
 }
@@ -692,6 +695,16 @@ static int nr_sim_reg_select(int A, int Nt, int Bv, int Nv, int d, int prec) {
     return NR_SEL_NONE;
 }
 
+// Block shapes whose one-pass forms are ALSO built on fp16 planes (NR_PREC_F16): the ones the BASELINE configs' batch x batch
+// products reach -- 96 x 96 at 24 x 12 tokens (configs[1] and every small batch), 192 x 384 (configs[2]) and 256 x 256 at 64 x 64
+// tokens (configs[3]).  All of them doubled this file's one-pass kernels and the library's build time grew by 43 %; for the other
+// shapes the entry point and the plan call answer NR_EUNSUPPORTED and the host plan stays on split-bf16.
+template <typename C>
+constexpr bool nr_sim_reg_f16_built() {
+    return (C::MI == 3 && C::NI == 3 && C::TPS == 8 && C::FPS == 4 && C::WC == 2) || (C::MI == 6 && C::NI == 6 && C::WC == 4) ||
+           (C::MI == 8 && C::NI == 4 && C::RT == 2);
+}
+
 template <typename F>
 static int nr_sim_reg_visit(int sel, F&& f) {
     switch (sel) {
@@ -715,7 +728,7 @@ int nr_sim_reg_dispatch(const uint16_t* t_hi, const uint16_t* t_lo, const uint16
                         const float* w_t, const float* w_v, int A, int Nt, int Bv, int Nv, int d, int prec, int out_mode,
                         float* out, uint8_t* arg_v, uint8_t* arg_t, float* pmax, float* qmax, hipStream_t st) {
     NrSimRegArgs a{t_hi, t_lo, v_hi, v_lo, w_t, w_v, out, arg_v, arg_t, pmax, qmax, A, Bv, d, out_mode};
-    const bool x3 = prec == NR_PREC_BF16X3, args = arg_v != nullptr;
+    const bool x3 = prec == NR_PREC_BF16X3, f16 = prec == NR_PREC_F16, args = arg_v != nullptr;
     return nr_sim_reg_visit(nr_sim_reg_select(A, Nt, Bv, Nv, d, prec), [&](auto c) -> int {
         using C = decltype(c);
         constexpr int MI = C::MI, NI = C::NI, TPS = C::TPS, FPS = C::FPS, WC = C::WC, RT = C::RT;
@@ -724,6 +737,11 @@ int nr_sim_reg_dispatch(const uint16_t* t_hi, const uint16_t* t_lo, const uint16
             if (x3)       // split-bf16 as three accumulated passes on the one-pass tile
                 return args ? nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, true, 2, WC, true, RT, true>(a, st)
                             : nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, false, 2, WC, true, RT, true>(a, st);
+            if constexpr (nr_sim_reg_f16_built<C>())
+                if (f16)      // the same one-pass form on fp16 planes
+                    return args ? nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, true, 2, WC, true, RT, false, true>(a, st)
+                                : nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, false, 2, WC, true, RT, false, true>(a, st);
+            if (f16) return NR_EUNSUPPORTED;
             return args ? nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, true, 2, WC, true, RT>(a, st)
                         : nr_sim_reg_launch_s<MI, NI, TPS, FPS, false, false, 2, WC, true, RT>(a, st);
         } else {
@@ -731,9 +749,14 @@ int nr_sim_reg_dispatch(const uint16_t* t_hi, const uint16_t* t_lo, const uint16
             if constexpr (C::MODE != NR_CFG_ONE_PASS)
                 if (x3) return args ? nr_sim_reg_launch<MI, NI, TPS, FPS, true, true, WC>(a, st)
                                     : nr_sim_reg_launch<MI, NI, TPS, FPS, true, false, WC>(a, st);
-            if constexpr (C::MODE != NR_CFG_SPLIT)
+            if constexpr (C::MODE != NR_CFG_SPLIT) {
+                if constexpr (nr_sim_reg_f16_built<C>())
+                    if (f16) return args ? nr_sim_reg_launch<MI, NI, TPS, FPS, false, true, WC, true>(a, st)
+                                         : nr_sim_reg_launch<MI, NI, TPS, FPS, false, false, WC, true>(a, st);
+                if (f16) return NR_EUNSUPPORTED;
                 if (!x3) return args ? nr_sim_reg_launch<MI, NI, TPS, FPS, false, true, WC>(a, st)
                                      : nr_sim_reg_launch<MI, NI, TPS, FPS, false, false, WC>(a, st);
+            }
             return NR_EUNSUPPORTED;
         }
     });
@@ -746,6 +769,7 @@ int nr_sim_reg_describe(int A, int Nt, int Bv, int Nv, int d, int prec, int32_t*
     return nr_sim_reg_visit(nr_sim_reg_select(A, Nt, Bv, Nv, d, prec), [&](auto c) -> int {
         using C = decltype(c);
         constexpr int MI = C::MI, NI = C::NI, TPS = C::TPS, FPS = C::FPS, WC = C::WC, RT = C::RT;
+        if (prec == NR_PREC_F16 && !nr_sim_reg_f16_built<C>()) return NR_EUNSUPPORTED;
         NrSimRegArgs a{};
         a.A = A; a.Bv = Bv; a.K = d;
         nr_sim_reg_plan<MI, NI, TPS, FPS, WC, RT>(a);

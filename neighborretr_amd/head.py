@@ -34,6 +34,14 @@ class ScorerWeights:
         self.b2 = b2.detach().float().reshape(1).contiguous()
         self._w1 = w1.detach()
         self._w1t = None
+        self._w1_f16 = None
+
+    @property
+    def w1_f16(self):
+        """fp16 image of W1 (the hip.PREC_F16 operand): built on first use per version, cached with the bf16 halves."""
+        if self._w1_f16 is None:
+            self._w1_f16 = ops.split_f16(self._w1)
+        return self._w1_f16
 
     def w1_transposed(self):
         """bf16 pair of W1^T [d, H]: the operand of dX = dh W1 in the scorer's backward (built on first use per version)."""
@@ -47,18 +55,28 @@ class ScorerWeights:
         return self._w1t
 
 
+def _scorer_operands(sw, prec):
+    """(W1 operand, its lo half or None) of a scorer for a contraction precision."""
+    return (sw.w1_f16, None) if int(prec) == hip.PREC_F16 else (sw.w1_hi, sw.w1_lo)
+
+
 def token_weights(prep, mask, sw, n, N, prec, want_logits=False, scale_override=None):
     p = prep if scale_override is None else prep._replace(norm=scale_override)
-    return ops.token_weights(p, sw.w1_hi, sw.w1_lo, sw.b1, sw.w2, sw.b2, mask, n, N, prec, want_logits)
+    if int(prec) == hip.PREC_F16 and p.f16 is None and p.lo is not None:
+        # tokens prepared as a bf16 pair only, handed the training plan's scorer precision: they run the split passes they
+        # carry (what that plan ran before it had fp16 planes; no less exact)
+        prec = hip.PREC_BF16X3
+    w1_a, w1_b = _scorer_operands(sw, prec)
+    return ops.token_weights(p, w1_a, w1_b, sw.b1, sw.w2, sw.b2, mask, n, N, prec, want_logits)
 
 
 def similarity_matrix(text_feat, video_feat, text_mask, video_mask, sw_t, sw_v, prec=hip.PREC_BF16X3):
     """local_level forward only (eval path): [A,Nt,d] x [Bv,Nv,d] -> S [A,Bv]."""
     A, Nt, _ = text_feat.shape
     Bv, Nv, _ = video_feat.shape
-    lo = prec == hip.PREC_BF16X3
-    pt = ops.prepare_tokens(text_feat, text_mask, want_lo=lo)
-    pv = ops.prepare_tokens(video_feat, video_mask, want_lo=lo)
+    lo, f16 = prec == hip.PREC_BF16X3, prec == hip.PREC_F16
+    pt = ops.prepare_tokens(text_feat, text_mask, want_lo=lo, want_f16=f16)
+    pv = ops.prepare_tokens(video_feat, video_mask, want_lo=lo, want_f16=f16)
     w_t, _ = token_weights(pt, text_mask, sw_t, A, Nt, prec)
     w_v, _ = token_weights(pv, video_mask, sw_v, Bv, Nv, prec)
     S, _ = ops.local_level(pt, pv, w_t, w_v, A, Nt, Bv, Nv, prec)
@@ -104,17 +122,43 @@ def _check_global_tokens(gt, gv, hp):
 PREC_MIXED = 2   # host-level plan: split-bf16 where logit_scale amplifies the error, bf16 elsewhere
 
 
-def precision_plan(prec):
+def precision_plan(prec, shape=None):
     """(batch x batch similarity, batch-token scorer, memory-bank paths) kernel precisions.
 
     The centrality term feeds S*logit_scale (x100) into a log-softmax, so single-pass bf16 error on
-    the B x B similarity (~1.5e-4) shows up as ~2e-3 on that loss at small B.  The mixed plan keeps
-    the B x B product (11% of the contraction flops at the MSR-VTT shape) in split-bf16 and runs the
-    two memory-bank products -- whose outputs are only consumed as means over M entries -- and the
-    bank-side scorer in one bf16 pass."""
+    the B x B similarity (~1.5e-4) shows up as ~2e-3 on that loss at small B: bf16's 8 significand bits are
+    too few for the batch side.  The mixed plan runs the B x B product and the batch scorers in ONE fp16
+    pass (11 bits; the operands are normalised tokens and scorer weights: |dL| <= 2.5e-4 on the probe of
+    tools/prec_probe_f16.py, profiles/f16_prec_probe.txt) and the two memory-bank products -- whose outputs
+    are only consumed as means over M entries -- and the bank-side scorer in one bf16 pass.
+
+    This is the plan of the LOSS-ONLY step; a forward kept for the backward (head_forward(keep=True), the sharded training
+    node) runs backward_plan, i.e. split-bf16 on the batch side, because the gradients need the finer S (see head_forward).
+
+    shape = (B, Nt, Nv, d, H): the fp16 precision is returned only where the host-side plan calls
+    (hip.local_level_plan / hip.token_scorer_plan) say an fp16 form is built for that launch; a launch without
+    one stays split-bf16, as the whole batch side was before.  Without a shape: the plan's constants."""
     if prec == PREC_MIXED:
-        return hip.PREC_BF16X3, hip.PREC_BF16X3, hip.PREC_BF16
+        p_bb = p_mlp = hip.PREC_F16
+        if shape is not None:
+            B, Nt, Nv, d, H = (int(v) for v in shape)
+            if hip.local_level_plan(B, Nt, B, Nv, d, hip.PREC_F16) is None:
+                p_bb = hip.PREC_BF16X3
+            if (hip.token_scorer_plan(B * Nt, H, hip.PREC_F16, 0) is None
+                    or hip.token_scorer_plan(B * Nv, H, hip.PREC_F16, 0) is None):
+                p_mlp = hip.PREC_BF16X3
+        return p_bb, p_mlp, hip.PREC_BF16
     return prec, prec, prec
+
+
+def backward_plan(prec):
+    """precision_plan of a step that is differentiated, forward and backward: split-bf16 wherever the loss-only step runs one
+    fp16 pass (the backward kernels know the bf16 pair only, and the gradients need the finer forward: head_forward)."""
+    return tuple(backward_prec(p) for p in precision_plan(prec))
+
+
+def backward_prec(p):
+    return hip.PREC_BF16X3 if int(p) == hip.PREC_F16 else p
 
 
 # The step issues the two bank products as two launches (nr_sim_pair_kernel, one launch for both, makes the step slower:
@@ -161,11 +205,20 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
         raise ValueError("empty or inconsistent memory bank")
     if gt is None and join is None:
         raise ValueError("gt / gv missing and no join callable to produce them")
-    p_bb, p_mlp, p_bank = precision_plan(prec)
+    p_bb, p_mlp, p_bank = precision_plan(prec, (B, Nt, Nv, text_feat.shape[2], sw_t.b1.numel()))
+    if keep:
+        # A forward that will be differentiated keeps the batch side split-bf16: with one fp16 pass the losses hold (|dL| <= 3e-4)
+        # but the gradients do not -- d/d logit_scale is a sum of cancelling terms in S, and against the reference's autograd it
+        # moved from < 2e-3 to 6.4e-3 relative at c1_b16, the row sums of the text gradient to 1.7e-2 (bars 2e-3 / 5e-3,
+        # tests/test_head_gpu.py::test_backward_matches_reference).  The loss-only step has no such reader.
+        p_bb, p_mlp = backward_prec(p_bb), backward_prec(p_mlp)
     # masks as fp32 once (the loaders hand over int64); the kernels read them as multipliers
     text_mask, video_mask, mb_mask_t, mb_mask_v = (m if m.dtype == torch.float32 else m.float()
                                                    for m in (text_mask, video_mask, mb_mask_t, mb_mask_v))
-    lo_b = keep or hip.PREC_BF16X3 in (p_bb, p_mlp, p_bank)
+    f16_b = hip.PREC_F16 in (p_bb, p_mlp)
+    # who reads the batch's lo plane: the backward (keep), a split-bf16 launch, and -- on the fp16 plan -- the memory bank's
+    # prepared shadow, which takes the batch's hi / lo / norm rows at the push (prepared_out)
+    lo_b = keep or hip.PREC_BF16X3 in (p_bb, p_mlp, p_bank) or (f16_b and prepared_out is not None)
     lo_k = keep or p_bank == hip.PREC_BF16X3
     cur = torch.cuda.current_stream()
     # Loss-only step at B <= 128 ("split tail", below): the bank centralities stay PARTIAL sums (the row-loss kernel adds
@@ -179,13 +232,13 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
 
     def local_steps():
         L["pt"], L["pv"] = pt_, pv_ = ops.prepare_tokens_pair(text_feat, text_mask, video_feat, video_mask, want_lo=lo_b,
-                                                              want_colsum=True)
+                                                              want_colsum=True, want_f16=f16_b)
         yield
         if not keep and B * min(Nt, Nv) >= PAIR_BATCH_SCORERS_FROM:
             # the text and the video scorer in one grid; bit-identical to the two launches
             (L["w_t"], L["lg_t"]), (L["w_v"], L["lg_v"]) = ops.token_weights_pair(
-                [(pt_, sw_t.w1_hi, sw_t.w1_lo, sw_t.b1, sw_t.w2, sw_t.b2, text_mask, B, Nt),
-                 (pv_, sw_v.w1_hi, sw_v.w1_lo, sw_v.b1, sw_v.w2, sw_v.b2, video_mask, B, Nv)], p_mlp)
+                [(pt_, *_scorer_operands(sw_t, p_mlp), sw_t.b1, sw_t.w2, sw_t.b2, text_mask, B, Nt),
+                 (pv_, *_scorer_operands(sw_v, p_mlp), sw_v.b1, sw_v.w2, sw_v.b2, video_mask, B, Nv)], p_mlp)
             yield
         else:
             L["w_t"], L["lg_t"] = token_weights(pt_, text_mask, sw_t, B, Nt, p_mlp, keep)
@@ -458,7 +511,8 @@ def head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_fea
 def _rows(prep, first, count):
     """Rows [first, first + count) of a Prepared token set (contiguous views)."""
     return ops.Prepared(prep.hi[first:first + count], prep.lo[first:first + count] if prep.lo is not None else None,
-                        prep.norm[first:first + count], None, count, prep.d)
+                        prep.norm[first:first + count], None, count, prep.d,
+                        prep.f16[first:first + count] if prep.f16 is not None else None)
 
 
 def head_forward_sharded(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
@@ -490,14 +544,18 @@ def head_forward_sharded(text_feat, video_feat, text_mask, video_mask, mb_feat_t
     if gt is None and join is None:
         raise ValueError("gt / gv missing and no join callable to produce them")
     b, r0 = B // world, rank * (B // world)
-    p_bb, p_mlp, p_bank = precision_plan(prec)
+    # (the slabs are b x B and B x b products: the fp16 form must exist for both, or both stay split-bf16)
+    p_bb, p_mlp, p_bank = precision_plan(prec, (B, Nt, Nv, d, sw_t.b1.numel()))
+    if p_bb == hip.PREC_F16 and (hip.local_level_plan(b, Nt, B, Nv, d, p_bb) is None or hip.local_level_plan(B, Nt, b, Nv, d, p_bb) is None):
+        p_bb = hip.PREC_BF16X3
     text_mask, video_mask, mb_mask_t, mb_mask_v = (m if m.dtype == torch.float32 else m.float()
                                                    for m in (text_mask, video_mask, mb_mask_t, mb_mask_v))
-    lo_b = hip.PREC_BF16X3 in (p_bb, p_mlp, p_bank)
+    f16_b = hip.PREC_F16 in (p_bb, p_mlp)
+    lo_b = hip.PREC_BF16X3 in (p_bb, p_mlp, p_bank) or (f16_b and prepared_out is not None)
     L = {}
 
     def local_branch():
-        pt, pv = ops.prepare_tokens_pair(text_feat, text_mask, video_feat, video_mask, want_lo=lo_b, want_colsum=True)
+        pt, pv = ops.prepare_tokens_pair(text_feat, text_mask, video_feat, video_mask, want_lo=lo_b, want_colsum=True, want_f16=f16_b)
         w_t, _ = token_weights(pt, text_mask, sw_t, B, Nt, p_mlp)
         w_v, _ = token_weights(pv, video_mask, sw_v, B, Nv, p_mlp)
         if prepared_out is not None:

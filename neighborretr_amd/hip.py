@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("NR_HIP_LIB") or os.path.join(_HERE, "libnr_hip.so")
 
 PREC_BF16 = 0
 PREC_BF16X3 = 1
+PREC_F16 = 3                                 # NR_PREC_F16: one fp16 pass on fp16 operand planes (2 is head.PREC_MIXED, a host-level plan)
 OUT_FULL, OUT_ROWSUM, OUT_COLSUM = 0, 1, 2
 NR_EINVAL, NR_EUNSUPPORTED = -1, -2          # status codes of include/nr_hip.h
 ABI_VERSION = 5                              # NR_ABI_VERSION this binding was written for (checked at load)
@@ -176,6 +177,9 @@ _SIGNATURES = {
     "nr_prepare_tokens": ([_P, _P, _I, _I, _I, _P, _P, _P, _P, _P], _I),
     "nr_prepare_tokens_pair": ([_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P], _I),
     "nr_split_bf16": ([_P, _Z, _P, _P, _P], _I),
+    "nr_prepare_tokens_f16": ([_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
+    "nr_prepare_tokens_pair_f16": ([_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P], _I),
+    "nr_split_f16": ([_P, _Z, _P, _P], _I),
     "nr_token_logits_fwd": ([_P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P], _I),
     "nr_token_softmax": ([_P, _I, _P, _P, _I, _I, _P, _P, _P], _I),
     "nr_token_mlp_bwd_row_tiles": ([_I], _I),

@@ -11,7 +11,17 @@ import torch
 
 from . import hip
 
-Prepared = namedtuple("Prepared", "hi lo norm colsum n_tok d")
+# hi / lo: the bf16 pair; f16: the fp16 plane of the same values (the operand of hip.PREC_F16 contractions) or None
+Prepared = namedtuple("Prepared", "hi lo norm colsum n_tok d f16", defaults=(None,))
+
+
+def _planes(prep, prec):
+    """(first, second) operand planes of a Prepared for a contraction precision: the bf16 pair, or (fp16 plane, None)."""
+    if int(prec) == hip.PREC_F16:
+        if prep.f16 is None:
+            raise hip.NrHipError("PREC_F16 needs the fp16 plane: prepare the tokens with want_f16=True")
+        return prep.f16, None
+    return prep.hi, prep.lo
 
 
 _COUNTERS = {}
@@ -21,14 +31,21 @@ def _f32(t):
     return t if t.dtype == torch.float32 else t.float()
 
 
-def prepare_tokens(x, mask=None, normalize=True, want_lo=True, want_norm=True, want_colsum=False):
-    """x [..., d] f32 -> bf16 hi/lo of normalize(x)*mask  (nr_prepare_tokens)."""
+def prepare_tokens(x, mask=None, normalize=True, want_lo=None, want_norm=True, want_colsum=False, want_f16=None):
+    """x [..., d] f32 -> bf16 hi/lo of normalize(x)*mask  (nr_prepare_tokens), with want_f16 also their fp16 plane in the same
+    pass (nr_prepare_tokens_f16).  A caller that names no plane (want_lo and want_f16 both left out) gets every plane of the
+    normalised tokens, so that the result serves whatever precision it is handed to next."""
+    if want_f16 is None:
+        want_f16 = want_lo is None and bool(normalize)
+    if want_lo is None:
+        want_lo = True
     x = _f32(x).contiguous()
     d = x.shape[-1]
     n_tok = x.numel() // d
     dev = x.device
     hi = torch.empty((n_tok, d), dtype=torch.int16, device=dev)
     lo = torch.empty((n_tok, d), dtype=torch.int16, device=dev) if want_lo else None
+    f16 = torch.empty((n_tok, d), dtype=torch.int16, device=dev) if want_f16 else None
     norm = torch.empty((n_tok,), dtype=torch.float32, device=dev) if want_norm else None
     colsum = None
     if want_colsum:
@@ -38,14 +55,20 @@ def prepare_tokens(x, mask=None, normalize=True, want_lo=True, want_norm=True, w
         m = _f32(mask).contiguous()
         if m.numel() != n_tok:
             raise ValueError("mask does not match the token count")
+    if f16 is not None:
+        hip.call("nr_prepare_tokens_f16", hip.ptr(x, torch.float32), hip.ptr(m, allow_none=True), n_tok, d,
+                 1 if normalize else 0, hip.ptr(hi), hip.ptr(lo, allow_none=True), hip.ptr(f16), hip.ptr(norm, allow_none=True),
+                 hip.ptr(colsum, allow_none=True), hip.stream_ptr())
+        return Prepared(hi, lo, norm, colsum, n_tok, d, f16)
     hip.call("nr_prepare_tokens", hip.ptr(x, torch.float32), hip.ptr(m, allow_none=True), n_tok, d,
              1 if normalize else 0, hip.ptr(hi), hip.ptr(lo, allow_none=True), hip.ptr(norm, allow_none=True),
              hip.ptr(colsum, allow_none=True), hip.stream_ptr())
     return Prepared(hi, lo, norm, colsum, n_tok, d)
 
 
-def prepare_tokens_pair(x0, mask0, x1, mask1, want_lo=True, want_colsum=False):
-    """prepare_tokens of two token tensors of the same width in ONE launch (nr_prepare_tokens_pair) -> (Prepared, Prepared)."""
+def prepare_tokens_pair(x0, mask0, x1, mask1, want_lo=True, want_colsum=False, want_f16=False):
+    """prepare_tokens of two token tensors of the same width in ONE launch (nr_prepare_tokens_pair; with want_f16 the fp16 planes
+    too: nr_prepare_tokens_pair_f16) -> (Prepared, Prepared)."""
     x0, x1 = _f32(x0).contiguous(), _f32(x1).contiguous()
     d = x0.shape[-1]
     if x1.shape[-1] != d:
@@ -56,6 +79,7 @@ def prepare_tokens_pair(x0, mask0, x1, mask1, want_lo=True, want_colsum=False):
         n_tok = x.numel() // d
         hi = torch.empty((n_tok, d), dtype=torch.int16, device=dev)
         lo = torch.empty((n_tok, d), dtype=torch.int16, device=dev) if want_lo else None
+        f16 = torch.empty((n_tok, d), dtype=torch.int16, device=dev) if want_f16 else None
         norm = torch.empty((n_tok,), dtype=torch.float32, device=dev)
         colsum = torch.empty((hip.prepare_parts(n_tok), d), dtype=torch.float32, device=dev) if want_colsum else None
         m = None
@@ -63,10 +87,11 @@ def prepare_tokens_pair(x0, mask0, x1, mask1, want_lo=True, want_colsum=False):
             m = _f32(mask).contiguous()
             if m.numel() != n_tok:
                 raise ValueError("mask does not match the token count")
-        argv += [hip.ptr(x, torch.float32), hip.ptr(m, allow_none=True), n_tok, hip.ptr(hi), hip.ptr(lo, allow_none=True), hip.ptr(norm),
-                 hip.ptr(colsum, allow_none=True)]
-        out.append((Prepared(hi, lo, norm, colsum, n_tok, d), m))
-    hip.call("nr_prepare_tokens_pair", *argv, d, 1, hip.stream_ptr())
+        argv += [hip.ptr(x, torch.float32), hip.ptr(m, allow_none=True), n_tok, hip.ptr(hi), hip.ptr(lo, allow_none=True)]
+        argv += [hip.ptr(f16)] if want_f16 else []
+        argv += [hip.ptr(norm), hip.ptr(colsum, allow_none=True)]
+        out.append((Prepared(hi, lo, norm, colsum, n_tok, d, f16), m))
+    hip.call("nr_prepare_tokens_pair_f16" if want_f16 else "nr_prepare_tokens_pair", *argv, d, 1, hip.stream_ptr())
     return out[0][0], out[1][0]
 
 
@@ -79,11 +104,20 @@ def split_bf16(w, want_lo=True):
     return hi, lo
 
 
+def split_f16(w):
+    """fp32 -> fp16 plane (int16 storage) of a weight matrix (nr_split_f16): the PREC_F16 image of a scorer's W1."""
+    w = _f32(w).contiguous()
+    f16 = torch.empty(w.shape, dtype=torch.int16, device=w.device)
+    hip.call("nr_split_f16", hip.ptr(w, torch.float32), w.numel(), hip.ptr(f16), hip.stream_ptr())
+    return f16
+
+
 def token_logit_parts(prep, w1_hi, w1_lo, b1, w2, prec):
     """[H/128, n_tok] partial logits of the token scorer (nr_token_logits_fwd)."""
     H = w1_hi.shape[0]
     parts = torch.empty((H // 128, prep.n_tok), dtype=torch.float32, device=prep.hi.device)
-    hip.call("nr_token_logits_fwd", hip.ptr(prep.hi), hip.ptr(prep.lo, allow_none=True), hip.ptr(prep.norm), prep.n_tok,
+    t_a, t_b = _planes(prep, prec)
+    hip.call("nr_token_logits_fwd", hip.ptr(t_a), hip.ptr(t_b, allow_none=True), hip.ptr(prep.norm), prep.n_tok,
              prep.d, hip.ptr(w1_hi), hip.ptr(w1_lo, allow_none=True), hip.ptr(b1, torch.float32),
              hip.ptr(w2, torch.float32), H, prec, hip.ptr(parts), hip.stream_ptr())
     return parts
@@ -121,8 +155,10 @@ def _softmax_counters(dev, n_tok):
 def token_weights(prep, w1_hi, w1_lo, b1, w2, b2, mask, n_samples, N, prec, want_logits=False):
     """Token scorer + masked softmax (modeling.py:485-492): (w [n,N], logits or None).  One launch
     (nr_token_weights_fwd: the last column block of every row tile does the tile's softmax) when a block shape holds whole
-    samples, else nr_token_logits_fwd + nr_token_softmax."""
+    samples, else nr_token_logits_fwd + nr_token_softmax.  prec = hip.PREC_F16: w1_hi is the fp16 image of W1 (split_f16), w1_lo
+    None, and the tokens' fp16 plane is read."""
     dev = prep.hi.device
+    t_a, t_b = _planes(prep, prec)
     counters = _softmax_counters(dev, prep.n_tok) if FUSE_TOKEN_SOFTMAX else None
     if counters is not None:
         H = w1_hi.shape[0]
@@ -132,7 +168,7 @@ def token_weights(prep, w1_hi, w1_lo, b1, w2, b2, mask, n_samples, N, prec, want
         m = _f32(mask).contiguous() if mask is not None else None
         hip.N_CALLS += 1
         rc = hip.lib().nr_token_weights_fwd(
-            hip.ptr(prep.hi), hip.ptr(prep.lo, allow_none=True), hip.ptr(prep.norm), n_samples, N, prep.d, hip.ptr(w1_hi),
+            hip.ptr(t_a), hip.ptr(t_b, allow_none=True), hip.ptr(prep.norm), n_samples, N, prep.d, hip.ptr(w1_hi),
             hip.ptr(w1_lo, allow_none=True), hip.ptr(b1, torch.float32), hip.ptr(w2, torch.float32), hip.ptr(b2, torch.float32),
             H, prec, hip.ptr(m, allow_none=True), hip.ptr(parts), hip.ptr(counters), counters.numel(), hip.ptr(w),
             hip.ptr(logits, allow_none=True), hip.stream_ptr())
@@ -160,7 +196,8 @@ def token_weights_pair(calls, prec, want_logits=False):
         w = torch.empty((n_samples, N), dtype=torch.float32, device=dev)
         m = _f32(mask).contiguous() if mask is not None else None
         q = hip.TokenWeightsProblem()
-        q.tok_hi, q.tok_lo, q.norm = hip.ptr(prep.hi), hip.ptr(prep.lo, allow_none=True), hip.ptr(prep.norm)
+        t_a, t_b = _planes(prep, prec)
+        q.tok_hi, q.tok_lo, q.norm = hip.ptr(t_a), hip.ptr(t_b, allow_none=True), hip.ptr(prep.norm)
         q.w1_hi, q.w1_lo = hip.ptr(w1_hi), hip.ptr(w1_lo, allow_none=True)
         q.b1, q.w2, q.b2 = hip.ptr(b1, torch.float32), hip.ptr(w2, torch.float32), hip.ptr(b2, torch.float32)
         q.mask, q.logit_part, q.counters = hip.ptr(m, allow_none=True), hip.ptr(parts), hip.ptr(counters)
@@ -236,8 +273,9 @@ def local_level(prep_t, prep_v, w_t, w_v, A, Nt, Bv, Nv, prec=hip.PREC_BF16, out
         arg_t = torch.empty((A, Bv, Nv), dtype=torch.uint8, device=dev)
         pmax = torch.empty((A, Bv, Nt), dtype=torch.float32, device=dev)
         qmax = torch.empty((A, Bv, Nv), dtype=torch.float32, device=dev)
-    hip.call("nr_local_level_fwd", hip.ptr(prep_t.hi), hip.ptr(prep_t.lo, allow_none=True), hip.ptr(prep_v.hi),
-             hip.ptr(prep_v.lo, allow_none=True), hip.ptr(w_t, torch.float32), hip.ptr(w_v, torch.float32),
+    (t_a, t_b), (v_a, v_b) = _planes(prep_t, prec), _planes(prep_v, prec)
+    hip.call("nr_local_level_fwd", hip.ptr(t_a), hip.ptr(t_b, allow_none=True), hip.ptr(v_a),
+             hip.ptr(v_b, allow_none=True), hip.ptr(w_t, torch.float32), hip.ptr(w_v, torch.float32),
              A, Nt, Bv, Nv, prep_t.d, prec, out_mode, hip.ptr(out), hip.ptr(arg_v, allow_none=True),
              hip.ptr(arg_t, allow_none=True), hip.ptr(pmax, allow_none=True), hip.ptr(qmax, allow_none=True),
              hip.stream_ptr())

@@ -121,7 +121,8 @@ class SlabRowLossFn(torch.autograd.Function):
 
 def _rows(prep, first, count):
     return ops.Prepared(prep.hi[first:first + count], prep.lo[first:first + count] if prep.lo is not None else None,
-                        prep.norm[first:first + count], None, count, prep.d)
+                        prep.norm[first:first + count], None, count, prep.d,
+                        prep.f16[first:first + count] if prep.f16 is not None else None)
 
 
 class ShardedLocalFn(torch.autograd.Function):
@@ -136,8 +137,8 @@ class ShardedLocalFn(torch.autograd.Function):
         B, Nt, d = text_feat.shape
         Nv, M = video_feat.shape[1], mb_feat_v.shape[0]
         prec = model._prec()
-        p_bb, p_mlp, p_bank = head.precision_plan(prec)
         sw_t, sw_v = model.scorer_weights("text_weight_fc"), model.scorer_weights("video_weight_fc")
+        p_bb, p_mlp, p_bank = head.backward_plan(prec)          # a differentiated forward: split-bf16 on the batch side (head_forward)
         tf, vf = text_feat.detach(), video_feat.detach()
         pt, pv = ops.prepare_tokens_pair(tf, text_mask, vf, video_mask, want_lo=True, want_colsum=True)
         pbt, pbv = ops.prepare_tokens_pair(mb_feat_t, mb_mask_t, mb_feat_v, mb_mask_v, want_lo=True)
