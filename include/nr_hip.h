@@ -921,6 +921,48 @@ int nr_cand_norm_rerank(const float* fine, const int32_t* cand, int n, int C, in
                         const int32_t* active, float beta, int k, int32_t* out_idx, float* out_val, float* out_corr,
                         int32_t* out_gate, void* stream);
 
+/* Inverted-file (IVF) prefilter of two-stage retrieval: the gallery's pooled vectors x [n_items, d] are dealt to
+ * n_lists k-means lists and a query scans only the n_probe lists whose centroids it is closest to.  The reference has no such
+ * path.  An index is list_offsets [n_lists + 1] int32 (list l = the rows [list_offsets[l], list_offsets[l + 1]), empty lists
+ * allowed), list_items [n_items] int32 (the gallery index of every row; ascending inside a list) and rows [n_items, d] =
+ * x[list_items].  Device offsets and items are clamped to the index before they form an address.
+ *
+ * nr_ivf_list_sums (the k-means update): sums [n_lists, d], sums[l] = the members of list l added in list order,
+ *   one sequential fp32 addition per component (a float32 loop on the host gives the same bits; an empty list: zeros).  One
+ *   workgroup per list, no atomics.  NR_EINVAL before any launch: a null pointer; n_items, n_lists or d <= 0; n_lists > n_items.
+ *
+ * nr_ivf_scan (the pool scores of a chunk of n queries q [n, d]): probes [n, n_probe] int32 = every query's
+ *   lists in probe order (an entry outside [0, n_lists) is an empty list).  The pool of query i = the members of its probed
+ *   lists, concatenated in probe order: slot base(i, r) + j holds member j of the list of probe rank r, base = the sizes of the
+ *   lists of lower rank.  pool_item [n, stride] int32 = the gallery index, pool_score [n, stride] f32 = q_i . x_item with exactly
+ *   the bits nr_gemm_nt_f32 gives that pair (the same K split over four waves, MFMA sequence and combine), pool_len [n] int32 =
+ *   the pool's length; slots from pool_len[i] on are not written.  stride >= the sum of the n_probe largest list sizes (slots
+ *   past stride are dropped, never written).  The launch is list-major: the caller passes the (query, probe) pairs grouped by
+ *   list -- bucket b < n_lists = list b, bucket n_lists = the pairs without a list -- as pair_order [n * n_probe] int32 (pair ids
+ *   i * n_probe + r, bucket by bucket, ascending inside a bucket), group_offsets [n_lists + 2] int32 (where each bucket's pairs
+ *   start, and their total) and tile_offsets [n_lists + 2] int32 (prefix sums of ceil(bucket size / 16)); one workgroup scores 16
+ *   pairs of one bucket against 16 rows of its list.  max_list_size: the host's bound of a list's size (sizes the grid; surplus
+ *   workgroups exit).  No float atomics, every output element is written by exactly one workgroup.
+ *   NR_EINVAL before any launch: a null pointer; n, n_items, n_lists or d <= 0; n_lists > n_items; d % 16 != 0; n_probe outside
+ *   [1, min(n_lists, 128)]; max_list_size outside [0, n_items]; stride < 1.  NR_EUNSUPPORTED: more than 2^31 - 1 query tiles or
+ *   a list of more than 16 x 65535 rows.
+ *
+ * nr_ivf_select (the candidates of every pool line): cand [n, C] int32 = the top C of the pool_len[i] (clamped to
+ *   [0, stride]) entries of line i by (score descending, gallery index ascending; -0.0 == +0.0; NaN never taken), emitted in
+ *   ASCENDING GALLERY INDEX and padded with -1; score_out [n, C] f32 or null = their scores (the bits of pool_score; -inf at the
+ *   padding).  The items of a line must be distinct and >= 0.  One workgroup per line: a radix select on the 64-bit keys
+ *   (score key << 32) | ~item; lines of stride <= 16384 keep their keys in LDS, longer ones re-read memory in every pass.  Integer
+ *   counts only: bitwise reproducible.  NR_EINVAL before any launch: pool_score, pool_item, pool_len or cand null; n <= 0;
+ *   stride < 1; C outside [1, 128].                                                                                          */
+int nr_ivf_list_sums(const float* x, const int32_t* list_items, const int32_t* list_offsets, int n_items, int n_lists, int d,
+                     float* sums, void* stream);
+int nr_ivf_scan(const float* q, int n, const float* rows, const int32_t* list_items, const int32_t* list_offsets, int n_items,
+                int n_lists, int d, const int32_t* probes, int n_probe, const int32_t* pair_order, const int32_t* group_offsets,
+                const int32_t* tile_offsets, int max_list_size, float* pool_score, int32_t* pool_item, int32_t* pool_len,
+                int stride, void* stream);
+int nr_ivf_select(const float* pool_score, const int32_t* pool_item, const int32_t* pool_len, int n, int stride, int C,
+                  int32_t* cand, float* score_out, void* stream);
+
 /* Test-time Sinkhorn normalisation (DESIGN.md "Test-time Sinkhorn normalisation"): the log-domain iteration of the reference's
  * uniform regularisation (until_module.py:223-266; :248-250 is the order of the two half-steps) on a test similarity slab
  * S [n, L] instead of the batch's logits.  a[i,j] = fl(beta S[i,j]), beta finite and > 0; log_mu [n], log_nu [L]: the log

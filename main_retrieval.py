@@ -154,6 +154,15 @@ def get_args():
                         "--test_norm_beta and --qb_k; the statistics are computed once per gallery, one fused launch normalises "
                         "and re-ranks the lists; logs R@K, candidate recall and the gated share per direction and, with "
                         "--hubness_k K <= C, the hubness of the two-stage lists before and after (DESIGN.md 6.15); none = off")
+    p.add_argument("--rerank_lists", type=int, default=0, metavar="L",
+                   help="with --rerank_top C: the prefilter goes through an inverted file of L k-means lists over each gallery's "
+                        "pooled vectors and scores a query against its --rerank_probe closest lists only; logs the two-stage "
+                        "figures of those candidates, the mean pool size and the share of the exact prefilter's candidates kept "
+                        "(DESIGN.md 6.16); 0 = off, the exact prefilter")
+    p.add_argument("--rerank_probe", type=int, default=0, metavar="P",
+                   help="with --rerank_lists L: the lists a query scans, 1..min(L, 128)")
+    p.add_argument("--rerank_ivf_iters", type=int, default=10, help="with --rerank_lists: k-means rounds of the index build (>= 0)")
+    p.add_argument("--rerank_ivf_seed", type=int, default=0, help="with --rerank_lists: seed of the initial centroids")
     p.add_argument("--hip_graph", type=int, default=0,
                    help="1: the training step replayed from captured HIP graphs instead of ~90 eager launches.  One rank: forward + "
                         "backward as ONE graph.  Several ranks: the whole data-parallel step -- exchange, loss, backward, gradient "
@@ -236,6 +245,16 @@ def get_args():
         p.error("--rerank_top must lie in [0, 128] (0 = off)")
     if args.rerank_norm != "none" and args.rerank_top < 1:
         p.error("--rerank_norm normalises candidate lists: it needs --rerank_top >= 1")
+    if args.rerank_lists < 0:
+        p.error("--rerank_lists must be >= 0 (0 = off)")
+    if args.rerank_lists and args.rerank_top < 1:
+        p.error("--rerank_lists restricts the prefilter of two-stage retrieval: it needs --rerank_top >= 1")
+    if args.rerank_lists and not 1 <= args.rerank_probe <= min(args.rerank_lists, 128):
+        p.error(f"--rerank_probe must lie in [1, min(--rerank_lists, 128) = {min(args.rerank_lists, 128)}]")
+    if not args.rerank_lists and args.rerank_probe:
+        p.error("--rerank_probe needs --rerank_lists >= 1")
+    if args.rerank_ivf_iters < 0:
+        p.error("--rerank_ivf_iters must be >= 0")
     if args.hubness_test and not (args.hubness_k > 0 and args.permutation > 0):
         p.error("--hubness_test needs --hubness_k > 0 and --permutation > 0")
     if args.batch_size % max(1, int(os.environ.get("WORLD_SIZE", "1"))):
@@ -799,11 +818,13 @@ def eval_epoch(args, model, test, tag=""):
     they are the inputs), one packed all-gather + index scatter restores dataset order (evaluator.py:173-189), rank r
     computes rows [r N/W, (r+1) N/W) of the N x N similarity and the rank counts of its slab on the GPU, three small
     collectives complete them."""
-    from neighborretr_amd.evaluator import (correction_from_args, gather_eval_features, rank_sample_indices, rerank_norm_from_args,
-                                            rerank_top_from_args, sharded_evaluation, two_stage_evaluation, two_stage_label)
+    from neighborretr_amd.evaluator import (correction_from_args, gather_eval_features, rank_sample_indices, rerank_ivf_from_args,
+                                            rerank_norm_from_args, rerank_top_from_args, sharded_evaluation, two_stage_evaluation,
+                                            two_stage_ivf_label, two_stage_label)
     from neighborretr_amd.metrics import RetrievalMetrics
     correction, extras = correction_from_args(args, model)     # every flag checked before any work
     rerank_top = rerank_top_from_args(args)
+    rerank_ivf = rerank_ivf_from_args(args)
     rerank_norm = rerank_norm_from_args(args, model)
     hubness_k = extras["hubness_k"]
     log = _tagged_log(tag)
@@ -873,9 +894,11 @@ def eval_epoch(args, model, test, tag=""):
         torch.cuda.synchronize()
         tic = time.time()
         norm_kw = {} if rerank_norm is None else dict(rerank_norm, hubness_k=min(hubness_k, rerank_top))
-        t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, t, v, tm.float(), vm.float(), args, rerank_top, **norm_kw)
+        t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, t, v, tm.float(), vm.float(), args, rerank_top, **norm_kw,
+                                                                  **(rerank_ivf or {}))
         toc = time.time()
-        tag = two_stage_label(rerank_top)
+        tag = two_stage_label(rerank_top) if rerank_ivf is None else \
+            two_stage_ivf_label(rerank_top, rerank_ivf["n_lists"], rerank_ivf["nprobe"])
         for line in RetrievalMetrics.two_stage_lines(t2v["two_stage"], v2t["two_stage"], tag, ("text->video", "video->text"), " "):
             log(args, line)
         log(args, f"{tag} wall time {toc - tic:.2f}s")

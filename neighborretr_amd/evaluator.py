@@ -1434,21 +1434,54 @@ def rerank_norm_from_args(args, model):
     return kw
 
 
-def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None):
+def two_stage_ivf_label(n_candidates, n_lists, nprobe):
+    """The tag of the log lines of two-stage retrieval behind the inverted-file prefilter: "[two-stage C=64 IVF L=128 P=8]"."""
+    return f"[two-stage C={int(n_candidates)} IVF L={int(n_lists)} P={int(nprobe)}]"
+
+
+def rerank_ivf_from_args(args):
+    """args.rerank_lists / rerank_probe / rerank_ivf_iters / rerank_ivf_seed -> None (rerank_lists = 0: off) or the keyword
+    arguments of two_stage_evaluation (n_lists, nprobe, ivf_iters, ivf_seed), checked before any work: that rerank_top asks for
+    candidates, rerank_lists >= 1, rerank_probe in [1, min(rerank_lists, 128)], rerank_ivf_iters >= 0 and an integer seed.  That
+    the galleries hold at least rerank_lists items is checked by two_stage_evaluation, which knows their sizes."""
+    from .search import check_ivf_build, check_nprobe
+    lists = getattr(args, "rerank_lists", 0)
+    if lists is None or (lists == 0 and not isinstance(lists, bool)):
+        return None
+    if rerank_top_from_args(args) < 1:
+        raise ValueError("rerank_lists restricts the prefilter of two-stage retrieval: it needs rerank_top >= 1")
+    iters, seed = getattr(args, "rerank_ivf_iters", 10), getattr(args, "rerank_ivf_seed", 0)
+    try:
+        lists, iters, seed = check_ivf_build(lists, iters, seed, 1 << 31)
+    except ValueError as e:
+        raise ValueError(f"rerank_lists / rerank_ivf_iters / rerank_ivf_seed: {e}") from None
+    try:
+        probe = check_nprobe(getattr(args, "rerank_probe", 0), lists)
+    except ValueError:
+        raise ValueError(f"rerank_probe must be an integer in [1, min(rerank_lists, 128) = {min(lists, 128)}], got "
+                         f"{getattr(args, 'rerank_probe', 0)!r}") from None
+    return dict(n_lists=lists, nprobe=probe, ivf_iters=iters, ivf_seed=seed)
+
+
+def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None, nprobe=None):
     """(cand [n, C] int32, fine [n, C] fp32) on the device, the same on every rank: this rank's queries searched, one gather.
-    norm: (cand, fine, corr [n, C] fp32, gate [n] int32), all four in that one gather."""
+    norm: (cand, fine, corr [n, C] fp32, gate [n] int32), all four in that one gather.  nprobe: the candidates of the index's
+    inverted file, and as the last element stats [n, 3] int32 (GalleryIndex.candidates, ivf_stats), in that same gather."""
     n = q_feat.shape[0]
     r0, r1 = slab_bounds(n, W, rank)
-    out = index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk) if norm is None else \
-        index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk, norm=norm)
+    kw = {**({} if norm is None else dict(norm=norm)), **({} if nprobe is None else dict(nprobe=nprobe, ivf_stats=True))}
+    out = index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk, **kw)
     if W > 1:
         blocks = [out[0].T, out[1].view(torch.int32).T] + ([out[2].view(torch.int32).T, out[3][None]] if norm is not None else [])
+        blocks += [out[-1].T] if nprobe is not None else []
         mine = torch.zeros((sum(b.shape[0] for b in blocks), -(-n // W)), dtype=torch.int32, device=out[0].device)
         mine[:, :r1 - r0] = torch.cat(blocks, 0)
         rows = _gathered_rows(mine, n, W)
         out = (rows[:C].T.contiguous(), rows[C:2 * C].T.contiguous().view(torch.float32))
         if norm is not None:
             out += (rows[2 * C:3 * C].T.contiguous().view(torch.float32), rows[3 * C].contiguous())
+        if nprobe is not None:
+            out += (rows[-3:].T.contiguous(),)
     return out
 
 
@@ -1461,7 +1494,7 @@ def _two_stage_hubness(cand, score, K, n_gallery, gt_begin, gt_end):
 
 
 def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, n_candidates, cut_off_points=None, chunk=256,
-                         norm=None, beta=20.0, qb_k=1, querybank=None, hubness_k=0):
+                         norm=None, beta=20.0, qb_k=1, querybank=None, hubness_k=0, n_lists=0, nprobe=0, ivf_iters=10, ivf_seed=0):
     """-> (t2v, v2t) of two-stage retrieval with n_candidates (1..128) candidates per query, identical on every rank: R1 / R5 /
     R10 / R50 (None where K > C), cand_recall (percent of the queries whose ground truth is among their candidates),
     n_candidates, cols, and MR / MedianR / MeanR only when every query was found.  Every argument is checked before any work.
@@ -1470,8 +1503,14 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
     sharded_evaluation, None: the model's memory bank; the video index takes its texts, the text index its videos) with
     inverse temperature beta and, for qbnorm, the activation lists' length qb_k.  Each direction gains ["normalised"]: the same
     fields computed from the corrected scores, `gated` (percent of the queries normalised) and `label`.  hubness_k = K, 1 <= K
-    <= n_candidates: the raw and the normalised dictionary each gain ["hubness"] of the top-K of their candidate scores."""
-    from .search import GalleryIndex, check_candidates, check_chunk, check_norm
+    <= n_candidates: the raw and the normalised dictionary each gain ["hubness"] of the top-K of their candidate scores.
+
+    n_lists = L >= 1 with nprobe = P in [1, min(L, 128)] (0: off): both galleries get an inverted file of L lists
+    (build_ivf with ivf_iters rounds and ivf_seed, on every rank, deterministic) and every figure above is that of the candidates
+    taken from each query's P probed lists.  Each direction gains n_lists, nprobe, pool_mean (the mean pool length / the gallery's
+    size) and ivf_overlap (the mean share of the exact prefilter's candidates that the inverted file's lists kept; the exact
+    lists are computed for this figure only).  The per-query counts travel in the direction's one gather."""
+    from .search import GalleryIndex, check_candidates, check_chunk, check_ivf_build, check_norm, check_nprobe
     C, chunk = check_candidates(n_candidates), check_chunk(chunk)
     norm = check_norm(norm)
     hubness_k = _check_hubness_k(hubness_k)
@@ -1491,6 +1530,18 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
         ends = None
     else:
         ends = _group_ends(cut_off_points, n_rows, n_cols)
+    if isinstance(n_lists, bool) or not isinstance(n_lists, int) or n_lists < 0:
+        raise ValueError(f"n_lists must be an integer >= 0 (0 = the exact prefilter), got {n_lists!r}")
+    if n_lists:
+        try:
+            n_lists, ivf_iters, ivf_seed = check_ivf_build(n_lists, ivf_iters, ivf_seed, min(n_rows, n_cols))
+        except ValueError as e:
+            raise ValueError(f"{e} (n_lists / ivf_iters / ivf_seed of {n_rows} texts and {n_cols} videos)") from None
+        nprobe = check_nprobe(nprobe, n_lists)
+    elif nprobe not in (0, None) or isinstance(nprobe, bool):
+        raise ValueError(f"nprobe={nprobe!r} needs an inverted file: give n_lists >= 1")
+    else:
+        nprobe = None
     bank = _querybank(model, querybank, text_feat.device) if norm is not None else None
     W = _world(args)
     rank = comm.get_rank() if W > 1 else 0
@@ -1499,8 +1550,11 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
     if bank is not None:
         index_v.attach_querybank(bank[0], bank[1], beta, qb_k, chunk)
         index_t.attach_querybank(bank[2], bank[3], beta, qb_k, chunk)
-    lists_t = _two_stage_lists(index_v, text_feat, text_mask, C, W, rank, chunk, norm)
-    lists_v = _two_stage_lists(index_t, video_feat, video_mask, C, W, rank, chunk, norm)
+    if nprobe is not None:
+        index_v.build_ivf(n_lists, ivf_iters, ivf_seed, chunk)
+        index_t.build_ivf(n_lists, ivf_iters, ivf_seed, chunk)
+    lists_t = _two_stage_lists(index_v, text_feat, text_mask, C, W, rank, chunk, norm, nprobe)
+    lists_v = _two_stage_lists(index_t, video_feat, video_mask, C, W, rank, chunk, norm, nprobe)
     cand_t, cand_v = lists_t[0].cpu().numpy(), lists_v[0].cpu().numpy()
 
     def metrics(score_t, score_v):
@@ -1527,4 +1581,9 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
             m["gated"] = float(int(gate.sum())) * 100 / n
             m["label"] = label
             raw["normalised"] = m
+    if nprobe is not None:
+        for m, lists, n_gallery in ((t2v, lists_t, n_cols), (v2t, lists_v, n_rows)):
+            stats = lists[-1].cpu().numpy().astype(np.float64)                  # pool length, kept, the exact prefilter's count
+            share = np.where(stats[:, 2] > 0, stats[:, 1] / np.maximum(stats[:, 2], 1), 1.0)
+            m.update(n_lists=n_lists, nprobe=nprobe, pool_mean=float(stats[:, 0].mean()) / n_gallery, ivf_overlap=float(share.mean()))
     return t2v, v2t

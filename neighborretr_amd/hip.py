@@ -279,6 +279,9 @@ _SIGNATURES = {
     "nr_hubnorm_combine": ([_I, _P, _I, _P, _P, _P], _I),
     "nr_hubnorm_apply": ([_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P], _I),
     "nr_cand_norm_rerank": ([_P, _P, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _P], _I),
+    "nr_ivf_list_sums": ([_P, _P, _P, _I, _I, _I, _P, _P], _I),
+    "nr_ivf_scan": ([_P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P], _I),
+    "nr_ivf_select": ([_P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
     "nr_sinknorm_row": ([_P, _I, _I, _F, _P, _P, _P, _P], _I),
     "nr_sinknorm_col_stats": ([_P, _I, _I, _F, _P, _P, _P, _P], _I),
     "nr_sinknorm_finish_cols": ([_I, _P, _I, _P, _P, _P], _I),
@@ -310,6 +313,7 @@ _SIGNATURES = {
     "nr_ema_swap": ([_P, _I, _I, _P], _I),
 }
 TOPK_MAX = 128                               # largest k of the top-k entry points
+IVF_MAX_PROBE, IVF_CACHE_KEYS = 128, 16384   # nr_ivf_scan: the most probes; nr_ivf_select: the longest line whose keys stay in LDS
 HUBNORM_IS, HUBNORM_DSL = 0, 1               # nr_hubnorm_apply modes
 LOCALSCALE_CSLS, LOCALSCALE_NICDM, LOCALSCALE_LS = 0, 1, 2      # nr_localscale_apply modes
 MP_LINE_MAX = 1 << 23                        # a mutual-proximity reference line must be shorter: 2 c < 2^24 keeps the counts exact

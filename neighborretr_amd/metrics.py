@@ -149,6 +149,9 @@ class RetrievalMetrics:
                     continue
                 label = m.get("label", tag)
                 lines.append(RetrievalMetrics.format_two_stage(m, prefix=f"{side} {label}{sep}"))
+                if "ivf_overlap" in m:           # the inverted-file prefilter: one more line per direction
+                    lines.append(f"{side} {label}{sep}pool {m['pool_mean'] * 100:.1f}% of the gallery - kept "
+                                 f"{m['ivf_overlap'] * 100:.1f}% of the exact prefilter's candidates")
                 if "hubness" in m:
                     lines.append(RetrievalMetrics.format_hubness(m["hubness"], prefix=f"{side} {label} "))
         return lines

@@ -1135,6 +1135,99 @@ def cand_norm_rerank(fine, cand, n_gallery, k, norm=None, active=None, beta=20.0
     return idx, val, corr, gate
 
 
+def _ivf_index(list_items, list_offsets):
+    """(n_items, n_lists) of an inverted-file index given as list_items [n_items] / list_offsets [n_lists + 1] int32."""
+    for x, what in ((list_items, "list_items"), (list_offsets, "list_offsets")):
+        if x.dim() != 1 or x.dtype != torch.int32:
+            raise ValueError(f"{what} must be a torch.int32 vector, got {x.dtype} {tuple(x.shape)}")
+    n_items, n_lists = int(list_items.shape[0]), int(list_offsets.shape[0]) - 1
+    if not 1 <= n_lists <= n_items:
+        raise ValueError(f"1 <= n_lists <= n_items expected, got {n_lists} lists of {n_items} items")
+    return n_items, n_lists
+
+
+def ivf_list_sums(x, list_items, list_offsets):
+    """sums [L, d] fp32: the rows x[list_items[list_offsets[l] : list_offsets[l + 1]]] of every list added in list order, one
+    sequential fp32 addition per component (nr_ivf_list_sums)."""
+    n_items, n_lists = _ivf_index(list_items, list_offsets)
+    if x.dim() != 2 or x.shape[0] != n_items:
+        raise ValueError(f"x must be [n_items, d] = [{n_items}, d], got {tuple(x.shape)}")
+    x = _f32(x).contiguous()
+    d = int(x.shape[1])
+    sums = torch.empty((n_lists, d), dtype=torch.float32, device=x.device)
+    hip.call("nr_ivf_list_sums", hip.ptr(x), hip.ptr(list_items.contiguous(), torch.int32), hip.ptr(list_offsets.contiguous(), torch.int32),
+             n_items, n_lists, d, hip.ptr(sums), hip.stream_ptr())
+    return sums
+
+
+def ivf_scan(q, rows, list_items, list_offsets, probes, stride, max_list_size, out=None):
+    """(pool_score [n, stride] fp32, pool_item [n, stride] int32, pool_len [n] int32): the pools of the queries q [n, d] over the
+    lists probes [n, P] int32 names in probe order (nr_ivf_scan).  rows [n_items, d] = the indexed vectors list
+    by list.  Every score has the bits gemm_nt_f32 gives its (query, item) pair; slots from pool_len on are NOT written.  stride
+    >= the sum of the P largest list sizes and max_list_size >= the largest come from the host's copy of the sizes: nothing here
+    reads the device.  out: (pool_score, pool_item, pool_len) buffers to write into (at least n rows of `stride`).  The grouping
+    of the (query, probe) pairs by list -- a stable sort and two prefix sums -- is device plumbing in torch."""
+    n_items, n_lists = _ivf_index(list_items, list_offsets)
+    if q.dim() != 2 or rows.dim() != 2 or rows.shape[0] != n_items or q.shape[1] != rows.shape[1]:
+        raise ValueError(f"q must be [n, d] and rows [{n_items}, d], got {tuple(q.shape)} and {tuple(rows.shape)}")
+    n, d = int(q.shape[0]), int(q.shape[1])
+    if probes.dim() != 2 or probes.shape[0] != n or probes.dtype != torch.int32:
+        raise ValueError(f"probes must be a torch.int32 [n, P] = [{n}, P] tensor, got {probes.dtype} {tuple(probes.shape)}")
+    P, stride, max_list_size = int(probes.shape[1]), int(stride), int(max_list_size)
+    if not 1 <= P <= min(n_lists, hip.IVF_MAX_PROBE):
+        raise ValueError(f"the number of probes must lie in [1, min(n_lists, {hip.IVF_MAX_PROBE}) = {min(n_lists, hip.IVF_MAX_PROBE)}], got {P}")
+    if d % 16 != 0:
+        raise ValueError(f"d must be a multiple of 16, got {d}")
+    if stride < 1 or not 0 <= max_list_size <= n_items:
+        raise ValueError(f"stride >= 1 and 0 <= max_list_size <= n_items expected, got {stride} and {max_list_size}")
+    dev = q.device
+    if out is None:
+        out = (torch.empty((n, stride), dtype=torch.float32, device=dev), torch.empty((n, stride), dtype=torch.int32, device=dev),
+               torch.empty((n,), dtype=torch.int32, device=dev))
+    score, item, length = out
+    if tuple(score.shape) != (n, stride) or tuple(item.shape) != (n, stride) or tuple(length.shape) != (n,):
+        raise ValueError(f"out must be ([n, stride], [n, stride], [n]) = ([{n}, {stride}], [{n}, {stride}], [{n}])")
+    if n == 0:
+        return score, item, length
+    q, rows, probes = _f32(q).contiguous(), _f32(rows).contiguous(), probes.contiguous()
+    bucket = torch.where((probes >= 0) & (probes < n_lists), probes, torch.full_like(probes, n_lists)).reshape(-1)
+    ordered, order = torch.sort(bucket, stable=True)
+    order = order.to(torch.int32)
+    group = torch.searchsorted(ordered, torch.arange(n_lists + 2, dtype=torch.int32, device=dev), out_int32=True)
+    tiles = torch.zeros((n_lists + 2,), dtype=torch.int32, device=dev)
+    tiles[1:] = torch.cumsum((group[1:] - group[:-1] + 15) // 16, 0)
+    hip.call("nr_ivf_scan", hip.ptr(q), n, hip.ptr(rows), hip.ptr(list_items.contiguous(), torch.int32),
+             hip.ptr(list_offsets.contiguous(), torch.int32), n_items, n_lists, d, hip.ptr(probes, torch.int32), P,
+             hip.ptr(order, torch.int32), hip.ptr(group, torch.int32), hip.ptr(tiles, torch.int32), max_list_size,
+             hip.ptr(score, torch.float32), hip.ptr(item, torch.int32), hip.ptr(length, torch.int32), stride, hip.stream_ptr())
+    return score, item, length
+
+
+def ivf_select(pool_score, pool_item, pool_len, C, want_score=False):
+    """cand [n, C] int32 (and, with want_score, their scores [n, C] fp32): the top C of the first pool_len[i] entries of every pool
+    line by (score descending, gallery index ascending; NaN never taken), in ASCENDING GALLERY INDEX, padded with -1 / -inf
+    (nr_ivf_select).  The items of a line must be distinct."""
+    if pool_score.dim() != 2 or pool_score.shape != pool_item.shape or pool_item.dtype != torch.int32:
+        raise ValueError(f"pool_score (fp32) and pool_item (int32) must both be [n, stride], got {tuple(pool_score.shape)} and "
+                         f"{pool_item.dtype} {tuple(pool_item.shape)}")
+    n, stride = (int(s) for s in pool_score.shape)
+    if pool_len.dtype != torch.int32 or tuple(pool_len.shape) != (n,):
+        raise ValueError(f"pool_len must be a torch.int32 vector of {n} entries, got {pool_len.dtype} {tuple(pool_len.shape)}")
+    C = int(C)
+    if not 1 <= C <= hip.TOPK_MAX:
+        raise ValueError(f"C must lie in [1, {hip.TOPK_MAX}], got {C}")
+    if stride < 1:
+        raise ValueError("the pool lines are empty (stride < 1)")
+    dev = pool_score.device
+    cand = torch.empty((n, C), dtype=torch.int32, device=dev)
+    score = torch.empty((n, C), dtype=torch.float32, device=dev) if want_score else None
+    if n:
+        hip.call("nr_ivf_select", hip.ptr(_f32(pool_score).contiguous()), hip.ptr(pool_item.contiguous(), torch.int32),
+                 hip.ptr(pool_len.contiguous(), torch.int32), n, stride, C, hip.ptr(cand), hip.ptr(score, allow_none=True),
+                 hip.stream_ptr())
+    return (cand, score) if want_score else cand
+
+
 def _sink_vec(x, size, what):
     if x.dtype != torch.float32 or x.shape != (size,) or not x.is_contiguous():
         raise ValueError(f"{what} must be a contiguous fp32 vector of {size} entries, got {x.dtype} {tuple(x.shape)}")

@@ -18,7 +18,14 @@ on the chunk size or on which other queries share its batch.
 Query-bank normalisation: `attach_querybank` computes, once per gallery, every item's normaliser and the activation
 set from a bank of training queries; `candidates` / `search` with norm="is" | "qbnorm" then correct every query's candidate scores and
 re-rank them in one launch (nr_cand_norm_rerank).  Without the argument nothing changes.
+
+Inverted-file prefilter (DESIGN.md 6.16): `build_ivf` deals the gallery's pooled vectors to L k-means lists, once per gallery;
+`candidates` / `search` with nprobe=P then score a query against the members of the P lists whose centroids it is closest to
+(nr_ivf_scan) and take the candidates from that pool (nr_ivf_select) -- exactly the lists the exact prefilter selects from a
+coarse matrix whose entries outside the pool are -inf, and with P = L exactly today's.  Without the argument nothing changes.
 """
+from types import SimpleNamespace
+
 import torch
 
 from . import head, hip, ops
@@ -40,6 +47,27 @@ def check_chunk(chunk):
     if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
         raise ValueError(f"chunk must be an integer >= 1, got {chunk!r}")
     return int(chunk)
+
+
+def check_ivf_build(n_lists, iters, seed, n_items):
+    """(n_lists, iters, seed) of build_ivf as ints: 1 <= n_lists <= n_items, iters >= 0, any integer seed."""
+    def integer(x):
+        return isinstance(x, int) and not isinstance(x, bool)
+    if not integer(n_lists) or not 1 <= n_lists <= n_items:
+        raise ValueError(f"n_lists must be an integer in [1, {n_items}] (the gallery's size), got {n_lists!r}")
+    if not integer(iters) or iters < 0:
+        raise ValueError(f"iters must be an integer >= 0, got {iters!r}")
+    if not integer(seed):
+        raise ValueError(f"seed must be an integer, got {seed!r}")
+    return int(n_lists), int(iters), int(seed)
+
+
+def check_nprobe(nprobe, n_lists):
+    """nprobe as an int in [1, min(n_lists, 128)]."""
+    hi = min(int(n_lists), hip.IVF_MAX_PROBE)
+    if isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 1 <= nprobe <= hi:
+        raise ValueError(f"nprobe must be an integer in [1, min(n_lists, {hip.IVF_MAX_PROBE}) = {hi}], got {nprobe!r}")
+    return int(nprobe)
 
 
 def check_norm(norm):
@@ -104,6 +132,7 @@ class GalleryIndex:
             self.items = _Side(model, feat, mask, side)
         self.norm = self.active = self.norm_beta = self.qb_k = None
         self.n_bank = 0
+        self.ivf = None
 
     def __len__(self):
         return self.items.n
@@ -145,6 +174,93 @@ class GalleryIndex:
         self.norm_beta, self.qb_k, self.n_bank = beta, qb_k, M
         return self
 
+    def build_ivf(self, n_lists, iters=10, seed=0, chunk=256):
+        """The inverted-file index of the gallery's pooled vectors, built once -> self.  n_lists = L k-means
+        lists (1 <= L <= N), iters >= 0 rounds of assign + update, then one final assignment.  The initial centroids are
+        x[perm[:L]], perm = torch.randperm(N) of a CPU generator seeded with `seed`: every rank builds the same index.
+          assign   item g goes to argmax_l c_l . x_g (ops.gemm_nt_f32 in row chunks, ops.slab_topk_rows(., 1): ties to the lower
+                   list, a zero vector to list 0)
+          update   c_l = normalize(sum of the members of list l in ascending gallery index) (ops.ivf_list_sums, the norm of
+                   ops.prepare_tokens as pooled_vectors takes it); an empty list, or one whose sum is the zero vector, keeps its
+                   previous centroid
+        Stores self.ivf: centroids [L, d], list_offsets [L + 1] int32, list_items [N] int32 (ascending inside a list, lists in
+        order), pooled_sorted [N, d] = pooled[list_items], and on the host sizes (a list) and sizes_desc.  Every item lies in the
+        list the assignment names for the STORED centroids.  The build reads the list sizes back (one synchronisation); a search
+        never does.  Every argument is checked before any work; attach_querybank's statistics are not touched."""
+        N, d = self.items.n, self.items.d
+        L, iters, seed = check_ivf_build(n_lists, iters, seed, N)
+        chunk = check_chunk(chunk)
+        if d % 16 != 0:
+            raise ValueError(f"the pooled vectors are {d} wide: the inverted file needs a multiple of 16")
+        x = self.items.pooled
+        dev = x.device
+        perm = torch.randperm(N, generator=torch.Generator().manual_seed(seed))
+        lists = torch.arange(L + 1, dtype=torch.int32, device=dev)
+
+        def assign(cent):
+            a = torch.empty((N,), dtype=torch.int32, device=dev)
+            for lo in range(0, N, chunk):
+                a[lo:lo + chunk] = ops.slab_topk_rows(ops.gemm_nt_f32(x[lo:lo + chunk], cent), 1)[0][:, 0]
+            ordered, items = torch.sort(a.clamp_(min=0), stable=True)      # a row of NaN scores names no list: list 0
+            return items.to(torch.int32), torch.searchsorted(ordered, lists, out_int32=True)
+
+        with torch.no_grad():
+            cent = x[perm[:L].to(dev)].contiguous()
+            for _ in range(iters):
+                items, offsets = assign(cent)
+                sums = ops.ivf_list_sums(x, items, offsets)
+                new = sums / ops.prepare_tokens(sums, None, want_lo=False).norm[:, None]
+                keep = (offsets[1:] == offsets[:-1]) | (sums == 0).all(dim=1)
+                cent = torch.where(keep[:, None], cent, new)
+            items, offsets = assign(cent)
+            sizes = (offsets[1:] - offsets[:-1]).tolist()
+            self.ivf = SimpleNamespace(n_lists=L, iters=iters, seed=seed, centroids=cent, list_offsets=offsets, list_items=items,
+                                       pooled_sorted=x[items.long()].contiguous(), sizes=sizes, sizes_desc=sorted(sizes, reverse=True))
+        return self
+
+    def _check_nprobe(self, nprobe, n_candidates=None):
+        if nprobe is None:
+            return None
+        if self.ivf is None:
+            raise ValueError(f"nprobe={nprobe!r} needs the gallery's inverted file: call build_ivf(...) first")
+        nprobe = check_nprobe(nprobe, self.ivf.n_lists)
+        if n_candidates == 0:
+            raise ValueError("nprobe restricts the prefilter: the exhaustive path (n_candidates = 0) has none")
+        return nprobe
+
+    def ivf_candidates(self, pooled_q, n_candidates, nprobe, chunk=256):
+        """(cand [n, C] int32, pool_len [n] int32) of pooled query vectors [n, d]: every query's pool = the members of the nprobe
+        lists whose centroids score highest against it (the order of 6.1: score descending, ties by lower list), its candidates
+        = the top C of the pool by (coarse score descending, gallery index ascending) in ascending gallery index, -1 where the
+        pool holds fewer.  Per pass of queries: ops.gemm_nt_f32 + ops.slab_topk_rows name the probes, ops.ivf_scan scores the
+        pool, ops.ivf_select reduces it.  No host read: the buffers are sized by the P largest lists, known since the build."""
+        C, chunk = check_candidates(n_candidates), check_chunk(chunk)
+        P = self._check_nprobe(nprobe)
+        if P is None:
+            raise ValueError("ivf_candidates needs nprobe")
+        ivf = self.ivf
+        n, dev = pooled_q.shape[0], pooled_q.device
+        cand = torch.empty((n, C), dtype=torch.int32, device=dev)
+        pool_len = torch.empty((n,), dtype=torch.int32, device=dev)
+        if n == 0:
+            return cand, pool_len
+        stride = max(sum(ivf.sizes_desc[:P]), 1)
+        # a pass takes as many queries as fit the memory of the exact prefilter's [chunk, N] block: its two pool buffers are
+        # [rows, stride] of 4 bytes each, so rows = chunk N / (2 stride) >= chunk -- fewer, larger launches (the lists do not
+        # depend on the split)
+        chunk = max(chunk, chunk * len(self) // (2 * stride))
+        rows = min(chunk, n)
+        score = torch.empty((rows, stride), dtype=torch.float32, device=dev)
+        item = torch.empty((rows, stride), dtype=torch.int32, device=dev)
+        for lo in range(0, n, chunk):
+            pq = pooled_q[lo:lo + chunk].contiguous()
+            m = pq.shape[0]
+            probes, _ = ops.slab_topk_rows(ops.gemm_nt_f32(pq, ivf.centroids), P)
+            pool = ops.ivf_scan(pq, ivf.pooled_sorted, ivf.list_items, ivf.list_offsets, probes, stride, ivf.sizes_desc[0],
+                                out=(score[:m], item[:m], pool_len[lo:lo + m]))
+            cand[lo:lo + m] = ops.ivf_select(*pool, C)
+        return cand, pool_len
+
     def _check_norm(self, norm, n_candidates=None):
         if check_norm(norm) is None:
             return None
@@ -166,58 +282,87 @@ class GalleryIndex:
         fixed summation order per element)."""
         return ops.gemm_nt_f32(pooled_q, self.items.pooled)
 
-    def candidates(self, q_feat, q_mask, n_candidates, chunk=256, norm=None):
+    def candidates(self, q_feat, q_mask, n_candidates, chunk=256, norm=None, nprobe=None, ivf_stats=False):
         """(cand [n, C] int32, fine [n, C] fp32): every query's C candidates in ascending gallery index (padded with -1 when
         the gallery has fewer than C items) and their fine scores (-inf at the padding).  norm "is" | "qbnorm" (after
         attach_querybank): (cand, fine, corr [n, C] fp32, gate [n] int32), the corrected scores and which queries were normalised
-        ("is": all of them; "qbnorm": those whose top-1 candidate is in the activation set)."""
+        ("is": all of them; "qbnorm": those whose top-1 candidate is in the activation set).
+
+        nprobe = P (after build_ivf; 1 <= P <= min(L, 128)): the candidates come from the query's P probed lists only (DESIGN.md
+        6.16); None is the exact prefilter.  ivf_stats (with nprobe): one more result, stats [n, 3] int32 = (the pool's length,
+        how many of the exact prefilter's candidates the list kept, how many candidates the exact prefilter has): the exact
+        lists are computed for these counts only."""
         norm = self._check_norm(norm)
+        nprobe = self._check_nprobe(nprobe)
+        if ivf_stats and nprobe is None:
+            raise ValueError("ivf_stats describes the inverted-file prefilter: it needs nprobe")
         if norm is not None:
-            return self._normalised(q_feat, q_mask, 1, n_candidates, chunk, norm)[2:]
+            return self._normalised(q_feat, q_mask, 1, n_candidates, chunk, norm, nprobe, ivf_stats)[2:]
         C, chunk = check_candidates(n_candidates), check_chunk(chunk)
         self._check_queries(q_feat, q_mask)
         dev = q_feat.device
         n = q_feat.shape[0]
-        cand = torch.empty((n, C), dtype=torch.int32, device=dev)
         if n == 0:
-            return cand, torch.empty((n, C), dtype=torch.float32, device=dev)
+            empty = (torch.empty((n, C), dtype=torch.int32, device=dev), torch.empty((n, C), dtype=torch.float32, device=dev))
+            return empty + ((torch.empty((0, 3), dtype=torch.int32, device=dev),) if ivf_stats else ())
         with torch.no_grad():
             q = _Side(self.model, q_feat, q_mask, self.query_side)
-            big = torch.iinfo(torch.int32).max
-            for lo in range(0, n, chunk):
-                ci, _ = ops.slab_topk_rows(self.coarse_scores(q.pooled[lo:lo + chunk].contiguous()), C)
-                ci = torch.where(ci < 0, torch.full_like(ci, big), ci).sort(dim=1).values       # ascending index, padding last
-                cand[lo:lo + chunk] = torch.where(ci == big, torch.full_like(ci, -1), ci)
+            cand, pool_len, exact = self._prefilter(q.pooled, C, chunk, nprobe, ivf_stats)
             g = self.items
             fine = ops.local_level_cand(q.prep, g.prep, q.w, g.w, n, q.n_tok, g.n, g.n_tok, cand, hip.PREC_BF16X3)
+            if ivf_stats:
+                kept = torch.empty_like(pool_len)
+                for lo in range(0, n, chunk):                           # [chunk, C, C] comparisons at a time
+                    e = exact[lo:lo + chunk]
+                    kept[lo:lo + chunk] = ((e[:, :, None] == cand[lo:lo + chunk, None, :]) & (e[:, :, None] >= 0)).any(dim=2).sum(dim=1)
+                return cand, fine, torch.stack([pool_len, kept, (exact >= 0).sum(dim=1).to(torch.int32)], dim=1)
         return cand, fine
 
-    def _normalised(self, q_feat, q_mask, k, n_candidates, chunk, norm):
-        """(idx, val, cand, fine, corr, gate): the candidates and their fine scores, then nr_cand_norm_rerank in one launch."""
-        cand, fine = self.candidates(q_feat, q_mask, n_candidates, chunk)
+    def _prefilter(self, pooled_q, C, chunk, nprobe=None, want_exact=False):
+        """The coarse stage for pooled query vectors [n, d], n >= 1 -> (cand [n, C] int32, pool_len [n] int32 or None, exact).
+        nprobe None: the exact prefilter (cand is exact).  nprobe = P: the inverted file's candidates and pool lengths; exact =
+        the exact prefilter's lists when want_exact, else None."""
+        n = pooled_q.shape[0]
+        exact = None
+        if nprobe is None or want_exact:
+            exact = torch.empty((n, C), dtype=torch.int32, device=pooled_q.device)
+            big = torch.iinfo(torch.int32).max
+            for lo in range(0, n, chunk):
+                ci, _ = ops.slab_topk_rows(self.coarse_scores(pooled_q[lo:lo + chunk].contiguous()), C)
+                ci = torch.where(ci < 0, torch.full_like(ci, big), ci).sort(dim=1).values       # ascending index, padding last
+                exact[lo:lo + chunk] = torch.where(ci == big, torch.full_like(ci, -1), ci)
+        if nprobe is None:
+            return exact, None, exact
+        return self.ivf_candidates(pooled_q, C, nprobe, chunk) + (exact,)
+
+    def _normalised(self, q_feat, q_mask, k, n_candidates, chunk, norm, nprobe=None, ivf_stats=False):
+        """(idx, val, cand, fine, corr, gate[, stats]): the candidates and their fine scores, then nr_cand_norm_rerank in one launch."""
+        cand, fine, *stats = self.candidates(q_feat, q_mask, n_candidates, chunk, nprobe=nprobe, ivf_stats=ivf_stats)
         idx, val, corr, gate = ops.cand_norm_rerank(fine, cand, len(self), k, norm=self.norm,
                                                     active=self.active if norm == "qbnorm" else None, beta=self.norm_beta)
-        return idx, val, cand, fine, corr, gate
+        return (idx, val, cand, fine, corr, gate) + tuple(stats)
 
-    def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False, norm=None):
+    def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False, norm=None, nprobe=None):
         """-> (idx [n, k] int32, val [n, k] fp32): the top k of every query, fine score descending, ties by lower gallery index,
         padded with -1 / -inf when the gallery has fewer than k items.  1 <= k <= n_candidates <= 128; n_candidates = 0 scores
         every pair (the exhaustive path: the evaluator's slab similarity and ops.slab_topk_rows).  return_candidates: also the
         candidate lists and their fine scores, (idx, val, cand, fine).  norm "is" | "qbnorm" (after attach_querybank): the
-        order and val are those of the corrected scores; with return_candidates (idx, val, cand, fine, gate)."""
+        order and val are those of the corrected scores; with return_candidates (idx, val, cand, fine, gate).  nprobe = P (after
+        build_ivf): the candidates come from the P probed lists of the inverted file; not with n_candidates = 0."""
         C, chunk = check_candidates(n_candidates, allow_zero=True), check_chunk(chunk)
         if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > (C or hip.TOPK_MAX):
             raise ValueError(f"k must be an integer in [1, {C or hip.TOPK_MAX}] (1 <= k <= n_candidates), got {k!r}")
         norm = self._check_norm(norm, C)
+        nprobe = self._check_nprobe(nprobe, C)
         self._check_queries(q_feat, q_mask)
         if norm is not None:
-            idx, val, cand, fine, _, gate = self._normalised(q_feat, q_mask, k, C, chunk, norm)
+            idx, val, cand, fine, _, gate = self._normalised(q_feat, q_mask, k, C, chunk, norm, nprobe)
             return (idx, val, cand, fine, gate) if return_candidates else (idx, val)
         if C == 0:
             if return_candidates:
                 raise ValueError("the exhaustive path (n_candidates = 0) has no candidate lists")
             return self._exhaustive(q_feat, q_mask, k, chunk)
-        cand, fine = self.candidates(q_feat, q_mask, C, chunk)
+        cand, fine = self.candidates(q_feat, q_mask, C, chunk, nprobe=nprobe)
         idx, val = rerank(cand, fine, k)
         return (idx, val, cand, fine) if return_candidates else (idx, val)
 
