@@ -1013,6 +1013,30 @@ int nr_localscale_stats(const int32_t* idx, const float* val, int n, int k, floa
 int nr_localscale_apply(const float* S, int n, int L, int mode, const float* row_stat, const float* col_stat, float* T,
                         void* stream);
 
+/* Local scaling and re-ranking of CANDIDATE LISTS: the search-time stage of CSLS / NICDM / LS on two-stage retrieval (DESIGN.md
+ * "Local scaling of two-stage retrieval"; added at ABI version 5 as nr_cand_norm_rerank was).  The reference has no such path.
+ * One launch; fine / cand [n, C] as nr_cand_norm_rerank takes them (the lists in ascending gallery index); g_stat [n_gallery] f32:
+ * the gallery items' neighbourhood statistic against a query bank, computed once (the means for csls / nicdm, the k-th values for
+ * ls: nr_localscale_stats).  Per query i:
+ *   present   slot p is present iff 0 <= cand[i,p] < n_gallery; an absent slot never forms an address into g_stat, its out_corr
+ *             is -inf and it is never selected; selectable = present and not NaN; every order is value descending, ties by lower
+ *             position, -0.0 == +0.0 (nr_slab_topk_rows' order);
+ *   q stat    the top-ls_k list of the selectable RAW scores, c <= ls_k entries: q_mean = fl(fl(sum of the c values, added one
+ *             by one in list order starting from the first) / fl(c)), q_kth = the c-th value; c = 0: both NaN -- the statistics of
+ *             nr_localscale_stats on that list: the query's neighbourhood in the gallery, taken among its candidates;
+ *   corr      T(fine[i,p], row, col) of nr_localscale_apply's formulas (every operation rounded once, no fused multiply-add,
+ *             EPS = 2^-20, a NaN statistic gives NaN) with the query's statistic (q_mean; q_kth for ls) and g_stat[cand[i,p]]:
+ *             query_is_row = 1: (row, col) = (query, item) -- text queries on a video gallery; 0: (item, query);
+ *   output    the top k of corr over the present non-NaN slots: out_idx [n,k] = cand[...], out_val [n,k] = corr[...], missing
+ *             entries -1 / -inf.
+ * out_corr [n,C] and out_qstat [n,2] = (q_mean, q_kth) may be null.  Integer comparisons order both lists, the sum has one fixed
+ * order, no atomics: bitwise reproducible, and a query's output depends on its own line only.
+ * NR_EINVAL before any launch: fine, cand, g_stat, out_idx or out_val null; n, n_gallery or k <= 0; C outside [1, 128]; k > C;
+ * ls_k outside [1, C]; an unknown mode; query_is_row not 0 or 1.                                                          */
+int nr_cand_localscale_rerank(const float* fine, const int32_t* cand, int n, int C, int n_gallery, const float* g_stat, int mode,
+                              int ls_k, int query_is_row, int k, int32_t* out_idx, float* out_val, float* out_corr,
+                              float* out_qstat, void* stream);
+
 /* Mutual proximity (emp, gauss; DESIGN.md "Mutual proximity"; Schnitzer et al., JMLR 2012; the reference has no code for it): every
  * score s = S[i,j] of S [n, L] becomes the probability that it beats the scores of its row's reference line and of its column's
  * reference line, in the independent form MP_I = P_row P_col.  A line X has c(X) = #{x in X : x is not NaN} entries.

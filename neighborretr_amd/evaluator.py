@@ -1434,6 +1434,37 @@ def rerank_norm_from_args(args, model):
     return kw
 
 
+def two_stage_local_scaling_label(n_candidates, mode, k):
+    """The tag of the log lines of the locally scaled two-stage metrics: "[two-stage C=64 QB-CSLS k=10]"."""
+    return f"[two-stage C={int(n_candidates)} QB-{LOCAL_SCALING_LABELS[mode]} k={int(k)}]"
+
+
+def rerank_local_scaling_from_args(args, model):
+    """args.rerank_local_scaling / rerank_local_scaling_k -> None or the keyword arguments of two_stage_evaluation (local_scaling,
+    local_scaling_k), checked before any work: the mode, K, that it does not meet rerank_norm, that rerank_top asks for at least K
+    candidates and that the model's memory bank is filled.  Independent of the exhaustive flags."""
+    from .search import check_local_scaling, check_local_scaling_k
+    mode = getattr(args, "rerank_local_scaling", None) or "none"
+    if mode == "none":
+        return None
+    try:
+        check_local_scaling(mode)
+    except ValueError:
+        raise ValueError(f"rerank_local_scaling must be 'csls', 'nicdm' or 'ls', got {mode!r}") from None
+    k = getattr(args, "rerank_local_scaling_k", 10)
+    try:
+        k = check_local_scaling_k(k)
+    except ValueError:
+        raise ValueError(f"rerank_local_scaling_k must be an integer in [1, 128], got {k!r}") from None
+    if (getattr(args, "rerank_norm", None) or "none") != "none":
+        raise ValueError("rerank_local_scaling and rerank_norm both correct the candidate scores: choose one")
+    if rerank_top_from_args(args) < k:
+        raise ValueError(f"rerank_local_scaling takes a query's neighbourhood among its candidates: it needs rerank_top >= "
+                         f"rerank_local_scaling_k = {k}")
+    _querybank(model, None, model.mb_feat_t.device)             # checked where it lies: nothing is copied
+    return dict(local_scaling=mode, local_scaling_k=k)
+
+
 def two_stage_ivf_label(n_candidates, n_lists, nprobe):
     """The tag of the log lines of two-stage retrieval behind the inverted-file prefilter: "[two-stage C=64 IVF L=128 P=8]"."""
     return f"[two-stage C={int(n_candidates)} IVF L={int(n_lists)} P={int(nprobe)}]"
@@ -1463,16 +1494,19 @@ def rerank_ivf_from_args(args):
     return dict(n_lists=lists, nprobe=probe, ivf_iters=iters, ivf_seed=seed)
 
 
-def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None, nprobe=None):
+def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None, nprobe=None, local_scaling=None):
     """(cand [n, C] int32, fine [n, C] fp32) on the device, the same on every rank: this rank's queries searched, one gather.
-    norm: (cand, fine, corr [n, C] fp32, gate [n] int32), all four in that one gather.  nprobe: the candidates of the index's
-    inverted file, and as the last element stats [n, 3] int32 (GalleryIndex.candidates, ivf_stats), in that same gather."""
+    norm: (cand, fine, corr [n, C] fp32, gate [n] int32), all four in that one gather.  local_scaling (never with norm): (cand,
+    fine, corr [n, C] fp32, qstat [n, 2] fp32), all four in that one gather.  nprobe: the candidates of the index's inverted file,
+    and as the last element stats [n, 3] int32 (GalleryIndex.candidates, ivf_stats), in that same gather."""
     n = q_feat.shape[0]
     r0, r1 = slab_bounds(n, W, rank)
-    kw = {**({} if norm is None else dict(norm=norm)), **({} if nprobe is None else dict(nprobe=nprobe, ivf_stats=True))}
+    kw = {**({} if norm is None else dict(norm=norm)), **({} if nprobe is None else dict(nprobe=nprobe, ivf_stats=True)),
+          **({} if local_scaling is None else dict(local_scaling=local_scaling))}
     out = index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk, **kw)
     if W > 1:
         blocks = [out[0].T, out[1].view(torch.int32).T] + ([out[2].view(torch.int32).T, out[3][None]] if norm is not None else [])
+        blocks += [out[2].view(torch.int32).T, out[3].view(torch.int32).T] if local_scaling is not None else []
         blocks += [out[-1].T] if nprobe is not None else []
         mine = torch.zeros((sum(b.shape[0] for b in blocks), -(-n // W)), dtype=torch.int32, device=out[0].device)
         mine[:, :r1 - r0] = torch.cat(blocks, 0)
@@ -1480,6 +1514,8 @@ def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None, nprobe
         out = (rows[:C].T.contiguous(), rows[C:2 * C].T.contiguous().view(torch.float32))
         if norm is not None:
             out += (rows[2 * C:3 * C].T.contiguous().view(torch.float32), rows[3 * C].contiguous())
+        if local_scaling is not None:
+            out += (rows[2 * C:3 * C].T.contiguous().view(torch.float32), rows[3 * C:3 * C + 2].T.contiguous().view(torch.float32))
         if nprobe is not None:
             out += (rows[-3:].T.contiguous(),)
     return out
@@ -1494,7 +1530,8 @@ def _two_stage_hubness(cand, score, K, n_gallery, gt_begin, gt_end):
 
 
 def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, n_candidates, cut_off_points=None, chunk=256,
-                         norm=None, beta=20.0, qb_k=1, querybank=None, hubness_k=0, n_lists=0, nprobe=0, ivf_iters=10, ivf_seed=0):
+                         norm=None, beta=20.0, qb_k=1, querybank=None, hubness_k=0, n_lists=0, nprobe=0, ivf_iters=10, ivf_seed=0,
+                         local_scaling=None, local_scaling_k=10):
     """-> (t2v, v2t) of two-stage retrieval with n_candidates (1..128) candidates per query, identical on every rank: R1 / R5 /
     R10 / R50 (None where K > C), cand_recall (percent of the queries whose ground truth is among their candidates),
     n_candidates, cols, and MR / MedianR / MeanR only when every query was found.  Every argument is checked before any work.
@@ -1509,10 +1546,24 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
     (build_ivf with ivf_iters rounds and ivf_seed, on every rank, deterministic) and every figure above is that of the candidates
     taken from each query's P probed lists.  Each direction gains n_lists, nprobe, pool_mean (the mean pool length / the gallery's
     size) and ivf_overlap (the mean share of the exact prefilter's candidates that the inverted file's lists kept; the exact
-    lists are computed for this figure only).  The per-query counts travel in the direction's one gather."""
-    from .search import GalleryIndex, check_candidates, check_chunk, check_ivf_build, check_norm, check_nprobe
+    lists are computed for this figure only).  The per-query counts travel in the direction's one gather.
+
+    local_scaling "csls" | "nicdm" | "ls" with local_scaling_k = K in [1, n_candidates] (not with norm): the
+    candidate scores are also locally scaled -- every gallery item's neighbourhood of K is taken in the querybank (as for norm),
+    a query's among its own candidates.  Each direction gains ["local_scaled"]: the raw dictionary's fields computed from the
+    corrected scores, `mode`, `k` and `label`, and with hubness_k its ["hubness"].  corr and the queries' statistics travel in the
+    direction's one gather."""
+    from .search import (GalleryIndex, check_candidates, check_chunk, check_ivf_build, check_local_scaling, check_local_scaling_k,
+                         check_norm, check_nprobe)
     C, chunk = check_candidates(n_candidates), check_chunk(chunk)
     norm = check_norm(norm)
+    local_scaling = check_local_scaling(local_scaling)
+    if local_scaling is not None:
+        if norm is not None:
+            raise ValueError(f"local_scaling={local_scaling!r} and norm={norm!r} both correct the candidate scores: choose one")
+        local_scaling_k = check_local_scaling_k(local_scaling_k)
+        if local_scaling_k > C:
+            raise ValueError(f"local_scaling_k must lie in [1, n_candidates = {C}], got {local_scaling_k}")
     hubness_k = _check_hubness_k(hubness_k)
     if hubness_k > C:
         raise ValueError(f"hubness_k must lie in [1, n_candidates = {C}], got {hubness_k}")
@@ -1542,19 +1593,22 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
         raise ValueError(f"nprobe={nprobe!r} needs an inverted file: give n_lists >= 1")
     else:
         nprobe = None
-    bank = _querybank(model, querybank, text_feat.device) if norm is not None else None
+    bank = _querybank(model, querybank, text_feat.device) if norm is not None or local_scaling is not None else None
     W = _world(args)
     rank = comm.get_rank() if W > 1 else 0
     text_mask, video_mask = text_mask.float(), video_mask.float()
     index_v, index_t = GalleryIndex(model, video_feat, video_mask, "video"), GalleryIndex(model, text_feat, text_mask, "text")
-    if bank is not None:
+    if norm is not None:
         index_v.attach_querybank(bank[0], bank[1], beta, qb_k, chunk)
         index_t.attach_querybank(bank[2], bank[3], beta, qb_k, chunk)
+    if local_scaling is not None:
+        index_v.attach_localscale(bank[0], bank[1], local_scaling_k, chunk)
+        index_t.attach_localscale(bank[2], bank[3], local_scaling_k, chunk)
     if nprobe is not None:
         index_v.build_ivf(n_lists, ivf_iters, ivf_seed, chunk)
         index_t.build_ivf(n_lists, ivf_iters, ivf_seed, chunk)
-    lists_t = _two_stage_lists(index_v, text_feat, text_mask, C, W, rank, chunk, norm, nprobe)
-    lists_v = _two_stage_lists(index_t, video_feat, video_mask, C, W, rank, chunk, norm, nprobe)
+    lists_t = _two_stage_lists(index_v, text_feat, text_mask, C, W, rank, chunk, norm, nprobe, local_scaling)
+    lists_v = _two_stage_lists(index_t, video_feat, video_mask, C, W, rank, chunk, norm, nprobe, local_scaling)
     cand_t, cand_v = lists_t[0].cpu().numpy(), lists_v[0].cpu().numpy()
 
     def metrics(score_t, score_v):
@@ -1581,6 +1635,14 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
             m["gated"] = float(int(gate.sum())) * 100 / n
             m["label"] = label
             raw["normalised"] = m
+    if local_scaling is not None:
+        nt, nv = metrics(lists_t[2], lists_v[2])
+        if hubness_k:
+            add_hubness(nt, nv, lists_t[2], lists_v[2])
+        label = two_stage_local_scaling_label(C, local_scaling, local_scaling_k)
+        for m, raw in ((nt, t2v), (nv, v2t)):
+            m.update(mode=local_scaling, k=local_scaling_k, label=label)
+            raw["local_scaled"] = m
     if nprobe is not None:
         for m, lists, n_gallery in ((t2v, lists_t, n_cols), (v2t, lists_v, n_rows)):
             stats = lists[-1].cpu().numpy().astype(np.float64)                  # pool length, kept, the exact prefilter's count

@@ -279,6 +279,7 @@ _SIGNATURES = {
     "nr_hubnorm_combine": ([_I, _P, _I, _P, _P, _P], _I),
     "nr_hubnorm_apply": ([_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P], _I),
     "nr_cand_norm_rerank": ([_P, _P, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _P], _I),
+    "nr_cand_localscale_rerank": ([_P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
     "nr_ivf_list_sums": ([_P, _P, _P, _I, _I, _I, _P, _P], _I),
     "nr_ivf_scan": ([_P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P], _I),
     "nr_ivf_select": ([_P, _P, _P, _I, _I, _I, _P, _P, _P], _I),

@@ -1343,6 +1343,43 @@ def localscale_apply(S, mode, row_stat, col_stat):
     return T
 
 
+def cand_localscale_rerank(fine, cand, n_gallery, k, g_stat, mode, ls_k, query_is_row, want_corr=True):
+    """(idx [n, k] int32, val [n, k] fp32, corr [n, C] fp32 or None, qstat [n, 2] fp32) of candidate lists cand [n, C] int32
+    (ascending gallery index, entries outside [0, n_gallery) absent) with fine scores fine [n, C], in one launch
+    (nr_cand_localscale_rerank).  mode "csls" | "nicdm" | "ls"; g_stat [n_gallery] fp32: the gallery items' neighbourhood statistic
+    (localscale_stats' mean for csls / nicdm, its kth for ls).  qstat = (mean, kth) of every query's top-ls_k list of its raw
+    scores; corr = the formula of `mode` on (fine, the query's statistic, g_stat[cand]), the query being the row where
+    query_is_row, else the column; absent slots -inf.  idx / val: the top k of corr, ties by lower position, -1 / -inf where the
+    line has fewer than k present non-NaN slots.  1 <= k <= C <= 128, 1 <= ls_k <= C."""
+    if fine.dim() != 2 or cand.dim() != 2 or fine.shape != cand.shape:
+        raise ValueError(f"fine and cand must both be [n, C], got {tuple(fine.shape)} and {tuple(cand.shape)}")
+    if mode not in LOCALSCALE_MODES:
+        raise ValueError(f"mode must be one of {sorted(LOCALSCALE_MODES)}, got {mode!r}")
+    n, C = cand.shape
+    n_gallery, k = int(n_gallery), _check_k(k)
+    if not 1 <= C <= hip.TOPK_MAX or k > C:
+        raise ValueError(f"1 <= k <= C <= {hip.TOPK_MAX} expected, got k = {k}, C = {C}")
+    if isinstance(ls_k, bool) or not isinstance(ls_k, int) or not 1 <= ls_k <= C:
+        raise ValueError(f"ls_k must be an integer in [1, C = {C}], got {ls_k!r}")
+    if not isinstance(query_is_row, (bool, int)) or query_is_row not in (0, 1):
+        raise ValueError(f"query_is_row must be True or False, got {query_is_row!r}")
+    if n_gallery < 1:
+        raise ValueError("the gallery is empty")
+    dev = fine.device
+    if not torch.is_tensor(g_stat) or g_stat.dtype != torch.float32 or g_stat.shape != (n_gallery,) or g_stat.device != dev:
+        raise ValueError(f"g_stat must be a {torch.float32} vector of {n_gallery} entries on {dev}")
+    fine, cand = _f32(fine).contiguous(), cand.contiguous()
+    idx = torch.empty((n, k), dtype=torch.int32, device=dev)
+    val = torch.empty((n, k), dtype=torch.float32, device=dev)
+    corr = torch.empty((n, C), dtype=torch.float32, device=dev) if want_corr else None
+    qstat = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    if n:
+        hip.call("nr_cand_localscale_rerank", hip.ptr(fine), hip.ptr(cand, torch.int32), n, C, n_gallery, hip.ptr(g_stat.contiguous()),
+                 LOCALSCALE_MODES[mode], ls_k, int(query_is_row), k, hip.ptr(idx), hip.ptr(val), hip.ptr(corr, allow_none=True),
+                 hip.ptr(qstat), hip.stream_ptr())
+    return idx, val, corr, qstat
+
+
 def _mp_matrix(x, dtype, shape, what):
     if x.dtype != dtype or x.dim() != 2 or not x.is_contiguous() or (shape is not None and tuple(x.shape) != tuple(shape)):
         want = "2-D" if shape is None else f"{tuple(shape)}"

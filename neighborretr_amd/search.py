@@ -23,6 +23,11 @@ Inverted-file prefilter: `build_ivf` deals the gallery's pooled
 `candidates` / `search` with nprobe=P then score a query against the members of the P lists whose centroids it is closest to
 (nr_ivf_scan) and take the candidates from that pool (nr_ivf_select) -- exactly the lists the exact prefilter selects from a
 coarse matrix whose entries outside the pool are -inf, and with P = L exactly today's.  Without the argument nothing changes.
+
+Local scaling: `attach_localscale` computes, once per gallery, every item's k-nearest-neighbourhood statistics
+against a bank of training queries; `candidates` / `search` with local_scaling="csls" | "nicdm" | "ls" then take every query's own
+statistics from its candidates' fine scores, correct the scores and re-rank them in one launch (nr_cand_localscale_rerank).
+Without the argument nothing changes.
 """
 from types import SimpleNamespace
 
@@ -33,6 +38,7 @@ from . import head, hip, ops
 MAX_CANDIDATES = 128                      # nr_local_level_cand: C <= 128 (= hip.TOPK_MAX, the longest top-k list)
 _SCORER = {"video": "video_weight_fc", "text": "text_weight_fc"}
 NORM_MODES = ("is", "qbnorm")             # query-bank normalisation of the candidate scores
+LOCAL_SCALING_MODES = ("csls", "nicdm", "ls")       # local scaling of the candidate scores
 
 
 def check_candidates(n_candidates, allow_zero=False):
@@ -75,6 +81,20 @@ def check_norm(norm):
     if norm is not None and norm not in NORM_MODES:
         raise ValueError(f"norm must be None or one of {NORM_MODES}, got {norm!r}")
     return norm
+
+
+def check_local_scaling(mode):
+    """local_scaling as None, "csls", "nicdm" or "ls"."""
+    if mode is not None and (not isinstance(mode, str) or mode not in LOCAL_SCALING_MODES):
+        raise ValueError(f"local_scaling must be None or one of {LOCAL_SCALING_MODES}, got {mode!r}")
+    return mode
+
+
+def check_local_scaling_k(k):
+    """The neighbourhood size of local scaling as an int in [1, 128]."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= hip.TOPK_MAX:
+        raise ValueError(f"local scaling k must be an integer in [1, {hip.TOPK_MAX}], got {k!r}")
+    return int(k)
 
 
 def _check_tokens(feat, mask, what):
@@ -133,6 +153,8 @@ class GalleryIndex:
         self.norm = self.active = self.norm_beta = self.qb_k = None
         self.n_bank = 0
         self.ivf = None
+        self.ls_mean = self.ls_kth = self.ls_k = None
+        self.ls_n_bank = 0
 
     def __len__(self):
         return self.items.n
@@ -172,6 +194,37 @@ class GalleryIndex:
             occ, _ = ops.topk_occurrences(lists, N, none, none)
             self.norm, self.active = norm, (occ > 0).to(torch.int32)
         self.norm_beta, self.qb_k, self.n_bank = beta, qb_k, M
+        return self
+
+    def attach_localscale(self, bank_feat, bank_mask, k=10, chunk=256):
+        """The gallery's neighbourhood statistics against a query bank, computed once -> self.  The bank holds
+        items of `self.query_side`, as in attach_querybank.  Item j's neighbourhood is its top-k list among the M bank items
+        (ops.slab_topk_cols of Qt [M, N] for a video gallery, ops.slab_topk_rows of Qv [N, M] for a text gallery); stores ls_mean
+        [N] fp32 and ls_kth [N] fp32 (ops.localscale_stats: the list's mean and its last value; both are kept, so the mode is
+        chosen at search time), ls_k and ls_n_bank.  These are the bits the exhaustive bank form (evaluator._local_scaling_stats
+        with bank_slabs) computes for the columns (video gallery) or the rows (text gallery) at any world size.  Every argument is
+        checked before any work; the bank product is scored once, whole, and dropped (`chunk` only bounds the rows of one
+        similarity launch).  attach_querybank's and build_ivf's state is not touched."""
+        _check_tokens(bank_feat, bank_mask, "querybank")
+        if bank_feat.shape[0] < 1:
+            raise ValueError("the querybank is empty")
+        if bank_feat.shape[2] != self.items.d:
+            raise ValueError(f"the querybank is {bank_feat.shape[2]} wide, the gallery {self.items.d}")
+        if bank_feat.device != self.feat.device or bank_mask.device != self.feat.device:
+            raise ValueError("querybank and gallery must be on the same device")
+        k, chunk = check_local_scaling_k(k), check_chunk(chunk)
+        from .evaluator import _slab_similarity
+        N, M = len(self), bank_feat.shape[0]
+        bank_feat, bank_mask, feat, mask = bank_feat.float(), bank_mask.float(), self.feat.float(), self.mask.float()
+        with torch.no_grad():
+            if self.side == "video":
+                Q = _slab_similarity(self.model, bank_feat, feat, bank_mask, mask, 0, M, chunk)          # Qt [M, N]
+                lists = ops.slab_topk_cols(Q, 0, k)
+            else:
+                Q = _slab_similarity(self.model, feat, bank_feat, mask, bank_mask, 0, N, chunk)          # Qv [N, M]
+                lists = ops.slab_topk_rows(Q, k)
+            self.ls_mean, self.ls_kth = ops.localscale_stats(*lists)
+        self.ls_k, self.ls_n_bank = k, M
         return self
 
     def build_ivf(self, n_lists, iters=10, seed=0, chunk=256):
@@ -270,6 +323,21 @@ class GalleryIndex:
             raise ValueError("norm acts on candidate lists: the exhaustive path (n_candidates = 0) has the evaluator's corrections")
         return norm
 
+    def _check_local_scaling(self, mode, norm=None, n_candidates=None):
+        if check_local_scaling(mode) is None:
+            return None
+        if norm is not None:
+            raise ValueError(f"local_scaling={mode!r} and norm={norm!r} both correct the candidate scores: choose one")
+        if self.ls_mean is None:
+            raise ValueError(f"local_scaling={mode!r} needs the gallery's neighbourhood statistics: call attach_localscale(...) first")
+        C = check_candidates(n_candidates, allow_zero=True)
+        if C == 0:
+            raise ValueError("local_scaling acts on candidate lists: the exhaustive path (n_candidates = 0) has the evaluator's corrections")
+        if C < self.ls_k:
+            raise ValueError(f"local_scaling takes a query's neighbourhood of ls_k = {self.ls_k} among its candidates: "
+                             f"n_candidates >= {self.ls_k} expected, got {C}")
+        return mode
+
     def _check_queries(self, q_feat, q_mask):
         _check_tokens(q_feat, q_mask, "query")
         if q_feat.shape[2] != self.items.d:
@@ -282,7 +350,7 @@ class GalleryIndex:
         fixed summation order per element)."""
         return ops.gemm_nt_f32(pooled_q, self.items.pooled)
 
-    def candidates(self, q_feat, q_mask, n_candidates, chunk=256, norm=None, nprobe=None, ivf_stats=False):
+    def candidates(self, q_feat, q_mask, n_candidates, chunk=256, norm=None, nprobe=None, ivf_stats=False, local_scaling=None):
         """(cand [n, C] int32, fine [n, C] fp32): every query's C candidates in ascending gallery index (padded with -1 when
         the gallery has fewer than C items) and their fine scores (-inf at the padding).  norm "is" | "qbnorm" (after
         attach_querybank): (cand, fine, corr [n, C] fp32, gate [n] int32), the corrected scores and which queries were normalised
@@ -291,11 +359,18 @@ class GalleryIndex:
         nprobe = P (after build_ivf; 1 <= P <= min(L, 128)): the candidates come from the query's P probed lists only (DESIGN.md
         6.16); None is the exact prefilter.  ivf_stats (with nprobe): one more result, stats [n, 3] int32 = (the pool's length,
         how many of the exact prefilter's candidates the list kept, how many candidates the exact prefilter has): the exact
-        lists are computed for these counts only."""
+        lists are computed for these counts only.
+
+        local_scaling "csls" | "nicdm" | "ls" (after attach_localscale; not with norm; n_candidates >= ls_k): (cand, fine, corr
+        [n, C] fp32, qstat [n, 2] fp32), the locally scaled scores and every query's own (mean, kth) of the top
+        ls_k of its candidates' fine scores."""
         norm = self._check_norm(norm)
         nprobe = self._check_nprobe(nprobe)
         if ivf_stats and nprobe is None:
             raise ValueError("ivf_stats describes the inverted-file prefilter: it needs nprobe")
+        if local_scaling is not None:
+            mode = self._check_local_scaling(local_scaling, norm, n_candidates)
+            return self._local_scaled(q_feat, q_mask, 1, n_candidates, chunk, mode, nprobe, ivf_stats)[2:]
         if norm is not None:
             return self._normalised(q_feat, q_mask, 1, n_candidates, chunk, norm, nprobe, ivf_stats)[2:]
         C, chunk = check_candidates(n_candidates), check_chunk(chunk)
@@ -342,19 +417,33 @@ class GalleryIndex:
                                                     active=self.active if norm == "qbnorm" else None, beta=self.norm_beta)
         return (idx, val, cand, fine, corr, gate) + tuple(stats)
 
-    def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False, norm=None, nprobe=None):
+    def _local_scaled(self, q_feat, q_mask, k, n_candidates, chunk, mode, nprobe=None, ivf_stats=False):
+        """(idx, val, cand, fine, corr, qstat[, stats]): the candidates and their fine scores, then nr_cand_localscale_rerank in one
+        launch.  The text side is the row of the formulas: the query for a video gallery, the gallery item for a text gallery."""
+        cand, fine, *stats = self.candidates(q_feat, q_mask, n_candidates, chunk, nprobe=nprobe, ivf_stats=ivf_stats)
+        idx, val, corr, qstat = ops.cand_localscale_rerank(fine, cand, len(self), k, self.ls_kth if mode == "ls" else self.ls_mean,
+                                                           mode, self.ls_k, self.side == "video")
+        return (idx, val, cand, fine, corr, qstat) + tuple(stats)
+
+    def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False, norm=None, nprobe=None, local_scaling=None):
         """-> (idx [n, k] int32, val [n, k] fp32): the top k of every query, fine score descending, ties by lower gallery index,
         padded with -1 / -inf when the gallery has fewer than k items.  1 <= k <= n_candidates <= 128; n_candidates = 0 scores
         every pair (the exhaustive path: the evaluator's slab similarity and ops.slab_topk_rows).  return_candidates: also the
         candidate lists and their fine scores, (idx, val, cand, fine).  norm "is" | "qbnorm" (after attach_querybank): the
         order and val are those of the corrected scores; with return_candidates (idx, val, cand, fine, gate).  nprobe = P (after
-        build_ivf): the candidates come from the P probed lists of the inverted file; not with n_candidates = 0."""
+        build_ivf): the candidates come from the P probed lists of the inverted file; not with n_candidates = 0.
+        local_scaling "csls" | "nicdm" | "ls" (after attach_localscale; not with norm, n_candidates >= ls_k): the order and val are
+        those of the locally scaled scores; with return_candidates (idx, val, cand, fine, qstat)."""
         C, chunk = check_candidates(n_candidates, allow_zero=True), check_chunk(chunk)
         if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > (C or hip.TOPK_MAX):
             raise ValueError(f"k must be an integer in [1, {C or hip.TOPK_MAX}] (1 <= k <= n_candidates), got {k!r}")
         norm = self._check_norm(norm, C)
         nprobe = self._check_nprobe(nprobe, C)
+        local_scaling = self._check_local_scaling(local_scaling, norm, C)
         self._check_queries(q_feat, q_mask)
+        if local_scaling is not None:
+            idx, val, cand, fine, _, qstat = self._local_scaled(q_feat, q_mask, k, C, chunk, local_scaling, nprobe)
+            return (idx, val, cand, fine, qstat) if return_candidates else (idx, val)
         if norm is not None:
             idx, val, cand, fine, _, gate = self._normalised(q_feat, q_mask, k, C, chunk, norm, nprobe)
             return (idx, val, cand, fine, gate) if return_candidates else (idx, val)

@@ -161,14 +161,16 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
     (rank r: rows [r N/W, (r+1) N/W)).  Multi-sentence sets (`dataset.multi_sentence_per_video`): every rank walks the whole
     loader, as in the reference (:114-131), keeps the video of each group's last sentence (:137-149), and the
     sentence x video matrix is again scored in row slabs.  Both go through evaluator.sharded_evaluation."""
-    from .evaluator import (correction_from_args, dataset_order, gather_eval_features, rerank_ivf_from_args, rerank_norm_from_args,
-                            rerank_top_from_args, sharded_evaluation, two_stage_evaluation, two_stage_ivf_label, two_stage_label)
+    from .evaluator import (correction_from_args, dataset_order, gather_eval_features, rerank_ivf_from_args,
+                            rerank_local_scaling_from_args, rerank_norm_from_args, rerank_top_from_args, sharded_evaluation,
+                            two_stage_evaluation, two_stage_ivf_label, two_stage_label)
     correction, extras = correction_from_args(args, _unwrap(model))        # every flag checked before any work
     rerank_top = rerank_top_from_args(args)
     rerank_ivf = rerank_ivf_from_args(args)
     rerank_tag = two_stage_label(rerank_top) if rerank_ivf is None else \
         two_stage_ivf_label(rerank_top, rerank_ivf["n_lists"], rerank_ivf["nprobe"])
     rerank_norm = rerank_norm_from_args(args, _unwrap(model))
+    rerank_ls = rerank_local_scaling_from_args(args, _unwrap(model))
     hubness_k = extras["hubness_k"]
     logger = getattr(args, "logger", None)
     tracker = RetrievalMetrics(logger=logger)
@@ -197,6 +199,7 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
         toc2 = time.time()
         if rerank_top:                                     # two-stage retrieval next to the exhaustive figures, never instead of them
             norm_kw = {} if rerank_norm is None else dict(rerank_norm, hubness_k=min(hubness_k, rerank_top))
+            norm_kw = norm_kw if rerank_ls is None else dict(rerank_ls, hubness_k=min(hubness_k, rerank_top))
             t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, tf, vf, tm.float(), vm.float(), args, rerank_top,
                                                                       cut_off_points=cut_off_points, **norm_kw, **(rerank_ivf or {}))
         toc3 = time.time()
