@@ -910,8 +910,7 @@ def eval_epoch(args, model, test, tag=""):
     if rerank_top:                                          # two-stage retrieval next to the exhaustive figures, never instead of them
         torch.cuda.synchronize()
         tic = time.time()
-        norm_kw = {} if rerank_norm is None else dict(rerank_norm, hubness_k=min(hubness_k, rerank_top))
-        norm_kw = norm_kw if rerank_ls is None else dict(rerank_ls, hubness_k=min(hubness_k, rerank_top))
+        norm_kw = dict(rerank_ls or rerank_norm, hubness_k=min(hubness_k, rerank_top)) if rerank_ls or rerank_norm else {}
         t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, t, v, tm.float(), vm.float(), args, rerank_top, **norm_kw,
                                                                   **(rerank_ivf or {}))
         toc = time.time()

@@ -75,6 +75,19 @@ __device__ __forceinline__ void nr_split_pk(float a, float b, uint32_t& hi, uint
     lo = nr_f2bf_pk(a - __builtin_bit_cast(float, hi << 16), b - __builtin_bit_cast(float, hi & 0xFFFF0000u));
 }
 
+// Order-preserving 32-bit key of a score: a larger key is a larger score, -inf's key lies below every finite score's and +inf's
+// above.  The order of every top-k list, candidate line and IVF pool of this project.
+__device__ __forceinline__ uint32_t nr_order_key(float x) {
+    uint32_t u = __float_as_uint(x);
+    if (x != x) return 0u;                       // NaN: the lowest key, never selected
+    if (u == 0x80000000u) u = 0u;                // -0.0 == +0.0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// max(x, lo) that keeps a NaN x (fmaxf would return lo)
+__device__ __forceinline__ float nr_floor(float x, float lo) { return x < lo ? lo : x; }
+#define NR_SCALE_EPS 9.5367431640625e-07f        // 2^-20: the floor of a distance scale (local scaling) or deviation (mutual proximity)
+
 // ---- cross-lane reductions on DPP (data-parallel primitives): VALU-latency steps instead of the
 // LDS-crossbar round trip of ds_bpermute that __shfl_xor compiles to.  Steps: quad_perm xor-1, xor-2,
 // row_half_mirror (8 lanes), row_mirror (16 lanes), row_bcast15 / row_bcast31 (across the four rows);

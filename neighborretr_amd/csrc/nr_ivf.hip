@@ -197,16 +197,9 @@ extern "C" int nr_ivf_scan(const float* q, int n, const float* rows, const int32
 }
 
 // ---- selection ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t nr_ivf_score_key(float x) {      // nr_topk_key (nr_topk.hip): NaN -> 0, both zeros one key
-    uint32_t u = __float_as_uint(x);
-    if (x != x) return 0u;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // larger key = earlier in (score descending, gallery index ascending); the keys of a pool are distinct because its items are
 __device__ __forceinline__ unsigned long long nr_ivf_key(float score, int32_t item) {
-    return ((unsigned long long)nr_ivf_score_key(score) << 32) | (unsigned long long)(~(uint32_t)item);
+    return ((unsigned long long)nr_order_key(score) << 32) | (unsigned long long)(~(uint32_t)item);
 }
 
 // One workgroup per query.  Eight 8-bit radix passes with a 256-bin LDS histogram find T = the kk-th largest key (kk = min(C,

@@ -8,14 +8,9 @@
 //
 // Every operation is rounded once (no fused multiply-add), NaN passes through every max, the sum of a list has a fixed order:
 // the same inputs give the same bits, whatever the slab split.  No scratch, no float atomics, no hand-off between workgroups.
-#include "nr_common.h"
-#include "../../include/nr_hip.h"
+#include "nr_localscale.h"
 
 #define NR_LS_K_MAX 128                          // the longest list nr_topk.hip writes
-#define NR_LS_EPS 9.5367431640625e-07f           // 2^-20: the floor of a neighbourhood's distance scale
-
-// max(x, lo) that keeps a NaN x (fmaxf would return lo)
-__device__ __forceinline__ float nr_ls_floor(float x, float lo) { return x < lo ? lo : x; }
 
 // ---- statistics of the lists: one thread per line -----------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void nr_localscale_stats_kernel(const int32_t* __restrict__ idx, const float* __restrict__ val,
@@ -49,16 +44,8 @@ extern "C" int nr_localscale_stats(const int32_t* idx, const float* val, int n, 
 }
 
 // ---- apply: one read of S, one write of T -------------------------------------------------------------------------------------
-// r: the row's statistic for csls, its floored distance scale a[i] for nicdm / ls; c: the column's raw statistic.
-template <int MODE>
-__device__ __forceinline__ float nr_ls_score(float s, float r, float c) {
-    if (MODE == NR_LOCALSCALE_CSLS) return __fsub_rn(__fsub_rn(__fmul_rn(2.f, s), r), c);
-    const float d = nr_ls_floor(__fsub_rn(1.f, s), 0.f);
-    const float ab = __fmul_rn(r, nr_ls_floor(__fsub_rn(1.f, c), NR_LS_EPS));
-    if (MODE == NR_LOCALSCALE_NICDM) return -__fdiv_rn(d, __fsqrt_rn(ab));
-    return -__fdiv_rn(__fmul_rn(d, d), ab);
-}
-
+// The formulas are nr_localscale.h's with the mode a compile-time constant; the row's operand (a[i] for nicdm / ls) is taken once
+// per group.
 template <int MODE, int VEC>
 __global__ __launch_bounds__(256) void nr_localscale_apply_kernel(const float* __restrict__ S, int n, int L,
                                                                  const float* __restrict__ row_stat,
@@ -68,17 +55,16 @@ __global__ __launch_bounds__(256) void nr_localscale_apply_kernel(const float* _
         const long long e0 = g * VEC;
         const int i = (int)(e0 / L);
         const int j0 = (int)(e0 - (long long)i * L);         // VEC == 4: L % 4 == 0, the group lies in one row
-        float r = row_stat[i];
-        if (MODE != NR_LOCALSCALE_CSLS) r = nr_ls_floor(__fsub_rn(1.f, r), NR_LS_EPS);
+        const float r = nr_ls_operand(MODE, row_stat[i]);
         if (VEC == 4) {
             const f32x4_t x = *reinterpret_cast<const f32x4_t*>(S + e0);
             const f32x4_t c = *reinterpret_cast<const f32x4_t*>(col_stat + j0);
             f32x4_t t;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) t[q] = nr_ls_score<MODE>(x[q], r, c[q]);
+            for (int q = 0; q < 4; ++q) t[q] = nr_ls_score(MODE, x[q], r, nr_ls_operand(MODE, c[q]));
             *reinterpret_cast<f32x4_t*>(T + e0) = t;
         } else {
-            T[e0] = nr_ls_score<MODE>(S[e0], r, col_stat[j0]);
+            T[e0] = nr_ls_score(MODE, S[e0], r, nr_ls_operand(MODE, col_stat[j0]));
         }
     }
 }

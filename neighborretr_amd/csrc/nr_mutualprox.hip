@@ -4,6 +4,7 @@
 //   emp:   r2(s, X) = 2 #{x in X : x < s} + #{x in X : x == s},  c(X) = #{x in X : x is not NaN}
 //          T[i,j] = fl(fl(fl(r2_row) / fl(2 c_row)) fl(fl(r2_col) / fl(2 c_col)))
 //   gauss: z = fl(fl(s - mean) / max(sd, EPS)),  Q = fl(0.5 erfc(fl(z fl(1 / sqrt 2)))),  T[i,j] = -fl(fl(Q_r + Q_c) - fl(Q_r Q_c))
+//          EPS = NR_SCALE_EPS = 2^-20, the max is nr_floor (nr_common.h): it keeps a NaN sd
 //
 // The counts are integers (no order of summation), every float operation is rounded once (no fused multiply-add), the moments are
 // accumulated in fp64 in a fixed order.  No scratch, no float atomics, no hand-off between workgroups.
@@ -22,11 +23,7 @@ __device__ __forceinline__ float nr_mp_sub(float a, float b) { return a - b; }
 #define NR_MP_ROW_CHUNK 1024                     // floats of a reference row staged through LDS at a time
 #define NR_MP_COL_BLOCK_ROWS 64                  // rows of S a workgroup of the column kernel covers: 4 waves x NR_MP_TILE
 #define NR_MP_LINE_MAX (1 << 23)                 // 2 c must stay below 2^24: the counts convert to fp32 exactly
-#define NR_MP_EPS 9.5367431640625e-07f           // 2^-20: the floor of a line's standard deviation
 #define NR_MP_RSQRT2 0.707106781186547524f       // fl(1 / sqrt 2)
-
-// max(x, lo) that keeps a NaN x (fmaxf would return lo)
-__device__ __forceinline__ float nr_mp_floor(float x, float lo) { return x < lo ? lo : x; }
 
 // 2 [x < s] + [x == s] = [x < s] + [x <= s]: two compares and two adds per pair; a NaN on either side adds nothing
 __device__ __forceinline__ int nr_mp_pair(float x, float s) { return (int)(x < s) + (int)(x <= s); }
@@ -200,7 +197,7 @@ __device__ __forceinline__ float nr_mp_emp_score(float s, int r2, float row_den,
 }
 
 __device__ __forceinline__ float nr_mp_tail(float s, float mean, float sd) {
-    const float z = __fdiv_rn(nr_mp_sub(s, mean), nr_mp_floor(sd, NR_MP_EPS));
+    const float z = __fdiv_rn(nr_mp_sub(s, mean), nr_floor(sd, NR_SCALE_EPS));
     return nr_mp_mul(0.5f, erfcf(nr_mp_mul(z, NR_MP_RSQRT2)));
 }
 

@@ -17,13 +17,6 @@
 #define NR_TOPK_MAX 128
 #define NR_TOPK_CACHE_KEYS 12288   // 48 KB of dynamic LDS per workgroup
 
-__device__ __forceinline__ uint32_t nr_topk_key(float x) {
-    uint32_t u = __float_as_uint(x);
-    if (x != x) return 0u;                       // NaN: the lowest key, never selected
-    if (u == 0x80000000u) u = 0u;                // -0.0 == +0.0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // One list per line.  Line l starts at S + l * line_stride, its entry e sits at + e * elem_stride and is reported as
 // index idx0 + e.  Rows of a slab: (N, 1, 0); columns: (1, N, row0).
 template <bool CACHED>
@@ -50,13 +43,13 @@ __global__ __launch_bounds__(256) void nr_topk_lines_kernel(const float* __restr
             uint32_t key;
             if (CACHED) {
                 if (shift == 24) {
-                    key = nr_topk_key(line[(long long)e * elem_stride]);
+                    key = nr_order_key(line[(long long)e * elem_stride]);
                     cache[e] = key;
                 } else {
                     key = cache[e];
                 }
             } else {
-                key = nr_topk_key(line[(long long)e * elem_stride]);
+                key = nr_order_key(line[(long long)e * elem_stride]);
             }
             if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1);
         }
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(256) void nr_topk_lines_kernel(const float* __restr
         const int e = base + tid;
         const bool in = e < L;
         uint32_t key = 0;
-        if (in) key = CACHED ? cache[e] : nr_topk_key(line[(long long)e * elem_stride]);
+        if (in) key = CACHED ? cache[e] : nr_order_key(line[(long long)e * elem_stride]);
         if (in && key > T) {
             const int p = atomicAdd(&n_gt, 1);
             if (p < NR_TOPK_MAX) { sel_key[p] = key; sel_pos[p] = e; }
@@ -172,7 +165,7 @@ extern "C" int nr_slab_topk_cols(const float* S_slab, int n_rows, int N, int row
 // stay distinct and the result deterministic whatever the input.
 __device__ __forceinline__ bool nr_topk_ahead(int32_t i_b, float v_b, int list_b, uint32_t key, int32_t idx, int list) {
     if (i_b < 0 || v_b != v_b) return false;
-    const uint32_t kb = nr_topk_key(v_b);
+    const uint32_t kb = nr_order_key(v_b);
     return kb > key || (kb == key && (i_b < idx || (i_b == idx && list_b < list)));
 }
 
@@ -193,7 +186,7 @@ __global__ __launch_bounds__(256) void nr_topk_merge_kernel(const int32_t* __res
         const int32_t i = idx[at];
         const float v = val[at];
         if (i < 0 || v != v) continue;
-        const uint32_t key = nr_topk_key(v);
+        const uint32_t key = nr_order_key(v);
         int rank = p;
         for (int b = 0; b < n_lists && rank < k; ++b) {
             if (b == l) continue;

@@ -1416,17 +1416,24 @@ def two_stage_norm_label(n_candidates, mode, beta, qb_k=1):
     return f"[two-stage C={int(n_candidates)} {TEST_NORM_LABELS[mode]} b={beta:g}{tail}]"
 
 
+def _rerank_mode_from_args(args, flag, check, choices):
+    """args.<flag> -> None (unset or "none") or the mode, which search's `check` accepts."""
+    mode = getattr(args, flag, None) or "none"
+    if mode == "none":
+        return None
+    try:
+        return check(mode)
+    except ValueError:
+        raise ValueError(f"{flag} must be {choices}, got {mode!r}") from None
+
+
 def rerank_norm_from_args(args, model):
     """args.rerank_norm -> None or the keyword arguments of two_stage_evaluation (norm, beta, qb_k), checked before any work: the
     mode, that rerank_top asks for candidates, beta (test_norm_beta), qb_k and that the model's memory bank is filled."""
     from .search import check_norm
-    mode = getattr(args, "rerank_norm", None) or "none"
-    if mode == "none":
+    mode = _rerank_mode_from_args(args, "rerank_norm", check_norm, "'is' or 'qbnorm'")
+    if mode is None:
         return None
-    try:
-        check_norm(mode)
-    except ValueError:
-        raise ValueError(f"rerank_norm must be 'is' or 'qbnorm', got {mode!r}") from None
     if rerank_top_from_args(args) < 1:
         raise ValueError("rerank_norm normalises candidate lists: it needs rerank_top >= 1")
     kw = dict(norm=mode, beta=ops._check_beta(getattr(args, "test_norm_beta", 20.0)), qb_k=ops._check_k(getattr(args, "qb_k", 1)))
@@ -1444,13 +1451,9 @@ def rerank_local_scaling_from_args(args, model):
     local_scaling_k), checked before any work: the mode, K, that it does not meet rerank_norm, that rerank_top asks for at least K
     candidates and that the model's memory bank is filled.  Independent of the exhaustive flags."""
     from .search import check_local_scaling, check_local_scaling_k
-    mode = getattr(args, "rerank_local_scaling", None) or "none"
-    if mode == "none":
+    mode = _rerank_mode_from_args(args, "rerank_local_scaling", check_local_scaling, "'csls', 'nicdm' or 'ls'")
+    if mode is None:
         return None
-    try:
-        check_local_scaling(mode)
-    except ValueError:
-        raise ValueError(f"rerank_local_scaling must be 'csls', 'nicdm' or 'ls', got {mode!r}") from None
     k = getattr(args, "rerank_local_scaling_k", 10)
     try:
         k = check_local_scaling_k(k)
@@ -1494,31 +1497,44 @@ def rerank_ivf_from_args(args):
     return dict(n_lists=lists, nprobe=probe, ivf_iters=iters, ivf_seed=seed)
 
 
+def _pack_rows(tensors, width):
+    """This rank's m rows of any number of 32-bit tensors, [m] or [m, w], int32 or fp32 -> (mine [sum of w, width] int32 for
+    _gathered_rows: tensor after tensor, transposed, row i at column i, fp32 as its bits, zero past column m; spec: every
+    tensor's (w, dtype, dim)).  The spec does not depend on m: it is the same on every rank, one with no rows included."""
+    m = tensors[0].shape[0]
+    spec = [(1 if t.dim() == 1 else t.shape[1], t.dtype, t.dim()) for t in tensors]
+    mine = torch.zeros((sum(w for w, _, _ in spec), width), dtype=torch.int32, device=tensors[0].device)
+    mine[:, :m] = torch.cat([t.reshape(m, w).view(torch.int32).T for t, (w, _, _) in zip(tensors, spec)], 0)
+    return mine, spec
+
+
+def _unpack_rows(rows, spec):
+    """The inverse of _pack_rows on the gathered rows [sum of w, n]: the tensors [n] / [n, w] of every rank's rows, bit for bit."""
+    out = [part.T.contiguous().view(dtype) for part, (_, dtype, _) in zip(torch.split(rows, [w for w, _, _ in spec]), spec)]
+    return tuple(t[:, 0].contiguous() if dim == 1 else t for t, (_, _, dim) in zip(out, spec))
+
+
 def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None, nprobe=None, local_scaling=None):
     """(cand [n, C] int32, fine [n, C] fp32) on the device, the same on every rank: this rank's queries searched, one gather.
-    norm: (cand, fine, corr [n, C] fp32, gate [n] int32), all four in that one gather.  local_scaling (never with norm): (cand,
-    fine, corr [n, C] fp32, qstat [n, 2] fp32), all four in that one gather.  nprobe: the candidates of the index's inverted file,
-    and as the last element stats [n, 3] int32 (GalleryIndex.candidates, ivf_stats), in that same gather."""
+    norm: (cand, fine, corr [n, C] fp32, gate [n] int32); local_scaling (never with norm): (cand, fine, corr [n, C] fp32, qstat
+    [n, 2] fp32); nprobe: the candidates of the index's inverted file, and as the last element stats [n, 3] int32
+    (GalleryIndex.candidates, ivf_stats).  Whatever `candidates` returns travels in that one gather, in its order."""
     n = q_feat.shape[0]
     r0, r1 = slab_bounds(n, W, rank)
-    kw = {**({} if norm is None else dict(norm=norm)), **({} if nprobe is None else dict(nprobe=nprobe, ivf_stats=True)),
-          **({} if local_scaling is None else dict(local_scaling=local_scaling))}
-    out = index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk, **kw)
+    out = index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk, norm=norm, nprobe=nprobe, ivf_stats=nprobe is not None,
+                           local_scaling=local_scaling)
     if W > 1:
-        blocks = [out[0].T, out[1].view(torch.int32).T] + ([out[2].view(torch.int32).T, out[3][None]] if norm is not None else [])
-        blocks += [out[2].view(torch.int32).T, out[3].view(torch.int32).T] if local_scaling is not None else []
-        blocks += [out[-1].T] if nprobe is not None else []
-        mine = torch.zeros((sum(b.shape[0] for b in blocks), -(-n // W)), dtype=torch.int32, device=out[0].device)
-        mine[:, :r1 - r0] = torch.cat(blocks, 0)
-        rows = _gathered_rows(mine, n, W)
-        out = (rows[:C].T.contiguous(), rows[C:2 * C].T.contiguous().view(torch.float32))
-        if norm is not None:
-            out += (rows[2 * C:3 * C].T.contiguous().view(torch.float32), rows[3 * C].contiguous())
-        if local_scaling is not None:
-            out += (rows[2 * C:3 * C].T.contiguous().view(torch.float32), rows[3 * C:3 * C + 2].T.contiguous().view(torch.float32))
-        if nprobe is not None:
-            out += (rows[-3:].T.contiguous(),)
+        mine, spec = _pack_rows(out, -(-n // W))
+        out = _unpack_rows(_gathered_rows(mine, n, W), spec)
     return out
+
+
+class _TwoStageCorrection(NamedTuple):
+    """What two_stage_evaluation needs to know of the one correction of the candidate scores (norm or local_scaling)."""
+    key: str                    # the corrected dictionary's key in the raw one
+    label: str                  # its log tag
+    attach: Callable            # (index, bank items, their mask): the index-time statistics
+    fields: Callable            # (the direction's extra result of `candidates`, its number of queries) -> the fields it gains
 
 
 def _two_stage_hubness(cand, score, K, n_gallery, gt_begin, gt_end):
@@ -1553,14 +1569,10 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
     a query's among its own candidates.  Each direction gains ["local_scaled"]: the raw dictionary's fields computed from the
     corrected scores, `mode`, `k` and `label`, and with hubness_k its ["hubness"].  corr and the queries' statistics travel in the
     direction's one gather."""
-    from .search import (GalleryIndex, check_candidates, check_chunk, check_ivf_build, check_local_scaling, check_local_scaling_k,
-                         check_norm, check_nprobe)
+    from .search import GalleryIndex, check_candidates, check_chunk, check_correction, check_ivf_build, check_local_scaling_k, check_nprobe
     C, chunk = check_candidates(n_candidates), check_chunk(chunk)
-    norm = check_norm(norm)
-    local_scaling = check_local_scaling(local_scaling)
+    norm, local_scaling = check_correction(norm, local_scaling)
     if local_scaling is not None:
-        if norm is not None:
-            raise ValueError(f"local_scaling={local_scaling!r} and norm={norm!r} both correct the candidate scores: choose one")
         local_scaling_k = check_local_scaling_k(local_scaling_k)
         if local_scaling_k > C:
             raise ValueError(f"local_scaling_k must lie in [1, n_candidates = {C}], got {local_scaling_k}")
@@ -1598,12 +1610,18 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
     rank = comm.get_rank() if W > 1 else 0
     text_mask, video_mask = text_mask.float(), video_mask.float()
     index_v, index_t = GalleryIndex(model, video_feat, video_mask, "video"), GalleryIndex(model, text_feat, text_mask, "text")
+    corrected = None
     if norm is not None:
-        index_v.attach_querybank(bank[0], bank[1], beta, qb_k, chunk)
-        index_t.attach_querybank(bank[2], bank[3], beta, qb_k, chunk)
+        corrected = _TwoStageCorrection("normalised", two_stage_norm_label(C, norm, beta, qb_k),
+                                        lambda index, feat, mask: index.attach_querybank(feat, mask, beta, qb_k, chunk),
+                                        lambda gate, n: dict(gated=float(int(gate.sum())) * 100 / n))
     if local_scaling is not None:
-        index_v.attach_localscale(bank[0], bank[1], local_scaling_k, chunk)
-        index_t.attach_localscale(bank[2], bank[3], local_scaling_k, chunk)
+        corrected = _TwoStageCorrection("local_scaled", two_stage_local_scaling_label(C, local_scaling, local_scaling_k),
+                                        lambda index, feat, mask: index.attach_localscale(feat, mask, local_scaling_k, chunk),
+                                        lambda qstat, n: dict(mode=local_scaling, k=local_scaling_k))
+    if corrected is not None:
+        corrected.attach(index_v, bank[0], bank[1])
+        corrected.attach(index_t, bank[2], bank[3])
     if nprobe is not None:
         index_v.build_ivf(n_lists, ivf_iters, ivf_seed, chunk)
         index_t.build_ivf(n_lists, ivf_iters, ivf_seed, chunk)
@@ -1626,23 +1644,13 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
     t2v, v2t = metrics(lists_t[1], lists_v[1])
     if hubness_k:
         add_hubness(t2v, v2t, lists_t[1], lists_v[1])
-    if norm is not None:
+    if corrected is not None:
         nt, nv = metrics(lists_t[2], lists_v[2])
         if hubness_k:
             add_hubness(nt, nv, lists_t[2], lists_v[2])
-        label = two_stage_norm_label(C, norm, beta, qb_k)
-        for m, n, gate, raw in ((nt, n_rows, lists_t[3], t2v), (nv, n_cols, lists_v[3], v2t)):
-            m["gated"] = float(int(gate.sum())) * 100 / n
-            m["label"] = label
-            raw["normalised"] = m
-    if local_scaling is not None:
-        nt, nv = metrics(lists_t[2], lists_v[2])
-        if hubness_k:
-            add_hubness(nt, nv, lists_t[2], lists_v[2])
-        label = two_stage_local_scaling_label(C, local_scaling, local_scaling_k)
-        for m, raw in ((nt, t2v), (nv, v2t)):
-            m.update(mode=local_scaling, k=local_scaling_k, label=label)
-            raw["local_scaled"] = m
+        for m, n, extra, raw in ((nt, n_rows, lists_t[3], t2v), (nv, n_cols, lists_v[3], v2t)):
+            m.update(corrected.fields(extra, n), label=corrected.label)
+            raw[corrected.key] = m
     if nprobe is not None:
         for m, lists, n_gallery in ((t2v, lists_t, n_cols), (v2t, lists_v, n_rows)):
             stats = lists[-1].cpu().numpy().astype(np.float64)                  # pool length, kept, the exact prefilter's count

@@ -1101,13 +1101,9 @@ def hubnorm_apply(S, beta, mode, col_norm=None, row_gate=None, row_norm=None, co
     return T, V
 
 
-def cand_norm_rerank(fine, cand, n_gallery, k, norm=None, active=None, beta=20.0, want_corr=True):
-    """(idx [n, k] int32, val [n, k] fp32, corr [n, C] fp32 or None, gate [n] int32) of candidate lists cand [n, C] int32 (ascending
-    gallery index, entries outside [0, n_gallery) absent) with fine scores fine [n, C], in one launch (nr_cand_norm_rerank).
-    norm [n_gallery] fp32: the gallery's normalisers, active [n_gallery] int32: the activation set.  norm None: gate 0, corr =
-    fine -- search.rerank; active None: every query takes corr = fl(fl(beta fine) - norm[cand]) (mode "is"); with active only
-    the queries whose top-1 candidate is active (mode "qbnorm").  idx / val: the top k of corr, ties by lower position, -1 / -inf
-    where the line has fewer than k present non-NaN slots.  1 <= k <= C <= 128."""
+def _cand_lines(fine, cand, n_gallery, k, want_corr):
+    """The front the candidate re-rank wrappers share: checks (fine, cand, n_gallery, k) and allocates the outputs every one of
+    them has -> (fine, cand, n, C, n_gallery, k, idx [n, k] int32, val [n, k] fp32, corr [n, C] fp32 or None)."""
     if fine.dim() != 2 or cand.dim() != 2 or fine.shape != cand.shape:
         raise ValueError(f"fine and cand must both be [n, C], got {tuple(fine.shape)} and {tuple(cand.shape)}")
     n, C = cand.shape
@@ -1116,6 +1112,21 @@ def cand_norm_rerank(fine, cand, n_gallery, k, norm=None, active=None, beta=20.0
         raise ValueError(f"1 <= k <= C <= {hip.TOPK_MAX} expected, got k = {k}, C = {C}")
     if n_gallery < 1:
         raise ValueError("the gallery is empty")
+    dev = fine.device
+    idx = torch.empty((n, k), dtype=torch.int32, device=dev)
+    val = torch.empty((n, k), dtype=torch.float32, device=dev)
+    corr = torch.empty((n, C), dtype=torch.float32, device=dev) if want_corr else None
+    return _f32(fine).contiguous(), cand.contiguous(), n, C, n_gallery, k, idx, val, corr
+
+
+def cand_norm_rerank(fine, cand, n_gallery, k, norm=None, active=None, beta=20.0, want_corr=True):
+    """(idx [n, k] int32, val [n, k] fp32, corr [n, C] fp32 or None, gate [n] int32) of candidate lists cand [n, C] int32 (ascending
+    gallery index, entries outside [0, n_gallery) absent) with fine scores fine [n, C], in one launch (nr_cand_norm_rerank).
+    norm [n_gallery] fp32: the gallery's normalisers, active [n_gallery] int32: the activation set.  norm None: gate 0, corr =
+    fine -- search.rerank; active None: every query takes corr = fl(fl(beta fine) - norm[cand]) (mode "is"); with active only
+    the queries whose top-1 candidate is active (mode "qbnorm").  idx / val: the top k of corr, ties by lower position, -1 / -inf
+    where the line has fewer than k present non-NaN slots.  1 <= k <= C <= 128."""
+    fine, cand, n, C, n_gallery, k, idx, val, corr = _cand_lines(fine, cand, n_gallery, k, want_corr)
     if active is not None and norm is None:
         raise ValueError("an activation set needs the normalisers")
     beta = _check_beta(beta) if norm is not None else 0.0
@@ -1123,10 +1134,6 @@ def cand_norm_rerank(fine, cand, n_gallery, k, norm=None, active=None, beta=20.0
     for x, dtype, what in ((norm, torch.float32, "norm"), (active, torch.int32, "active")):
         if x is not None and (x.dtype != dtype or x.shape != (n_gallery,) or x.device != dev):
             raise ValueError(f"{what} must be a {dtype} vector of {n_gallery} entries on {dev}")
-    fine, cand = _f32(fine).contiguous(), cand.contiguous()
-    idx = torch.empty((n, k), dtype=torch.int32, device=dev)
-    val = torch.empty((n, k), dtype=torch.float32, device=dev)
-    corr = torch.empty((n, C), dtype=torch.float32, device=dev) if want_corr else None
     gate = torch.empty((n,), dtype=torch.int32, device=dev)
     if n:
         p = lambda x: hip.ptr(None if x is None else x.contiguous(), allow_none=True)        # noqa: E731
@@ -1351,27 +1358,16 @@ def cand_localscale_rerank(fine, cand, n_gallery, k, g_stat, mode, ls_k, query_i
     scores; corr = the formula of `mode` on (fine, the query's statistic, g_stat[cand]), the query being the row where
     query_is_row, else the column; absent slots -inf.  idx / val: the top k of corr, ties by lower position, -1 / -inf where the
     line has fewer than k present non-NaN slots.  1 <= k <= C <= 128, 1 <= ls_k <= C."""
-    if fine.dim() != 2 or cand.dim() != 2 or fine.shape != cand.shape:
-        raise ValueError(f"fine and cand must both be [n, C], got {tuple(fine.shape)} and {tuple(cand.shape)}")
+    fine, cand, n, C, n_gallery, k, idx, val, corr = _cand_lines(fine, cand, n_gallery, k, want_corr)
     if mode not in LOCALSCALE_MODES:
         raise ValueError(f"mode must be one of {sorted(LOCALSCALE_MODES)}, got {mode!r}")
-    n, C = cand.shape
-    n_gallery, k = int(n_gallery), _check_k(k)
-    if not 1 <= C <= hip.TOPK_MAX or k > C:
-        raise ValueError(f"1 <= k <= C <= {hip.TOPK_MAX} expected, got k = {k}, C = {C}")
     if isinstance(ls_k, bool) or not isinstance(ls_k, int) or not 1 <= ls_k <= C:
         raise ValueError(f"ls_k must be an integer in [1, C = {C}], got {ls_k!r}")
     if not isinstance(query_is_row, (bool, int)) or query_is_row not in (0, 1):
         raise ValueError(f"query_is_row must be True or False, got {query_is_row!r}")
-    if n_gallery < 1:
-        raise ValueError("the gallery is empty")
     dev = fine.device
     if not torch.is_tensor(g_stat) or g_stat.dtype != torch.float32 or g_stat.shape != (n_gallery,) or g_stat.device != dev:
         raise ValueError(f"g_stat must be a {torch.float32} vector of {n_gallery} entries on {dev}")
-    fine, cand = _f32(fine).contiguous(), cand.contiguous()
-    idx = torch.empty((n, k), dtype=torch.int32, device=dev)
-    val = torch.empty((n, k), dtype=torch.float32, device=dev)
-    corr = torch.empty((n, C), dtype=torch.float32, device=dev) if want_corr else None
     qstat = torch.empty((n, 2), dtype=torch.float32, device=dev)
     if n:
         hip.call("nr_cand_localscale_rerank", hip.ptr(fine), hip.ptr(cand, torch.int32), n, C, n_gallery, hip.ptr(g_stat.contiguous()),

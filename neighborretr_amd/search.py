@@ -30,6 +30,7 @@ statistics from its candidates' fine scores, correct the scores and re-rank them
 Without the argument nothing changes.
 """
 from types import SimpleNamespace
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -41,29 +42,32 @@ NORM_MODES = ("is", "qbnorm")             # query-bank normalisation of the cand
 LOCAL_SCALING_MODES = ("csls", "nicdm", "ls")       # local scaling of the candidate scores
 
 
+def _int_in(x, lo=None, hi=None):
+    """x is an int, not a bool, with lo <= x <= hi (None: no bound)."""
+    return isinstance(x, int) and not isinstance(x, bool) and (lo is None or lo <= x) and (hi is None or x <= hi)
+
+
 def check_candidates(n_candidates, allow_zero=False):
     """n_candidates as an int in [1, 128] (allow_zero: 0 = the exhaustive path)."""
     lo = 0 if allow_zero else 1
-    if isinstance(n_candidates, bool) or not isinstance(n_candidates, int) or not lo <= n_candidates <= MAX_CANDIDATES:
+    if not _int_in(n_candidates, lo, MAX_CANDIDATES):
         raise ValueError(f"n_candidates must be an integer in [{lo}, {MAX_CANDIDATES}], got {n_candidates!r}")
     return int(n_candidates)
 
 
 def check_chunk(chunk):
-    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+    if not _int_in(chunk, 1):
         raise ValueError(f"chunk must be an integer >= 1, got {chunk!r}")
     return int(chunk)
 
 
 def check_ivf_build(n_lists, iters, seed, n_items):
     """(n_lists, iters, seed) of build_ivf as ints: 1 <= n_lists <= n_items, iters >= 0, any integer seed."""
-    def integer(x):
-        return isinstance(x, int) and not isinstance(x, bool)
-    if not integer(n_lists) or not 1 <= n_lists <= n_items:
+    if not _int_in(n_lists, 1, n_items):
         raise ValueError(f"n_lists must be an integer in [1, {n_items}] (the gallery's size), got {n_lists!r}")
-    if not integer(iters) or iters < 0:
+    if not _int_in(iters, 0):
         raise ValueError(f"iters must be an integer >= 0, got {iters!r}")
-    if not integer(seed):
+    if not _int_in(seed):
         raise ValueError(f"seed must be an integer, got {seed!r}")
     return int(n_lists), int(iters), int(seed)
 
@@ -71,7 +75,7 @@ def check_ivf_build(n_lists, iters, seed, n_items):
 def check_nprobe(nprobe, n_lists):
     """nprobe as an int in [1, min(n_lists, 128)]."""
     hi = min(int(n_lists), hip.IVF_MAX_PROBE)
-    if isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 1 <= nprobe <= hi:
+    if not _int_in(nprobe, 1, hi):
         raise ValueError(f"nprobe must be an integer in [1, min(n_lists, {hip.IVF_MAX_PROBE}) = {hi}], got {nprobe!r}")
     return int(nprobe)
 
@@ -92,9 +96,17 @@ def check_local_scaling(mode):
 
 def check_local_scaling_k(k):
     """The neighbourhood size of local scaling as an int in [1, 128]."""
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= hip.TOPK_MAX:
+    if not _int_in(k, 1, hip.TOPK_MAX):
         raise ValueError(f"local scaling k must be an integer in [1, {hip.TOPK_MAX}], got {k!r}")
     return int(k)
+
+
+def check_correction(norm, local_scaling):
+    """(norm, local_scaling) as check_norm and check_local_scaling take them, at most one of them set: both correct the scores."""
+    norm, local_scaling = check_norm(norm), check_local_scaling(local_scaling)
+    if norm is not None and local_scaling is not None:
+        raise ValueError(f"local_scaling={local_scaling!r} and norm={norm!r} both correct the candidate scores: choose one")
+    return norm, local_scaling
 
 
 def _check_tokens(feat, mask, what):
@@ -102,6 +114,28 @@ def _check_tokens(feat, mask, what):
         raise ValueError(f"{what} features must be a [n, tokens, d] tensor")
     if not torch.is_tensor(mask) or mask.dim() != 2 or tuple(mask.shape) != tuple(feat.shape[:2]):
         raise ValueError(f"{what} mask must be [n, tokens] = {tuple(feat.shape[:2])}")
+
+
+class CandCorrection(NamedTuple):
+    """One correction of candidate scores, in the manner of evaluator.Correction: what `candidates` / `search` need to know of it."""
+    name: str                                 # the argument of candidates / search that carries its mode
+    needs: str                                # the attribute of the index its attach_* sets: None = not attached
+    missing: str                              # the refusal when it is not attached; {mode!r} is filled in
+    min_candidates: Callable                  # index -> the smallest n_candidates it can work on
+    too_few: Optional[str]                    # the refusal below that; {need} and {C} are filled in
+    rerank: Callable                          # (index, mode, fine, cand, k) -> (idx, val, corr, extra): its ONE ops call
+
+
+_NORM = CandCorrection(
+    "norm", "norm", "norm={mode!r} needs the gallery's query-bank statistics: call attach_querybank(...) first", lambda index: 1, None,
+    lambda index, mode, fine, cand, k: ops.cand_norm_rerank(
+        fine, cand, len(index), k, norm=index.norm, active=index.active if mode == "qbnorm" else None, beta=index.norm_beta))
+# the text side is the row of the formulas: the query for a video gallery, the gallery item for a text gallery
+_LOCAL_SCALING = CandCorrection(
+    "local_scaling", "ls_mean", "local_scaling={mode!r} needs the gallery's neighbourhood statistics: call attach_localscale(...) first",
+    lambda index: index.ls_k, "local_scaling takes a query's neighbourhood of ls_k = {need} among its candidates: n_candidates >= {need} "
+    "expected, got {C}", lambda index, mode, fine, cand, k: ops.cand_localscale_rerank(
+        fine, cand, len(index), k, index.ls_kth if mode == "ls" else index.ls_mean, mode, index.ls_k, index.side == "video"))
 
 
 def pooled_vectors(feat, mask, norm, w):
@@ -159,6 +193,24 @@ class GalleryIndex:
     def __len__(self):
         return self.items.n
 
+    def _bank_scores(self, bank_feat, bank_mask, chunk):
+        """The bank x gallery similarity in the evaluator's orientation (texts are rows), after the bank and chunk are checked: Qt
+        [M, N] for a video gallery, Qv [N, M] for a text gallery.  Scored once, whole; `chunk` only bounds the rows of one launch."""
+        _check_tokens(bank_feat, bank_mask, "querybank")
+        if bank_feat.shape[0] < 1:
+            raise ValueError("the querybank is empty")
+        if bank_feat.shape[2] != self.items.d:
+            raise ValueError(f"the querybank is {bank_feat.shape[2]} wide, the gallery {self.items.d}")
+        if bank_feat.device != self.feat.device or bank_mask.device != self.feat.device:
+            raise ValueError("querybank and gallery must be on the same device")
+        chunk = check_chunk(chunk)
+        from .evaluator import _slab_similarity
+        N, M = len(self), bank_feat.shape[0]
+        bank_feat, bank_mask, feat, mask = bank_feat.float(), bank_mask.float(), self.feat.float(), self.mask.float()
+        if self.side == "video":
+            return _slab_similarity(self.model, bank_feat, feat, bank_mask, mask, 0, M, chunk)
+        return _slab_similarity(self.model, feat, bank_feat, mask, bank_mask, 0, N, chunk)
+
     def attach_querybank(self, bank_feat, bank_mask, beta=20.0, qb_k=1, chunk=256):
         """The gallery's query-bank statistics, computed once -> self.  The bank holds items of
         `self.query_side` (texts for a video gallery, videos for a text gallery), [M, tokens, d] with a mask [M, tokens].
@@ -170,24 +222,14 @@ class GalleryIndex:
         The bank product (bank x gallery similarity, 4 M N bytes: 41 MB at M = 512, N = 20 000) is scored once, whole, and
         dropped.  The statistics are never chunked over bank items: merging (max, sum) pairs is not associative bit for bit,
         so `norm` would depend on the chunk size (`chunk` only bounds the rows of one similarity launch)."""
-        _check_tokens(bank_feat, bank_mask, "querybank")
-        if bank_feat.shape[0] < 1:
-            raise ValueError("the querybank is empty")
-        if bank_feat.shape[2] != self.items.d:
-            raise ValueError(f"the querybank is {bank_feat.shape[2]} wide, the gallery {self.items.d}")
-        if bank_feat.device != self.feat.device or bank_mask.device != self.feat.device:
-            raise ValueError("querybank and gallery must be on the same device")
-        beta, qb_k, chunk = ops._check_beta(beta), ops._check_k(qb_k), check_chunk(chunk)
-        from .evaluator import _slab_similarity
-        N, M = len(self), bank_feat.shape[0]
-        bank_feat, bank_mask, feat, mask = bank_feat.float(), bank_mask.float(), self.feat.float(), self.mask.float()
+        beta, qb_k = ops._check_beta(beta), ops._check_k(qb_k)
         with torch.no_grad():
+            Q = self._bank_scores(bank_feat, bank_mask, chunk)
+            N, M = len(self), bank_feat.shape[0]
             if self.side == "video":
-                Q = _slab_similarity(self.model, bank_feat, feat, bank_mask, mask, 0, M, chunk)          # Qt [M, N]
                 norm = ops.hubnorm_combine(ops.hubnorm_col_stats(Q, beta)[None])
                 lists, _ = ops.slab_topk_rows(Q, qb_k)
             else:
-                Q = _slab_similarity(self.model, feat, bank_feat, mask, bank_mask, 0, N, chunk)          # Qv [N, M]
                 norm = ops.hubnorm_row_lse(Q, beta)
                 lists, _ = ops.slab_topk_cols(Q, 0, qb_k)
             none = torch.zeros((M,), dtype=torch.int32, device=Q.device)
@@ -205,26 +247,12 @@ class GalleryIndex:
         with bank_slabs) computes for the columns (video gallery) or the rows (text gallery) at any world size.  Every argument is
         checked before any work; the bank product is scored once, whole, and dropped (`chunk` only bounds the rows of one
         similarity launch).  attach_querybank's and build_ivf's state is not touched."""
-        _check_tokens(bank_feat, bank_mask, "querybank")
-        if bank_feat.shape[0] < 1:
-            raise ValueError("the querybank is empty")
-        if bank_feat.shape[2] != self.items.d:
-            raise ValueError(f"the querybank is {bank_feat.shape[2]} wide, the gallery {self.items.d}")
-        if bank_feat.device != self.feat.device or bank_mask.device != self.feat.device:
-            raise ValueError("querybank and gallery must be on the same device")
-        k, chunk = check_local_scaling_k(k), check_chunk(chunk)
-        from .evaluator import _slab_similarity
-        N, M = len(self), bank_feat.shape[0]
-        bank_feat, bank_mask, feat, mask = bank_feat.float(), bank_mask.float(), self.feat.float(), self.mask.float()
+        k = check_local_scaling_k(k)
         with torch.no_grad():
-            if self.side == "video":
-                Q = _slab_similarity(self.model, bank_feat, feat, bank_mask, mask, 0, M, chunk)          # Qt [M, N]
-                lists = ops.slab_topk_cols(Q, 0, k)
-            else:
-                Q = _slab_similarity(self.model, feat, bank_feat, mask, bank_mask, 0, N, chunk)          # Qv [N, M]
-                lists = ops.slab_topk_rows(Q, k)
+            Q = self._bank_scores(bank_feat, bank_mask, chunk)
+            lists = ops.slab_topk_cols(Q, 0, k) if self.side == "video" else ops.slab_topk_rows(Q, k)
             self.ls_mean, self.ls_kth = ops.localscale_stats(*lists)
-        self.ls_k, self.ls_n_bank = k, M
+        self.ls_k, self.ls_n_bank = k, bank_feat.shape[0]
         return self
 
     def build_ivf(self, n_lists, iters=10, seed=0, chunk=256):
@@ -314,29 +342,21 @@ class GalleryIndex:
             cand[lo:lo + m] = ops.ivf_select(*pool, C)
         return cand, pool_len
 
-    def _check_norm(self, norm, n_candidates=None):
-        if check_norm(norm) is None:
+    def _check_correction(self, norm, local_scaling, n_candidates, allow_zero=True):
+        """The correction the arguments ask for -> (CandCorrection, mode), or None without one.  Refuses an unknown mode, two
+        corrections at once, one that is not attached, the exhaustive path and fewer candidates than the correction works on."""
+        norm, local_scaling = check_correction(norm, local_scaling)
+        if norm is None and local_scaling is None:
             return None
-        if self.norm is None:
-            raise ValueError(f"norm={norm!r} needs the gallery's query-bank statistics: call attach_querybank(...) first")
-        if n_candidates == 0:
-            raise ValueError("norm acts on candidate lists: the exhaustive path (n_candidates = 0) has the evaluator's corrections")
-        return norm
-
-    def _check_local_scaling(self, mode, norm=None, n_candidates=None):
-        if check_local_scaling(mode) is None:
-            return None
-        if norm is not None:
-            raise ValueError(f"local_scaling={mode!r} and norm={norm!r} both correct the candidate scores: choose one")
-        if self.ls_mean is None:
-            raise ValueError(f"local_scaling={mode!r} needs the gallery's neighbourhood statistics: call attach_localscale(...) first")
-        C = check_candidates(n_candidates, allow_zero=True)
+        c, mode = (_NORM, norm) if norm is not None else (_LOCAL_SCALING, local_scaling)
+        if getattr(self, c.needs) is None:
+            raise ValueError(c.missing.format(mode=mode))
+        C = check_candidates(n_candidates, allow_zero)      # `candidates` has no exhaustive path: 0 is out of its range
         if C == 0:
-            raise ValueError("local_scaling acts on candidate lists: the exhaustive path (n_candidates = 0) has the evaluator's corrections")
-        if C < self.ls_k:
-            raise ValueError(f"local_scaling takes a query's neighbourhood of ls_k = {self.ls_k} among its candidates: "
-                             f"n_candidates >= {self.ls_k} expected, got {C}")
-        return mode
+            raise ValueError(f"{c.name} acts on candidate lists: the exhaustive path (n_candidates = 0) has the evaluator's corrections")
+        if C < c.min_candidates(self):
+            raise ValueError(c.too_few.format(need=c.min_candidates(self), C=C))
+        return c, mode
 
     def _check_queries(self, q_feat, q_mask):
         _check_tokens(q_feat, q_mask, "query")
@@ -364,15 +384,12 @@ class GalleryIndex:
         local_scaling "csls" | "nicdm" | "ls" (after attach_localscale; not with norm; n_candidates >= ls_k): (cand, fine, corr
         [n, C] fp32, qstat [n, 2] fp32), the locally scaled scores and every query's own (mean, kth) of the top
         ls_k of its candidates' fine scores."""
-        norm = self._check_norm(norm)
+        correction = self._check_correction(norm, local_scaling, n_candidates, allow_zero=False)
         nprobe = self._check_nprobe(nprobe)
         if ivf_stats and nprobe is None:
             raise ValueError("ivf_stats describes the inverted-file prefilter: it needs nprobe")
-        if local_scaling is not None:
-            mode = self._check_local_scaling(local_scaling, norm, n_candidates)
-            return self._local_scaled(q_feat, q_mask, 1, n_candidates, chunk, mode, nprobe, ivf_stats)[2:]
-        if norm is not None:
-            return self._normalised(q_feat, q_mask, 1, n_candidates, chunk, norm, nprobe, ivf_stats)[2:]
+        if correction is not None:
+            return self._corrected(q_feat, q_mask, 1, n_candidates, chunk, correction, nprobe, ivf_stats)[2:]
         C, chunk = check_candidates(n_candidates), check_chunk(chunk)
         self._check_queries(q_feat, q_mask)
         dev = q_feat.device
@@ -410,20 +427,13 @@ class GalleryIndex:
             return exact, None, exact
         return self.ivf_candidates(pooled_q, C, nprobe, chunk) + (exact,)
 
-    def _normalised(self, q_feat, q_mask, k, n_candidates, chunk, norm, nprobe=None, ivf_stats=False):
-        """(idx, val, cand, fine, corr, gate[, stats]): the candidates and their fine scores, then nr_cand_norm_rerank in one launch."""
+    def _corrected(self, q_feat, q_mask, k, n_candidates, chunk, correction, nprobe=None, ivf_stats=False):
+        """(idx, val, cand, fine, corr, extra[, stats]): the candidates and their fine scores, then the correction's one launch
+        (extra: gate of norm, qstat of local_scaling)."""
+        c, mode = correction
         cand, fine, *stats = self.candidates(q_feat, q_mask, n_candidates, chunk, nprobe=nprobe, ivf_stats=ivf_stats)
-        idx, val, corr, gate = ops.cand_norm_rerank(fine, cand, len(self), k, norm=self.norm,
-                                                    active=self.active if norm == "qbnorm" else None, beta=self.norm_beta)
-        return (idx, val, cand, fine, corr, gate) + tuple(stats)
-
-    def _local_scaled(self, q_feat, q_mask, k, n_candidates, chunk, mode, nprobe=None, ivf_stats=False):
-        """(idx, val, cand, fine, corr, qstat[, stats]): the candidates and their fine scores, then nr_cand_localscale_rerank in one
-        launch.  The text side is the row of the formulas: the query for a video gallery, the gallery item for a text gallery."""
-        cand, fine, *stats = self.candidates(q_feat, q_mask, n_candidates, chunk, nprobe=nprobe, ivf_stats=ivf_stats)
-        idx, val, corr, qstat = ops.cand_localscale_rerank(fine, cand, len(self), k, self.ls_kth if mode == "ls" else self.ls_mean,
-                                                           mode, self.ls_k, self.side == "video")
-        return (idx, val, cand, fine, corr, qstat) + tuple(stats)
+        idx, val, corr, extra = c.rerank(self, mode, fine, cand, k)
+        return (idx, val, cand, fine, corr, extra) + tuple(stats)
 
     def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False, norm=None, nprobe=None, local_scaling=None):
         """-> (idx [n, k] int32, val [n, k] fp32): the top k of every query, fine score descending, ties by lower gallery index,
@@ -435,18 +445,14 @@ class GalleryIndex:
         local_scaling "csls" | "nicdm" | "ls" (after attach_localscale; not with norm, n_candidates >= ls_k): the order and val are
         those of the locally scaled scores; with return_candidates (idx, val, cand, fine, qstat)."""
         C, chunk = check_candidates(n_candidates, allow_zero=True), check_chunk(chunk)
-        if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > (C or hip.TOPK_MAX):
+        if not _int_in(k, 1, C or hip.TOPK_MAX):
             raise ValueError(f"k must be an integer in [1, {C or hip.TOPK_MAX}] (1 <= k <= n_candidates), got {k!r}")
-        norm = self._check_norm(norm, C)
+        correction = self._check_correction(norm, local_scaling, C)
         nprobe = self._check_nprobe(nprobe, C)
-        local_scaling = self._check_local_scaling(local_scaling, norm, C)
         self._check_queries(q_feat, q_mask)
-        if local_scaling is not None:
-            idx, val, cand, fine, _, qstat = self._local_scaled(q_feat, q_mask, k, C, chunk, local_scaling, nprobe)
-            return (idx, val, cand, fine, qstat) if return_candidates else (idx, val)
-        if norm is not None:
-            idx, val, cand, fine, _, gate = self._normalised(q_feat, q_mask, k, C, chunk, norm, nprobe)
-            return (idx, val, cand, fine, gate) if return_candidates else (idx, val)
+        if correction is not None:
+            idx, val, cand, fine, _, extra = self._corrected(q_feat, q_mask, k, C, chunk, correction, nprobe)
+            return (idx, val, cand, fine, extra) if return_candidates else (idx, val)
         if C == 0:
             if return_candidates:
                 raise ValueError("the exhaustive path (n_candidates = 0) has no candidate lists")

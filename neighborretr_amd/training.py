@@ -198,8 +198,7 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
         t2v, v2t = sharded_evaluation(model, tf, vf, tm.float(), vm.float(), args, correction, cut_off_points=cut_off_points, **extras)
         toc2 = time.time()
         if rerank_top:                                     # two-stage retrieval next to the exhaustive figures, never instead of them
-            norm_kw = {} if rerank_norm is None else dict(rerank_norm, hubness_k=min(hubness_k, rerank_top))
-            norm_kw = norm_kw if rerank_ls is None else dict(rerank_ls, hubness_k=min(hubness_k, rerank_top))
+            norm_kw = dict(rerank_ls or rerank_norm, hubness_k=min(hubness_k, rerank_top)) if rerank_ls or rerank_norm else {}
             t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, tf, vf, tm.float(), vm.float(), args, rerank_top,
                                                                       cut_off_points=cut_off_points, **norm_kw, **(rerank_ivf or {}))
         toc3 = time.time()

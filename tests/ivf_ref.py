@@ -18,7 +18,7 @@ import numpy as np
 
 
 def score_key(x):
-    """The order-preserving uint32 key of float32 scores (nr_topk_key): NaN -> 0, both zeros one key."""
+    """The order-preserving uint32 key of float32 scores (nr_order_key of csrc/nr_common.h): NaN -> 0, both zeros one key."""
     x = np.asarray(x, dtype=np.float32)
     u = x.view(np.uint32).copy()
     u[u == 0x80000000] = 0

@@ -166,3 +166,118 @@ def test_rerank_top_is_checked_by_both_eval_epochs_and_the_command_line(monkeypa
         with pytest.raises(SystemExit):
             parse(argv)
         assert "--rerank_top" in capsys.readouterr().err
+
+
+# ---- the one gather of two_stage_evaluation: its pack / unpack pair ------------------------------------------------------------------------
+def _bits(t):
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+@pytest.mark.parametrize("n, W", ((5, 2), (4, 4), (1, 3)))
+def test_the_gathers_pack_and_unpack_round_trip_bit_for_bit(n, W):
+    """cand, fine and extras of widths 1, 2, 3 and C (and a vector, as norm's gate), packed on every rank's slice -- for (1, 3) two
+    ranks own no row --, joined as _gathered_rows joins the ranks' blocks, unpacked: the unsliced tensors, every bit of them."""
+    C = 6
+    g = torch.Generator().manual_seed(100 * n + W)
+    cand = torch.randint(-1, 40, (n, C), generator=g, dtype=torch.int32)
+    cand[0, C - 1] = -1
+    fine = torch.randn((n, C), generator=g)
+    nans = torch.tensor([0x7FC00000, 0x7FC00001, -0x00400000 + 5, 0x7F800001], dtype=torch.int32).view(torch.float32)     # four payloads
+    special = torch.cat([nans, torch.tensor([-0.0, float("-inf"), 0.0, -1.0])])
+
+    def extra(w, dtype):
+        if dtype == torch.int32:
+            return torch.randint(-1, 2 ** 31 - 1, (n, w), generator=g, dtype=torch.int32)
+        x = torch.randn((n, w), generator=g)
+        x.view(-1)[::2] = special[torch.arange((n * w + 1) // 2) % len(special)]
+        return x
+    fine[0, :4], fine[n - 1, 4:] = nans, torch.tensor([-0.0, float("-inf")])
+    whole = (cand, fine, extra(1, torch.float32), extra(2, torch.float32), extra(3, torch.int32), extra(C, torch.float32),
+             extra(1, torch.int32)[:, 0].contiguous())
+    width = -(-n // W)
+    packed, specs = zip(*(evaluator._pack_rows(tuple(t[slice(*evaluator.slab_bounds(n, W, r))] for t in whole), width) for r in range(W)))
+    assert all(s == specs[0] for s in specs) and [s[0] for s in specs[0]] == [C, C, 1, 2, 3, C, 1]
+    assert all(p.dtype == torch.int32 and tuple(p.shape) == (2 * C + 1 + 2 + 3 + C + 1, width) for p in packed)
+    rows = torch.cat([p[:, :evaluator.slab_rows(n, W, r)] for r, p in enumerate(packed)], dim=1).contiguous()
+    if W == 3:
+        assert [evaluator.slab_rows(n, W, r) for r in range(W)] == [1, 0, 0]
+    got = evaluator._unpack_rows(rows, specs[0])
+    assert len(got) == len(whole)
+    for a, b in zip(got, whole):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.is_contiguous() and torch.equal(_bits(a), _bits(b))
+    assert torch.isnan(got[1][0, :4]).all() and torch.equal(got[1][0, :4].view(torch.int32), nans.view(torch.int32))
+
+
+# ---- the refusals of search.py, word for word -------------------------------------------------------------------------------------------------
+def _bare_index(**attached):
+    """A GalleryIndex with nothing prepared: what the argument checks read, and nothing else."""
+    from neighborretr_amd import search
+    index = object.__new__(search.GalleryIndex)
+    index.model, index.side, index.query_side = None, "video", "text"
+    index.feat, index.mask, index.items = torch.zeros((5, 3, 64)), torch.ones((5, 3)), NS(n=5, n_tok=3, d=64)
+    index.norm = index.active = index.norm_beta = index.qb_k = index.ivf = index.ls_mean = index.ls_kth = index.ls_k = None
+    index.n_bank = index.ls_n_bank = 0
+    for name, value in attached.items():
+        setattr(index, name, value)
+    return index
+
+
+def _refusals():
+    """(id, call(search module), the message): the strings are those of the commit before the checks were folded together."""
+    q, qm, z = torch.zeros((2, 3, 64)), torch.ones((2, 3)), torch.zeros((5,))
+    out = []
+    for bad in (True, 2.0, 0, 129, -1):
+        out.append((f"candidates-{bad!r}", lambda s, bad=bad: s.check_candidates(bad), f"n_candidates must be an integer in [1, 128], got {bad!r}"))
+        out.append((f"local_scaling_k-{bad!r}", lambda s, bad=bad: s.check_local_scaling_k(bad),
+                    f"local scaling k must be an integer in [1, 128], got {bad!r}"))
+    for bad in (False, 1.5, -1, 129):
+        out.append((f"candidates0-{bad!r}", lambda s, bad=bad: s.check_candidates(bad, allow_zero=True),
+                    f"n_candidates must be an integer in [0, 128], got {bad!r}"))
+    for bad in (True, 8.0, 0, -2):
+        out.append((f"chunk-{bad!r}", lambda s, bad=bad: s.check_chunk(bad), f"chunk must be an integer >= 1, got {bad!r}"))
+    for bad in (True, 4.0, 0, 10):
+        out.append((f"n_lists-{bad!r}", lambda s, bad=bad: s.check_ivf_build(bad, 10, 0, 9),
+                    f"n_lists must be an integer in [1, 9] (the gallery's size), got {bad!r}"))
+    for bad in (False, 1.0, -1):
+        out.append((f"iters-{bad!r}", lambda s, bad=bad: s.check_ivf_build(4, bad, 0, 9), f"iters must be an integer >= 0, got {bad!r}"))
+    for bad in (True, 0.0, None):
+        out.append((f"seed-{bad!r}", lambda s, bad=bad: s.check_ivf_build(4, 10, bad, 9), f"seed must be an integer, got {bad!r}"))
+    for bad in (True, 2.0, 0, 17):
+        out.append((f"nprobe-{bad!r}", lambda s, bad=bad: s.check_nprobe(bad, 16),
+                    f"nprobe must be an integer in [1, min(n_lists, 128) = 16], got {bad!r}"))
+    out.append(("nprobe-200", lambda s: s.check_nprobe(129, 200), "nprobe must be an integer in [1, min(n_lists, 128) = 128], got 129"))
+    out.append(("norm-mode", lambda s: s.check_norm("dsl"), "norm must be None or one of ('is', 'qbnorm'), got 'dsl'"))
+    out.append(("local_scaling-mode", lambda s: s.check_local_scaling("mp"),
+                "local_scaling must be None or one of ('csls', 'nicdm', 'ls'), got 'mp'"))
+    for how in ("candidates", "search"):
+        def call(index, how=how, **kw):
+            return index.candidates(q, qm, kw.pop("C", 4), **kw) if how == "candidates" else index.search(q, qm, 2, kw.pop("C", 4), **kw)
+        out.append((f"{how}-k" if how == "search" else f"{how}-ivf_stats",
+                    (lambda s: _bare_index().search(q, qm, True, 4)) if how == "search" else (lambda s: _bare_index().candidates(q, qm, 4, ivf_stats=True)),
+                    "k must be an integer in [1, 4] (1 <= k <= n_candidates), got True" if how == "search" else
+                    "ivf_stats describes the inverted-file prefilter: it needs nprobe"))
+        out.append((f"{how}-no-ivf", lambda s, call=call: call(_bare_index(), nprobe=2),
+                    "nprobe=2 needs the gallery's inverted file: call build_ivf(...) first"))
+        out.append((f"{how}-no-querybank", lambda s, call=call: call(_bare_index(ls_mean=z, ls_kth=z, ls_k=2), norm="is"),
+                    "norm='is' needs the gallery's query-bank statistics: call attach_querybank(...) first"))
+        out.append((f"{how}-no-localscale", lambda s, call=call: call(_bare_index(norm=z), local_scaling="csls"),
+                    "local_scaling='csls' needs the gallery's neighbourhood statistics: call attach_localscale(...) first"))
+        out.append((f"{how}-both", lambda s, call=call: call(_bare_index(norm=z, ls_mean=z, ls_kth=z, ls_k=2), norm="qbnorm", local_scaling="ls"),
+                    "local_scaling='ls' and norm='qbnorm' both correct the candidate scores: choose one"))
+        out.append((f"{how}-too-few", lambda s, call=call: call(_bare_index(ls_mean=z, ls_kth=z, ls_k=3), C=2, local_scaling="nicdm"),
+                    "local_scaling takes a query's neighbourhood of ls_k = 3 among its candidates: n_candidates >= 3 expected, got 2"))
+    for name in ("norm", "local_scaling"):
+        out.append((f"search-exhaustive-{name}",
+                    lambda s, name=name: _bare_index(norm=z, ls_mean=z, ls_kth=z, ls_k=2).search(q, qm, 2, 0, **{name: "is" if name == "norm" else "ls"}),
+                    f"{name} acts on candidate lists: the exhaustive path (n_candidates = 0) has the evaluator's corrections"))
+    out.append(("search-exhaustive-nprobe", lambda s: _bare_index(ivf=NS(n_lists=4)).search(q, qm, 2, 0, nprobe=2),
+                "nprobe restricts the prefilter: the exhaustive path (n_candidates = 0) has none"))
+    return out
+
+
+@pytest.mark.parametrize("call, message", [pytest.param(c, m, id=i) for i, c, m in _refusals()])
+def test_search_refusals_keep_their_wording(call, message):
+    from neighborretr_amd import search
+    with pytest.raises(ValueError) as e:
+        call(search)
+    assert str(e.value) == message

@@ -188,6 +188,34 @@ def test_a_line_does_not_depend_on_its_batch(C):
             assert np.array_equal(one[0][0], many[0][i]) and all(Q.same_bits(one[x][0], many[x][i]) for x in (1, 2, 3))
 
 
+def test_the_candidate_kernel_and_the_exhaustive_kernel_give_one_formulas_bits():
+    """Every item a candidate (cand = 0 .. 64 on every line): corr of nr_cand_localscale_rerank is ops.localscale_apply on the same
+    scores with the query's returned statistic on its side and g_stat on the gallery's -- as int32 patterns, NaN for NaN.  Five
+    queries: two workgroups, the second with one live wave.  Both kernels take the formula from csrc/nr_localscale.h."""
+    n, C, ls_k = 5, 65, 10
+    rng = np.random.default_rng(65)
+    fine = rng.uniform(-0.2, 1.2, (n, C)).astype(np.float32)
+    fine[0, 3], fine[0, 9], fine[1, 5], fine[2, 7], fine[3, 11], fine[4, 13] = 0.0, -0.0, 1.0, 1.15, np.nan, np.inf      # 1.15: d floors to 0
+    g = rng.uniform(0.2, 1.1, C).astype(np.float32)
+    g[17], g[23] = np.float32(1) - np.float32(2.0 ** -22), np.nan                    # above 1 - 2^-20: the EPS floor acts
+    assert 1 - g[17] < 2.0 ** -20 and (fine > 1).any() and np.signbit(fine[0, 9])
+    cand = np.tile(np.arange(C, dtype=np.int32), (n, 1))
+    fine_d, g_d = torch.from_numpy(fine).to(DEV), torch.from_numpy(g).to(DEV)
+    for mode in MODES:
+        for row in (True, False):
+            _, _, corr, qstat = _run(cand, fine, 1, g, mode, ls_k, row, n_gallery=C)
+            q_d = torch.from_numpy(np.ascontiguousarray(qstat[:, 1 if mode == "ls" else 0])).to(DEV)
+            if row:
+                want = ops.localscale_apply(fine_d, mode, q_d, g_d)
+            else:
+                want = ops.localscale_apply(fine_d.T.contiguous(), mode, g_d, q_d).T
+            want = want.contiguous().cpu().numpy()
+            nan = np.isnan(want)
+            assert np.array_equal(np.isnan(corr), nan), (mode, row)
+            assert np.array_equal(corr.view(np.int32)[~nan], want.view(np.int32)[~nan]), (mode, row)
+            assert nan[:, 23].all() and nan[3, 11] and (~nan).sum() > n * (C - 3)      # the planted NaNs, and little else
+
+
 # ---- 2. through the index -----------------------------------------------------------------------------------------------------------------
 # A tiny model of width 256 (nr_prepare_tokens takes multiples of 256), 37 videos x 12 tokens, 37 texts x 24 tokens, a bank of 9
 # texts and 7 videos.  SEED: one for which the fp64 reference separates every rank-deciding pair of corrected scores, in all three
