@@ -12,6 +12,7 @@ The memory-bank FEATURES get no gradient; the bank tokens' scorer weights do (pa
 import torch
 
 from . import head, hip, ops
+from .functional import head_args
 
 
 def _coef_rowloss(g, hp, B):
@@ -239,10 +240,8 @@ class HeadLossFn(torch.autograd.Function):
         prec = model._prec()
         losses, sv = head.head_forward(text_feat.detach(), video_feat.detach(), text_mask, video_mask,
                                        mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt.detach(), gv.detach(),
-                                       model.scorer_weights("text_weight_fc"), model.scorer_weights("video_weight_fc"),
-                                       hp, logit_scale.detach(), prec, keep=True, join=model._take_join(),
-                                       bank_streams=model._bank_streams(text_feat.device),
-                                       **model._global_scorers(text_feat, video_feat))
+                                       hp=hp, logit_scale=logit_scale.detach(), keep=True,
+                                       **head_args(model, text_feat, video_feat, model._take_join(), local_stream=False))
         ctx.sv, ctx.hp, ctx.exact = sv, dict(hp), prec == hip.PREC_BF16X3
         ctx.model, ctx.plan = model, head.backward_plan(prec)
         ctx.masks = (text_mask, video_mask)
@@ -428,19 +427,14 @@ class HeadLocalFn(torch.autograd.Function):
         stepwise = bridge.pop("join", None)       # gt = gv = None: the clustering's launches, a generator driven by the head
         if stepwise is not None:
             # the clustering is issued launch by launch on THIS stream, interleaved (in capture order) with the local branch and
-            # the early bank chains on the local stream -- the loss-only step's schedule (head.head_forward)
-            extra = dict(join=stepwise, local_stream=model._local_stream(text_feat.device), bank_early=model.bank_early,
-                         capture_order=getattr(model, "train_capture_order", None) or model.capture_order)
-            gt_in = gv_in = None
+            # the early bank chains on the local stream -- the loss-only step's schedule (head._run_branches)
+            join, gt_in, gv_in = stepwise, None, None
         else:
-            extra = dict(join=model._take_join())
-            gt_in, gv_in = gt.detach(), gv.detach()
+            join, gt_in, gv_in = model._take_join(), gt.detach(), gv.detach()
         losses, sv = head.head_forward(text_feat.detach(), video_feat.detach(), text_mask, video_mask,
                                        mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt_in, gv_in,
-                                       model.scorer_weights("text_weight_fc"), model.scorer_weights("video_weight_fc"),
-                                       hp, logit_scale.detach(), prec, keep=True,
-                                       bank_streams=model._bank_streams(text_feat.device),
-                                       **extra, **model._global_scorers(text_feat, video_feat))
+                                       hp=hp, logit_scale=logit_scale.detach(), keep=True,
+                                       **head_args(model, text_feat, video_feat, join, local_stream=stepwise is not None))
         ctx.sv, ctx.exact = sv, prec == hip.PREC_BF16X3
         ctx.model, ctx.plan = model, head.backward_plan(prec)
         ctx.masks = (text_mask, video_mask)

@@ -24,6 +24,24 @@ def _mlp_params(model, name):
     return m[0].weight, m[0].bias, m[2].weight, m[2].bias
 
 
+def head_args(model, text_feat, video_feat, join, local_stream, bank=None):
+    """The keyword arguments of head.head_forward that come from the model: scorer weights, precision, streams, schedule.
+    local_stream: the local branch goes to the model's local stream (the clustering runs inside `join`).  bank = (mb_feat_t,
+    mb_feat_v): the LOSS-ONLY step, which also reads the bank's prepared shadow, hands the batch's prepared tokens and the push
+    to the head and may be one of a pipeline; a differentiated forward (bank None) takes its schedule from
+    model.train_capture_order when that is set."""
+    dev = text_feat.device
+    args = dict(sw_t=model.scorer_weights("text_weight_fc"), sw_v=model.scorer_weights("video_weight_fc"), prec=model._prec(),
+                join=join, bank_streams=model._bank_streams(dev), local_stream=model._local_stream(dev) if local_stream else None,
+                bank_early=model.bank_early, capture_order=model.capture_order)
+    if bank is None:
+        args["capture_order"] = getattr(model, "train_capture_order", None) or model.capture_order
+    else:
+        args.update(bank_prepared=model._bank_shadow(*bank), prepared_out=model._last_prepared,
+                    bank_push=getattr(model, "_push_fn", None), slot=model._slot(), pipeline=model._pipeline_for_head(dev))
+    return dict(args, **model._global_scorers(text_feat, video_feat))
+
+
 def head_losses(model, text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
                 gt, gv, hp, logit_scale, cluster=None):
     """Returns a [5] tensor (total, centrality, uniform, neighbour, kl)."""
@@ -36,15 +54,10 @@ def head_losses(model, text_feat, video_feat, text_mask, video_mask, mb_feat_t, 
         return head_loss_nodes(model, hp, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
                                text_feat, video_feat, gt, gv, logit_scale, (*pt_params, *pv_params),
                                (*_mlp_params(model, "text_weight_fc1"), *_mlp_params(model, "video_weight_fc1")), cluster=cluster)
-    losses, _ = head.head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t,
-                                  mb_mask_v, gt, gv, model.scorer_weights("text_weight_fc"),
-                                  model.scorer_weights("video_weight_fc"), hp, logit_scale, model._prec(),
-                                  join=model._take_join(), bank_streams=model._bank_streams(text_feat.device),
-                                  local_stream=model._local_stream(text_feat.device) if gt is None else None,
-                                  bank_early=model.bank_early, capture_order=model.capture_order,
-                                  bank_prepared=model._bank_shadow(mb_feat_t, mb_feat_v), prepared_out=model._last_prepared,
-                                  bank_push=getattr(model, "_push_fn", None), slot=model._slot(), pipeline=model._pipeline_for_head(text_feat.device),
-                                  **model._global_scorers(text_feat, video_feat))
+    losses, _ = head.head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt, gv,
+                                  hp=hp, logit_scale=logit_scale,
+                                  **head_args(model, text_feat, video_feat, model._take_join(), local_stream=gt is None,
+                                              bank=(mb_feat_t, mb_feat_v)))
     return losses
 
 

@@ -32,7 +32,7 @@ import torch
 
 from . import comm, ops
 from .functional import local_level_sim
-
+from .head import _masks_f32, _rows
 
 
 class _GatherCat(torch.autograd.Function):
@@ -117,12 +117,6 @@ class SlabRowLossFn(torch.autograd.Function):
         d_wt[r0:r0 + n], d_wv[r0:r0 + n] = dwc[0], dwc[1]
         return (dS[0], dS[1].t().contiguous(), dG, None, None, dC[0].sum(0), dC[1].sum(0), d_wt, d_wv,
                 dls.sum().reshape(1), None, None)
-
-
-def _rows(prep, first, count):
-    return ops.Prepared(prep.hi[first:first + count], prep.lo[first:first + count] if prep.lo is not None else None,
-                        prep.norm[first:first + count], None, count, prep.d,
-                        prep.f16[first:first + count] if prep.f16 is not None else None)
 
 
 class ShardedLocalFn(torch.autograd.Function):
@@ -292,8 +286,7 @@ def sharded_training_losses(model, text_feat, video_feat, text_mask, video_mask,
         raise ValueError(f"num_neighbors={K} > batch={B}")
     b, r0 = B // world, rank * (B // world)
     sl = slice(r0, r0 + b)
-    text_mask, video_mask, mb_mask_t, mb_mask_v = (m if m.dtype == torch.float32 else m.float()
-                                                   for m in (text_mask, video_mask, mb_mask_t, mb_mask_v))
+    text_mask, video_mask, mb_mask_t, mb_mask_v = _masks_f32(text_mask, video_mask, mb_mask_t, mb_mask_v)
     # ---- token clustering: every rank clusters ITS samples (fused forward + hand-derived backward; the batch-wide maximum
     # distance of the masked stage is exchanged inside, modeling._merge_sharded) and the global tokens are gathered with a
     # differentiable all-gather: d gt of a rank's samples = the sum of every rank's W dL_r / d gt, so the clustering
