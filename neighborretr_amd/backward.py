@@ -232,7 +232,7 @@ class HeadLossFn(torch.autograd.Function):
     """Fused _compute_losses (modeling.py:314-360) given the global tokens."""
 
     @staticmethod
-    def forward(ctx, model, hp, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
+    def forward(ctx, model, hp, join, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
                 text_feat, video_feat, gt, gv, logit_scale, w1t, b1t, w2t, b2t, w1v, b1v, w2v, b2v,
                 g1_w1t, g1_b1t, g1_w2t, g1_b2t, g1_w1v, g1_b1v, g1_w2v, g1_b2v):
         """The last eight inputs are the *_weight_fc1 scorers of global_level (modeling.py:518-523): they matter (and get a
@@ -241,7 +241,7 @@ class HeadLossFn(torch.autograd.Function):
         losses, sv = head.head_forward(text_feat.detach(), video_feat.detach(), text_mask, video_mask,
                                        mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt.detach(), gv.detach(),
                                        hp=hp, logit_scale=logit_scale.detach(), keep=True,
-                                       **head_args(model, text_feat, video_feat, model._take_join(), local_stream=False))
+                                       **head_args(model, text_feat, video_feat, join, local_stream=False))
         ctx.sv, ctx.hp, ctx.exact = sv, dict(hp), prec == hip.PREC_BF16X3
         ctx.model, ctx.plan = model, head.backward_plan(prec)
         ctx.masks = (text_mask, video_mask)
@@ -257,7 +257,7 @@ class HeadLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gs):
         if all(g is None for g in gs):
-            return (None,) * 29
+            return (None,) * 30
         (text_feat, video_feat, mb_feat_t, mb_feat_v, w1t, b1t, w2t, w1v, b1v, w2v,
          g1_w1t, g1_b1t, g1_w2t, g1_w1v, g1_b1v, g1_w2v) = ctx.saved_tensors
         sv = _saved_state(ctx, "HeadLossFn")
@@ -267,7 +267,7 @@ class HeadLossFn(torch.autograd.Function):
                                                   mb_feat_t, mb_feat_v, (w1t, b1t, w2t, w1v, b1v, w2v), dS, d_c0, d_c1, dmean_t,
                                                   dmean_v)
         ctx.sv = ctx.model = None
-        return (None, None, None, None, None, None, None, None, d_text, d_video, d_gt, d_gv, d_ls, *scorer, *g1)
+        return (None,) * 9 + (d_text, d_video, d_gt, d_gv, d_ls, *scorer, *g1)
 
 
 def _global_backward(sv, hp, shapes, gs, g1_params):
@@ -424,17 +424,15 @@ class HeadLocalFn(torch.autograd.Function):
     def forward(ctx, model, hp, bridge, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt, gv, logit_scale,
                 g1, text_feat, video_feat, w1t, b1t, w2t, b2t, w1v, b1v, w2v, b2v):
         prec = model._prec()
-        stepwise = bridge.pop("join", None)       # gt = gv = None: the clustering's launches, a generator driven by the head
-        if stepwise is not None:
-            # the clustering is issued launch by launch on THIS stream, interleaved (in capture order) with the local branch and
-            # the early bank chains on the local stream -- the loss-only step's schedule (head._run_branches)
-            join, gt_in, gv_in = stepwise, None, None
-        else:
-            join, gt_in, gv_in = model._take_join(), gt.detach(), gv.detach()
+        # gt = gv = None: the join is the clustering's launches, a generator driven by the head -- issued launch by launch on THIS
+        # stream, interleaved (in capture order) with the local branch and the early bank chains on the local stream: the
+        # loss-only step's schedule (head._run_branches).  Otherwise it waits for the global tokens (or is None).
+        join, stepwise = bridge.pop("join", None), gt is None
+        gt_in, gv_in = (None, None) if stepwise else (gt.detach(), gv.detach())
         losses, sv = head.head_forward(text_feat.detach(), video_feat.detach(), text_mask, video_mask,
                                        mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt_in, gv_in,
                                        hp=hp, logit_scale=logit_scale.detach(), keep=True,
-                                       **head_args(model, text_feat, video_feat, join, local_stream=stepwise is not None))
+                                       **head_args(model, text_feat, video_feat, join, local_stream=stepwise))
         ctx.sv, ctx.exact = sv, prec == hip.PREC_BF16X3
         ctx.model, ctx.plan = model, head.backward_plan(prec)
         ctx.masks = (text_mask, video_mask)
@@ -483,18 +481,17 @@ SPLIT_HEAD_NODES = True       # False: the head as ONE autograd node (HeadLossFn
 
 
 def head_loss_nodes(model, hp, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, text_feat, video_feat, gt, gv,
-                    logit_scale, scorer_params, g1_params, cluster=None):
+                    logit_scale, scorer_params, g1_params, cluster=None, join=None):
     """The differentiable fused head -> (total, centrality, uniform, neighbour, kl).
     cluster: None (gt / gv are the global tokens, autograd-tracked), or (launches, make_nodes) with gt = gv = None: `launches` a
     generator that issues the token clustering launch by launch and returns (gt, gv) -- HeadLocalFn's forward drives it,
     interleaved with the head's local branch -- and make_nodes() -> (gt, gv) creating the clustering's autograd nodes afterwards
-    (their forwards only wrap what has been computed; see modeling._compute_losses)."""
+    (their forwards only wrap what has been computed; see modeling._route_training_interleaved).  join: with gt / gv given, what
+    the head calls before it reads them (the clustering's stream joins the step's), or None."""
     if not SPLIT_HEAD_NODES:
-        return HeadLossFn.apply(model, hp, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
+        return HeadLossFn.apply(model, hp, join, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
                                 text_feat, video_feat, gt, gv, logit_scale, *scorer_params, *g1_params)
-    bridge = {}
-    if cluster is not None:
-        bridge["join"] = cluster[0]
+    bridge = {"join": cluster[0] if cluster is not None else join}
     S, c0, c1, mean_t, mean_v = HeadLocalFn.apply(model, hp, bridge, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t,
                                                   mb_mask_v, gt, gv, logit_scale, None, text_feat, video_feat, *scorer_params)
     if cluster is not None:

@@ -8,11 +8,13 @@ What the step runs -- the GROUPED stage, text and video in the same seven launch
     cluster_stages_train       the same forward as an autograd node (ClusterStagesFn) with the hand-derived backward
     build_stage_weights        the bf16 pairs of the stages' weights the GEMMs read, one split launch for all stale ones
 The ONE-PROBLEM chain -- ctm_stage_fused: nr_shift_concat -> GEMM -> nr_ctm_front -> nr_ctm_back -> GEMM q, kv ->
-nr_tc_attention -> GEMM proj, eight launches per modality -- is what modeling._merge_one runs (it takes C % 64) and the
-independent implementation tests/test_kernels_gpu.py holds the grouped stage against.
+nr_tc_attention -> GEMM proj, eight launches per modality -- is what modeling._merge_one runs (it takes C % 64) on the
+"two_streams" and "inline" routes of cluster_fused.cluster_route, the one place that decides which of the forms above a step takes,
+and the independent implementation tests/test_kernels_gpu.py holds the grouped stage against.
 """
 import functools
 import math
+from collections import namedtuple
 
 import torch
 
@@ -237,6 +239,58 @@ def grouped_stages_supported(Nt, Nv, C, heads, k=(3, 3, 3, 3)):
     stage0 = [(1, Nt, C, k[0], t0, heads, True, False), (1, Nv, C, k[1], v0, heads, True, False)]
     stage1 = [(1, t0, C, k[2], t1, heads, False, True), (1, v0, C, k[3], v1, heads, False, True)]
     return hip.ctm_stage_plan(stage0) is not None and hip.ctm_stage_plan(stage1) is not None
+
+
+# One clustering stage of the model's four (modeling.NeighborRetr._stages): cache key, CTM and TCBlock modules, key of its noise draw
+Stage = namedtuple("Stage", "key ctm block noise")
+Route = namedtuple("Route", "name sharded_clustering", defaults=(None,))
+
+
+def stage_problems(stages, feats, masks, nz):
+    """ctm_stage_group's problem list of one stage level.  stages: the level's entries of the stage table (text, video); level 0
+    takes the token features and their masks, level 1 the outputs of level 0 and masks = None."""
+    return [(s.key, x, m, s.ctm, s.block, nz.get(s.noise)) for s, x, m in zip(stages, feats, masks or (None,) * len(stages))]
+
+
+def stage_weight_list(stages):
+    """build_stage_weights' list of the given entries of the stage table."""
+    return [(s.key, s.ctm, s.block) for s in stages]
+
+
+def cluster_route(gpu, grad, shard_now, use_side_streams, group_clustering, fuse_clustering, fused_training_clustering,
+                  cluster_side_stream, interleave_training_forward, split_head_nodes, has_local_stream, shard_clustering,
+                  fusable, grouped_ok):
+    """Which way a step runs its token clustering, decided once, on the host -> Route(name[, sharded_clustering]); the model
+    dispatches to its _route_<name> method (modeling.NeighborRetr._compute_losses).  First match wins:
+        sharded_training          shard_now with gradients (neighborretr_amd.sharded)
+        sharded_loss_only         shard_now without; sharded_clustering = shard_clustering: every rank clusters its own samples,
+                                  else the whole batch.  Shapes the gates refuse fall through to the replicated routes below.
+        grouped_steps             loss-only: grouped launches driven step by step from the head (side streams, group_clustering)
+        training_one_stream       training on the grouped kernels, on the step's stream (no stream of the clustering's own)
+        training_interleaved      ... launches interleaved with the head's (interleave_training_forward, split head nodes and a
+                                  local stream)
+        training_cluster_stream   ... on the clustering's own stream
+        two_streams               text and video on two side streams (one-problem kernels or traced modules)
+        inline                    on one stream (and every CPU tensor)
+    fused_training_clustering None means the default, True.  The three last arguments are CALLABLES, asked only where the
+    decision needs them: has_local_stream(); fusable() -- the one-problem gate for both modalities (_can_fuse_clustering) -- and
+    grouped_ok() -- the library's planner (grouped_stages_supported), which raises where fewer tokens than k reach a stage.  A
+    CPU tensor or fuse_clustering = False never asks either gate."""
+    def grouped_forward():
+        return gpu and fuse_clustering and fusable() and grouped_ok()
+    if shard_now and grad:
+        return Route("sharded_training")
+    if shard_now and grouped_forward():
+        return Route("sharded_loss_only", bool(shard_clustering))
+    if gpu and use_side_streams and group_clustering and not grad and grouped_forward():
+        return Route("grouped_steps")
+    if gpu and fuse_clustering and grad and (fused_training_clustering is None or fused_training_clustering) and grouped_ok():
+        if not (use_side_streams and cluster_side_stream):
+            return Route("training_one_stream")
+        if interleave_training_forward and split_head_nodes and has_local_stream():
+            return Route("training_interleaved")
+        return Route("training_cluster_stream")
+    return Route("two_streams" if gpu and use_side_streams else "inline")
 
 
 def ctm_stage_group(problems, cache, stepwise=False, want_assign=False, want_saved=False, exchange=None):

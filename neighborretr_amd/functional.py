@@ -43,8 +43,9 @@ def head_args(model, text_feat, video_feat, join, local_stream, bank=None):
 
 
 def head_losses(model, text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
-                gt, gv, hp, logit_scale, cluster=None):
-    """Returns a [5] tensor (total, centrality, uniform, neighbour, kl)."""
+                gt, gv, hp, logit_scale, join=None, cluster=None):
+    """Returns a [5] tensor (total, centrality, uniform, neighbour, kl).  join / cluster: how the global tokens reach the head
+    when they are not here yet or gt = gv = None (modeling.Clustered)."""
     pt_params = _mlp_params(model, "text_weight_fc")
     pv_params = _mlp_params(model, "video_weight_fc")
     if not torch.is_tensor(logit_scale):
@@ -53,10 +54,10 @@ def head_losses(model, text_feat, video_feat, text_mask, video_mask, mb_feat_t, 
         from .backward import head_loss_nodes
         return head_loss_nodes(model, hp, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
                                text_feat, video_feat, gt, gv, logit_scale, (*pt_params, *pv_params),
-                               (*_mlp_params(model, "text_weight_fc1"), *_mlp_params(model, "video_weight_fc1")), cluster=cluster)
+                               (*_mlp_params(model, "text_weight_fc1"), *_mlp_params(model, "video_weight_fc1")), cluster=cluster, join=join)
     losses, _ = head.head_forward(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt, gv,
                                   hp=hp, logit_scale=logit_scale,
-                                  **head_args(model, text_feat, video_feat, model._take_join(), local_stream=gt is None,
+                                  **head_args(model, text_feat, video_feat, join, local_stream=gt is None,
                                               bank=(mb_feat_t, mb_feat_v)))
     return losses
 

@@ -14,6 +14,7 @@ already -- which is what bench.py, the tests and `main_retrieval.py --synthetic`
 import contextlib
 import math
 import os
+from collections import namedtuple
 from types import SimpleNamespace
 
 import torch
@@ -22,6 +23,8 @@ from torch import nn
 from . import head, hip, ops
 from .capture_guard import wait_stream
 from .cluster import CTM, TCBlock
+from .cluster_fused import (Stage, build_stage_weights, cluster_route, cluster_stages_train, ctm_stage_group, route_on_this_stream,
+                            stage_params, stage_problems, stage_weight_list)
 from .until_module import (AllGather, CentralityWeightingLoss, KLDivergenceLoss, NeighborAdjustingLoss,
                            UniformRegularizationLoss)
 
@@ -143,6 +146,12 @@ class OwnedSlot:
         ops.copy_group(dst, src)                  # one launch (nr_copy_group); torch._foreach_copy_ issues one copy kernel per tensor here
 
 
+# What a route of the clustering (cluster_fused.cluster_route) hands to the head: the global tokens (gt, gv) or (None, None); the join
+# through which the head gets or waits for them (a callable, a generator of launches, or None); (launches, make_nodes) of the
+# interleaved training route or None
+Clustered = namedtuple("Clustered", "tokens join cluster", defaults=((None, None), None, None))
+
+
 class NeighborRetr(nn.Module):
     def __init__(self, config, clip=None, width=512, precision="bf16", with_encoders=False, encoder_dims=None):
         """clip: any module with encode_text / encode_image / logit_scale (e.g. the reference's own CLIP).
@@ -202,7 +211,6 @@ class NeighborRetr(nn.Module):
         self.video_ctm1 = CTM(sample_ratio=1 / 3, embed_dim=width, dim_out=width, k=3)
         self.video_block1 = TCBlock(dim=width, num_heads=8)
         self._scorer_cache = {}
-        self._join_global = None
         self.cluster_side_stream = True      # training step: clustering (forward + backward) on its own stream, see _compute_losses
         self.interleave_training_forward = True   # ... its forward launches interleaved with the head's local branch
         # side streams inside the step (and inside its capture).  With ONE hardware queue (GPU_MAX_HW_QUEUES=1) any capture
@@ -704,158 +712,152 @@ class NeighborRetr(nn.Module):
                         mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
                         centrality_scale, beta, num_neighbors, temperature, logit_scale, noise=None):
         hp = self._hp(centrality_scale, beta, num_neighbors, temperature)
-        from .functional import head_losses
         if noise is None and text_feat.is_cuda:
             noise = self._draw_noise(text_feat.shape[0], text_feat.shape[1], video_feat.shape[1], text_feat.device)
-        mods = tuple(getattr(self, f"{w}_{k}") for w in ("text", "video") for k in ("ctm0", "block0", "ctm1", "block1"))
-        nz = noise or {}
         world = int(getattr(self.config, "world_size", 1))
         shard_now = self._shard_now(world, text_feat, video_tokens=video_feat.shape[1])
-        if shard_now and torch.is_grad_enabled():
-            # training step with the loss sharded over the ranks (neighborretr_amd.sharded)
+        route = self._cluster_route(text_feat, video_feat, shard_now)
+        batch, bank = (text_feat, video_feat, text_mask, video_mask), (mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v)
+        if route.name == "sharded_training":
+            # training step with the loss sharded over the ranks (neighborretr_amd.sharded, which chooses its clustering itself)
             from . import comm
             from .sharded import sharded_training_losses
-            losses = sharded_training_losses(self, text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v,
-                                             mb_mask_t, mb_mask_v, hp, logit_scale, comm.get_rank(), world, noise)
-            return losses[0], losses[1], losses[2], losses[3], losses[4]
-        if (shard_now and not torch.is_grad_enabled()
-                and self._can_fuse_clustering(text_feat, mods) and self._can_fuse_clustering(video_feat, mods)
-                and self._grouped_stages_supported(text_feat, video_feat)):
-            from . import comm
-            # The clustering is sharded by samples too: every rank clusters ITS b samples and the [b, c, d] global tokens are
-            # all-gathered.  Its masked stage fills distances with the maximum over the WHOLE gathered batch
-            # (cluster.py:473-475, `dist_matrix.max()`), so the ranks exchange that maximum (one all-reduce of two floats)
-            # between the stage's front and back kernels -- without it the densities of samples with fewer than k valid
-            # tokens would differ from the replicated result.
-            rank_ = comm.get_rank()
-            if self.shard_clustering:
-                def join():
-                    return self._gather_global(*self._merge_sharded(text_feat, video_feat, text_mask, video_mask, nz, rank_, world), world)
-            else:
-                def join():
-                    return self._merge_grouped(text_feat, video_feat, text_mask, video_mask, nz)
-            # the clustering (+ the gather of the global tokens) runs on THIS stream, the local branch beside it
-            losses = head.head_forward_sharded(text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v,
-                                               mb_mask_t, mb_mask_v, None, None, self.scorer_weights("text_weight_fc"),
-                                               self.scorer_weights("video_weight_fc"), hp, logit_scale, self._prec(),
-                                               rank_, world, bank_prepared=self._bank_shadow(mb_feat_t, mb_feat_v),
-                                               prepared_out=self._last_prepared, join=join,
-                                               local_stream=self._local_stream(text_feat.device),
-                                               **self._global_scorers(text_feat, video_feat))
-            return losses[0], losses[1], losses[2], losses[3], losses[4]
-        if (text_feat.is_cuda and self.use_side_streams and self.group_clustering and not torch.is_grad_enabled()
-                and self._can_fuse_clustering(text_feat, mods) and self._can_fuse_clustering(video_feat, mods)
-                and self._grouped_stages_supported(text_feat, video_feat)):
-            # loss-only step: the text and video clustering advance together inside grouped launches on THIS
-            # stream (the critical path); the local branch runs beside them on a side stream, the two bank
-            # chains beside the Sinkhorn solve (head.head_forward).
-            gt = gv = None
-
-            self._join_global = self._merge_grouped_steps(text_feat, video_feat, text_mask, video_mask, nz)
-        elif (text_feat.is_cuda and self.fuse_clustering and torch.is_grad_enabled()
-              and (self.fused_training_clustering is None or self.fused_training_clustering)
-              and self._grouped_stages_supported(text_feat, video_feat)):
-            # training step: the clustering forward on the grouped HIP kernels, the backward hand-derived from what they
-            # leave in their workspaces (cluster_fused.ClusterStagesFn, cluster_backward.stage_backward)
-            from .cluster_fused import build_stage_weights, cluster_stages_train, route_on_this_stream, stage_params
-            mods0 = ((self.text_ctm0, self.text_block0), (self.video_ctm0, self.video_block0))
-            mods1 = ((self.text_ctm1, self.text_block1), (self.video_ctm1, self.video_block1))
-            side = self._cluster_stream(text_feat.device)
-            routed, (tf_c, vf_c) = ({}, (text_feat, video_feat))
-            if side is not None:
-                # the clustering runs on its own stream: its parameters and the leaf features enter it through one identity
-                # node of THIS stream, so that their gradients are accumulated on this stream (cluster_fused.route_on_this_stream)
-                routed, (tf_c, vf_c) = route_on_this_stream([p for ctm, blk in mods0 + mods1 for p in stage_params(ctm, blk)],
-                                                            (text_feat, video_feat))
-
-            def stages():
-                # the bf16 pairs of all four stages' weights (stale after every optimizer step) in ONE split launch
-                build_stage_weights(self._ctm_cache, [("text0", self.text_ctm0, self.text_block0), ("video0", self.video_ctm0, self.video_block0),
-                                                      ("text1", self.text_ctm1, self.text_block1), ("video1", self.video_ctm1, self.video_block1)])
-                t, v = cluster_stages_train(mods0, self._ctm_cache, ("text0", "video0"), tf_c, text_mask, nz.get("t0"),
-                                            vf_c, video_mask, nz.get("v0"), routed=routed)
-                return cluster_stages_train(mods1, self._ctm_cache, ("text1", "video1"), t, None, nz.get("t1"), v, None, nz.get("v1"),
-                                            routed=routed)
-            from . import backward as _bw
-            if (side is not None and self.interleave_training_forward and _bw.SPLIT_HEAD_NODES
-                    and self._local_stream(text_feat.device) is not None):
-                # The training forward on the loss-only step's schedule: the clustering's launches are set up here (nothing is
-                # issued yet) and driven one by one by the head, interleaved in capture order with its local branch and the
-                # bank chains (459 -> ~340 us for the forward of the captured step: a branch captured behind all of the
-                # clustering started ~200 us late).  The clustering's autograd nodes are created afterwards, on the stream
-                # their backward is to run on; their forwards only wrap the stages' outputs and saved intermediates.
-                from .cluster_fused import ctm_stage_group
-                build_stage_weights(self._ctm_cache, [("text0", self.text_ctm0, self.text_block0), ("video0", self.video_ctm0, self.video_block0),
-                                                      ("text1", self.text_ctm1, self.text_block1), ("video1", self.video_ctm1, self.video_block1)])
-                o0, g0, sv0 = ctm_stage_group([("text0", text_feat, text_mask, *mods0[0], nz.get("t0")),
-                                               ("video0", video_feat, video_mask, *mods0[1], nz.get("v0"))], self._ctm_cache,
-                                              stepwise=True, want_saved=True)
-                o1, g1, sv1 = ctm_stage_group([("text1", o0[0], None, *mods1[0], nz.get("t1")),
-                                               ("video1", o0[1], None, *mods1[1], nz.get("v1"))], self._ctm_cache,
-                                              stepwise=True, want_saved=True)
-
-                def launches():
-                    yield from g0
-                    yield from g1
-                    return o1[0], o1[1]
-
-                def make_nodes():
-                    with torch.cuda.stream(side):
-                        t, v = cluster_stages_train(mods0, self._ctm_cache, ("text0", "video0"), tf_c, text_mask, nz.get("t0"),
-                                                    vf_c, video_mask, nz.get("v0"), pre=((o0[0], o0[1]), sv0), routed=routed)
-                        return cluster_stages_train(mods1, self._ctm_cache, ("text1", "video1"), t, None, nz.get("t1"), v, None,
-                                                    nz.get("v1"), pre=((o1[0], o1[1]), sv1), routed=routed)
-                losses = head_losses(self, text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v,
-                                     None, None, hp, logit_scale, cluster=(launches(), make_nodes))
-                return losses[0], losses[1], losses[2], losses[3], losses[4]
-            if side is None:
-                gt, gv = stages()
-            else:
-                # The clustering is issued on its own stream: in the forward it runs beside the head's local branch (joined
-                # right before the global logits), and -- what matters more -- autograd runs its BACKWARD on that stream too,
-                # beside the backward of the head's token side (backward.HeadLocalFn), once the short HeadGlobalFn node has
-                # produced the gradients of the global tokens.  Fork from / join into the step's stream only.
-                cur = torch.cuda.current_stream()
-                wait_stream(side, cur)
-                with torch.cuda.stream(side):
-                    gt, gv = stages()
-                gt.record_stream(cur)
-                gv.record_stream(cur)
-
-                def join():
-                    wait_stream(cur, side)
-                self._join_global = join
-        elif text_feat.is_cuda and self.use_side_streams:
-            # three independent branches: text clustering | video clustering | local products.
-            # The two clustering branches run on side streams (in a captured HIP graph: parallel
-            # branches) and are joined right before the global logits need them.
-            cur = torch.cuda.current_stream()
-            s_t, s_v = self._side_streams(text_feat.device)
-            tf_c, vf_c = text_feat, video_feat
-            if torch.is_grad_enabled():
-                # leaf features enter the side streams through an identity node of THIS stream: the head's local branch uses
-                # them on this stream as well, and their AccumulateGrad nodes then see one stream (cluster_fused.route_on_this_stream)
-                from .cluster_fused import route_on_this_stream
-                _, (tf_c, vf_c) = route_on_this_stream([], (text_feat, video_feat))
-            wait_stream(s_t, cur)
-            wait_stream(s_v, cur)
-            with torch.cuda.stream(s_t):
-                gt = self._merge_one("text", tf_c, text_mask, nz.get("t0"), nz.get("t1"))
-            with torch.cuda.stream(s_v):
-                gv = self._merge_one("video", vf_c, video_mask, nz.get("v0"), nz.get("v1"))
-            gt.record_stream(cur)
-            gv.record_stream(cur)
-
-            def join():
-                wait_stream(cur, s_t)
-                wait_stream(cur, s_v)
-            self._join_global = join
+            losses = sharded_training_losses(self, *batch, *bank, hp, logit_scale, comm.get_rank(), world, noise)
         else:
-            gt, gv = self.merge_global_features(text_feat, video_feat, text_mask, video_mask, noise)
-        losses = head_losses(self, text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v,
-                             mb_mask_t, mb_mask_v, gt, gv, hp, logit_scale)
-        self._take_join()      # joined by now; never leave a stale closure behind
+            clustered = getattr(self, "_route_" + route.name)(batch, noise or {}, route)
+            losses = (self._sharded_head if route.name == "sharded_loss_only" else self._head)(batch, bank, clustered, hp, logit_scale)
         return losses[0], losses[1], losses[2], losses[3], losses[4]
+
+    def _cluster_route(self, text_feat, video_feat, shard_now):
+        """cluster_route on this model's flags and this step's tensors; the two shape gates go in as callables."""
+        from . import backward
+        return cluster_route(
+            text_feat.is_cuda, torch.is_grad_enabled(), shard_now, self.use_side_streams, self.group_clustering, self.fuse_clustering,
+            self.fused_training_clustering, self.cluster_side_stream, self.interleave_training_forward, backward.SPLIT_HEAD_NODES,
+            lambda: self._local_stream(text_feat.device) is not None, self.shard_clustering,
+            fusable=lambda: self._can_fuse_clustering(text_feat, ()) and self._can_fuse_clustering(video_feat, ()),
+            grouped_ok=lambda: self._grouped_stages_supported(text_feat, video_feat))
+
+    def _head(self, batch, bank, clustered, hp, logit_scale):
+        from .functional import head_losses
+        return head_losses(self, *batch, *bank, *clustered.tokens, hp, logit_scale, join=clustered.join, cluster=clustered.cluster)
+
+    def _sharded_head(self, batch, bank, clustered, hp, logit_scale):
+        from . import comm
+        text_feat, video_feat = batch[:2]
+        # the clustering (+ the gather of the global tokens) runs on THIS stream, the local branch beside it
+        return head.head_forward_sharded(*batch, *bank, None, None, self.scorer_weights("text_weight_fc"),
+                                         self.scorer_weights("video_weight_fc"), hp, logit_scale, self._prec(),
+                                         comm.get_rank(), int(self.config.world_size),
+                                         bank_prepared=self._bank_shadow(bank[0], bank[1]),
+                                         prepared_out=self._last_prepared, join=clustered.join,
+                                         local_stream=self._local_stream(text_feat.device),
+                                         **self._global_scorers(text_feat, video_feat))
+
+    # One method per route of cluster_route -> Clustered: the global tokens or (None, None), the join that produces them / waits for them
+    # (a callable, a generator of launches, or None) and, on the interleaved training route, (launches, make_nodes).
+    def _route_sharded_loss_only(self, batch, nz, route):
+        from . import comm
+        # The clustering is sharded by samples too: every rank clusters ITS b samples and the [b, c, d] global tokens are
+        # all-gathered.  Its masked stage fills distances with the maximum over the WHOLE gathered batch
+        # (cluster.py:473-475, `dist_matrix.max()`), so the ranks exchange that maximum (one all-reduce of two floats)
+        # between the stage's front and back kernels -- without it the densities of samples with fewer than k valid
+        # tokens would differ from the replicated result.
+        rank, world = comm.get_rank(), int(self.config.world_size)
+        if route.sharded_clustering:
+            def join():
+                return self._gather_global(*self._merge_sharded(*batch, nz, rank, world), world)
+        else:
+            def join():
+                return self._merge_grouped(*batch, nz)
+        return Clustered(join=join)
+
+    def _route_grouped_steps(self, batch, nz, route):
+        # loss-only step: the text and video clustering advance together inside grouped launches on THIS
+        # stream (the critical path); the local branch runs beside them on a side stream, the two bank
+        # chains beside the Sinkhorn solve (head.head_forward), which interleaves the generator's launches with the local
+        # branch's, because a captured HIP graph starts its nodes in capture order.
+        return Clustered(join=self._two_stages(*batch, nz, stepwise=True))
+
+    def _routed_for_training(self, text_feat, video_feat):
+        """(cluster stream or None, routed parameters, (text_feat, video_feat) as the clustering is to read them) of the
+        training routes on the grouped kernels."""
+        side = self._cluster_stream(text_feat.device)
+        if side is None:
+            return None, {}, (text_feat, video_feat)
+        # the clustering runs on its own stream: its parameters and the leaf features enter it through one identity
+        # node of THIS stream, so that their gradients are accumulated on this stream (cluster_fused.route_on_this_stream)
+        routed, feats = route_on_this_stream([p for s in self._stages() for p in stage_params(s.ctm, s.block)], (text_feat, video_feat))
+        return side, routed, feats
+
+    def _route_training_one_stream(self, batch, nz, route):
+        _, routed, feats = self._routed_for_training(*batch[:2])
+        return Clustered(self._stages_train(feats, batch[2:], nz, routed=routed, build_all=True))
+
+    def _route_training_cluster_stream(self, batch, nz, route):
+        # The clustering is issued on its own stream: in the forward it runs beside the head's local branch (joined
+        # right before the global logits), and -- what matters more -- autograd runs its BACKWARD on that stream too,
+        # beside the backward of the head's token side (backward.HeadLocalFn), once the short HeadGlobalFn node has
+        # produced the gradients of the global tokens.  Fork from / join into the step's stream only.
+        side, routed, feats = self._routed_for_training(*batch[:2])
+        cur = torch.cuda.current_stream()
+        wait_stream(side, cur)
+        with torch.cuda.stream(side):
+            gt, gv = self._stages_train(feats, batch[2:], nz, routed=routed, build_all=True)
+        gt.record_stream(cur)
+        gv.record_stream(cur)
+        return Clustered((gt, gv), lambda: wait_stream(cur, side))
+
+    def _route_training_interleaved(self, batch, nz, route):
+        # The training forward on the loss-only step's schedule: the clustering's launches are set up here (nothing is
+        # issued yet) and driven one by one by the head, interleaved in capture order with its local branch and the
+        # bank chains (459 -> ~340 us for the forward of the captured step: a branch captured behind all of the
+        # clustering started ~200 us late).  The clustering's autograd nodes are created afterwards, on the stream
+        # their backward is to run on; their forwards only wrap the stages' outputs and saved intermediates.
+        side, routed, feats = self._routed_for_training(*batch[:2])
+        stages = self._stages()
+        build_stage_weights(self._ctm_cache, stage_weight_list(stages))
+        o0, g0, sv0 = ctm_stage_group(stage_problems(stages[:2], batch[:2], batch[2:], nz), self._ctm_cache, stepwise=True, want_saved=True)
+        o1, g1, sv1 = ctm_stage_group(stage_problems(stages[2:], o0, None, nz), self._ctm_cache, stepwise=True, want_saved=True)
+
+        def launches():
+            yield from g0
+            yield from g1
+            return o1[0], o1[1]
+
+        def make_nodes():
+            with torch.cuda.stream(side):
+                return self._stages_train(feats, batch[2:], nz, pre=(((o0[0], o0[1]), sv0), ((o1[0], o1[1]), sv1)), routed=routed)
+        return Clustered(cluster=(launches(), make_nodes))
+
+    def _route_two_streams(self, batch, nz, route):
+        # three independent branches: text clustering | video clustering | local products.
+        # The two clustering branches run on side streams (in a captured HIP graph: parallel
+        # branches) and are joined right before the global logits need them.
+        text_feat, video_feat, text_mask, video_mask = batch
+        cur = torch.cuda.current_stream()
+        s_t, s_v = self._side_streams(text_feat.device)
+        tf_c, vf_c = text_feat, video_feat
+        if torch.is_grad_enabled():
+            # leaf features enter the side streams through an identity node of THIS stream: the head's local branch uses
+            # them on this stream as well, and their AccumulateGrad nodes then see one stream (cluster_fused.route_on_this_stream)
+            _, (tf_c, vf_c) = route_on_this_stream([], (text_feat, video_feat))
+        wait_stream(s_t, cur)
+        wait_stream(s_v, cur)
+        with torch.cuda.stream(s_t):
+            gt = self._merge_one("text", tf_c, text_mask, nz.get("t0"), nz.get("t1"))
+        with torch.cuda.stream(s_v):
+            gv = self._merge_one("video", vf_c, video_mask, nz.get("v0"), nz.get("v1"))
+        gt.record_stream(cur)
+        gv.record_stream(cur)
+
+        def join():
+            wait_stream(cur, s_t)
+            wait_stream(cur, s_v)
+        return Clustered((gt, gv), join)
+
+    def _route_inline(self, batch, nz, route):
+        return Clustered(self.merge_global_features(*batch, nz))
 
     @contextlib.contextmanager
     def graph_capture_mode(self):
@@ -902,38 +904,50 @@ class NeighborRetr(nn.Module):
         return (self._merge_one("text", text_feat, text_mask, nz.get("t0"), nz.get("t1")),
                 self._merge_one("video", video_feat, video_mask, nz.get("v0"), nz.get("v1")))
 
-    def _merge_grouped_steps(self, text_feat, video_feat, text_mask, video_mask, nz):
-        """The two grouped clustering stages as a generator that issues ONE kernel launch per next() (on the
-        then-current stream) and returns (gt, gv): head.head_forward interleaves these launches with the local
-        branch's, because a captured HIP graph starts its nodes in capture order."""
-        from .cluster_fused import ctm_stage_group
-        (t, v), steps = ctm_stage_group(
-            [("text0", text_feat, text_mask, self.text_ctm0, self.text_block0, nz.get("t0")),
-             ("video0", video_feat, video_mask, self.video_ctm0, self.video_block0, nz.get("v0"))], self._ctm_cache, stepwise=True)
-        yield from steps
-        (t, v), steps = ctm_stage_group(
-            [("text1", t, None, self.text_ctm1, self.text_block1, nz.get("t1")),
-             ("video1", v, None, self.video_ctm1, self.video_block1, nz.get("v1"))], self._ctm_cache, stepwise=True)
-        yield from steps
-        return t, v
+    def _stages(self):
+        """THE table of the four clustering stages, in the order every grouped call lists them: text0, video0, text1, video1."""
+        return (Stage("text0", self.text_ctm0, self.text_block0, "t0"), Stage("video0", self.video_ctm0, self.video_block0, "v0"),
+                Stage("text1", self.text_ctm1, self.text_block1, "t1"), Stage("video1", self.video_ctm1, self.video_block1, "v1"))
+
+    def _two_stages(self, text_feat, video_feat, text_mask, video_mask, nz, stepwise=False, exchange=None):
+        """THE no-grad forward of both modalities through the two clustering stages in grouped launches, on the rows it is
+        given, as a generator that returns (gt, gv) (head.exhaust runs it to its end).  stepwise: ONE kernel launch per
+        next(), on the then-current stream; otherwise nothing is yielded.  exchange: see ctm_stage_group (the masked stage)."""
+        stages, out, masks = self._stages(), (text_feat, video_feat), (text_mask, video_mask)
+        for pair in (stages[:2], stages[2:]):
+            out = ctm_stage_group(stage_problems(pair, out, masks, nz), self._ctm_cache, stepwise=stepwise, exchange=exchange)
+            if stepwise:
+                out, steps = out
+                yield from steps
+            masks = exchange = None
+        return out[0], out[1]
+
+    def _stages_train(self, feats, masks, nz, exchange=None, pre=(None, None), routed=None, build_all=False):
+        """Both modalities through the two stages for the training step: the forward on the grouped HIP kernels, the backward
+        hand-derived from what they leave in their workspaces (cluster_fused.ClusterStagesFn, cluster_backward.stage_backward).
+        exchange: for the masked stage; pre: per stage, what ClusterStagesFn takes as already issued; routed:
+        route_on_this_stream's map; build_all: the bf16 pairs of all four stages' weights (stale after every optimizer step) in
+        ONE split launch first."""
+        stages, out = self._stages(), feats
+        if build_all:
+            build_stage_weights(self._ctm_cache, stage_weight_list(stages))
+        for (s_t, s_v), p in zip((stages[:2], stages[2:]), pre):
+            m_t, m_v = masks or (None, None)
+            out = cluster_stages_train(((s_t.ctm, s_t.block), (s_v.ctm, s_v.block)), self._ctm_cache, (s_t.key, s_v.key),
+                                       out[0], m_t, nz.get(s_t.noise), out[1], m_v, nz.get(s_v.noise), exchange=exchange, pre=p,
+                                       routed=routed)
+            masks = exchange = None
+        return out
 
     def _merge_grouped(self, text_feat, video_feat, text_mask, video_mask, nz):
         """Both modalities through the two clustering stages in grouped launches (no-grad forward)."""
-        from .cluster_fused import ctm_stage_group
-        t, v = ctm_stage_group([("text0", text_feat, text_mask, self.text_ctm0, self.text_block0, nz.get("t0")),
-                                ("video0", video_feat, video_mask, self.video_ctm0, self.video_block0, nz.get("v0"))],
-                               self._ctm_cache)
-        t, v = ctm_stage_group([("text1", t, None, self.text_ctm1, self.text_block1, nz.get("t1")),
-                                ("video1", v, None, self.video_ctm1, self.video_block1, nz.get("v1"))],
-                               self._ctm_cache)
-        return t, v
+        return head.exhaust(self._two_stages(text_feat, video_feat, text_mask, video_mask, nz))
 
     def _merge_sharded(self, text_feat, video_feat, text_mask, video_mask, nz, rank, world):
         """Both clustering stages on THIS rank's samples of the gathered batch (rows [rank b, (rank+1) b)) -> the rank's
         global tokens (gt [b,c,d], gv [b,c,d]); differentiable when gradients are enabled (ClusterStagesFn).  The noise rows
         are the rank's rows of the batch-wide draw, so the result equals the rank's rows of the replicated clustering."""
         from . import comm
-        from .cluster_fused import cluster_stages_train, ctm_stage_group
         b = text_feat.shape[0] // world
         rows = slice(rank * b, (rank + 1) * b)
         tf, vf = text_feat[rows].contiguous(), video_feat[rows].contiguous()
@@ -945,18 +959,9 @@ class NeighborRetr(nn.Module):
             comm.all_reduce(g, op="max")
             for s_, v in zip(smax, g):
                 s_[:1] = v
-        mods0 = ((self.text_ctm0, self.text_block0), (self.video_ctm0, self.video_block0))
-        mods1 = ((self.text_ctm1, self.text_block1), (self.video_ctm1, self.video_block1))
         if torch.is_grad_enabled():
-            t, v = cluster_stages_train(mods0, self._ctm_cache, ("text0", "video0"), tf, tm, n.get("t0"), vf, vm, n.get("v0"),
-                                        exchange=exchange)
-            return cluster_stages_train(mods1, self._ctm_cache, ("text1", "video1"), t, None, n.get("t1"), v, None, n.get("v1"))
-        t, v = ctm_stage_group([("text0", tf, tm, self.text_ctm0, self.text_block0, n.get("t0")),
-                                ("video0", vf, vm, self.video_ctm0, self.video_block0, n.get("v0"))], self._ctm_cache,
-                               exchange=exchange)
-        t, v = ctm_stage_group([("text1", t, None, self.text_ctm1, self.text_block1, n.get("t1")),
-                                ("video1", v, None, self.video_ctm1, self.video_block1, n.get("v1"))], self._ctm_cache)
-        return t, v
+            return self._stages_train((tf, vf), (tm, vm), n, exchange=exchange)
+        return head.exhaust(self._two_stages(tf, vf, tm, vm, n, exchange=exchange))
 
     @staticmethod
     def _gather_global(gt, gv, world):
@@ -976,23 +981,22 @@ class NeighborRetr(nn.Module):
 
     def _merge_one(self, which, feat, mask, noise0=None, noise1=None):
         """Two CTM + TCBlock stages of one modality: [B,N,d] -> [B,1,d] at the MSR-VTT token counts."""
-        ctm0, blk0 = getattr(self, which + "_ctm0"), getattr(self, which + "_block0")
-        ctm1, blk1 = getattr(self, which + "_ctm1"), getattr(self, which + "_block1")
-        if self._can_fuse_clustering(feat, (ctm0, blk0, ctm1, blk1)):
+        s0, s1 = (s for s in self._stages() if s.key.startswith(which))
+        if self._can_fuse_clustering(feat, (s0.ctm, s0.block, s1.ctm, s1.block)):
             from .cluster_fused import ctm_stage_fused
-            t = ctm_stage_fused(feat, mask, ctm0, blk0, noise0, self._ctm_cache, which + "0")
-            return ctm_stage_fused(t, None, ctm1, blk1, noise1, self._ctm_cache, which + "1")
-        t = blk0(ctm0({"x": feat, "mask": mask.detach()}, noise0))
-        return blk1(ctm1(t, noise1))["x"]
+            t = ctm_stage_fused(feat, mask, s0.ctm, s0.block, noise0, self._ctm_cache, s0.key)
+            return ctm_stage_fused(t, None, s1.ctm, s1.block, noise1, self._ctm_cache, s1.key)
+        t = s0.block(s0.ctm({"x": feat, "mask": mask.detach()}, noise0))
+        return s1.block(s1.ctm(t, noise1))["x"]
 
     def _grouped_stages_supported(self, text_feat, video_feat):
         """Whether the GROUPED stage (ctm_stage_group / cluster_stages_train) takes these token counts and this width: the
         library's planner answers (cluster_fused.grouped_stages_supported, memoised).  Shapes only -- flags, gradients, device
         and streams are the caller's conditions."""
         from .cluster_fused import grouped_stages_supported
-        ks = tuple(int(getattr(self, n).k) for n in ("text_ctm0", "video_ctm0", "text_ctm1", "video_ctm1"))
+        stages = self._stages()
         return grouped_stages_supported(text_feat.shape[1], video_feat.shape[1], text_feat.shape[2],
-                                        int(self.text_block0.attn.num_heads), ks)
+                                        int(stages[0].block.attn.num_heads), tuple(int(s.ctm.k) for s in stages))
 
     def _can_fuse_clustering(self, feat, mods):
         """The ONE-PROBLEM fused forward (ctm_stage_fused, which takes C % 64) when no gradient is wanted; autograd-traced torch
@@ -1099,10 +1103,6 @@ class NeighborRetr(nn.Module):
             return None
         from . import streams
         return tuple(streams.side(self, self._sname(n), device) for n in ("bank0", "bank1", "push"))      # two bank chains + the bank push
-
-    def _take_join(self):
-        j, self._join_global = self._join_global, None
-        return j
 
     # ------------------------------------------------------------------ similarity API
     def local_level(self, text_feat, video_feat, text_mask, video_mask):

@@ -103,14 +103,14 @@ def _model(K, **cfg):
     return m.train()
 
 
-def _loss_only(seed, B, Nt, Nv, M, K, frozen=False, side_streams=True, **cfg):
+def _loss_only(seed, B, Nt, Nv, M, K, frozen=False, side_streams=True, group=True, **cfg):
     """A model with its bank filled as test_a_failing_bank_push_does_not_poison_later_steps does -> step(): the five losses."""
     x = problem(seed, B, Nt, Nv, M, device=DEV)
     m = _model(K, **cfg)
     for k in ("mb_feat_t", "mb_feat_v", "mb_mask_t", "mb_mask_v"):
         setattr(m, k, x[k].clone().float() if "mask" in k else x[k].clone())
     m.mb_ind = torch.arange(M, device=DEV)
-    m.bank_frozen, m.use_side_streams = frozen, side_streams
+    m.bank_frozen, m.use_side_streams, m.group_clustering = frozen, side_streams, group
 
     def step():
         m._rng_state = None
@@ -147,8 +147,8 @@ def _pipelined(seed, B, Nt, Nv, M, K, U=2):
     return m, steps
 
 
-def _training(fused):
-    """The forward of test_backward_matches_reference at c1_b16, shipping precision plan."""
+def _training(fused, **flags):
+    """The forward of test_backward_matches_reference at c1_b16, shipping precision plan.  flags: model attributes to set."""
     g = golden("c1_b16")
     B, Nt, Nv, M, K = (int(g[k]) for k in ("B", "Nt", "Nv", "M", "K"))
     x = problem(int(g["seed"]), B, Nt, Nv, M, device=DEV)
@@ -156,6 +156,8 @@ def _training(fused):
     m = _model(K)
     if not fused:
         m.fused_training_clustering = False
+    for k, v in flags.items():
+        setattr(m, k, v)
     x["text_feat"].requires_grad_(True)
     x["video_feat"].requires_grad_(True)
     c = m.config
@@ -165,6 +167,32 @@ def _training(fused):
                                    x["mb_mask_t"], x["mb_mask_v"], c.centrality_scale, c.beta, K, c.temperature,
                                    m.clip.logit_scale.exp(), noise=nz)
         return [torch.stack([l.detach() for l in losses])]
+    return m, step
+
+
+def _sharded_loss_only(seed, B, Nt, Nv, M, K, shard_clustering, W=2, rank=1):
+    """Rank `rank` of a W-rank loss-only step with the loss sharded, in an emulated world without a process group (the peers'
+    parts of every collective are device copies): the first step() settles the world over all ranks, every step() runs the
+    rank.  The bank stays frozen, so that every rank of every sweep sees the same one."""
+    from neighborretr_amd import comm
+    x = problem(seed, B, Nt, Nv, M, device=DEV)
+    m, _ = _loss_only(seed, B, Nt, Nv, M, K, frozen=True, world_size=W)
+    m.shard_loss, m.shard_clustering = True, shard_clustering
+    world, b = comm.EmulatedWorld(W, real_collectives=False), B // W
+
+    def run(r):
+        m.config.local_rank = r
+        m._rng_state = None                            # (every rank of a real job draws the same batch-wide noise)
+        torch.manual_seed(5)
+        sl = slice(r * b, (r + 1) * b)
+        with comm.use(world.comm(r)), torch.no_grad():
+            return torch.stack(m(x["text_feat"][sl].contiguous(), x["text_mask"][sl].contiguous(), x["video_feat"][sl].contiguous(),
+                                 x["video_mask"][sl].contiguous(), x["idx"][sl].contiguous(), 0))
+
+    def step():
+        if world.recording:
+            world.settle(run)
+        return [run(rank)]
     return m, step
 
 
@@ -179,6 +207,12 @@ FORMS = {
     "paired_batch_scorers": lambda: _loss_only(1005, 128, 64, 64, 64, 20, centrality_multi_token="mean"),
     "training_interleaved": lambda: _training(True),
     "training_traced_clustering": lambda: _training(False),
+    # the routes of cluster_fused.cluster_route that no form above reaches
+    "training_cluster_stream": lambda: _training(True, interleave_training_forward=False),
+    "training_one_stream": lambda: _training(True, cluster_side_stream=False),
+    "loss_only_two_cluster_streams": lambda: _loss_only(1005, 32, 24, 12, 64, 8, group=False),
+    "sharded_loss_only": lambda: _sharded_loss_only(1005, 32, 24, 12, 64, 8, shard_clustering=True),
+    "sharded_loss_only_replicated_clustering": lambda: _sharded_loss_only(1005, 32, 24, 12, 64, 8, shard_clustering=False),
 }
 
 

@@ -1,7 +1,8 @@
 """GPU: the launch schedule of every step form -- which C-ABI entries, in which order, on which streams, with which wait edges
 and how many record_stream calls per stream -- equals the schedule recorded from the commit before the head's orchestration was
-split into phases (tests/head_schedule_ref.py), and the losses are the same bits.  Losses alone cannot see a branch that is
-issued late; a captured graph starts its nodes in the order they were issued."""
+split into phases (tests/head_schedule_ref.py; the last five forms, one per remaining route of cluster_fused.cluster_route, from
+the commit before the route plan), and the losses are the same bits.  Losses alone cannot see a branch that is issued late; a
+captured graph starts its nodes in the order they were issued."""
 import pytest
 
 import head_schedule_ref as REF
