@@ -56,7 +56,7 @@ __global__ __launch_bounds__(NR_CAND_WAVES * 64) void nr_cand_localscale_rerank_
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int j = 4 * g + e;
-                if (j < cnt) sum = j ? __fadd_rn(sum, v[e]) : v[e];        // the sum starts from the first value
+                if (j < cnt) sum = j ? nr_rn_add(sum, v[e]) : v[e];        // the sum starts from the first value
             }
         }
         q_mean = __fdiv_rn(sum, (float)cnt);

@@ -10,15 +10,11 @@
 // The top-1 is a wave reduction on (key, position); one placement against the corrected scores' keys in LDS gives the output.  A
 // query's output depends on its own line only.
 #include "nr_cand_line.h"
+#include "nr_round.h"
 #include "../../include/nr_hip.h"
 
-// fl(fl(beta f) - c): two roundings.  The pragma keeps the compiler from contracting the pair into one fused multiply-add
-// (__fmul_rn / __fsub_rn are plain operators to it), so NumPy float32 gives the same bits.
-__device__ __forceinline__ float nr_cn_is(float beta, float f, float c) {
-#pragma clang fp contract(off)
-    const float b = beta * f;
-    return b - c;
-}
+// fl(fl(beta f) - c): two roundings (nr_round.h), so NumPy float32 gives the same bits.
+__device__ __forceinline__ float nr_cn_is(float beta, float f, float c) { return nr_rn_sub(nr_rn_mul(beta, f), c); }
 
 // (key, position) of the better of two slots: larger key, equal keys by lower position
 template <int CTRL, int ROW_MASK>

@@ -1,6 +1,8 @@
-// Online (max, sum) log-sum-exp pairs shared by the test-time normalisation kernels (nr_hubnorm.hip, nr_sinknorm.hip).
+// Online (max, sum) log-sum-exp pairs shared by the test-time normalisation kernels (nr_hubnorm.hip, nr_sinknorm.hip).  Every
+// operation says how it is rounded (nr_round.h): a difference of maxima and a sum are values of their own, the rescaled sum is one
+// fused multiply-add.
 #pragma once
-#include "nr_common.h"
+#include "nr_round.h"
 
 #define NR_HN_ROWS 64          // rows per column-partial block: the workspace holds ceil(n / 64) pairs per column
 
@@ -10,18 +12,18 @@ __device__ __forceinline__ void nr_hn_merge(float& m, float& s, float m2, float 
     if (s2 == 0.f) return;                       // an empty pair (no entry)
     if (s == 0.f) { m = m2; s = s2; return; }
     if (m2 > m) {
-        s = s2 + s * expf(m - m2);
+        s = fmaf(s, expf(nr_rn_sub(m, m2)), s2);
         m = m2;
     } else if (m2 == m) {
-        s = s + s2;
+        s = nr_rn_add(s, s2);
     } else {
-        s = s + s2 * expf(m2 - m);
+        s = fmaf(s2, expf(nr_rn_sub(m2, m)), s);
     }
 }
 
 __device__ __forceinline__ void nr_hn_add(float& m, float& s, float beta, float x) {
     if (x != x) return;                          // NaN: skipped
-    nr_hn_merge(m, s, __fmul_rn(beta, x), 1.f);
+    nr_hn_merge(m, s, nr_rn_mul(beta, x), 1.f);
 }
 
-__device__ __forceinline__ float nr_hn_lse(float m, float s) { return s > 0.f ? m + logf(s) : -INFINITY; }
+__device__ __forceinline__ float nr_hn_lse(float m, float s) { return s > 0.f ? nr_rn_add(m, logf(s)) : -INFINITY; }

@@ -9,6 +9,7 @@
 // Every operation is rounded once (no fused multiply-add), NaN passes through every max, the sum of a list has a fixed order:
 // the same inputs give the same bits, whatever the slab split.  No scratch, no float atomics, no hand-off between workgroups.
 #include "nr_localscale.h"
+#include "nr_slab.h"
 
 #define NR_LS_K_MAX 128                          // the longest list nr_topk.hip writes
 
@@ -24,7 +25,7 @@ __global__ __launch_bounds__(256) void nr_localscale_stats_kernel(const int32_t*
     for (int e = 0; e < k; ++e) {
         if (li[e] < 0) continue;                 // an absent slot
         const float x = lv[e];
-        sum = c ? __fadd_rn(sum, x) : x;         // the sum starts from the first present value
+        sum = c ? nr_rn_add(sum, x) : x;           // the sum starts from the first present value
         last = x;
         ++c;
     }
@@ -43,49 +44,29 @@ extern "C" int nr_localscale_stats(const int32_t* idx, const float* val, int n, 
     return NR_OK;
 }
 
-// ---- apply: one read of S, one write of T -------------------------------------------------------------------------------------
+// ---- apply: one read of S, one write of T (the loop is nr_slab.h's) -----------------------------------------------------------------
 // The formulas are nr_localscale.h's with the mode a compile-time constant; the row's operand (a[i] for nicdm / ls) is taken once
 // per group.
-template <int MODE, int VEC>
-__global__ __launch_bounds__(256) void nr_localscale_apply_kernel(const float* __restrict__ S, int n, int L,
-                                                                 const float* __restrict__ row_stat,
-                                                                 const float* __restrict__ col_stat, float* __restrict__ T) {
-    const long long n_groups = (long long)n * L / VEC;
-    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += (long long)gridDim.x * 256) {
-        const long long e0 = g * VEC;
-        const int i = (int)(e0 / L);
-        const int j0 = (int)(e0 - (long long)i * L);         // VEC == 4: L % 4 == 0, the group lies in one row
-        const float r = nr_ls_operand(MODE, row_stat[i]);
-        if (VEC == 4) {
-            const f32x4_t x = *reinterpret_cast<const f32x4_t*>(S + e0);
-            const f32x4_t c = *reinterpret_cast<const f32x4_t*>(col_stat + j0);
-            f32x4_t t;
+template <int MODE>
+struct nr_ls_apply {
+    static constexpr int OUTS = 1;
+    const float* row_stat;
+    const float* col_stat;
+    __device__ float row(int i) const { return nr_ls_operand(MODE, row_stat[i]); }
+    template <int VEC>
+    __device__ void values(int, const float (&s)[VEC], float r, int j0, long long, float (&t)[VEC]) const {
+        float c[VEC];
+        nr_slab_load<VEC>(col_stat + j0, c);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) t[q] = nr_ls_score(MODE, x[q], r, nr_ls_operand(MODE, c[q]));
-            *reinterpret_cast<f32x4_t*>(T + e0) = t;
-        } else {
-            T[e0] = nr_ls_score(MODE, S[e0], r, nr_ls_operand(MODE, col_stat[j0]));
-        }
+        for (int q = 0; q < VEC; ++q) t[q] = nr_ls_score(MODE, s[q], r, nr_ls_operand(MODE, c[q]));
     }
-}
+};
 
 template <int MODE>
 static int nr_localscale_apply_launch(const float* S, int n, int L, const float* row_stat, const float* col_stat, float* T,
                                       void* stream) {
-    const bool vec = (L % 4 == 0) && ((uintptr_t)S % 16 == 0) && ((uintptr_t)T % 16 == 0) && ((uintptr_t)col_stat % 16 == 0);
-    const long long groups = (long long)n * L / (vec ? 4 : 1);
-    const unsigned blocks = (unsigned)std::min<long long>((groups + 255) / 256, 16384);
-    if (vec) {
-        hipLaunchKernelGGL((nr_localscale_apply_kernel<MODE, 4>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, n, L, row_stat,
-                           col_stat, T);
-    } else {
-        hipLaunchKernelGGL((nr_localscale_apply_kernel<MODE, 1>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, n, L, row_stat,
-                           col_stat, T);
-    }
-    NR_LAUNCH_CHECK();
-    return NR_OK;
+    return nr_slab_apply<nr_ls_apply<MODE>>(S, n, L, T, nullptr, {col_stat}, stream, row_stat, col_stat);
 }
-
 extern "C" int nr_localscale_apply(const float* S, int n, int L, int mode, const float* row_stat, const float* col_stat, float* T,
                                    void* stream) {
     if (!S || !row_stat || !col_stat || !T) return NR_EINVAL;

@@ -8,16 +8,8 @@
 //
 // The counts are integers (no order of summation), every float operation is rounded once (no fused multiply-add), the moments are
 // accumulated in fp64 in a fixed order.  No scratch, no float atomics, no hand-off between workgroups.
-#include "nr_common.h"
+#include "nr_slab.h"
 #include "../../include/nr_hip.h"
-
-// Every float operation of this file is rounded on its own.  hipcc's __fmul_rn / __fadd_rn / __fsub_rn are plain operators
-// compiled under the default contraction, which fuses them once they are inlined (the last step of gauss became an fma): the
-// three below are compiled with contraction off instead.
-#pragma clang fp contract(off)
-__device__ __forceinline__ float nr_mp_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float nr_mp_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float nr_mp_sub(float a, float b) { return a - b; }
 
 #define NR_MP_TILE 16                            // scores a lane keeps in registers while the reference values stream past
 #define NR_MP_ROW_CHUNK 1024                     // floats of a reference row staged through LDS at a time
@@ -189,50 +181,43 @@ extern "C" int nr_mp_line_counts(const float* R, int n, int Lr, int32_t* row_cnt
     return NR_OK;
 }
 
-// ---- the two applies: one read of every input, one write of T ------------------------------------------------------------------
+// ---- the two applies: one read of every input, one write of T (emp's loop is nr_slab.h's) ----------------------------------------
 __device__ __forceinline__ float nr_mp_emp_score(float s, int r2, float row_den, int c2, int col_cnt) {
     const float p = __fdiv_rn((float)r2, row_den);
     const float q = __fdiv_rn((float)c2, (float)(2 * col_cnt));
-    return s != s ? s : nr_mp_mul(p, q);
+    return s != s ? s : nr_rn_mul(p, q);
 }
 
 __device__ __forceinline__ float nr_mp_tail(float s, float mean, float sd) {
-    const float z = __fdiv_rn(nr_mp_sub(s, mean), nr_floor(sd, NR_SCALE_EPS));
-    return nr_mp_mul(0.5f, erfcf(nr_mp_mul(z, NR_MP_RSQRT2)));
+    const float z = __fdiv_rn(nr_rn_sub(s, mean), nr_floor(sd, NR_SCALE_EPS));
+    return nr_rn_mul(0.5f, erfcf(nr_rn_mul(z, NR_MP_RSQRT2)));
 }
 
 __device__ __forceinline__ float nr_mp_gauss_score(float s, float rm, float rs, float cm, float cs) {
     const float a = nr_mp_tail(s, rm, rs), b = nr_mp_tail(s, cm, cs);
-    return -nr_mp_sub(nr_mp_add(a, b), nr_mp_mul(a, b));
+    return -nr_rn_sub(nr_rn_add(a, b), nr_rn_mul(a, b));
 }
 
-typedef __attribute__((ext_vector_type(4))) int nr_i32x4_t;
-
-template <int VEC>
-__global__ __launch_bounds__(256) void nr_mp_emp_apply_kernel(const float* __restrict__ S, int n, int L, const int32_t* __restrict__ r2,
-                                                              const int32_t* __restrict__ c2, const int32_t* __restrict__ row_cnt,
-                                                              const int32_t* __restrict__ col_cnt, float* __restrict__ T) {
-    const long long n_groups = (long long)n * L / VEC;
-    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += (long long)gridDim.x * 256) {
-        const long long e0 = g * VEC;
-        const int i = (int)(e0 / L);
-        const int j0 = (int)(e0 - (long long)i * L);         // VEC == 4: L % 4 == 0, the group lies in one row
-        const float row_den = (float)(2 * row_cnt[i]);
-        if (VEC == 4) {
-            const f32x4_t x = *reinterpret_cast<const f32x4_t*>(S + e0);
-            const nr_i32x4_t a = *reinterpret_cast<const nr_i32x4_t*>(r2 + e0);
-            const nr_i32x4_t b = *reinterpret_cast<const nr_i32x4_t*>(c2 + e0);
-            const nr_i32x4_t c = *reinterpret_cast<const nr_i32x4_t*>(col_cnt + j0);
-            f32x4_t t;
+struct nr_mp_emp {
+    static constexpr int OUTS = 1;
+    const int32_t* r2;
+    const int32_t* c2;
+    const int32_t* row_cnt;
+    const int32_t* col_cnt;
+    __device__ float row(int i) const { return (float)(2 * row_cnt[i]); }
+    template <int VEC>
+    __device__ void values(int, const float (&s)[VEC], float row_den, int j0, long long e0, float (&t)[VEC]) const {
+        int32_t a[VEC], b[VEC], c[VEC];
+        nr_slab_load<VEC>(r2 + e0, a);
+        nr_slab_load<VEC>(c2 + e0, b);
+        nr_slab_load<VEC>(col_cnt + j0, c);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) t[q] = nr_mp_emp_score(x[q], a[q], row_den, b[q], c[q]);
-            *reinterpret_cast<f32x4_t*>(T + e0) = t;
-        } else {
-            T[e0] = nr_mp_emp_score(S[e0], r2[e0], row_den, c2[e0], col_cnt[j0]);
-        }
+        for (int q = 0; q < VEC; ++q) t[q] = nr_mp_emp_score(s[q], a[q], row_den, b[q], c[q]);
     }
-}
+};
 
+// gauss stays written out: on the skeleton the same operations were scheduled with four more registers and ten more hazard nops,
+// 4-5 % slower (the kernel is the one apply that is bound by its arithmetic, two erfc per entry, not by memory).
 template <int VEC>
 __global__ __launch_bounds__(256) void nr_mp_gauss_apply_kernel(const float* __restrict__ S, int n, int L, const float* __restrict__ row_mean,
                                                                 const float* __restrict__ row_sd, const float* __restrict__ col_mean,
@@ -257,25 +242,12 @@ __global__ __launch_bounds__(256) void nr_mp_gauss_apply_kernel(const float* __r
     }
 }
 
-static bool nr_mp_aligned(const void* p) { return (uintptr_t)p % 16 == 0; }
-static unsigned nr_mp_apply_blocks(long long groups) { return (unsigned)std::min<long long>((groups + 255) / 256, 16384); }
-
 extern "C" int nr_mp_emp_apply(const float* S, int n, int L, const int32_t* r2, const int32_t* c2, const int32_t* row_cnt,
                                const int32_t* col_cnt, float* T, void* stream) {
     if (!S || !r2 || !c2 || !row_cnt || !col_cnt || !T) return NR_EINVAL;
     if (n < 0 || L < 0) return NR_EINVAL;
     if (n == 0 || L == 0) return NR_OK;
-    const bool vec = (L % 4 == 0) && nr_mp_aligned(S) && nr_mp_aligned(r2) && nr_mp_aligned(c2) && nr_mp_aligned(col_cnt) && nr_mp_aligned(T);
-    const long long groups = (long long)n * L / (vec ? 4 : 1);
-    if (vec) {
-        hipLaunchKernelGGL(nr_mp_emp_apply_kernel<4>, dim3(nr_mp_apply_blocks(groups)), dim3(256), 0, (hipStream_t)stream, S, n, L, r2, c2,
-                           row_cnt, col_cnt, T);
-    } else {
-        hipLaunchKernelGGL(nr_mp_emp_apply_kernel<1>, dim3(nr_mp_apply_blocks(groups)), dim3(256), 0, (hipStream_t)stream, S, n, L, r2, c2,
-                           row_cnt, col_cnt, T);
-    }
-    NR_LAUNCH_CHECK();
-    return NR_OK;
+    return nr_slab_apply<nr_mp_emp>(S, n, L, T, nullptr, {r2, c2, col_cnt}, stream, r2, c2, row_cnt, col_cnt);
 }
 
 extern "C" int nr_mp_gauss_apply(const float* S, int n, int L, const float* row_mean, const float* row_sd, const float* col_mean,
@@ -283,19 +255,20 @@ extern "C" int nr_mp_gauss_apply(const float* S, int n, int L, const float* row_
     if (!S || !row_mean || !row_sd || !col_mean || !col_sd || !T) return NR_EINVAL;
     if (n < 0 || L < 0) return NR_EINVAL;
     if (n == 0 || L == 0) return NR_OK;
-    const bool vec = (L % 4 == 0) && nr_mp_aligned(S) && nr_mp_aligned(col_mean) && nr_mp_aligned(col_sd) && nr_mp_aligned(T);
+    const bool vec = nr_slab_vec(L, {S, col_mean, col_sd, T});
     const long long groups = (long long)n * L / (vec ? 4 : 1);
+    const dim3 blocks((unsigned)std::min<long long>((groups + 255) / 256, 16384));
     if (vec) {
-        hipLaunchKernelGGL(nr_mp_gauss_apply_kernel<4>, dim3(nr_mp_apply_blocks(groups)), dim3(256), 0, (hipStream_t)stream, S, n, L,
-                           row_mean, row_sd, col_mean, col_sd, T);
+        hipLaunchKernelGGL(nr_mp_gauss_apply_kernel<4>, blocks, dim3(256), 0, (hipStream_t)stream, S, n, L, row_mean, row_sd, col_mean, col_sd, T);
     } else {
-        hipLaunchKernelGGL(nr_mp_gauss_apply_kernel<1>, dim3(nr_mp_apply_blocks(groups)), dim3(256), 0, (hipStream_t)stream, S, n, L,
-                           row_mean, row_sd, col_mean, col_sd, T);
+        hipLaunchKernelGGL(nr_mp_gauss_apply_kernel<1>, blocks, dim3(256), 0, (hipStream_t)stream, S, n, L, row_mean, row_sd, col_mean, col_sd, T);
     }
     NR_LAUNCH_CHECK();
     return NR_OK;
 }
 
+// The fp64 sums below are compiled with contraction off, as they always were: a squared distance is rounded before it is added.
+#pragma clang fp contract(off)
 // ---- moments for gauss: fp64, two passes (the sum, then the squared distances from the mean), fixed orders --------------------
 __device__ __forceinline__ double nr_mp_wave_sum_f64(double v) {
 #pragma unroll

@@ -1,97 +1,67 @@
 // Test-time Sinkhorn normalisation of a similarity slab (DESIGN.md "Test-time Sinkhorn normalisation"): the log-domain
 // iteration of the reference's uniform regularisation (until_module.py:223-266) applied to the test similarity.
 //
-//   a[i,j] = fl(beta S[i,j]);   u[i] = log_mu[i] - LSE_j(a[i,j] + v[j]);   v[j] = log_nu[j] - LSE_i(a[i,j] + u[i])
-//   T[i,j] = fl(fl(a[i,j] + u[i]) + v[j])
+//   au[i,j] = fma(beta, S[i,j], u[i]);   av[i,j] = fma(beta, S[i,j], v[j])       one rounding each: product plus first potential
+//   u[i] = log_mu[i] - LSE_j(av[i,j]);   v[j] = log_nu[j] - LSE_i(au[i,j]);   T[i,j] = fl(au[i,j] + v[j])
+//
+// Two roundings per entry of T, not the three of fl(fl(fl(beta S) + u) + v): the product is never a value of its own here, unlike
+// the `is` apply of nr_hubnorm.hip, which rounds fl(beta S) first.  nr_sn_shift is the one place that says so.
 //
 // One iteration is plain launches on the caller's stream: the row half-step (one wave per row, writes u), the column
 // partials (blocks of 64 rows write (max, sum) pairs to the caller's workspace) and the column finish (pairs merged in index
-// order, writes v).  The (max, sum) pairs are those of nr_hubnorm.hip: NaN entries are skipped, an entry equal to the max adds
-// exactly 1, every reduction runs in a fixed order (lanes, a fixed butterfly; blocks in index order).  No float atomics, no
-// hand-off between workgroups: bitwise reproducible run to run.  A line whose LSE is not finite keeps potential 0.
-#include "nr_hubnorm.h"
+// order, writes v); the loops are nr_slab.h's.  The (max, sum) pairs are those of nr_hubnorm.hip: NaN entries are skipped, an
+// entry equal to the max adds exactly 1, every reduction runs in a fixed order (lanes, a fixed butterfly; blocks in index order).
+// No float atomics, no hand-off between workgroups: bitwise reproducible run to run.  A line whose LSE is not finite keeps
+// potential 0.
+#include "nr_slab.h"
 #include "../../include/nr_hip.h"
 
-// one more entry of a line: x = fl(beta s), shifted by the other side's potential(s)
-__device__ __forceinline__ void nr_sn_add(float& m, float& s, float beta, float x, float p) {
-    if (x != x) return;                          // NaN: carries no mass
-    nr_hn_merge(m, s, __fadd_rn(__fmul_rn(beta, x), p), 1.f);
-}
-__device__ __forceinline__ void nr_sn_add2(float& m, float& s, float beta, float x, float u, float v) {
-    if (x != x) return;
-    nr_hn_merge(m, s, __fadd_rn(__fadd_rn(__fmul_rn(beta, x), u), v), 1.f);
-}
+// beta s + p in one rounding; every kernel of this file takes its entries through here
+__device__ __forceinline__ float nr_sn_shift(float beta, float s, float p) { return fmaf(beta, s, p); }
 
 __device__ __forceinline__ bool nr_sn_finite(float x) { return fabsf(x) < INFINITY; }      // false for NaN too
 
-// ---- row half-step: one wave per row ------------------------------------------------------------------------------------------
-// ERR = false: out[i] = u[i] = log_mu[i] - LSE_j(a[i,j] + v[j]), 0 when the LSE is not finite.
-// ERR = true:  out[i] = |exp(LSE_j(fl(fl(a[i,j] + u[i]) + v[j]) - log_mu[i]) - 1|, the row's distance from its marginal, 0 for
-//              a row that takes no part.
-template <bool VEC, bool ERR>
-__global__ __launch_bounds__(256) void nr_sinknorm_row_kernel(const float* __restrict__ S, int n, int L, float beta,
-                                                             const float* __restrict__ u, const float* __restrict__ v,
-                                                             const float* __restrict__ log_mu, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;                        // whole waves leave together: the shuffles below stay full-wave
-    const float* line = S + (long long)row * L;
-    const float ui = ERR ? u[row] : 0.f;
-    float m = -INFINITY, s = 0.f;
-    if (VEC) {
-        const f32x4_t* l4 = reinterpret_cast<const f32x4_t*>(line);
-        const f32x4_t* v4 = reinterpret_cast<const f32x4_t*>(v);
-        for (int c = lane; c < (L >> 2); c += 64) {
-            const f32x4_t x = l4[c];
-            const f32x4_t p = v4[c];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (ERR) nr_sn_add2(m, s, beta, x[k], ui, p[k]);
-                else nr_sn_add(m, s, beta, x[k], p[k]);
-            }
-        }
-    } else {
-        for (int e = lane; e < L; e += 64) {
-            if (ERR) nr_sn_add2(m, s, beta, line[e], ui, v[e]);
-            else nr_sn_add(m, s, beta, line[e], v[e]);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float m2 = __shfl_xor(m, o), s2 = __shfl_xor(s, o);
-        nr_hn_merge(m, s, m2, s2);
-    }
-    if (lane == 0) {
-        const float lse = nr_hn_lse(m, s);
-        if (ERR) out[row] = nr_sn_finite(lse) ? fabsf(expf(lse - log_mu[row]) - 1.f) : 0.f;
-        else out[row] = nr_sn_finite(lse) ? log_mu[row] - lse : 0.f;
-    }
-}
-
-template <bool ERR>
-static int nr_sinknorm_row_launch(const float* S, int n, int L, float beta, const float* u, const float* v, const float* log_mu,
-                                  float* out, void* stream) {
-    const bool vec = (L % 4 == 0) && ((uintptr_t)S % 16 == 0) && ((uintptr_t)v % 16 == 0);
-    const dim3 grid((n + 3) / 4);
-    if (vec) {
-        hipLaunchKernelGGL((nr_sinknorm_row_kernel<true, ERR>), grid, dim3(256), 0, (hipStream_t)stream, S, n, L, beta, u, v,
-                           log_mu, out);
-    } else {
-        hipLaunchKernelGGL((nr_sinknorm_row_kernel<false, ERR>), grid, dim3(256), 0, (hipStream_t)stream, S, n, L, beta, u, v,
-                           log_mu, out);
-    }
-    NR_LAUNCH_CHECK();
-    return NR_OK;
+// line i's potential from its pairs' lse: its marginal's log (read only then) minus the lse, 0 when the lse is not finite
+__device__ __forceinline__ float nr_sn_potential(const float* log_marginal, long long i, float m, float s) {
+    const float lse = nr_hn_lse(m, s);
+    return nr_sn_finite(lse) ? nr_rn_sub(log_marginal[i], lse) : 0.f;
 }
 
 static bool nr_sn_bad(int n, int L, float beta) { return n < 0 || L < 0 || !(beta > 0.f) || !(beta < INFINITY); }
+
+// ---- row half-step ------------------------------------------------------------------------------------------------------------
+// ERR = false: out[i] = u[i] = log_mu[i] - LSE_j(av[i,j]), 0 when the LSE is not finite.
+// ERR = true:  out[i] = |exp(LSE_j(T[i,j]) - log_mu[i]) - 1|, the row's distance from its marginal, 0 for a row that takes no part.
+template <bool ERR>
+struct nr_sn_row {
+    float beta;
+    const float* u;
+    const float* v;
+    const float* log_mu;
+    __device__ float row(int i) const { return ERR ? u[i] : 0.f; }
+    template <int VEC>
+    __device__ void add_line(float& m, float& s, const float (&x)[VEC], float ui, int j0) const {
+        float p[VEC];
+        nr_slab_load<VEC>(v + j0, p);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            if (x[k] != x[k]) continue;          // NaN: carries no mass
+            nr_hn_merge(m, s, ERR ? nr_rn_add(nr_sn_shift(beta, x[k], ui), p[k]) : nr_sn_shift(beta, x[k], p[k]), 1.f);
+        }
+    }
+    __device__ float finish(float m, float s, int i) const {
+        if (!ERR) return nr_sn_potential(log_mu, i, m, s);
+        const float lse = nr_hn_lse(m, s);
+        return nr_sn_finite(lse) ? fabsf(nr_rn_sub(expf(nr_rn_sub(lse, log_mu[i])), 1.f)) : 0.f;
+    }
+};
 
 extern "C" int nr_sinknorm_row(const float* S, int n, int L, float beta, const float* v, const float* log_mu, float* u,
                                void* stream) {
     if (!S || !v || !log_mu || !u) return NR_EINVAL;
     if (nr_sn_bad(n, L, beta)) return NR_EINVAL;
     if (n == 0) return NR_OK;
-    return nr_sinknorm_row_launch<false>(S, n, L, beta, nullptr, v, log_mu, u, stream);
+    return nr_slab_rows<nr_sn_row<false>>(S, n, L, u, {v}, stream, beta, (const float*)nullptr, v, log_mu);
 }
 
 extern "C" int nr_sinknorm_row_err(const float* S, int n, int L, float beta, const float* u, const float* v, const float* log_mu,
@@ -99,43 +69,19 @@ extern "C" int nr_sinknorm_row_err(const float* S, int n, int L, float beta, con
     if (!S || !u || !v || !log_mu || !err) return NR_EINVAL;
     if (nr_sn_bad(n, L, beta)) return NR_EINVAL;
     if (n == 0) return NR_OK;
-    return nr_sinknorm_row_launch<true>(S, n, L, beta, u, v, log_mu, err, stream);
+    return nr_slab_rows<nr_sn_row<true>>(S, n, L, err, {v}, stream, beta, u, v, log_mu);
 }
 
-// ---- column half-step: partial pairs per block of NR_HN_ROWS rows ---------------------------------------------------------------
-// Partial p of column c: part[(2p) L + c] = max, part[(2p + 1) L + c] = sum of fl(a[r,c] + u[r]) over the block's rows in row
-// order (u[r] is uniform per row: a scalar load), so a column's partial does not depend on VEC.
-template <int VEC>
-__global__ __launch_bounds__(256) void nr_sinknorm_col_part_kernel(const float* __restrict__ S, int n, int L, float beta,
-                                                                  const float* __restrict__ u, float* __restrict__ part) {
-    const long long c0 = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
-    if (c0 >= L) return;
-    const int p = blockIdx.y;
-    const int r0 = p * NR_HN_ROWS, r1 = min(n, r0 + NR_HN_ROWS);
-    float m[VEC], s[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) { m[k] = -INFINITY; s[k] = 0.f; }
-    for (int r = r0; r < r1; ++r) {
-        const float* at = S + (long long)r * L + c0;
-        const float ur = u[r];
-        if (VEC == 4) {
-            const f32x4_t x = *reinterpret_cast<const f32x4_t*>(at);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) nr_sn_add(m[k], s[k], beta, x[k], ur);
-        } else {
-            nr_sn_add(m[0], s[0], beta, at[0], ur);
-        }
+// ---- column half-step: the pairs of au down the columns (u[r] is uniform per row: a scalar load) ----------------------------------
+struct nr_sn_col {
+    float beta;
+    const float* u;
+    __device__ float row(int r) const { return u[r]; }
+    __device__ void add(float& m, float& s, float x, float ur) const {
+        if (x != x) return;
+        nr_hn_merge(m, s, nr_sn_shift(beta, x, ur), 1.f);
     }
-    float* pm = part + (long long)(2 * p) * L + c0;
-    float* ps = pm + L;
-    if (VEC == 4) {
-        *reinterpret_cast<f32x4_t*>(pm) = f32x4_t{m[0], m[1], m[2], m[3]};
-        *reinterpret_cast<f32x4_t*>(ps) = f32x4_t{s[0], s[1], s[2], s[3]};
-    } else {
-        pm[0] = m[0];
-        ps[0] = s[0];
-    }
-}
+};
 
 extern "C" int nr_sinknorm_col_stats(const float* S, int n, int L, float beta, const float* u, void* workspace, float* stats,
                                      void* stream) {
@@ -143,80 +89,47 @@ extern "C" int nr_sinknorm_col_stats(const float* S, int n, int L, float beta, c
     if (n == 0 && !stats) return NR_EINVAL;      // nothing to write at all
     if (nr_sn_bad(n, L, beta)) return NR_EINVAL;
     if (L == 0) return NR_OK;
-    const int P = (n + NR_HN_ROWS - 1) / NR_HN_ROWS;
     float* part = static_cast<float*>(workspace);
-    if (P > 0) {
-        const bool vec = (L % 4 == 0) && ((uintptr_t)S % 16 == 0) && ((uintptr_t)part % 16 == 0);
-        if (vec) {
-            const dim3 grid((unsigned)((L / 4 + 255) / 256), (unsigned)P);
-            hipLaunchKernelGGL(nr_sinknorm_col_part_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, S, n, L, beta, u, part);
-        } else {
-            const dim3 grid((unsigned)((L + 255) / 256), (unsigned)P);
-            hipLaunchKernelGGL(nr_sinknorm_col_part_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, S, n, L, beta, u, part);
-        }
-        NR_LAUNCH_CHECK();
+    if (n > 0) {
+        const int rc = nr_slab_col_parts<nr_sn_col>(S, n, L, part, stream, beta, u);
+        if (rc != NR_OK) return rc;
     }
     if (!stats) return NR_OK;                    // the caller finishes from the workspace's P pairs
-    return nr_hubnorm_combine(P, part, L, stats, nullptr, stream);           // P = 0: every column (-inf, 0)
+    return nr_hubnorm_combine((n + NR_HN_ROWS - 1) / NR_HN_ROWS, part, L, stats, nullptr, stream);      // n = 0: every column (-inf, 0)
 }
 
-// P pairs per column, parts [P, 2, L], merged in index order -> v[j] = log_nu[j] - lse, 0 when the lse is not finite.
-__global__ __launch_bounds__(256) void nr_sinknorm_finish_cols_kernel(int P, const float* __restrict__ parts, int L,
-                                                                     const float* __restrict__ log_nu, float* __restrict__ v) {
-    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (c >= L) return;
-    float m = -INFINITY, s = 0.f;
-    for (int p = 0; p < P; ++p) nr_hn_merge(m, s, parts[(long long)(2 * p) * L + c], parts[(long long)(2 * p + 1) * L + c]);
-    const float lse = nr_hn_lse(m, s);
-    v[c] = nr_sn_finite(lse) ? log_nu[c] - lse : 0.f;
-}
+// merged pairs -> v[j] = log_nu[j] - lse, 0 when the lse is not finite
+struct nr_sn_finish {
+    const float* log_nu;
+    float* v;
+    __device__ void finish(long long c, float m, float s) const { v[c] = nr_sn_potential(log_nu, c, m, s); }
+};
 
 extern "C" int nr_sinknorm_finish_cols(int P, const float* parts, int L, const float* log_nu, float* v, void* stream) {
     if (!log_nu || !v || (P > 0 && !parts)) return NR_EINVAL;
     if (P < 0 || L < 0) return NR_EINVAL;
     if (L == 0) return NR_OK;
-    hipLaunchKernelGGL(nr_sinknorm_finish_cols_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P,
-                       parts, L, log_nu, v);
-    NR_LAUNCH_CHECK();
-    return NR_OK;
+    return nr_slab_merge<nr_sn_finish>(P, parts, L, stream, log_nu, v);
 }
 
 // ---- apply: one read of S, one write of T -----------------------------------------------------------------------------------------
-template <int VEC>
-__global__ __launch_bounds__(256) void nr_sinknorm_apply_kernel(const float* __restrict__ S, int n, int L, float beta,
-                                                               const float* __restrict__ u, const float* __restrict__ v,
-                                                               float* __restrict__ T) {
-    const long long n_groups = (long long)n * L / VEC;
-    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += (long long)gridDim.x * 256) {
-        const long long e0 = g * VEC;
-        const int i = (int)(e0 / L);
-        const int j0 = (int)(e0 - (long long)i * L);         // VEC == 4: L % 4 == 0, the group lies in one row
-        const float ui = u[i];
-        if (VEC == 4) {
-            const f32x4_t x = *reinterpret_cast<const f32x4_t*>(S + e0);
-            f32x4_t t;
+struct nr_sn_apply {
+    static constexpr int OUTS = 1;
+    float beta;
+    const float* u;
+    const float* v;
+    __device__ float row(int i) const { return u[i]; }
+    template <int VEC>
+    __device__ void values(int, const float (&s)[VEC], float ui, int j0, long long, float (&t)[VEC]) const {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) t[k] = __fadd_rn(__fadd_rn(__fmul_rn(beta, x[k]), ui), v[j0 + k]);
-            *reinterpret_cast<f32x4_t*>(T + e0) = t;
-        } else {
-            T[e0] = __fadd_rn(__fadd_rn(__fmul_rn(beta, S[e0]), ui), v[j0]);
-        }
+        for (int k = 0; k < VEC; ++k) t[k] = nr_rn_add(nr_sn_shift(beta, s[k], ui), v[j0 + k]);
     }
-}
+};
 
 extern "C" int nr_sinknorm_apply(const float* S, int n, int L, float beta, const float* u, const float* v, float* T,
                                  void* stream) {
     if (!S || !u || !v || !T) return NR_EINVAL;
     if (nr_sn_bad(n, L, beta)) return NR_EINVAL;
     if (n == 0 || L == 0) return NR_OK;
-    const bool vec = (L % 4 == 0) && ((uintptr_t)S % 16 == 0) && ((uintptr_t)T % 16 == 0);
-    const long long groups = (long long)n * L / (vec ? 4 : 1);
-    const unsigned blocks = (unsigned)std::min<long long>((groups + 255) / 256, 16384);
-    if (vec) {
-        hipLaunchKernelGGL(nr_sinknorm_apply_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, n, L, beta, u, v, T);
-    } else {
-        hipLaunchKernelGGL(nr_sinknorm_apply_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, n, L, beta, u, v, T);
-    }
-    NR_LAUNCH_CHECK();
-    return NR_OK;
+    return nr_slab_apply<nr_sn_apply>(S, n, L, T, nullptr, {}, stream, beta, u, v);
 }

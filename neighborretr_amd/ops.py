@@ -1235,9 +1235,11 @@ def ivf_select(pool_score, pool_item, pool_len, C, want_score=False):
     return (cand, score) if want_score else cand
 
 
-def _sink_vec(x, size, what):
-    if x.dtype != torch.float32 or x.shape != (size,) or not x.is_contiguous():
-        raise ValueError(f"{what} must be a contiguous fp32 vector of {size} entries, got {x.dtype} {tuple(x.shape)}")
+def _flat_vec(x, size, what, dtype=torch.float32):
+    """x, a vector operand of a slab kernel, taken as it is: refused (never converted) unless contiguous, of `dtype` and `size`."""
+    if x.dtype != dtype or x.shape != (size,) or not x.is_contiguous():
+        name = "fp32" if dtype == torch.float32 else dtype
+        raise ValueError(f"{what} must be a contiguous {name} vector of {size} entries, got {x.dtype} {tuple(x.shape)}")
     return x
 
 
@@ -1247,14 +1249,14 @@ def sinknorm_workspace(n, L, device):
 
 
 def sinknorm_row(S, beta, v, log_mu, out=None):
-    """u [n] = log_mu - LSE_j(fl(fl(beta S) + v[j])) of every row of S [n, L], 0 for a row whose LSE is not finite
+    """u [n] = log_mu - LSE_j(fma(beta, S, v[j])) of every row of S [n, L], 0 for a row whose LSE is not finite
     (nr_sinknorm_row; until_module.py:249).  out: the u to overwrite."""
     beta = _check_beta(beta)
     S = _slab_2d(S)
     n, L = S.shape
-    u = torch.empty((n,), dtype=torch.float32, device=S.device) if out is None else _sink_vec(out, n, "out")
+    u = torch.empty((n,), dtype=torch.float32, device=S.device) if out is None else _flat_vec(out, n, "out")
     if n and L:
-        hip.call("nr_sinknorm_row", hip.ptr(S), n, L, beta, hip.ptr(_sink_vec(v, L, "v")), hip.ptr(_sink_vec(log_mu, n, "log_mu")),
+        hip.call("nr_sinknorm_row", hip.ptr(S), n, L, beta, hip.ptr(_flat_vec(v, L, "v")), hip.ptr(_flat_vec(log_mu, n, "log_mu")),
                  hip.ptr(u), hip.stream_ptr())
     else:
         u.zero_()
@@ -1262,7 +1264,7 @@ def sinknorm_row(S, beta, v, log_mu, out=None):
 
 
 def sinknorm_col_stats(S, beta, u, workspace=None, want_stats=True):
-    """The (max, sum) pairs of fl(fl(beta S) + u[i]) down the columns of S [n, L] (nr_sinknorm_col_stats; until_module.py:250).
+    """The (max, sum) pairs of fma(beta, S, u[i]) down the columns of S [n, L] (nr_sinknorm_col_stats; until_module.py:250).
     want_stats: stats [2, L], this slab's pairs merged in block order (what a rank contributes to the cross-rank gather).
     Otherwise the blocks' pairs [ceil(n / 64), 2, L], a view of `workspace`, for sinknorm_finish_cols."""
     beta = _check_beta(beta)
@@ -1274,7 +1276,7 @@ def sinknorm_col_stats(S, beta, u, workspace=None, want_stats=True):
         raise ValueError(f"workspace must be uint8 with at least {need} bytes")
     stats = torch.empty((2, L), dtype=torch.float32, device=S.device) if want_stats else None
     if L and (n or want_stats):
-        hip.call("nr_sinknorm_col_stats", hip.ptr(S) if n else None, n, L, beta, hip.ptr(_sink_vec(u, n, "u")) if n else None,
+        hip.call("nr_sinknorm_col_stats", hip.ptr(S) if n else None, n, L, beta, hip.ptr(_flat_vec(u, n, "u")) if n else None,
                  hip.ptr(ws) if need else None, hip.ptr(stats, allow_none=True), hip.stream_ptr())
     return stats if want_stats else ws[:need].view(torch.float32).view((n + 63) // 64, 2, L)
 
@@ -1285,21 +1287,21 @@ def sinknorm_finish_cols(parts, log_nu, out=None):
     if parts.dtype != torch.float32 or parts.dim() != 3 or parts.shape[1] != 2 or not parts.is_contiguous():
         raise ValueError("parts must be a contiguous fp32 [P, 2, L]")
     P, _, L = parts.shape
-    v = torch.empty((L,), dtype=torch.float32, device=parts.device) if out is None else _sink_vec(out, L, "out")
+    v = torch.empty((L,), dtype=torch.float32, device=parts.device) if out is None else _flat_vec(out, L, "out")
     if L:
-        hip.call("nr_sinknorm_finish_cols", P, hip.ptr(parts) if P else None, L, hip.ptr(_sink_vec(log_nu, L, "log_nu")), hip.ptr(v),
+        hip.call("nr_sinknorm_finish_cols", P, hip.ptr(parts) if P else None, L, hip.ptr(_flat_vec(log_nu, L, "log_nu")), hip.ptr(v),
                  hip.stream_ptr())
     return v
 
 
 def sinknorm_apply(S, beta, u, v):
-    """T [n, L] = fl(fl(fl(beta S) + u[i]) + v[j]) (nr_sinknorm_apply; until_module.py:253-257 in the log domain)."""
+    """T [n, L] = fl(fma(beta, S, u[i]) + v[j]), two roundings (nr_sinknorm_apply; until_module.py:253-257 in the log domain)."""
     beta = _check_beta(beta)
     S = _slab_2d(S)
     n, L = S.shape
     T = torch.empty_like(S)
     if n and L:
-        hip.call("nr_sinknorm_apply", hip.ptr(S), n, L, beta, hip.ptr(_sink_vec(u, n, "u")), hip.ptr(_sink_vec(v, L, "v")), hip.ptr(T),
+        hip.call("nr_sinknorm_apply", hip.ptr(S), n, L, beta, hip.ptr(_flat_vec(u, n, "u")), hip.ptr(_flat_vec(v, L, "v")), hip.ptr(T),
                  hip.stream_ptr())
     return T
 
@@ -1312,8 +1314,8 @@ def sinknorm_row_err(S, beta, u, v, log_mu):
     n, L = S.shape
     err = torch.zeros((n,), dtype=torch.float32, device=S.device)
     if n and L:
-        hip.call("nr_sinknorm_row_err", hip.ptr(S), n, L, beta, hip.ptr(_sink_vec(u, n, "u")), hip.ptr(_sink_vec(v, L, "v")),
-                 hip.ptr(_sink_vec(log_mu, n, "log_mu")), hip.ptr(err), hip.stream_ptr())
+        hip.call("nr_sinknorm_row_err", hip.ptr(S), n, L, beta, hip.ptr(_flat_vec(u, n, "u")), hip.ptr(_flat_vec(v, L, "v")),
+                 hip.ptr(_flat_vec(log_mu, n, "log_mu")), hip.ptr(err), hip.stream_ptr())
     return err
 
 
@@ -1345,8 +1347,8 @@ def localscale_apply(S, mode, row_stat, col_stat):
     n, L = S.shape
     T = torch.empty_like(S)
     if n and L:
-        hip.call("nr_localscale_apply", hip.ptr(S), n, L, LOCALSCALE_MODES[mode], hip.ptr(_sink_vec(row_stat, n, "row_stat")),
-                 hip.ptr(_sink_vec(col_stat, L, "col_stat")), hip.ptr(T), hip.stream_ptr())
+        hip.call("nr_localscale_apply", hip.ptr(S), n, L, LOCALSCALE_MODES[mode], hip.ptr(_flat_vec(row_stat, n, "row_stat")),
+                 hip.ptr(_flat_vec(col_stat, L, "col_stat")), hip.ptr(T), hip.stream_ptr())
     return T
 
 
@@ -1380,12 +1382,6 @@ def _mp_matrix(x, dtype, shape, what):
     if x.dtype != dtype or x.dim() != 2 or not x.is_contiguous() or (shape is not None and tuple(x.shape) != tuple(shape)):
         want = "2-D" if shape is None else f"{tuple(shape)}"
         raise ValueError(f"{what} must be a contiguous {dtype} matrix, {want}, got {x.dtype} {tuple(x.shape)}")
-    return x
-
-
-def _mp_vec(x, dtype, size, what):
-    if x.dtype != dtype or x.shape != (size,) or not x.is_contiguous():
-        raise ValueError(f"{what} must be a contiguous {dtype} vector of {size} entries, got {x.dtype} {tuple(x.shape)}")
     return x
 
 
@@ -1457,7 +1453,7 @@ def mp_emp_apply(S, r2, c2, row_cnt, col_cnt):
     S = _slab_2d(S)
     n, L = S.shape
     r2, c2 = _mp_matrix(r2, torch.int32, (n, L), "r2"), _mp_matrix(c2, torch.int32, (n, L), "c2")
-    row_cnt, col_cnt = _mp_vec(row_cnt, torch.int32, n, "row_cnt"), _mp_vec(col_cnt, torch.int32, L, "col_cnt")
+    row_cnt, col_cnt = _flat_vec(row_cnt, n, "row_cnt", torch.int32), _flat_vec(col_cnt, L, "col_cnt", torch.int32)
     T = torch.empty_like(S)
     if n and L:
         hip.call("nr_mp_emp_apply", hip.ptr(S), n, L, hip.ptr(r2), hip.ptr(c2), hip.ptr(row_cnt), hip.ptr(col_cnt), hip.ptr(T),
@@ -1507,8 +1503,8 @@ def mp_gauss_apply(S, row_mean, row_sd, col_mean, col_sd):
     S = _slab_2d(S)
     n, L = S.shape
     T = torch.empty_like(S)
-    vecs = (_sink_vec(row_mean, n, "row_mean"), _sink_vec(row_sd, n, "row_sd"), _sink_vec(col_mean, L, "col_mean"),
-            _sink_vec(col_sd, L, "col_sd"))
+    vecs = (_flat_vec(row_mean, n, "row_mean"), _flat_vec(row_sd, n, "row_sd"), _flat_vec(col_mean, L, "col_mean"),
+            _flat_vec(col_sd, L, "col_sd"))
     if n and L:
         hip.call("nr_mp_gauss_apply", hip.ptr(S), n, L, *(hip.ptr(x) for x in vecs), hip.ptr(T), hip.stream_ptr())
     return T

@@ -14,8 +14,9 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 # slab passes (4 N^2 bytes each) one launch of the kernel makes; the vectors and the [N, k] lists are left out
-PASSES = {"nr_localscale_apply_kernel": 2, "nr_sinknorm_apply_kernel": 2}
-SHOWN = ("nr_localscale", "nr_sinknorm_apply", "nr_topk", "nr_slab_topk")
+# (the applies are nr_slab.h's skeleton, named after the family struct it is instantiated with)
+PASSES = {"nr_ls_apply": 2, "nr_sn_apply": 2}
+SHOWN = ("nr_localscale", "nr_ls_apply", "nr_sn_apply", "nr_topk", "nr_slab_topk")
 
 
 def run(N, k, repeats):
@@ -64,7 +65,7 @@ def summary(d, N):
     for name, calls, us in rows:
         if not any(s in name for s in SHOWN):
             continue
-        if "nr_sinknorm" not in name:
+        if "nr_sn_apply" not in name:
             total += us
             if "topk" in name:
                 lists += us

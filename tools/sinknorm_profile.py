@@ -13,7 +13,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 # slab passes (4 N^2 bytes each) one launch of the kernel makes; the vectors and the 1/32-slab workspace are left out
-PASSES = {"nr_sinknorm_row_kernel": 1, "nr_sinknorm_col_part_kernel": 1, "nr_sinknorm_apply_kernel": 2}
+# (the kernels are nr_slab.h's skeletons, named after the family struct they are instantiated with)
+PASSES = {"nr_sn_row": 1, "nr_sn_col": 1, "nr_sn_apply": 2}
 
 
 def run(N, n_iter, repeats):
@@ -45,7 +46,7 @@ def summary(d, N):
     slab = 4.0 * N * N
     total = 0.0
     for name, calls, us in rows:
-        if "nr_sinknorm" not in name and "nr_hubnorm" not in name:
+        if "nr_sn_" not in name and "nr_hn_" not in name:
             continue
         total += us
         passes = next((p for k, p in PASSES.items() if k in name), 0)
