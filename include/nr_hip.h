@@ -1076,6 +1076,34 @@ int nr_mp_moments_combine(int P, const double* parts, int L, float* mean, float*
 int nr_mp_gauss_apply(const float* S, int n, int L, const float* row_mean, const float* row_sd, const float* col_mean,
                       const float* col_sd, float* T, void* stream);
 
+/* Mutual proximity and re-ranking of CANDIDATE LISTS: the search-time stage of emp / gauss on two-stage retrieval (DESIGN.md
+ * "Mutual proximity of two-stage retrieval"; added at ABI version 5 as nr_cand_norm_rerank was).  The reference has no such path.
+ * One launch; fine / cand [n, C] as nr_cand_norm_rerank takes them (the lists in ascending gallery index).  Computed once per
+ * gallery against a query bank of M items: g_line [n_gallery, M] f32, item-major, item g's M bank scores; g_cnt [n_gallery] i32 =
+ * c(g_line[g,:]) (nr_mp_line_counts); g_mean / g_sd [n_gallery] f32 its moments (nr_mp_row_moments, or nr_mp_col_moments +
+ * nr_mp_moments_combine).  Per query i:
+ *   present   slot p is present iff 0 <= cand[i,p] < n_gallery; an absent slot never forms an address into g_line, g_cnt, g_mean
+ *             or g_sd, its out_corr is -inf and it is never selected; selectable = present and not NaN; every order is value
+ *             descending, ties by lower position, -0.0 == +0.0 (nr_slab_topk_rows' order);
+ *   q line    the selectable slots' RAW scores, c_q of them; q_mean, q_sd = their mean and population sd, accumulated in fp64 in
+ *             position order (the sum, then the squared distances from the fp64 mean), delivered as fp32; c_q = 0: both NaN;
+ *   corr      with s = fine[i,p], g = cand[i,p], the formulas of nr_mp_emp_apply / nr_mp_gauss_apply (MP_I = P_query P_item; every
+ *             operation rounded once, EPS = 2^-20, the same erfcf):
+ *             emp:   fl(fl(fl(r2(s, q line)) / fl(2 c_q)) fl(fl(r2(s, g_line[g,:])) / fl(2 g_cnt[g])));  a NaN s gives NaN, an
+ *                    item whose line is all NaN 0 / 0 = NaN;
+ *             gauss: -fl(fl(Q_q + Q_g) - fl(Q_q Q_g)),  Q_q the upper tail of (q_mean, q_sd) at s, Q_g that of (g_mean[g], g_sd[g]);
+ *   output    the top k of corr over the present slots whose corr is not NaN: out_idx [n,k] = cand[...], out_val [n,k] = corr[...],
+ *             missing entries -1 / -inf.
+ * out_corr [n,C] and out_qstat [n,3] = (fl(c_q), q_mean, q_sd), written in both modes, may be null.  Integer counts and comparisons,
+ * the fp64 sums in one fixed order, no atomics: bitwise reproducible, and a query's output depends on its own line only.
+ * NR_EINVAL before any launch: fine, cand, out_idx or out_val null; n, n_gallery or k <= 0; C outside [1, 128]; k > C; an unknown
+ * mode; emp with g_line or g_cnt null or M outside [1, 2^23); gauss with g_mean or g_sd null (a mode reads its own arrays only). */
+#define NR_MUTUALPROX_EMP 0
+#define NR_MUTUALPROX_GAUSS 1
+int nr_cand_mutualprox_rerank(const float* fine, const int32_t* cand, int n, int C, int n_gallery, int mode, const float* g_line,
+                              const int32_t* g_cnt, int M, const float* g_mean, const float* g_sd, int k, int32_t* out_idx,
+                              float* out_val, float* out_corr, float* out_qstat, void* stream);
+
 /* Bootstrap of rank statistics (DESIGN.md "Bootstrap confidence intervals"; Efron 1979; the reference has no code for it): n_boot
  * resamples of U units (queries; the videos of a multi-sentence set) drawn with replacement, for V = 1 or 2 rankings over the same
  * units (ranks_b NULL: V = 1, unit_end_b and E_b are ignored).  Ranking v: ranks_v [E_v] int32, 0-based, 0 <= r < 2^30; unit_end_v [U]

@@ -162,6 +162,13 @@ def get_args():
                         "with --rerank_norm; none = off")
     p.add_argument("--rerank_local_scaling_k", type=int, default=10, metavar="K",
                    help="with --rerank_local_scaling: the neighbourhood size, 1..--rerank_top")
+    p.add_argument("--rerank_mutual_proximity", default="none", choices=["none", "emp", "gauss"],
+                   help="with --rerank_top C: the candidate scores are also replaced by their mutual proximity (empirical counts or "
+                        "the Gaussian model; no temperature, no k) -- every gallery item's line of scores is taken once per gallery "
+                        "in the memory bank as querybank, a query's among its own candidates; one fused launch corrects and re-ranks "
+                        "the lists; logs R@K and candidate recall per direction and, with --hubness_k K <= C, the hubness of the "
+                        "two-stage lists before and after (DESIGN.md 6.18); not with --rerank_norm or --rerank_local_scaling; "
+                        "none = off")
     p.add_argument("--rerank_lists", type=int, default=0, metavar="L",
                    help="with --rerank_top C: the prefilter goes through an inverted file of L k-means lists over each gallery's "
                         "pooled vectors and scores a query against its --rerank_probe closest lists only; logs the two-stage "
@@ -261,6 +268,12 @@ def get_args():
         if args.rerank_top < args.rerank_local_scaling_k:
             p.error(f"--rerank_local_scaling takes a query's neighbourhood among its candidates: it needs --rerank_top >= "
                     f"--rerank_local_scaling_k = {args.rerank_local_scaling_k}")
+    if args.rerank_mutual_proximity != "none":
+        for flag, value in (("--rerank_norm", args.rerank_norm), ("--rerank_local_scaling", args.rerank_local_scaling)):
+            if value != "none":
+                p.error(f"--rerank_mutual_proximity and {flag} both correct the candidate scores: choose one")
+        if args.rerank_top < 1:
+            p.error("--rerank_mutual_proximity corrects candidate lists: it needs --rerank_top >= 1")
     if args.rerank_lists < 0:
         p.error("--rerank_lists must be >= 0 (0 = off)")
     if args.rerank_lists and args.rerank_top < 1:
@@ -835,14 +848,15 @@ def eval_epoch(args, model, test, tag=""):
     computes rows [r N/W, (r+1) N/W) of the N x N similarity and the rank counts of its slab on the GPU, three small
     collectives complete them."""
     from neighborretr_amd.evaluator import (correction_from_args, gather_eval_features, rank_sample_indices, rerank_ivf_from_args,
-                                            rerank_local_scaling_from_args, rerank_norm_from_args, rerank_top_from_args,
-                                            sharded_evaluation, two_stage_evaluation, two_stage_ivf_label, two_stage_label)
+                                            rerank_local_scaling_from_args, rerank_mutual_proximity_from_args, rerank_norm_from_args,
+                                            rerank_top_from_args, sharded_evaluation, two_stage_evaluation, two_stage_ivf_label, two_stage_label)
     from neighborretr_amd.metrics import RetrievalMetrics
     correction, extras = correction_from_args(args, model)     # every flag checked before any work
     rerank_top = rerank_top_from_args(args)
     rerank_ivf = rerank_ivf_from_args(args)
     rerank_norm = rerank_norm_from_args(args, model)
     rerank_ls = rerank_local_scaling_from_args(args, model)
+    rerank_mp = rerank_mutual_proximity_from_args(args, model)
     hubness_k = extras["hubness_k"]
     log = _tagged_log(tag)
 
@@ -910,7 +924,8 @@ def eval_epoch(args, model, test, tag=""):
     if rerank_top:                                          # two-stage retrieval next to the exhaustive figures, never instead of them
         torch.cuda.synchronize()
         tic = time.time()
-        norm_kw = dict(rerank_ls or rerank_norm, hubness_k=min(hubness_k, rerank_top)) if rerank_ls or rerank_norm else {}
+        rerank_corr = rerank_mp or rerank_ls or rerank_norm
+        norm_kw = dict(rerank_corr, hubness_k=min(hubness_k, rerank_top)) if rerank_corr else {}
         t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, t, v, tm.float(), vm.float(), args, rerank_top, **norm_kw,
                                                                   **(rerank_ivf or {}))
         toc = time.time()
@@ -1042,7 +1057,7 @@ def main():
     elif args.do_eval:
         with_bank = args.test_norm in ("qbnorm", "qbsinkhorn") or (args.local_scaling != "none" and args.local_scaling_bank) \
             or (args.mutual_proximity != "none" and args.mutual_proximity_bank) or args.rerank_norm != "none" \
-            or args.rerank_local_scaling != "none"
+            or args.rerank_local_scaling != "none" or args.rerank_mutual_proximity != "none"
         if with_bank:                                      # the querybank: the memory bank of the training set
             load_memory_bank(args, model, train)
         result = eval_epoch(args, model, test)

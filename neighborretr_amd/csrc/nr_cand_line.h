@@ -1,4 +1,5 @@
-// What the candidate re-rank kernels (nr_cand_norm.hip, nr_cand_localscale.hip) share: one query's line of candidates.
+// What the candidate re-rank kernels (nr_cand_norm.hip, nr_cand_localscale.hip, nr_cand_mutualprox.hip) share: one query's line of
+// candidates.
 //
 // A line: C <= NR_CAND_MAX_C slots (cand[i,p], fine[i,p]) in ascending gallery index.  A slot is PRESENT iff 0 <= cand < n_gallery;
 // an absent slot never forms an address into a per-item array, its corrected score is -inf and it is never selected.  Selectable =

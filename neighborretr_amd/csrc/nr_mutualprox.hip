@@ -9,16 +9,12 @@
 // The counts are integers (no order of summation), every float operation is rounded once (no fused multiply-add), the moments are
 // accumulated in fp64 in a fixed order.  No scratch, no float atomics, no hand-off between workgroups.
 #include "nr_slab.h"
+#include "nr_mutualprox.h"
 #include "../../include/nr_hip.h"
 
 #define NR_MP_TILE 16                            // scores a lane keeps in registers while the reference values stream past
 #define NR_MP_ROW_CHUNK 1024                     // floats of a reference row staged through LDS at a time
 #define NR_MP_COL_BLOCK_ROWS 64                  // rows of S a workgroup of the column kernel covers: 4 waves x NR_MP_TILE
-#define NR_MP_LINE_MAX (1 << 23)                 // 2 c must stay below 2^24: the counts convert to fp32 exactly
-#define NR_MP_RSQRT2 0.707106781186547524f       // fl(1 / sqrt 2)
-
-// 2 [x < s] + [x == s] = [x < s] + [x <= s]: two compares and two adds per pair; a NaN on either side adds nothing
-__device__ __forceinline__ int nr_mp_pair(float x, float s) { return (int)(x < s) + (int)(x <= s); }
 
 // ---- row counts: one wave per (row, 1024 columns); the reference row goes through LDS and is read as a broadcast ----------------
 __global__ __launch_bounds__(64) void nr_mp_row_counts_kernel(const float* __restrict__ S, const float* __restrict__ R, int L, int Lr,
@@ -181,23 +177,7 @@ extern "C" int nr_mp_line_counts(const float* R, int n, int Lr, int32_t* row_cnt
     return NR_OK;
 }
 
-// ---- the two applies: one read of every input, one write of T (emp's loop is nr_slab.h's) ----------------------------------------
-__device__ __forceinline__ float nr_mp_emp_score(float s, int r2, float row_den, int c2, int col_cnt) {
-    const float p = __fdiv_rn((float)r2, row_den);
-    const float q = __fdiv_rn((float)c2, (float)(2 * col_cnt));
-    return s != s ? s : nr_rn_mul(p, q);
-}
-
-__device__ __forceinline__ float nr_mp_tail(float s, float mean, float sd) {
-    const float z = __fdiv_rn(nr_rn_sub(s, mean), nr_floor(sd, NR_SCALE_EPS));
-    return nr_rn_mul(0.5f, erfcf(nr_rn_mul(z, NR_MP_RSQRT2)));
-}
-
-__device__ __forceinline__ float nr_mp_gauss_score(float s, float rm, float rs, float cm, float cs) {
-    const float a = nr_mp_tail(s, rm, rs), b = nr_mp_tail(s, cm, cs);
-    return -nr_rn_sub(nr_rn_add(a, b), nr_rn_mul(a, b));
-}
-
+// ---- the two applies: one read of every input, one write of T (emp's loop is nr_slab.h's, the formulas nr_mutualprox.h's) ----------
 struct nr_mp_emp {
     static constexpr int OUTS = 1;
     const int32_t* r2;

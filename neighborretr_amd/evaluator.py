@@ -1468,6 +1468,28 @@ def rerank_local_scaling_from_args(args, model):
     return dict(local_scaling=mode, local_scaling_k=k)
 
 
+def two_stage_mutual_proximity_label(n_candidates, mode):
+    """The tag of the log lines of the two-stage metrics under mutual proximity: "[two-stage C=64 QB-MP-emp]"."""
+    return f"[two-stage C={int(n_candidates)} QB-MP-{mode}]"
+
+
+def rerank_mutual_proximity_from_args(args, model):
+    """args.rerank_mutual_proximity -> None or the keyword arguments of two_stage_evaluation (mutual_proximity), checked before any
+    work: the mode, that it meets neither rerank_norm nor rerank_local_scaling, that rerank_top asks for candidates and that the
+    model's memory bank is filled.  Independent of the exhaustive flags."""
+    from .search import check_mutual_proximity
+    mode = _rerank_mode_from_args(args, "rerank_mutual_proximity", check_mutual_proximity, "'emp' or 'gauss'")
+    if mode is None:
+        return None
+    for other in ("rerank_norm", "rerank_local_scaling"):
+        if (getattr(args, other, None) or "none") != "none":
+            raise ValueError(f"rerank_mutual_proximity and {other} both correct the candidate scores: choose one")
+    if rerank_top_from_args(args) < 1:
+        raise ValueError("rerank_mutual_proximity corrects candidate lists: it needs rerank_top >= 1")
+    _querybank(model, None, model.mb_feat_t.device)             # checked where it lies: nothing is copied
+    return dict(mutual_proximity=mode)
+
+
 def two_stage_ivf_label(n_candidates, n_lists, nprobe):
     """The tag of the log lines of two-stage retrieval behind the inverted-file prefilter: "[two-stage C=64 IVF L=128 P=8]"."""
     return f"[two-stage C={int(n_candidates)} IVF L={int(n_lists)} P={int(nprobe)}]"
@@ -1514,15 +1536,16 @@ def _unpack_rows(rows, spec):
     return tuple(t[:, 0].contiguous() if dim == 1 else t for t, (_, _, dim) in zip(out, spec))
 
 
-def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None, nprobe=None, local_scaling=None):
+def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None, nprobe=None, local_scaling=None, mutual_proximity=None):
     """(cand [n, C] int32, fine [n, C] fp32) on the device, the same on every rank: this rank's queries searched, one gather.
     norm: (cand, fine, corr [n, C] fp32, gate [n] int32); local_scaling (never with norm): (cand, fine, corr [n, C] fp32, qstat
-    [n, 2] fp32); nprobe: the candidates of the index's inverted file, and as the last element stats [n, 3] int32
-    (GalleryIndex.candidates, ivf_stats).  Whatever `candidates` returns travels in that one gather, in its order."""
+    [n, 2] fp32); mutual_proximity (never with either): (cand, fine, corr [n, C] fp32, qstat [n, 3] fp32); nprobe: the candidates
+    of the index's inverted file, and as the last element stats [n, 3] int32 (GalleryIndex.candidates, ivf_stats).  Whatever
+    `candidates` returns travels in that one gather, in its order."""
     n = q_feat.shape[0]
     r0, r1 = slab_bounds(n, W, rank)
     out = index.candidates(q_feat[r0:r1], q_mask[r0:r1], C, chunk, norm=norm, nprobe=nprobe, ivf_stats=nprobe is not None,
-                           local_scaling=local_scaling)
+                           local_scaling=local_scaling, mutual_proximity=mutual_proximity)
     if W > 1:
         mine, spec = _pack_rows(out, -(-n // W))
         out = _unpack_rows(_gathered_rows(mine, n, W), spec)
@@ -1530,7 +1553,8 @@ def _two_stage_lists(index, q_feat, q_mask, C, W, rank, chunk, norm=None, nprobe
 
 
 class _TwoStageCorrection(NamedTuple):
-    """What two_stage_evaluation needs to know of the one correction of the candidate scores (norm or local_scaling)."""
+    """What two_stage_evaluation needs to know of the one correction of the candidate scores (norm, local_scaling or
+    mutual_proximity)."""
     key: str                    # the corrected dictionary's key in the raw one
     label: str                  # its log tag
     attach: Callable            # (index, bank items, their mask): the index-time statistics
@@ -1547,7 +1571,7 @@ def _two_stage_hubness(cand, score, K, n_gallery, gt_begin, gt_end):
 
 def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, args, n_candidates, cut_off_points=None, chunk=256,
                          norm=None, beta=20.0, qb_k=1, querybank=None, hubness_k=0, n_lists=0, nprobe=0, ivf_iters=10, ivf_seed=0,
-                         local_scaling=None, local_scaling_k=10):
+                         local_scaling=None, local_scaling_k=10, mutual_proximity=None):
     """-> (t2v, v2t) of two-stage retrieval with n_candidates (1..128) candidates per query, identical on every rank: R1 / R5 /
     R10 / R50 (None where K > C), cand_recall (percent of the queries whose ground truth is among their candidates),
     n_candidates, cols, and MR / MedianR / MeanR only when every query was found.  Every argument is checked before any work.
@@ -1568,10 +1592,16 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
     candidate scores are also locally scaled -- every gallery item's neighbourhood of K is taken in the querybank (as for norm),
     a query's among its own candidates.  Each direction gains ["local_scaled"]: the raw dictionary's fields computed from the
     corrected scores, `mode`, `k` and `label`, and with hubness_k its ["hubness"].  corr and the queries' statistics travel in the
-    direction's one gather."""
-    from .search import GalleryIndex, check_candidates, check_chunk, check_correction, check_ivf_build, check_local_scaling_k, check_nprobe
+    direction's one gather.
+
+    mutual_proximity "emp" | "gauss" (not with norm or local_scaling): the candidate scores are also replaced by
+    their mutual proximity -- every gallery item's line is taken in the querybank (as for norm), a query's among its own
+    candidates.  Each direction gains ["mutual_proximity"]: the raw dictionary's fields computed from the corrected scores, `mode`
+    and `label`, and with hubness_k its ["hubness"].  corr and the queries' statistics travel in the direction's one gather."""
+    from .search import (GalleryIndex, check_candidates, check_chunk, check_corrections, check_ivf_build, check_local_scaling_k,
+                         check_nprobe)
     C, chunk = check_candidates(n_candidates), check_chunk(chunk)
-    norm, local_scaling = check_correction(norm, local_scaling)
+    norm, local_scaling, mutual_proximity = check_corrections(norm, local_scaling, mutual_proximity)
     if local_scaling is not None:
         local_scaling_k = check_local_scaling_k(local_scaling_k)
         if local_scaling_k > C:
@@ -1605,7 +1635,8 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
         raise ValueError(f"nprobe={nprobe!r} needs an inverted file: give n_lists >= 1")
     else:
         nprobe = None
-    bank = _querybank(model, querybank, text_feat.device) if norm is not None or local_scaling is not None else None
+    corrects = norm is not None or local_scaling is not None or mutual_proximity is not None
+    bank = _querybank(model, querybank, text_feat.device) if corrects else None
     W = _world(args)
     rank = comm.get_rank() if W > 1 else 0
     text_mask, video_mask = text_mask.float(), video_mask.float()
@@ -1619,14 +1650,18 @@ def two_stage_evaluation(model, text_feat, video_feat, text_mask, video_mask, ar
         corrected = _TwoStageCorrection("local_scaled", two_stage_local_scaling_label(C, local_scaling, local_scaling_k),
                                         lambda index, feat, mask: index.attach_localscale(feat, mask, local_scaling_k, chunk),
                                         lambda qstat, n: dict(mode=local_scaling, k=local_scaling_k))
+    if mutual_proximity is not None:
+        corrected = _TwoStageCorrection("mutual_proximity", two_stage_mutual_proximity_label(C, mutual_proximity),
+                                        lambda index, feat, mask: index.attach_mutualprox(feat, mask, chunk),
+                                        lambda qstat, n: dict(mode=mutual_proximity))
     if corrected is not None:
         corrected.attach(index_v, bank[0], bank[1])
         corrected.attach(index_t, bank[2], bank[3])
     if nprobe is not None:
         index_v.build_ivf(n_lists, ivf_iters, ivf_seed, chunk)
         index_t.build_ivf(n_lists, ivf_iters, ivf_seed, chunk)
-    lists_t = _two_stage_lists(index_v, text_feat, text_mask, C, W, rank, chunk, norm, nprobe, local_scaling)
-    lists_v = _two_stage_lists(index_t, video_feat, video_mask, C, W, rank, chunk, norm, nprobe, local_scaling)
+    lists_t = _two_stage_lists(index_v, text_feat, text_mask, C, W, rank, chunk, norm, nprobe, local_scaling, mutual_proximity)
+    lists_v = _two_stage_lists(index_t, video_feat, video_mask, C, W, rank, chunk, norm, nprobe, local_scaling, mutual_proximity)
     cand_t, cand_v = lists_t[0].cpu().numpy(), lists_v[0].cpu().numpy()
 
     def metrics(score_t, score_v):

@@ -280,6 +280,7 @@ _SIGNATURES = {
     "nr_hubnorm_apply": ([_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P], _I),
     "nr_cand_norm_rerank": ([_P, _P, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _P], _I),
     "nr_cand_localscale_rerank": ([_P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
+    "nr_cand_mutualprox_rerank": ([_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P], _I),
     "nr_ivf_list_sums": ([_P, _P, _P, _I, _I, _I, _P, _P], _I),
     "nr_ivf_scan": ([_P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P], _I),
     "nr_ivf_select": ([_P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
@@ -317,6 +318,7 @@ TOPK_MAX = 128                               # largest k of the top-k entry poin
 IVF_MAX_PROBE, IVF_CACHE_KEYS = 128, 16384   # nr_ivf_scan: the most probes; nr_ivf_select: the longest line whose keys stay in LDS
 HUBNORM_IS, HUBNORM_DSL = 0, 1               # nr_hubnorm_apply modes
 LOCALSCALE_CSLS, LOCALSCALE_NICDM, LOCALSCALE_LS = 0, 1, 2      # nr_localscale_apply modes
+MUTUALPROX_EMP, MUTUALPROX_GAUSS = 0, 1      # nr_cand_mutualprox_rerank modes
 MP_LINE_MAX = 1 << 23                        # a mutual-proximity reference line must be shorter: 2 c < 2^24 keeps the counts exact
 BOOT_MAX_UNITS, BOOT_MAX_CUTS, BOOT_RANK_LIMIT = 1 << 24, 8, 1 << 30      # nr_bootstrap_rank_stats: U, K and the ranks' bound
 BOOT_MAX_COLS, BOOT_SUM_LIMIT = 16, 1 << 62  # nr_bootstrap_unit_sums: Q and the bound of U max|value|

@@ -140,10 +140,11 @@ class RetrievalMetrics:
     def two_stage_lines(t2v, v2t, tag, sides=("Text-to-Video", "Video-to-Text"), sep=": "):
         """The log lines of evaluator.two_stage_evaluation: one per direction tagged `tag`; with a query-bank normalisation one
         more per direction tagged with its label ("[two-stage C=64 QB-Norm b=20 k=1]", with the gated share), with local scaling
-        one more tagged with its own ("[two-stage C=64 QB-CSLS k=10]"); with hubness, the line of each dictionary's top-K lists
-        after it."""
+        one more tagged with its own ("[two-stage C=64 QB-CSLS k=10]"), with mutual proximity likewise ("[two-stage C=64 QB-MP-emp]");
+        with hubness, the line of each dictionary's top-K lists after it."""
         lines = []
-        for pick in (lambda m: m, lambda m: m.get("normalised"), lambda m: m.get("local_scaled")):
+        for pick in (lambda m: m, lambda m: m.get("normalised"), lambda m: m.get("local_scaled"),
+                     lambda m: m.get("mutual_proximity")):
             for side, raw in zip(sides, (t2v, v2t)):
                 m = pick(raw)
                 if m is None:

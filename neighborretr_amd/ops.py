@@ -1510,6 +1510,47 @@ def mp_gauss_apply(S, row_mean, row_sd, col_mean, col_sd):
     return T
 
 
+MUTUALPROX_MODES = {"emp": hip.MUTUALPROX_EMP, "gauss": hip.MUTUALPROX_GAUSS}
+
+
+def cand_mutualprox_rerank(fine, cand, n_gallery, k, mode, g_line=None, g_cnt=None, g_mean=None, g_sd=None, want_corr=True):
+    """(idx [n, k] int32, val [n, k] fp32, corr [n, C] fp32 or None, qstat [n, 3] fp32) of candidate lists cand [n, C] int32
+    (ascending gallery index, entries outside [0, n_gallery) absent) with fine scores fine [n, C], in one launch
+    (nr_cand_mutualprox_rerank).  mode "emp": g_line [n_gallery, M] fp32 (item-major: item g's M bank scores) and g_cnt [n_gallery]
+    int32 (their non-NaN counts, mp_line_counts); mode "gauss": g_mean, g_sd [n_gallery] fp32 (the lines' moments, mp_row_moments or
+    mp_col_moments + mp_moments_combine); a mode reads its own arrays only.  qstat = (c_q, mean, sd) of every query's own line, the
+    selectable slots' raw scores (fp64 sums in position order, population sd), in both modes.  corr = the formula of mp_emp_apply /
+    mp_gauss_apply with the query's line on one side and the item's on the other; absent slots -inf.  idx / val: the top k of corr,
+    ties by lower position, -1 / -inf where the line has fewer than k present slots with a non-NaN corr.  1 <= k <= C <= 128."""
+    fine, cand, n, C, n_gallery, k, idx, val, corr = _cand_lines(fine, cand, n_gallery, k, want_corr)
+    if not isinstance(mode, str) or mode not in MUTUALPROX_MODES:
+        raise ValueError(f"mode must be one of {sorted(MUTUALPROX_MODES)}, got {mode!r}")
+    dev = fine.device
+    M = 0
+    if mode == "emp":
+        if (not torch.is_tensor(g_line) or g_line.dtype != torch.float32 or g_line.dim() != 2 or g_line.shape[0] != n_gallery
+                or g_line.shape[1] < 1 or g_line.device != dev or not g_line.is_contiguous()):
+            raise ValueError(f"g_line must be a contiguous {torch.float32} matrix of {n_gallery} rows (M >= 1 columns) on {dev}")
+        M = g_line.shape[1]
+        _mp_line(M, "cand_mutualprox_rerank")
+        needs = ((g_cnt, torch.int32, "g_cnt"),)
+    else:
+        needs = ((g_mean, torch.float32, "g_mean"), (g_sd, torch.float32, "g_sd"))
+    for x, dtype, what in needs:
+        if not torch.is_tensor(x) or x.dtype != dtype or x.shape != (n_gallery,) or x.device != dev:
+            raise ValueError(f"{what} must be a {dtype} vector of {n_gallery} entries on {dev}")
+    qstat = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if n:
+        emp = mode == "emp"
+        # the mode's own arrays, contiguous, held in `used` until the call has returned; the other mode's are not passed
+        used = [x.contiguous() if on else None for x, on in ((g_line, emp), (g_cnt, emp), (g_mean, not emp), (g_sd, not emp))]
+        line, cnt, mean, sd = (hip.ptr(x, allow_none=True) for x in used)
+        hip.call("nr_cand_mutualprox_rerank", hip.ptr(fine), hip.ptr(cand, torch.int32), n, C, n_gallery, MUTUALPROX_MODES[mode],
+                 line, cnt, M, mean, sd, k, hip.ptr(idx), hip.ptr(val), hip.ptr(corr, allow_none=True), hip.ptr(qstat),
+                 hip.stream_ptr())
+    return idx, val, corr, qstat
+
+
 def _boot_cuts(cuts):
     cuts = [c for c in cuts]
     if not 1 <= len(cuts) <= hip.BOOT_MAX_CUTS:

@@ -28,6 +28,11 @@ Local scaling: `attach_localscale` computes, once per gallery, 
 against a bank of training queries; `candidates` / `search` with local_scaling="csls" | "nicdm" | "ls" then take every query's own
 statistics from its candidates' fine scores, correct the scores and re-rank them in one launch (nr_cand_localscale_rerank).
 Without the argument nothing changes.
+
+Mutual proximity: `attach_mutualprox` keeps, once per gallery, every item's line of scores against a bank of
+training queries, its non-NaN count and its moments; `candidates` / `search` with mutual_proximity="emp" | "gauss" then take every
+query's own line among its candidates' fine scores, correct the scores and re-rank them in one launch (nr_cand_mutualprox_rerank).
+Without the argument nothing changes.
 """
 from types import SimpleNamespace
 from typing import Callable, NamedTuple, Optional
@@ -40,6 +45,7 @@ MAX_CANDIDATES = 128                      # nr_local_level_cand: C <= 128 (= hip
 _SCORER = {"video": "video_weight_fc", "text": "text_weight_fc"}
 NORM_MODES = ("is", "qbnorm")             # query-bank normalisation of the candidate scores
 LOCAL_SCALING_MODES = ("csls", "nicdm", "ls")       # local scaling of the candidate scores
+MUTUAL_PROXIMITY_MODES = ("emp", "gauss")           # mutual proximity of the candidate scores
 
 
 def _int_in(x, lo=None, hi=None):
@@ -109,6 +115,23 @@ def check_correction(norm, local_scaling):
     return norm, local_scaling
 
 
+def check_mutual_proximity(mode):
+    """mutual_proximity as None, "emp" or "gauss"."""
+    if mode is not None and (not isinstance(mode, str) or mode not in MUTUAL_PROXIMITY_MODES):
+        raise ValueError(f"mutual_proximity must be None or one of {MUTUAL_PROXIMITY_MODES}, got {mode!r}")
+    return mode
+
+
+def check_corrections(norm, local_scaling, mutual_proximity):
+    """(norm, local_scaling, mutual_proximity) as their own checks take them, at most one of them set: each corrects the scores."""
+    norm, local_scaling = check_correction(norm, local_scaling)
+    mutual_proximity = check_mutual_proximity(mutual_proximity)
+    for name, other in (("norm", norm), ("local_scaling", local_scaling)):
+        if mutual_proximity is not None and other is not None:
+            raise ValueError(f"mutual_proximity={mutual_proximity!r} and {name}={other!r} both correct the candidate scores: choose one")
+    return norm, local_scaling, mutual_proximity
+
+
 def _check_tokens(feat, mask, what):
     if not torch.is_tensor(feat) or feat.dim() != 3:
         raise ValueError(f"{what} features must be a [n, tokens, d] tensor")
@@ -136,6 +159,11 @@ _LOCAL_SCALING = CandCorrection(
     lambda index: index.ls_k, "local_scaling takes a query's neighbourhood of ls_k = {need} among its candidates: n_candidates >= {need} "
     "expected, got {C}", lambda index, mode, fine, cand, k: ops.cand_localscale_rerank(
         fine, cand, len(index), k, index.ls_kth if mode == "ls" else index.ls_mean, mode, index.ls_k, index.side == "video"))
+# the formulas are symmetric in their two lines: neither side needs to know which one is the row
+_MUTUAL_PROXIMITY = CandCorrection(
+    "mutual_proximity", "mp_mean", "mutual_proximity={mode!r} needs the gallery's bank lines: call attach_mutualprox(...) first",
+    lambda index: 1, None, lambda index, mode, fine, cand, k: ops.cand_mutualprox_rerank(
+        fine, cand, len(index), k, mode, g_line=index.mp_line, g_cnt=index.mp_cnt, g_mean=index.mp_mean, g_sd=index.mp_sd))
 
 
 def pooled_vectors(feat, mask, norm, w):
@@ -189,6 +217,8 @@ class GalleryIndex:
         self.ivf = None
         self.ls_mean = self.ls_kth = self.ls_k = None
         self.ls_n_bank = 0
+        self.mp_line = self.mp_cnt = self.mp_mean = self.mp_sd = None
+        self.mp_n_bank = 0
 
     def __len__(self):
         return self.items.n
@@ -253,6 +283,32 @@ class GalleryIndex:
             lists = ops.slab_topk_cols(Q, 0, k) if self.side == "video" else ops.slab_topk_rows(Q, k)
             self.ls_mean, self.ls_kth = ops.localscale_stats(*lists)
         self.ls_k, self.ls_n_bank = k, bank_feat.shape[0]
+        return self
+
+    def attach_mutualprox(self, bank_feat, bank_mask, chunk=256):
+        """The gallery's mutual-proximity lines against a query bank, computed once -> self.  The bank holds
+        items of `self.query_side`, as in attach_querybank.  Stores mp_line [N, M] fp32, item-major: row j = the M bank scores of
+        item j in bank order (Qt.T.contiguous() of Qt [M, N] for a video gallery, Qv [N, M] itself for a text gallery); mp_cnt [N]
+        int32, the lines' non-NaN counts (ops.mp_line_counts); mp_mean, mp_sd [N] fp32, their moments (ops.mp_col_moments +
+        ops.mp_moments_combine of Qt, ops.mp_row_moments of Qv: the bits the exhaustive `--mutual_proximity gauss
+        --mutual_proximity_bank 1` has for those lines at one rank); mp_n_bank = M.  Both modes' state is kept, so the mode is
+        chosen at search time.  The lines take 4 N M bytes: 41 MB at N = 20 000, M = 512, about 8 % of the prepared tokens.
+        Every argument is checked before any work; the bank product is scored once, whole (`chunk` only bounds the rows of one
+        similarity launch).  attach_querybank's, attach_localscale's and build_ivf's state is not touched."""
+        if torch.is_tensor(bank_feat) and bank_feat.dim() == 3:
+            ops._mp_line(bank_feat.shape[0], "attach_mutualprox")      # everything else is _bank_scores' to refuse
+        with torch.no_grad():
+            Q = self._bank_scores(bank_feat, bank_mask, chunk)
+            M = bank_feat.shape[0]
+            if self.side == "video":
+                line = Q.T.contiguous()
+                mean, sd = ops.mp_moments_combine(ops.mp_col_moments(Q)[None])
+            else:
+                line = Q
+                mean, sd = ops.mp_row_moments(Q)
+            cnt, _ = ops.mp_line_counts(R=line)
+            self.mp_line, self.mp_cnt, self.mp_mean, self.mp_sd = line, cnt, mean, sd
+        self.mp_n_bank = M
         return self
 
     def build_ivf(self, n_lists, iters=10, seed=0, chunk=256):
@@ -342,13 +398,14 @@ class GalleryIndex:
             cand[lo:lo + m] = ops.ivf_select(*pool, C)
         return cand, pool_len
 
-    def _check_correction(self, norm, local_scaling, n_candidates, allow_zero=True):
+    def _check_correction(self, norm, local_scaling, n_candidates, allow_zero=True, mutual_proximity=None):
         """The correction the arguments ask for -> (CandCorrection, mode), or None without one.  Refuses an unknown mode, two
         corrections at once, one that is not attached, the exhaustive path and fewer candidates than the correction works on."""
-        norm, local_scaling = check_correction(norm, local_scaling)
-        if norm is None and local_scaling is None:
+        modes = check_corrections(norm, local_scaling, mutual_proximity)
+        asked = [(c, mode) for c, mode in zip((_NORM, _LOCAL_SCALING, _MUTUAL_PROXIMITY), modes) if mode is not None]
+        if not asked:
             return None
-        c, mode = (_NORM, norm) if norm is not None else (_LOCAL_SCALING, local_scaling)
+        c, mode = asked[0]
         if getattr(self, c.needs) is None:
             raise ValueError(c.missing.format(mode=mode))
         C = check_candidates(n_candidates, allow_zero)      # `candidates` has no exhaustive path: 0 is out of its range
@@ -370,7 +427,8 @@ class GalleryIndex:
         fixed summation order per element)."""
         return ops.gemm_nt_f32(pooled_q, self.items.pooled)
 
-    def candidates(self, q_feat, q_mask, n_candidates, chunk=256, norm=None, nprobe=None, ivf_stats=False, local_scaling=None):
+    def candidates(self, q_feat, q_mask, n_candidates, chunk=256, norm=None, nprobe=None, ivf_stats=False, local_scaling=None,
+                   mutual_proximity=None):
         """(cand [n, C] int32, fine [n, C] fp32): every query's C candidates in ascending gallery index (padded with -1 when
         the gallery has fewer than C items) and their fine scores (-inf at the padding).  norm "is" | "qbnorm" (after
         attach_querybank): (cand, fine, corr [n, C] fp32, gate [n] int32), the corrected scores and which queries were normalised
@@ -383,8 +441,12 @@ class GalleryIndex:
 
         local_scaling "csls" | "nicdm" | "ls" (after attach_localscale; not with norm; n_candidates >= ls_k): (cand, fine, corr
         [n, C] fp32, qstat [n, 2] fp32), the locally scaled scores and every query's own (mean, kth) of the top
-        ls_k of its candidates' fine scores."""
-        correction = self._check_correction(norm, local_scaling, n_candidates, allow_zero=False)
+        ls_k of its candidates' fine scores.
+
+        mutual_proximity "emp" | "gauss" (after attach_mutualprox; not with norm or local_scaling): (cand, fine, corr [n, C] fp32,
+        qstat [n, 3] fp32), the mutual-proximity scores and every query's own (count, mean, sd) of its
+        candidates' fine scores."""
+        correction = self._check_correction(norm, local_scaling, n_candidates, allow_zero=False, mutual_proximity=mutual_proximity)
         nprobe = self._check_nprobe(nprobe)
         if ivf_stats and nprobe is None:
             raise ValueError("ivf_stats describes the inverted-file prefilter: it needs nprobe")
@@ -429,13 +491,14 @@ class GalleryIndex:
 
     def _corrected(self, q_feat, q_mask, k, n_candidates, chunk, correction, nprobe=None, ivf_stats=False):
         """(idx, val, cand, fine, corr, extra[, stats]): the candidates and their fine scores, then the correction's one launch
-        (extra: gate of norm, qstat of local_scaling)."""
+        (extra: gate of norm, qstat of local_scaling and of mutual_proximity)."""
         c, mode = correction
         cand, fine, *stats = self.candidates(q_feat, q_mask, n_candidates, chunk, nprobe=nprobe, ivf_stats=ivf_stats)
         idx, val, corr, extra = c.rerank(self, mode, fine, cand, k)
         return (idx, val, cand, fine, corr, extra) + tuple(stats)
 
-    def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False, norm=None, nprobe=None, local_scaling=None):
+    def search(self, q_feat, q_mask, k, n_candidates, chunk=256, return_candidates=False, norm=None, nprobe=None, local_scaling=None,
+               mutual_proximity=None):
         """-> (idx [n, k] int32, val [n, k] fp32): the top k of every query, fine score descending, ties by lower gallery index,
         padded with -1 / -inf when the gallery has fewer than k items.  1 <= k <= n_candidates <= 128; n_candidates = 0 scores
         every pair (the exhaustive path: the evaluator's slab similarity and ops.slab_topk_rows).  return_candidates: also the
@@ -443,11 +506,13 @@ class GalleryIndex:
         order and val are those of the corrected scores; with return_candidates (idx, val, cand, fine, gate).  nprobe = P (after
         build_ivf): the candidates come from the P probed lists of the inverted file; not with n_candidates = 0.
         local_scaling "csls" | "nicdm" | "ls" (after attach_localscale; not with norm, n_candidates >= ls_k): the order and val are
-        those of the locally scaled scores; with return_candidates (idx, val, cand, fine, qstat)."""
+        those of the locally scaled scores; with return_candidates (idx, val, cand, fine, qstat).
+        mutual_proximity "emp" | "gauss" (after attach_mutualprox; not with norm or local_scaling): the order and val are those of
+        the mutual-proximity scores; with return_candidates (idx, val, cand, fine, qstat [n, 3])."""
         C, chunk = check_candidates(n_candidates, allow_zero=True), check_chunk(chunk)
         if not _int_in(k, 1, C or hip.TOPK_MAX):
             raise ValueError(f"k must be an integer in [1, {C or hip.TOPK_MAX}] (1 <= k <= n_candidates), got {k!r}")
-        correction = self._check_correction(norm, local_scaling, C)
+        correction = self._check_correction(norm, local_scaling, C, mutual_proximity=mutual_proximity)
         nprobe = self._check_nprobe(nprobe, C)
         self._check_queries(q_feat, q_mask)
         if correction is not None:

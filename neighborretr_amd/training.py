@@ -162,8 +162,8 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
     loader, as in the reference (:114-131), keeps the video of each group's last sentence (:137-149), and the
     sentence x video matrix is again scored in row slabs.  Both go through evaluator.sharded_evaluation."""
     from .evaluator import (correction_from_args, dataset_order, gather_eval_features, rerank_ivf_from_args,
-                            rerank_local_scaling_from_args, rerank_norm_from_args, rerank_top_from_args, sharded_evaluation,
-                            two_stage_evaluation, two_stage_ivf_label, two_stage_label)
+                            rerank_local_scaling_from_args, rerank_mutual_proximity_from_args, rerank_norm_from_args,
+                            rerank_top_from_args, sharded_evaluation, two_stage_evaluation, two_stage_ivf_label, two_stage_label)
     correction, extras = correction_from_args(args, _unwrap(model))        # every flag checked before any work
     rerank_top = rerank_top_from_args(args)
     rerank_ivf = rerank_ivf_from_args(args)
@@ -171,6 +171,7 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
         two_stage_ivf_label(rerank_top, rerank_ivf["n_lists"], rerank_ivf["nprobe"])
     rerank_norm = rerank_norm_from_args(args, _unwrap(model))
     rerank_ls = rerank_local_scaling_from_args(args, _unwrap(model))
+    rerank_mp = rerank_mutual_proximity_from_args(args, _unwrap(model))
     hubness_k = extras["hubness_k"]
     logger = getattr(args, "logger", None)
     tracker = RetrievalMetrics(logger=logger)
@@ -198,7 +199,8 @@ def eval_epoch(args, model, test_dataloader, device, tag=""):
         t2v, v2t = sharded_evaluation(model, tf, vf, tm.float(), vm.float(), args, correction, cut_off_points=cut_off_points, **extras)
         toc2 = time.time()
         if rerank_top:                                     # two-stage retrieval next to the exhaustive figures, never instead of them
-            norm_kw = dict(rerank_ls or rerank_norm, hubness_k=min(hubness_k, rerank_top)) if rerank_ls or rerank_norm else {}
+            rerank_corr = rerank_mp or rerank_ls or rerank_norm
+            norm_kw = dict(rerank_corr, hubness_k=min(hubness_k, rerank_top)) if rerank_corr else {}
             t2v["two_stage"], v2t["two_stage"] = two_stage_evaluation(model, tf, vf, tm.float(), vm.float(), args, rerank_top,
                                                                       cut_off_points=cut_off_points, **norm_kw, **(rerank_ivf or {}))
         toc3 = time.time()
