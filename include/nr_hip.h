@@ -454,6 +454,13 @@ typedef struct NrLinearProblem {
                                                     (rows outside r's sample read as zeros); every problem of the launch then is */
 } NrLinearProblem;                               /* 80 bytes */
 int nr_linear_group(int n, const NrLinearProblem* problems, void* stream);
+/* nr_linear_plan: which kernel form a launch of these problems runs, as a pure function (host-only, nothing launched; unit-tested
+ * without a GPU; pointers are only compared with NULL).  single = 0: nr_linear_group(n, problems); single = 1: nr_linear_x3 of
+ * problems[0] (n == 1).  Returns the status the launch would return (validation included); when that is 0, plan[0..5] =
+ * MI, NI, STAGES, WC, conv, one_pass: blocks of 32 MI x 16 WC NI outputs on 2 x WC waves, a STAGES-deep ring of 64-wide K slices,
+ * conv = 1 the token convolution read in place, one_pass = 1 the product of the hi halves only.                            */
+#define NR_LINEAR_PLAN_WORDS 6
+int nr_linear_plan(int n, const NrLinearProblem* problems, int single, int32_t* plan);
 
 /* Score-biased attention backward (cluster.py:868-885) per sample for up to NR_CTM_MAX_GROUP problems: from q [n*cnum,C],
  * kv [n*N,2C] (k | v), score [n,N] and d_att [n*cnum,C] (gradient of the attention output, = upstream x proj.weight) to

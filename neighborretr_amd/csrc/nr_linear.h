@@ -26,6 +26,15 @@ struct NrLinearArgs {
 // conv = true: every problem is a token convolution (conv_n > 0 each).
 int nr_linear_group_launch(const NrLinearArgs* probs, int n_probs, hipStream_t stream, bool conv = false);
 
+// What a launch will run: block of 32 MI x 16 WC NI on 2 x WC waves, ring depth, conv / one-pass form.  nr_linear_choose is the
+// ONE place that decides it, for the grouped launch above (single = false) and for nr_linear_x3 (single = true: one problem,
+// split-bf16, 256-thread blocks); pure host code (no device call), exported as nr_linear_plan (include/nr_hip.h).  Returns the
+// status the launch would return for these problems; the plan is meaningful when that is NR_OK.
+struct NrLinearPlan {
+    int mi, ni, stages, wc, conv, one_pass;
+};
+int nr_linear_choose(const NrLinearArgs* probs, int n_probs, bool conv, bool single, NrLinearPlan& plan);
+
 // The same grouped launch with the clustering stage's DPC-KNN / merge workgroups ("back", nr_ctm_back_body) in FRONT of the GEMM
 // tiles in one grid of 512-thread workgroups: the kv projection depends on the stage's front launch alone, like the back half,
 // so the two run beside each other instead of one behind the other (the back half is a latency chain on a few waves per

@@ -162,13 +162,6 @@ static int nr_linear_launch_s(NrLinearArgs& a, hipStream_t st) {
     return NR_OK;
 }
 
-template <int MI, int NI>
-static int nr_linear_launch(NrLinearArgs& a, hipStream_t st) {
-    long n_wg = (long)((a.N + 32 * NI - 1) / (32 * NI)) * ((a.M + 32 * MI - 1) / (32 * MI));
-    if (nr_pick_stages(n_wg) == 1) return nr_linear_launch_s<MI, NI, 1>(a, st);
-    return nr_linear_launch_s<MI, NI, 2>(a, st);
-}
-
 template <int MI, int NI, int STAGES, int WC = 2, bool CONV = false, bool X3 = true>
 static int nr_linear_group_launch_s(const NrLinearArgs* probs, int n, hipStream_t st) {
     using Tile = NrGemmTile<MI, NI, X3, 16, 16, STAGES, WC>;
@@ -191,8 +184,25 @@ static int nr_linear_group_launch_s(const NrLinearArgs* probs, int n, hipStream_
     return NR_OK;
 }
 
-// Tile shape / ring depth of a grouped launch.  NR_LINEAR_TILE="MI,NI,STAGES" overrides (tuning only).
-int nr_linear_group_launch(const NrLinearArgs* probs, int n, hipStream_t st, bool conv) {
+// The tile choice of both launch forms as ONE pure host function (no device call; exported as nr_linear_plan and unit-tested
+// without a GPU): validates the problems and picks block shape, ring depth, waves along the columns.  single = false: a grouped
+// launch (nr_linear_group_launch; conv as there); single = true: nr_linear_x3's one problem on 256-thread blocks.
+// NR_LINEAR_TILE="MI,NI,STAGES[,WC]" overrides the grouped choice (tuning builds only).
+int nr_linear_choose(const NrLinearArgs* probs, int n, bool conv, bool single, NrLinearPlan& pl) {
+    pl = NrLinearPlan{0, 0, 0, 0, conv ? 1 : 0, 0};
+    if (single) {
+        if (!probs || n != 1 || conv) return NR_EINVAL;
+        const NrLinearArgs& a = probs[0];
+        if (!a.x_hi || !a.x_lo || !a.w_hi || !a.w_lo || !a.out || a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K % 64) != 0) return NR_EINVAL;
+        // enough workgroups to cover the 256 CUs: 128x128 tiles when that already gives >= 192 of them
+        const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
+        pl.mi = t128 >= 192 ? 4 : 2;
+        pl.ni = 4;
+        pl.wc = 2;
+        const long n_wg = (long)((a.N + 32 * pl.ni - 1) / (32 * pl.ni)) * ((a.M + 32 * pl.mi - 1) / (32 * pl.mi));
+        pl.stages = nr_pick_stages(n_wg);
+        return NR_OK;
+    }
     if (!probs || n <= 0 || n > NR_LINEAR_MAX_GROUP) return NR_EINVAL;
     for (int i = 0; i < n; ++i) {
         if (conv != (probs[i].conv_n > 0)) return NR_EINVAL;
@@ -201,6 +211,7 @@ int nr_linear_group_launch(const NrLinearArgs* probs, int n, hipStream_t st, boo
     }
     long t32x64 = 0, t128 = 0;
     const bool one_pass = !probs[0].x_lo && !probs[0].w_lo;
+    pl.one_pass = one_pass ? 1 : 0;
     for (int i = 0; i < n; ++i) {
         const NrLinearArgs& a = probs[i];
         if (!a.x_hi || !a.w_hi || !a.out || a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K % 64) != 0) return NR_EINVAL;
@@ -240,6 +251,26 @@ int nr_linear_group_launch(const NrLinearArgs* probs, int n, hipStream_t st, boo
             int a_, b_, c_, d_;
             if (sscanf(ov, "%d,%d,%d,%d", &a_, &b_, &c_, &d_) == 4) { mi = a_; ni = b_; stg = c_; wcols = d_; }
         }
+    } else if (conv) {               // token convolutions: the two shapes the clustering stages use (and their neighbours)
+        if (wcols == 4 || mi > 2) { mi = 2; ni = 2; stg = 1; }
+        if (const char* ov = nr_tune_env("NR_LINEAR_TILE_CONV")) {          // the convolutions only: "MI,NI,STAGES"
+            int a_, b_, c_;
+            if (sscanf(ov, "%d,%d,%d", &a_, &b_, &c_) == 3 && t32x64 > 256) { mi = a_; ni = b_; stg = c_; }
+        }
+        wcols = 2;
+    }
+    pl.mi = mi; pl.ni = ni; pl.stages = stg; pl.wc = wcols;
+    return NR_OK;
+}
+
+// Grouped launch: the plan's kernel instantiation (a shape no instantiation covers -- the hooks of a tuning build can ask for
+// one -- is NR_EUNSUPPORTED, nothing launched).
+int nr_linear_group_launch(const NrLinearArgs* probs, int n, hipStream_t st, bool conv) {
+    NrLinearPlan pl;
+    const int rc = nr_linear_choose(probs, n, conv, false, pl);
+    if (rc != NR_OK) return rc;
+    const int mi = pl.mi, ni = pl.ni, stg = pl.stages, wcols = pl.wc;
+    if (pl.one_pass) {
 #define NR_LG1_CASE(MI_, NI_, ST_, WC_) if (mi == MI_ && ni == NI_ && stg == ST_ && wcols == WC_) return nr_linear_group_launch_s<MI_, NI_, ST_, WC_, false, false>(probs, n, st)
         NR_LG1_CASE(2, 2, 1, 4); NR_LG1_CASE(2, 2, 2, 4); NR_LG1_CASE(2, 2, 1, 2); NR_LG1_CASE(2, 2, 2, 2);
 #ifdef NR_TUNE      // shapes only the NR_LINEAR_TILE1 hook of a tuning build asks for
@@ -248,12 +279,7 @@ int nr_linear_group_launch(const NrLinearArgs* probs, int n, hipStream_t st, boo
 #undef NR_LG1_CASE
         return NR_EUNSUPPORTED;
     }
-    if (conv) {                      // token convolutions: the two shapes the clustering stages use (and their neighbours)
-        if (wcols == 4 || mi > 2) { mi = 2; ni = 2; stg = 1; }
-        if (const char* ov = nr_tune_env("NR_LINEAR_TILE_CONV")) {          // the convolutions only: "MI,NI,STAGES"
-            int a_, b_, c_;
-            if (sscanf(ov, "%d,%d,%d", &a_, &b_, &c_) == 3 && t32x64 > 256) { mi = a_; ni = b_; stg = c_; }
-        }
+    if (conv) {
 #define NR_LGC_CASE(MI_, NI_, ST_) if (mi == MI_ && ni == NI_ && stg == ST_) return nr_linear_group_launch_s<MI_, NI_, ST_, 2, true>(probs, n, st)
         NR_LGC_CASE(2, 2, 1); NR_LGC_CASE(1, 2, 2); NR_LGC_CASE(1, 2, 4);
 #ifdef NR_TUNE
@@ -289,13 +315,33 @@ int nr_linear_group_launch(const NrLinearArgs* probs, int n, hipStream_t st, boo
 
 extern "C" int nr_linear_x3(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t* w_hi, const uint16_t* w_lo,
                             const float* bias, const float* residual, int M, int N, int K, float* out, void* stream) {
-    if (!x_hi || !x_lo || !w_hi || !w_lo || !out || M <= 0 || N <= 0 || K <= 0 || (K % 64) != 0) return NR_EINVAL;
     NrLinearArgs a{x_hi, x_lo, w_hi, w_lo, bias, residual, out, M, N, K};
     hipStream_t st = (hipStream_t)stream;
-    // enough workgroups to cover the 256 CUs: 128x128 tiles when that already gives >= 192 of them
-    long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-    if (t128 >= 192) return nr_linear_launch<4, 4>(a, st);
-    return nr_linear_launch<2, 4>(a, st);
+    NrLinearPlan pl;
+    const int rc = nr_linear_choose(&a, 1, false, true, pl);
+    if (rc != NR_OK) return rc;
+    if (pl.mi == 4) return pl.stages == 1 ? nr_linear_launch_s<4, 4, 1>(a, st) : nr_linear_launch_s<4, 4, 2>(a, st);
+    return pl.stages == 1 ? nr_linear_launch_s<2, 4, 1>(a, st) : nr_linear_launch_s<2, 4, 2>(a, st);
+}
+
+// The plan behind the C ABI (include/nr_hip.h): host-only, launches nothing.
+extern "C" int nr_linear_plan(int n, const NrLinearProblem* probs, int single, int32_t* plan) {
+    if (!probs || !plan || n <= 0) return NR_EINVAL;
+    if (n > NR_LINEAR_MAX_GROUP) return NR_EUNSUPPORTED;
+    NrLinearArgs a[NR_LINEAR_MAX_GROUP];
+    bool conv = false;
+    for (int i = 0; i < n; ++i) {
+        if (probs[i].conv_n < 0) return NR_EINVAL;
+        a[i] = NrLinearArgs{probs[i].x_hi, probs[i].x_lo, probs[i].w_hi, probs[i].w_lo, probs[i].bias, probs[i].residual,
+                            probs[i].out, probs[i].M, probs[i].N, probs[i].K};
+        a[i].ld = probs[i].ld;
+        a[i].conv_n = probs[i].conv_n;
+        conv = conv || probs[i].conv_n > 0;
+    }
+    NrLinearPlan pl;
+    const int rc = nr_linear_choose(a, n, conv, single != 0, pl);
+    plan[0] = pl.mi; plan[1] = pl.ni; plan[2] = pl.stages; plan[3] = pl.wc; plan[4] = pl.conv; plan[5] = pl.one_pass;
+    return rc;
 }
 
 // x[n-1] | x[n] | x[n+1] written directly as bf16 hi / lo (operand of the conv GEMM); body in nr_ctm_bodies.h

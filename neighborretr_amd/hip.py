@@ -215,6 +215,7 @@ _SIGNATURES = {
     "nr_split_group": ([_I, ctypes.POINTER(SplitItem), _P], _I),
     "nr_colsum_group": ([_I, ctypes.POINTER(ColsumItem), _P], _I),
     "nr_linear_group": ([_I, ctypes.POINTER(LinearProblem), _P], _I),
+    "nr_linear_plan": ([_I, ctypes.POINTER(LinearProblem), _I, ctypes.POINTER(ctypes.c_int32)], _I),
     "nr_ctm_attn_bwd": ([_I, ctypes.POINTER(CtmAttnBwdDesc), _P], _I),
     "nr_ctm_mid_bwd": ([_I, ctypes.POINTER(CtmMidBwdDesc), _P], _I),
     "nr_ctm_stage_fwd": ([ctypes.POINTER(CtmStageDesc), _I, _P], _I),
@@ -481,6 +482,30 @@ def ctm_stage_plan(problems):
         return None
     _check("nr_ctm_stage_plan", rc)
     return tuple(words)
+
+
+LINEAR_PLAN_WORDS = 6                        # NR_LINEAR_PLAN_WORDS
+
+
+def linear_plan(problems, single=False):
+    """(status, (MI, NI, STAGES, WC, conv, one_pass)) of one nr_linear_group launch, or of nr_linear_x3 with single=True
+    (nr_linear_plan; host only, nothing launched).  problems: a LinearProblem array, or a list of (M, N, K[, ld[, conv_n[,
+    one_pass]]]) -- the plan reads the extents and whether the operand pointers are given, nothing else.  The status is the one
+    the launch would return (0, NR_EINVAL, NR_EUNSUPPORTED): returned, never raised."""
+    if not isinstance(problems, ctypes.Array):
+        arr = (LinearProblem * max(len(problems), 1))()
+        for a, p in zip(arr, problems):
+            a.M, a.N, a.K = int(p[0]), int(p[1]), int(p[2])
+            a.ld = int(p[3]) if len(p) > 3 else 0
+            a.conv_n = int(p[4]) if len(p) > 4 else 0
+            a.x_hi = a.w_hi = a.out = 1                     # (never dereferenced: given or not)
+            a.x_lo = a.w_lo = None if (len(p) > 5 and p[5]) else 1
+        n, problems = len(problems), arr
+    else:
+        n = len(problems)
+    words = (ctypes.c_int32 * LINEAR_PLAN_WORDS)()
+    rc = int(lib().nr_linear_plan(n, problems, 1 if single else 0, words))
+    return rc, tuple(words)
 
 
 def local_level_group_kind(A, Nt, Bv, Nv, d, prec):
