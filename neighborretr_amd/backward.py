@@ -15,7 +15,7 @@ from . import head, hip, ops
 from .functional import head_args
 
 
-def _coef_rowloss(g, hp, B):
+def coef_rowloss(g, hp, B):
     """d(objective)/d(rowloss[dir,term,row]) for upstream g [5] on (total, cent, unif, neigh, kl)."""
     wu, wn, wkl = hp["uniform_weight"], hp["neighbor_weight"], hp["kl_weight"]
     c = torch.stack((g[0] + g[1], g[0] * wu + g[2], g[0] * wn + g[3], (g[0] * wkl + g[4]) / B)) * (0.5 / B)
@@ -42,12 +42,11 @@ def _mm(a, b_t):
     return a @ b_t.t()
 
 
-def _mlp_backward(feats, dlogits, w1, b1, w2, n_dx, exact):
+def _mlp_backward(feats, dlogits, w1, b1, w2, n_dx):
     """Backward of Linear(d,H)-ReLU-Linear(H,1) over the concatenation of `feats` (list of [n_i,d] tensors) with upstream
     `dlogits` (list of [n_i]).  The three GEMMs -- the recomputed hidden layer X W1^T, dW1 = dh^T X and dX = dh W1 -- run
     on the build's split-bf16 MFMA engine (nr_linear_x3, fp32-grade products; no library GEMM on the training path); the
-    two H-vectors dW2 / db1 are plain column sums.  `exact` is kept for the callers' signature: both precision
-    plans now get the same fp32-grade gradients.  Returns dW1, db1, dW2, db2 and dX of the first `n_dx` rows (or None)."""
+    two H-vectors dW2 / db1 are plain column sums.  Returns dW1, db1, dW2, db2 and dX of the first `n_dx` rows (or None)."""
     X = torch.cat([f.reshape(-1, f.shape[-1]) for f in feats], 0).float()
     dl = torch.cat([d.reshape(-1) for d in dlogits], 0).float()
     w1f = w1.detach().float()
@@ -228,6 +227,25 @@ def ctypes_ptr(t, elem_offset):
     return ctypes.c_void_p(t.data_ptr() + 4 * int(elem_offset))
 
 
+def _head_forward_keep(ctx, model, hp, join, local_stream, text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v,
+                       mb_mask_t, mb_mask_v, gt, gv, logit_scale):
+    """The keep=True forward of a head node, and the ctx fields its backward reads -> (losses, saved state)."""
+    prec = model._prec()
+    losses, sv = head.head_forward(text_feat.detach(), video_feat.detach(), text_mask, video_mask,
+                                   mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt, gv,
+                                   hp=hp, logit_scale=logit_scale.detach(), keep=True,
+                                   **head_args(model, text_feat, video_feat, join, local_stream=local_stream))
+    ctx.sv, ctx.exact = sv, prec == hip.PREC_BF16X3
+    ctx.model, ctx.plan = model, head.backward_plan(prec)
+    ctx.masks = (text_mask, video_mask)
+    ctx.shapes = (text_feat.shape, video_feat.shape, mb_feat_t.shape, mb_feat_v.shape, sv["gt2"].shape, sv["gv2"].shape)
+    sv["gt2"], sv["gv2"] = sv["gt2"].reshape(-1, sv["gt2"].shape[-1]), sv["gv2"].reshape(-1, sv["gv2"].shape[-1])
+    # a loss (or output) that is not differentiated brings no gradient (not a zero tensor), and backward() on one of them needs
+    # no select-backward fill / copy launches
+    ctx.set_materialize_grads(False)
+    return losses, sv
+
+
 class HeadLossFn(torch.autograd.Function):
     """Fused _compute_losses (modeling.py:314-360) given the global tokens."""
 
@@ -237,22 +255,12 @@ class HeadLossFn(torch.autograd.Function):
                 g1_w1t, g1_b1t, g1_w2t, g1_b2t, g1_w1v, g1_b1v, g1_w2v, g1_b2v):
         """The last eight inputs are the *_weight_fc1 scorers of global_level (modeling.py:518-523): they matter (and get a
         gradient) only with several global tokens per sample; with one token their softmax weight is the constant 1."""
-        prec = model._prec()
-        losses, sv = head.head_forward(text_feat.detach(), video_feat.detach(), text_mask, video_mask,
-                                       mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt.detach(), gv.detach(),
-                                       hp=hp, logit_scale=logit_scale.detach(), keep=True,
-                                       **head_args(model, text_feat, video_feat, join, local_stream=False))
-        ctx.sv, ctx.hp, ctx.exact = sv, dict(hp), prec == hip.PREC_BF16X3
-        ctx.model, ctx.plan = model, head.backward_plan(prec)
-        ctx.masks = (text_mask, video_mask)
-        ctx.shapes = (text_feat.shape, video_feat.shape, mb_feat_t.shape, mb_feat_v.shape, gt.shape, gv.shape)
-        sv["gt2"], sv["gv2"] = sv["gt2"].reshape(-1, sv["gt2"].shape[-1]), sv["gv2"].reshape(-1, sv["gv2"].shape[-1])
+        losses, _ = _head_forward_keep(ctx, model, hp, join, False, text_feat, video_feat, text_mask, video_mask, mb_feat_t, mb_feat_v,
+                                       mb_mask_t, mb_mask_v, gt.detach(), gv.detach(), logit_scale)
+        ctx.hp = dict(hp)
         ctx.save_for_backward(text_feat, video_feat, mb_feat_t, mb_feat_v, w1t, b1t, w2t, w1v, b1v, w2v,
                               g1_w1t, g1_b1t, g1_w2t, g1_w1v, g1_b1v, g1_w2v)
-        # five scalar outputs (total, centrality, uniform, neighbour, kl): a loss that is not differentiated brings no gradient
-        # (not a zero tensor), and backward() on one of them needs no select-backward fill / copy launches
-        ctx.set_materialize_grads(False)
-        return tuple(losses.unbind(0))
+        return tuple(losses.unbind(0))          # five scalar outputs (total, centrality, uniform, neighbour, kl)
 
     @staticmethod
     def backward(ctx, *gs):
@@ -270,6 +278,20 @@ class HeadLossFn(torch.autograd.Function):
         return (None,) * 9 + (d_text, d_video, d_gt, d_gv, d_ls, *scorer, *g1)
 
 
+def multi_global_backward(saved, dG, gt2, gv2, params, B, Gt, Bv, Gv):
+    """Backward of global_level with several global tokens per sample (head.global_logits' fused product on the un-normalised
+    tokens): arg-max-routed gradient, softmax and *_weight_fc1 scorer backward -> d_gt [B Gt, d], d_gv [Bv Gv, d] (each with
+    its scorer's input gradient added) and [dW1t, db1t, dW2t, db2t, dW1v, db1v, dW2v, db2v]."""
+    w1t, b1t, w2t, w1v, b1v, w2v = params
+    d_gt, d_wgt = ops.local_level_bwd(0, dG, 0, 1.0, saved["pv"], saved["w_t"], saved["w_v"], saved["aux"], B, Gt, Bv, Gv, use_lo=True)
+    d_gv, d_wgv = ops.local_level_bwd(1, dG, 0, 1.0, saved["pt"], saved["w_v"], saved["w_t"], saved["aux"], B, Gt, Bv, Gv, use_lo=True)
+    dl_gt = ops.token_softmax_bwd(saved["w_t"], d_wgt.view(B, Gt))
+    dl_gv = ops.token_softmax_bwd(saved["w_v"], d_wgv.view(Bv, Gv))
+    *g_t, gXt = _mlp_backward([gt2], [dl_gt], w1t, b1t, w2t, B * Gt)
+    *g_v, gXv = _mlp_backward([gv2], [dl_gv], w1v, b1v, w2v, Bv * Gv)
+    return d_gt + gXt, d_gv + gXv, g_t + g_v
+
+
 def _global_backward(sv, hp, shapes, gs, g1_params):
     """The part of the loss head's backward that does not touch the token features: from the gradients of the five losses
     through the row terms (nr_row_losses_bwd) to  dS [B,B], d bank means d_c0 / d_c1 [B], d centrality means dmean_t / dmean_v
@@ -277,7 +299,6 @@ def _global_backward(sv, hp, shapes, gs, g1_params):
     (B, Nt, d), (_, Nv, _), (M, _, _), _, gt_shape, gv_shape = shapes
     Gt, Gv = gt_shape[1], gv_shape[1]
     K, T = int(hp["num_neighbors"]), hp["temperature"]
-    g1_w1t, g1_b1t, g1_w2t, g1_w1v, g1_b1v, g1_w2v = g1_params
     if sv["S"].is_cuda:
         _record_on_current_stream(sv)
     coef = ops.rowloss_coef(gs, hp, B)
@@ -288,17 +309,8 @@ def _global_backward(sv, hp, shapes, gs, g1_params):
     if sv["g_saved"] is None:
         d_gt = d_gv = None              # global logits G = gt gv^T: tiny plain GEMMs, folded into the centrality step below
     else:
-        # several global tokens per sample: G is the fused product on the un-normalised global tokens with the
-        # *_weight_fc1 softmax weights (modeling.py:516-539): arg-max-routed gradient + softmax + scorer-MLP backward
-        gs_ = sv["g_saved"]
-        d_gt, d_wgt = ops.local_level_bwd(0, dG, 0, 1.0, gs_["pv"], gs_["w_t"], gs_["w_v"], gs_["aux"], B, Gt, B, Gv, use_lo=True)
-        d_gv, d_wgv = ops.local_level_bwd(1, dG, 0, 1.0, gs_["pt"], gs_["w_v"], gs_["w_t"], gs_["aux"], B, Gt, B, Gv, use_lo=True)
-        dl_gt = ops.token_softmax_bwd(gs_["w_t"], d_wgt.view(B, Gt))
-        dl_gv = ops.token_softmax_bwd(gs_["w_v"], d_wgv.view(B, Gv))
-        gW1t, gb1t, gW2t, gb2t, gXt = _mlp_backward([sv["gt2"]], [dl_gt], g1_w1t, g1_b1t, g1_w2t, B * Gt, True)
-        gW1v, gb1v, gW2v, gb2v, gXv = _mlp_backward([sv["gv2"]], [dl_gv], g1_w1v, g1_b1v, g1_w2v, B * Gv, True)
-        d_gt, d_gv = d_gt + gXt, d_gv + gXv
-        g1 = [gW1t, gb1t, gW2t, gb2t, gW1v, gb1v, gW2v, gb2v]
+        # several global tokens per sample: G is the fused product with the *_weight_fc1 softmax weights (modeling.py:516-539)
+        d_gt, d_gv, g1 = multi_global_backward(sv["g_saved"], dG, sv["gt2"], sv["gv2"], g1_params, B, Gt, B, Gv)
     # centrality weights: w_i = mean over the sample's global tokens of exp(c <g_hat, mean>)  (one token: the reference's)
     cs = hp["centrality_scale"]
     gn_t, gn_v, wtok_t, wtok_v = sv["cw_aux"]
@@ -339,74 +351,49 @@ def _record_on_current_stream(obj, seen=None):
             stack.extend(o)
 
 
+def token_tail(sets, feats, masks, grads, dmeans, plan, model, unfused_params=None):
+    """From the similarity backward's results to the features and the scorers: normalisation / mask / centrality-mean backward,
+    token softmax backward, scorer MLPs.  sets = the (text, video, bank-text, bank-video) ops.TokenSets, feats their raw features,
+    grads their (d_x or None, d_w) -> d text_feat, d video_feat and (dW1t, db1t, dW2t, db2t, dW1v, db1v, dW2v, db2v).
+    unfused_params: the scorers' (w1t, b1t, w2t, w1v, b1v, w2v) for the torch-op form of their backward (FUSED_MLP_BACKWARD)."""
+    t, v, bt, bv = sets
+    text_feat, video_feat, mb_feat_t, mb_feat_v = feats
+    d_text = ops.normalize_bwd(text_feat, t.prep.norm, masks[0], grads[0][0], dmeans[0])
+    d_video = ops.normalize_bwd(video_feat, v.prep.norm, masks[1], grads[1][0], dmeans[1])
+    dl_t, dl_v, dl_bt, dl_bv = [ops.token_softmax_bwd(s.w, d_w.view(s.n, s.N)) for s, (_, d_w) in zip(sets, grads)]
+    if unfused_params is None:
+        _, p_mlp, p_bank = plan
+        # the scorer's input gradient is added to the similarity path's inside its GEMM (residual operand)
+        (*g_t, d_text), (*g_v, d_video) = _mlp_backward_hip([
+            dict(sw=model.scorer_weights("text_weight_fc"), add_to=d_text,
+                 sets=[(t.prep, text_feat, dl_t, p_mlp), (bt.prep, mb_feat_t, dl_bt, p_bank)]),
+            dict(sw=model.scorer_weights("video_weight_fc"), add_to=d_video,
+                 sets=[(v.prep, video_feat, dl_v, p_mlp), (bv.prep, mb_feat_v, dl_bv, p_bank)])])
+        return d_text.view(text_feat.shape), d_video.view(video_feat.shape), (*g_t, *g_v)
+    w1t, b1t, w2t, w1v, b1v, w2v = unfused_params
+    *g_t, dXt = _mlp_backward([text_feat, mb_feat_t], [dl_t, dl_bt], w1t, b1t, w2t, t.prep.n_tok)
+    *g_v, dXv = _mlp_backward([video_feat, mb_feat_v], [dl_v, dl_bv], w1v, b1v, w2v, v.prep.n_tok)
+    return d_text + dXt.view_as(d_text), d_video + dXv.view_as(d_video), (*g_t, *g_v)
+
+
 def _local_backward(sv, shapes, masks, exact, plan, model, text_feat, video_feat, mb_feat_t, mb_feat_v, scorer_params,
                     dS, d_c0, d_c1, dmean_t, dmean_v):
     """The token side of the loss head's backward: the three fused products (batch x batch, text x bank-video, bank-text x video)
-    through their stored arg-max routes, normalisation / mask / centrality mean, token softmax and the scorer MLPs ->
+    through their stored arg-max routes (ops.sim_backward: each product stated once), then token_tail ->
     d text_feat, d video_feat and the *_weight_fc gradients (dW1t, db1t, dW2t, db2t, dW1v, db1v, dW2v, db2v)."""
-    (B, Nt, d), (_, Nv, _), (M, _, _), _, _, _ = shapes
-    text_mask, video_mask = masks
-    w1t, b1t, w2t, w1v, b1v, w2v = scorer_params
+    M = shapes[2][0]
     if dS.is_cuda:
         _record_on_current_stream(sv)
-    pt, pv, pbt, pbv = sv["pt"], sv["pv"], sv["pbt"], sv["pbv"]
-    lo = exact
+    t, v = ops.TokenSet(sv["pt"], sv["w_t"]), ops.TokenSet(sv["pv"], sv["w_v"])
+    bt, bv = ops.TokenSet(sv["pbt"], sv["w_bt"]), ops.TokenSet(sv["pbv"], sv["w_bv"])
     aux0, aux1, aux2 = sv["aux"]
-    f32 = dict(dtype=torch.float32, device=dS.device)
-    d_tn, d_vn = torch.empty((B * Nt, d), **f32), torch.empty((B * Nv, d), **f32)
-    d_wt, d_wv = torch.empty((B * Nt,), **f32), torch.empty((B * Nv,), **f32)
-    d_wbt, d_wbv = torch.empty((M * Nt,), **f32), torch.empty((M * Nv,), **f32)
-    if ops.USE_MFMA_BACKWARD and bool(hip.lib().nr_local_level_bwd_mfma_supported(Nt, Nv, d)):
-        # token gradients: the four products' routing matrices on the matrix cores in ONE launch (their "other" operands
-        # transposed in one launch before it), the chunks of a gradient's two products summed by one more
-        T_pv, T_pt, T_pbv, T_pbt = ops.transpose_prepared([pv, pt, pbv, pbt], use_lo=lo)
-        ops.local_level_bwd_group([
-            dict(side=0, dS=dS, ds_mode=0, ds_scale=1.0, other_T=T_pv, w_self=sv["w_t"], w_other=sv["w_v"], aux=aux0,
-                 A=B, Nt=Nt, Bv=B, Nv=Nv, d_x=d_tn),
-            dict(side=0, dS=d_c1, ds_mode=1, ds_scale=1.0 / M, other_T=T_pbv, w_self=sv["w_t"], w_other=sv["w_bv"], aux=aux1,
-                 A=B, Nt=Nt, Bv=M, Nv=Nv, d_x=d_tn),
-            dict(side=1, dS=dS, ds_mode=0, ds_scale=1.0, other_T=T_pt, w_self=sv["w_v"], w_other=sv["w_t"], aux=aux0,
-                 A=B, Nt=Nt, Bv=B, Nv=Nv, d_x=d_vn),
-            dict(side=1, dS=d_c0, ds_mode=2, ds_scale=1.0 / M, other_T=T_pbt, w_self=sv["w_v"], w_other=sv["w_bt"], aux=aux2,
-                 A=M, Nt=Nt, Bv=B, Nv=Nv, d_x=d_vn)], use_lo=lo)
-        # token-weight gradients of the batch and of the bank, all six sums in one launch
-        ops.pool_weight_bwd_group([
-            dict(side=0, N=Nt, d_w=d_wt, srcs=[(dS, 0, 1.0, aux0[2], B, B), (d_c1, 1, 1.0 / M, aux1[2], B, M)]),
-            dict(side=1, N=Nv, d_w=d_wv, srcs=[(dS, 0, 1.0, aux0[3], B, B), (d_c0, 2, 1.0 / M, aux2[3], M, B)]),
-            dict(side=1, N=Nv, d_w=d_wbv, srcs=[(d_c1, 1, 1.0 / M, aux1[3], B, M)]),
-            dict(side=0, N=Nt, d_w=d_wbt, srcs=[(d_c0, 2, 1.0 / M, aux2[2], M, B)])])
-    else:
-        ops.local_level_bwd(0, dS, 0, 1.0, pv, sv["w_t"], sv["w_v"], aux0, B, Nt, B, Nv, d_x=d_tn, d_w=d_wt, use_lo=lo)
-        ops.local_level_bwd(1, dS, 0, 1.0, pt, sv["w_v"], sv["w_t"], aux0, B, Nt, B, Nv, d_x=d_vn, d_w=d_wv, use_lo=lo)
-        ops.local_level_bwd(0, d_c1, 1, 1.0 / M, pbv, sv["w_t"], sv["w_bv"], aux1, B, Nt, M, Nv, d_x=d_tn, d_w=d_wt,
-                            accumulate=True, use_lo=lo)
-        ops.local_level_bwd(1, d_c1, 1, 1.0 / M, pt, sv["w_bv"], sv["w_t"], aux1, B, Nt, M, Nv, d_w=d_wbv, want_dx=False)
-        ops.local_level_bwd(1, d_c0, 2, 1.0 / M, pbt, sv["w_v"], sv["w_bt"], aux2, M, Nt, B, Nv, d_x=d_vn, d_w=d_wv,
-                            accumulate=True, use_lo=lo)
-        ops.local_level_bwd(0, d_c0, 2, 1.0 / M, pv, sv["w_bt"], sv["w_v"], aux2, M, Nt, B, Nv, d_w=d_wbt, want_dx=False)
-    # normalise / mask / centrality-mean backward
-    d_text = ops.normalize_bwd(text_feat, pt.norm, text_mask, d_tn, dmean_t)
-    d_video = ops.normalize_bwd(video_feat, pv.norm, video_mask, d_vn, dmean_v)
-    # token weights -> logits -> scorer MLPs
-    dl_t = ops.token_softmax_bwd(sv["w_t"], d_wt.view(B, Nt))
-    dl_v = ops.token_softmax_bwd(sv["w_v"], d_wv.view(B, Nv))
-    dl_bt = ops.token_softmax_bwd(sv["w_bt"], d_wbt.view(M, Nt))
-    dl_bv = ops.token_softmax_bwd(sv["w_bv"], d_wbv.view(M, Nv))
-    if FUSED_MLP_BACKWARD:
-        _, p_mlp, p_bank = plan
-        # the scorer's input gradient is added to the similarity path's inside its GEMM (residual operand)
-        (dW1t, db1t, dW2t, db2t, d_text), (dW1v, db1v, dW2v, db2v, d_video) = _mlp_backward_hip([
-            dict(sw=model.scorer_weights("text_weight_fc"), add_to=d_text,
-                 sets=[(pt, text_feat, dl_t, p_mlp), (pbt, mb_feat_t, dl_bt, p_bank)]),
-            dict(sw=model.scorer_weights("video_weight_fc"), add_to=d_video,
-                 sets=[(pv, video_feat, dl_v, p_mlp), (pbv, mb_feat_v, dl_bv, p_bank)])])
-        d_text, d_video = d_text.view(text_feat.shape), d_video.view(video_feat.shape)
-    else:
-        dW1t, db1t, dW2t, db2t, dXt = _mlp_backward([text_feat, mb_feat_t], [dl_t, dl_bt], w1t, b1t, w2t, B * Nt, exact)
-        dW1v, db1v, dW2v, db2v, dXv = _mlp_backward([video_feat, mb_feat_v], [dl_v, dl_bv], w1v, b1v, w2v, B * Nv, exact)
-        d_text = d_text + dXt.view_as(d_text)
-        d_video = d_video + dXv.view_as(d_video)
-    return d_text, d_video, (dW1t, db1t, dW2t, db2t, dW1v, db1v, dW2v, db2v)
+    P0 = ops.SimProduct(t, v, dS, 0, 1.0, aux0)
+    P1 = ops.SimProduct(t, bv, d_c1, 1, 1.0 / M, aux1)
+    P2 = ops.SimProduct(bt, v, d_c0, 2, 1.0 / M, aux2)
+    g_t, g_v, g_bv, g_bt = ops.sim_backward([ops.SimTarget(t, [P0, P1]), ops.SimTarget(v, [P0, P2]), ops.SimTarget(bv, [P1], False),
+                                             ops.SimTarget(bt, [P2], False)], use_lo=exact)
+    return token_tail((t, v, bt, bv), (text_feat, video_feat, mb_feat_t, mb_feat_v), masks, (g_t, g_v, g_bt, g_bv),
+                      (dmean_t, dmean_v), plan, model, None if FUSED_MLP_BACKWARD else scorer_params)
 
 
 class HeadLocalFn(torch.autograd.Function):
@@ -423,24 +410,15 @@ class HeadLocalFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, hp, bridge, text_mask, video_mask, mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt, gv, logit_scale,
                 g1, text_feat, video_feat, w1t, b1t, w2t, b2t, w1v, b1v, w2v, b2v):
-        prec = model._prec()
         # gt = gv = None: the join is the clustering's launches, a generator driven by the head -- issued launch by launch on THIS
         # stream, interleaved (in capture order) with the local branch and the early bank chains on the local stream: the
         # loss-only step's schedule (head._run_branches).  Otherwise it waits for the global tokens (or is None).
         join, stepwise = bridge.pop("join", None), gt is None
         gt_in, gv_in = (None, None) if stepwise else (gt.detach(), gv.detach())
-        losses, sv = head.head_forward(text_feat.detach(), video_feat.detach(), text_mask, video_mask,
-                                       mb_feat_t, mb_feat_v, mb_mask_t, mb_mask_v, gt_in, gv_in,
-                                       hp=hp, logit_scale=logit_scale.detach(), keep=True,
-                                       **head_args(model, text_feat, video_feat, join, local_stream=stepwise))
-        ctx.sv, ctx.exact = sv, prec == hip.PREC_BF16X3
-        ctx.model, ctx.plan = model, head.backward_plan(prec)
-        ctx.masks = (text_mask, video_mask)
-        ctx.shapes = (text_feat.shape, video_feat.shape, mb_feat_t.shape, mb_feat_v.shape, sv["gt2"].shape, sv["gv2"].shape)
-        sv["gt2"], sv["gv2"] = sv["gt2"].reshape(-1, sv["gt2"].shape[-1]), sv["gv2"].reshape(-1, sv["gv2"].shape[-1])
+        losses, sv = _head_forward_keep(ctx, model, hp, join, stepwise, text_feat, video_feat, text_mask, video_mask, mb_feat_t,
+                                        mb_feat_v, mb_mask_t, mb_mask_v, gt_in, gv_in, logit_scale)
         ctx.save_for_backward(text_feat, video_feat, mb_feat_t, mb_feat_v, w1t, b1t, w2t, w1v, b1v, w2v)
         bridge["losses"], bridge["sv"], bridge["shapes"] = losses, sv, ctx.shapes
-        ctx.set_materialize_grads(False)
         return sv["S"], sv["c0"], sv["c1"], sv["mean_t"], sv["mean_v"]
 
     @staticmethod
@@ -524,23 +502,11 @@ class LocalLevelFn(torch.autograd.Function):
         A, Nt, d = text_feat.shape
         Bv, Nv, _ = video_feat.shape
         dS = dS.float().contiguous()
-        if ops.USE_MFMA_BACKWARD and bool(hip.lib().nr_local_level_bwd_mfma_supported(Nt, Nv, d)):
-            # both operands' token gradients in one launch (+ the slab sum), both weight sums in one more: the same grouped
-            # kernels as the loss head's backward (this node serves the sharded training loss, four products per step)
-            f32 = dict(dtype=torch.float32, device=dS.device)
-            d_tn, d_vn = torch.empty((A * Nt, d), **f32), torch.empty((Bv * Nv, d), **f32)
-            d_wt, d_wv = torch.empty((A * Nt,), **f32), torch.empty((Bv * Nv,), **f32)
-            T_pv, T_pt = ops.transpose_prepared([pv, pt], use_lo=exact)
-            ops.local_level_bwd_group([
-                dict(side=0, dS=dS, ds_mode=0, ds_scale=1.0, other_T=T_pv, w_self=w_t, w_other=w_v, aux=aux, A=A, Nt=Nt, Bv=Bv, Nv=Nv,
-                     d_x=d_tn),
-                dict(side=1, dS=dS, ds_mode=0, ds_scale=1.0, other_T=T_pt, w_self=w_v, w_other=w_t, aux=aux, A=A, Nt=Nt, Bv=Bv, Nv=Nv,
-                     d_x=d_vn)], use_lo=exact)
-            ops.pool_weight_bwd_group([dict(side=0, N=Nt, d_w=d_wt, srcs=[(dS, 0, 1.0, aux[2], A, Bv)]),
-                                       dict(side=1, N=Nv, d_w=d_wv, srcs=[(dS, 0, 1.0, aux[3], A, Bv)])])
-        else:
-            d_tn, d_wt = ops.local_level_bwd(0, dS, 0, 1.0, pv, w_t, w_v, aux, A, Nt, Bv, Nv, use_lo=exact)
-            d_vn, d_wv = ops.local_level_bwd(1, dS, 0, 1.0, pt, w_v, w_t, aux, A, Nt, Bv, Nv, use_lo=exact)
+        # both operands' token gradients in one launch (+ the slab sum), both weight sums in one more: the same grouped kernels as
+        # the loss head's backward
+        t, v = ops.TokenSet(pt, w_t), ops.TokenSet(pv, w_v)
+        P = ops.SimProduct(t, v, dS, 0, 1.0, aux)
+        (d_tn, d_wt), (d_vn, d_wv) = ops.sim_backward([ops.SimTarget(t, [P]), ops.SimTarget(v, [P])], use_lo=exact)
         d_text = ops.normalize_bwd(text_feat, pt.norm, text_mask, d_tn, None)
         d_video = ops.normalize_bwd(video_feat, pv.norm, video_mask, d_vn, None)
         dl_t = ops.token_softmax_bwd(w_t, d_wt.view(A, Nt))
@@ -551,8 +517,8 @@ class LocalLevelFn(torch.autograd.Function):
         # pre-activation is within rounding of zero decides a ReLU differently in the fused form (which recomputes it from the
         # normalised bf16 pairs, exactly as the forward kernel did) and moves a dW1 entry by 1e-2 of the largest
         # (tools/dbg_mlp.py: either form flips somewhere against fp64 on random data; the fused one about ten times as often).
-        dW1t, db1t, dW2t, db2t, dXt = _mlp_backward([text_feat], [dl_t], w1t, b1t, w2t, A * Nt, exact)
-        dW1v, db1v, dW2v, db2v, dXv = _mlp_backward([video_feat], [dl_v], w1v, b1v, w2v, Bv * Nv, exact)
+        dW1t, db1t, dW2t, db2t, dXt = _mlp_backward([text_feat], [dl_t], w1t, b1t, w2t, A * Nt)
+        dW1v, db1v, dW2v, db2v, dXv = _mlp_backward([video_feat], [dl_v], w1v, b1v, w2v, Bv * Nv)
         return (None, None, None, d_text + dXt.view_as(d_text), d_video + dXv.view_as(d_video),
                 dW1t, db1t, dW2t, db2t, dW1v, db1v, dW2v, db2v)
 
@@ -590,21 +556,14 @@ class GlobalLevelMultiFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dG):
-        gs_ = ctx.st
-        gt, gv, w1t, b1t, w2t, w1v, b1v, w2v = ctx.saved_tensors
+        gt, gv, *params = ctx.saved_tensors
         B, Gt, d = gt.shape
         Bv, Gv, _ = gv.shape
         dG = dG.float().contiguous()
         gt2, gv2 = gt.detach().float().contiguous(), gv.detach().float().contiguous()
-        d_gt, d_wgt = ops.local_level_bwd(0, dG, 0, 1.0, gs_["pv"], gs_["w_t"], gs_["w_v"], gs_["aux"], B, Gt, Bv, Gv, use_lo=True)
-        d_gv, d_wgv = ops.local_level_bwd(1, dG, 0, 1.0, gs_["pt"], gs_["w_v"], gs_["w_t"], gs_["aux"], B, Gt, Bv, Gv, use_lo=True)
-        dl_gt = ops.token_softmax_bwd(gs_["w_t"], d_wgt.view(B, Gt))
-        dl_gv = ops.token_softmax_bwd(gs_["w_v"], d_wgv.view(Bv, Gv))
-        gW1t, gb1t, gW2t, gb2t, gXt = _mlp_backward([gt2], [dl_gt], w1t, b1t, w2t, B * Gt, True)
-        gW1v, gb1v, gW2v, gb2v, gXv = _mlp_backward([gv2], [dl_gv], w1v, b1v, w2v, Bv * Gv, True)
+        d_gt, d_gv, g1 = multi_global_backward(ctx.st, dG, gt2, gv2, params, B, Gt, Bv, Gv)
         ctx.st = None
-        return (None, (d_gt.view_as(gt2) + gXt.view_as(gt2)).to(gt.dtype), (d_gv.view_as(gv2) + gXv.view_as(gv2)).to(gv.dtype),
-                gW1t, gb1t, gW2t, gb2t, gW1v, gb1v, gW2v, gb2v)
+        return (None, d_gt.view_as(gt2).to(gt.dtype), d_gv.view_as(gv2).to(gv.dtype), *g1)
 
 
 class RowLossFn(torch.autograd.Function):

@@ -698,42 +698,115 @@ def pool_weight_bwd_group(jobs):
     hip.call("nr_pool_weight_bwd_group", len(jobs), arr, hip.stream_ptr())
 
 
+class TokenSet(namedtuple("TokenSet", "prep w T", defaults=(None,))):
+    """One operand of the similarity backward: its Prepared tokens, its softmax weights [n, N] (n samples of N tokens), and
+    optionally T, its transposed form from transpose_prepared when the caller has made it already."""
+    n = property(lambda self: self.w.shape[0])
+    N = property(lambda self: self.w.shape[1])
+
+
+# One fused product text x video with its upstream gradient dS (ds_mode 0: [A, Bv]; 1 / 2: a row / column mean's [A] / [Bv]
+# vector, times ds_scale) and the forward's aux = (arg_v, arg_t, pmax, qmax).  A and Bv are the two sets' n.
+SimProduct = namedtuple("SimProduct", "text video dS ds_mode ds_scale aux")
+# One token set whose gradient is wanted, the products it is an operand of in summation order (at most two: PoolWJob has two
+# sources), and whether d_x is wanted besides d_w (a memory-bank set: weights only).
+SimTarget = namedtuple("SimTarget", "set products want_dx", defaults=(True,))
+
+
+def sim_backward_launches(targets, group_max=hip.SIM_BWD_GROUP_MAX):
+    """Host only, by identity (`is`) of the sets and products: the launches of a table of SimTargets ->
+        d_x launches  [[(set, product, side), ...], ...]   the targets in order, each one's products in order, cut every group_max
+        jobs          [(set, [(product, side), ...]), ...]  one weight sum per target
+        transposes    [[set, ...], ...]                     the distinct "other" operands of the d_x items in first-use order
+    side: 0 where the set is the product's text operand (its pooled maxima are aux[2]), 1 where the video operand (aux[3]).
+    The mapping is fixed because it is part of the result: nr_local_level_bwd_group chooses its chunking, and with it the
+    summation order of d_x, from the composition of a launch, and sums the products of one d_x in item order."""
+    items, jobs, others = [], [], []
+    for k, tg in enumerate(targets):
+        if any(tg.set is u.set for u in targets[:k]):
+            raise ValueError("a token set is the target of one entry")
+        sides = [(p, 0 if p.text is tg.set else 1) for p in tg.products]
+        if not (1 <= len(sides) <= 2 and all((p.text, p.video)[side] is tg.set and side == sides[0][1] for p, side in sides)):
+            raise ValueError("a target is the same operand (text or video) of its one or two products")
+        jobs.append((tg.set, sides))
+        for p, side in sides if tg.want_dx else ():
+            items.append((tg.set, p, side))
+            other = p.video if side == 0 else p.text
+            if not any(other is o for o in others):
+                others.append(other)
+    cut = lambda xs: [xs[k:k + group_max] for k in range(0, len(xs), group_max)]      # noqa: E731
+    return cut(items), jobs, cut(others)
+
+
+def _pool_src(p, side):
+    """A product as a source of nr_pool_weight_bwd_group: the pooled maxima of the operand's side (pmax = aux[2] / qmax = aux[3])."""
+    return p.dS, p.ds_mode, p.ds_scale, p.aux[2 + side], p.text.n, p.video.n
+
+
+def sim_backward(targets, use_lo=True, out=None, accumulate=False, scalar_dw=False, fallback=True):
+    """The token side of the similarity backward from ONE description of each product: (d_x [n N, d] or None, d_w [n N]) per
+    SimTarget, written into the buffers that `out` gives (None: a new one).  The only place that decides between the matrix-core
+    kernel (nr_local_level_bwd_group, launches as sim_backward_launches states them, one nr_pool_weight_bwd_group for every d_w)
+    and, with USE_MFMA_BACKWARD off or token counts the kernel refuses, nr_local_level_bwd's entry-by-entry walk: target by
+    target, product by product, a target's second product accumulating (fallback=False: NrHipError instead).
+    accumulate: keep the buffers' content.  scalar_dw: d_w from the walk's own sum (the cross-check of the tests)."""
+    launches, jobs, transposes = sim_backward_launches(targets)
+    d = next(s.prep.d for tg in targets for p in tg.products for s in (p.text, p.video) if s.prep is not None)
+    dev = targets[0].set.w.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
+    out = [((d_x if d_x is not None else new(tg.set.n * tg.set.N, d)) if tg.want_dx else None,
+            d_w if d_w is not None else new(tg.set.n * tg.set.N)) for tg, (d_x, d_w) in zip(targets, out or [(None, None)] * len(targets))]
+    buf = {id(tg.set): o for tg, o in zip(targets, out)}
+    P0 = targets[0].products[0]
+    mfma = bool(launches) and USE_MFMA_BACKWARD and bool(hip.lib().nr_local_level_bwd_mfma_supported(P0.text.N, P0.video.N, d))
+    if launches and not (mfma or fallback):
+        raise hip.NrHipError("the matrix-core similarity backward is required here (USE_MFMA_BACKWARD off, or token counts "
+                             "outside nr_local_level_bwd_mfma_supported)")
+    if mfma:
+        T = {}
+        for chunk in transposes:
+            todo = [s for s in chunk if s.T is None]
+            T.update([(id(s), s.T) for s in chunk if s.T is not None])
+            T.update(zip(map(id, todo), transpose_prepared([s.prep for s in todo], use_lo=use_lo)))
+        first = {id(tg.set): tg.products[0] for tg in targets}
+        for launch in launches:
+            local_level_bwd_group([
+                dict(side=side, dS=p.dS, ds_mode=p.ds_mode, ds_scale=p.ds_scale, other_T=T[id((p.video, p.text)[side])],
+                     w_self=s.w, w_other=(p.video, p.text)[side].w, aux=p.aux, A=p.text.n, Nt=p.text.N, Bv=p.video.n, Nv=p.video.N,
+                     d_x=buf[id(s)][0], accumulate=accumulate and p is first[id(s)]) for s, p, side in launch], use_lo=use_lo)
+        if not scalar_dw:
+            pool_weight_bwd_group([dict(side=sides[0][1], N=s.N, d_w=buf[id(s)][1], accumulate=accumulate,
+                                        srcs=[_pool_src(p, side) for p, side in sides]) for s, sides in jobs])
+    if not mfma or scalar_dw:
+        for s, sides in jobs:
+            d_x, d_w = (None if mfma else buf[id(s)][0]), buf[id(s)][1]
+            for k, (p, side) in enumerate(sides):
+                acc = accumulate or k > 0
+                if d_x is not None or scalar_dw:
+                    other = (p.video, p.text)[side]
+                    ws = torch.empty((int(hip.lib().nr_local_level_bwd_workspace_bytes(side, p.text.n, p.text.N, p.video.n, p.video.N,
+                                                                                       d)),), dtype=torch.uint8, device=dev)
+                    hip.call("nr_local_level_bwd", side, hip.ptr(p.dS, torch.float32), int(p.ds_mode), float(p.ds_scale),
+                             hip.ptr(other.prep.hi), hip.ptr(other.prep.lo if use_lo else None, allow_none=True),
+                             hip.ptr(s.w, torch.float32), hip.ptr(other.w, torch.float32), *(hip.ptr(a) for a in p.aux),
+                             p.text.n, p.text.N, p.video.n, p.video.N, d, hip.ptr(d_x, allow_none=True),
+                             hip.ptr(d_w if scalar_dw else None, allow_none=True), 1 if acc else 0, hip.ptr(ws), hip.stream_ptr())
+                if not scalar_dw:
+                    pool_weight_bwd_group([dict(side=side, N=s.N, d_w=d_w, accumulate=acc, srcs=[_pool_src(p, side)])])
+    return out
+
+
 def local_level_bwd(side, dS, ds_mode, ds_scale, other, w_self, w_other, aux, A, Nt, Bv, Nv, d_x=None, d_w=None,
                     want_dx=True, accumulate=False, use_lo=True, other_T=None, scalar_dw=False):
-    """Arg-max-routed gradient for one operand.  `other` is the Prepared token set of the opposite operand.
-    d_x: nr_local_level_bwd_group (matrix cores) where the token counts allow, else nr_local_level_bwd's entry-by-entry walk;
-    d_w: nr_pool_weight_bwd_group (scalar_dw=True: the walk's own sum, kept as the cross-check of the tests).
+    """Arg-max-routed gradient for one operand: sim_backward of one target with one product.  `other` is the Prepared token set
+    of the opposite operand (other_T: its transposed form, where the caller made it already).
     Returns (d_x [n_self*N, d] or None, d_w [n_self*N])."""
-    arg_v, arg_t, pmax, qmax = aux
-    n_self = (A * Nt) if side == 0 else (Bv * Nv)
-    d = other.d
-    dev = w_self.device
     if accumulate and ((want_dx and d_x is None) or d_w is None):
         raise ValueError("accumulate=True needs existing d_x / d_w buffers")
-    if want_dx and d_x is None:
-        d_x = torch.empty((n_self, d), dtype=torch.float32, device=dev)
-    if d_w is None:
-        d_w = torch.empty((n_self,), dtype=torch.float32, device=dev)
-    mfma = want_dx and USE_MFMA_BACKWARD and bool(hip.lib().nr_local_level_bwd_mfma_supported(Nt, Nv, d))
-    if mfma:
-        if other_T is None:                          # else: transposed up front, several operands in one launch
-            other_T = transpose_prepared([other], use_lo=use_lo)[0]
-        local_level_bwd_group([dict(side=side, dS=dS, ds_mode=ds_mode, ds_scale=ds_scale, other_T=other_T, w_self=w_self,
-                                    w_other=w_other, aux=aux, A=A, Nt=Nt, Bv=Bv, Nv=Nv, d_x=d_x, accumulate=accumulate)],
-                              use_lo=use_lo)
-    scalar_dx = want_dx and not mfma
-    if scalar_dx or scalar_dw:
-        ws = torch.empty((int(hip.lib().nr_local_level_bwd_workspace_bytes(int(side), A, Nt, Bv, Nv, d)),), dtype=torch.uint8,
-                         device=dev)
-        hip.call("nr_local_level_bwd", int(side), hip.ptr(dS, torch.float32), int(ds_mode), float(ds_scale),
-                 hip.ptr(other.hi), hip.ptr(other.lo if use_lo else None, allow_none=True), hip.ptr(w_self, torch.float32),
-                 hip.ptr(w_other, torch.float32), hip.ptr(arg_v), hip.ptr(arg_t), hip.ptr(pmax), hip.ptr(qmax),
-                 A, Nt, Bv, Nv, d, hip.ptr(d_x if scalar_dx else None, allow_none=True),
-                 hip.ptr(d_w if scalar_dw else None, allow_none=True), 1 if accumulate else 0, hip.ptr(ws), hip.stream_ptr())
-    if not scalar_dw:
-        pool_weight_bwd_group([dict(side=side, N=Nt if side == 0 else Nv, d_w=d_w, accumulate=accumulate,
-                                    srcs=[(dS, ds_mode, ds_scale, pmax if side == 0 else qmax, A, Bv)])])
-    return (d_x if want_dx else None), d_w
+    me = TokenSet(None, w_self.reshape((A, Nt) if side == 0 else (Bv, Nv)))
+    ot = TokenSet(other, w_other.reshape((Bv, Nv) if side == 0 else (A, Nt)), other_T)
+    P = SimProduct(*((me, ot) if side == 0 else (ot, me)), dS, ds_mode, ds_scale, aux)
+    return sim_backward([SimTarget(me, [P], want_dx)], use_lo, [(d_x, d_w)], accumulate, scalar_dw)[0]
 
 
 def normalize_bwd(x, norm, mask, d_xn, dmean):

@@ -103,11 +103,11 @@ class SlabRowLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .backward import _coef_rowloss
+        from .backward import coef_rowloss
         S_rows, S_cols, G, tgt_r, tgt_c, c0, c1, wc_text, wc_video, ls = ctx.saved_tensors
         hp, r0 = ctx.hp, ctx.row0
         n, B = S_rows.shape
-        coef = _coef_rowloss(g.float().contiguous(), hp, B)
+        coef = coef_rowloss(g.float().contiguous(), hp, B)
         dS, dG_dir, dC, dwc, dls = ops.row_losses_bwd_slab(S_rows, S_cols, r0, G, tgt_r, tgt_c, c0, c1, wc_text, wc_video, ls,
                                                            int(hp["num_neighbors"]), float(hp["temperature"]), coef)
         dG = torch.zeros_like(G)
@@ -157,80 +157,40 @@ class ShardedLocalFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dS_rows, dS_cols, d_c1, d_c0, dmean_t, dmean_v):
-        from . import hip
-        from .backward import _mlp_backward_hip
+        from .backward import token_tail
         st = ctx.st
         if st is None:
             raise RuntimeError("ShardedLocalFn: backward a second time (its saved state is released by the first)")
-        text_feat, video_feat, mb_feat_t, mb_feat_v = ctx.saved_tensors
-        text_mask, video_mask, mb_mask_t, mb_mask_v = st["masks"]
-        B, Nt, d = text_feat.shape
-        Nv, M = video_feat.shape[1], mb_feat_v.shape[0]
-        r0, b, lo = st["r0"], st["b"], st["exact"]
+        feats = ctx.saved_tensors
+        text_mask, video_mask, _, _ = st["masks"]
+        Nt, Nv, M = feats[0].shape[1], feats[1].shape[1], feats[3].shape[0]
+        B, r0, b = feats[0].shape[0], st["r0"], st["b"]
         aux_r, aux_c, aux1, aux2 = st["aux"]
-        dev = text_feat.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        z = lambda *shape: torch.zeros(shape, **f32)       # noqa: E731 -- a slab that brought no gradient
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=feats[0].device)       # noqa: E731 -- a slab that brought no gradient
         dS_rows = z(b, B) if dS_rows is None else dS_rows.float().contiguous()
         dS_cols = z(B, b) if dS_cols is None else dS_cols.float().contiguous()
         d_c1 = z(b) if d_c1 is None else d_c1.float().contiguous()
         d_c0 = z(b) if d_c0 is None else d_c0.float().contiguous()
-        pt, pv, pbt, pbv, pt_r, pv_r = st["pt"], st["pv"], st["pbt"], st["pbv"], st["pt_r"], st["pv_r"]
-        if not (ops.USE_MFMA_BACKWARD and bool(hip.lib().nr_local_level_bwd_mfma_supported(Nt, Nv, d))):
-            raise hip.NrHipError("the sharded training loss needs the matrix-core similarity backward (token counts outside "
-                                 "nr_local_level_bwd_mfma_supported)")
-        # ---- token gradients of the four products: two grouped launches.  A gradient that only a row range of the tokens
-        # receives (the rank's b texts / videos) is accumulated in a buffer of its own and added to the full one afterwards.
-        d_tn, d_vn = torch.empty((B * Nt, d), **f32), torch.empty((B * Nv, d), **f32)
-        d_tn_r, d_vn_r = torch.empty((b * Nt, d), **f32), torch.empty((b * Nv, d), **f32)
-        T_pv, T_pv_r, T_pbv, T_pt_r = ops.transpose_prepared([pv, pv_r, pbv, pt_r], use_lo=lo)
-        T_pt, T_pbt = ops.transpose_prepared([pt, pbt], use_lo=lo)
-        ops.local_level_bwd_group([
-            dict(side=0, dS=dS_cols, ds_mode=0, ds_scale=1.0, other_T=T_pv_r, w_self=st["w_t"], w_other=st["w_v_r"], aux=aux_c,
-                 A=B, Nt=Nt, Bv=b, Nv=Nv, d_x=d_tn),
-            dict(side=0, dS=dS_rows, ds_mode=0, ds_scale=1.0, other_T=T_pv, w_self=st["w_t_r"], w_other=st["w_v"], aux=aux_r,
-                 A=b, Nt=Nt, Bv=B, Nv=Nv, d_x=d_tn_r),
-            dict(side=0, dS=d_c1, ds_mode=1, ds_scale=1.0 / M, other_T=T_pbv, w_self=st["w_t_r"], w_other=st["w_bv"], aux=aux1,
-                 A=b, Nt=Nt, Bv=M, Nv=Nv, d_x=d_tn_r),
-            dict(side=1, dS=dS_rows, ds_mode=0, ds_scale=1.0, other_T=T_pt_r, w_self=st["w_v"], w_other=st["w_t_r"], aux=aux_r,
-                 A=b, Nt=Nt, Bv=B, Nv=Nv, d_x=d_vn)], use_lo=lo)
-        ops.local_level_bwd_group([
-            dict(side=1, dS=dS_cols, ds_mode=0, ds_scale=1.0, other_T=T_pt, w_self=st["w_v_r"], w_other=st["w_t"], aux=aux_c,
-                 A=B, Nt=Nt, Bv=b, Nv=Nv, d_x=d_vn_r),
-            dict(side=1, dS=d_c0, ds_mode=2, ds_scale=1.0 / M, other_T=T_pbt, w_self=st["w_v_r"], w_other=st["w_bt"], aux=aux2,
-                 A=M, Nt=Nt, Bv=b, Nv=Nv, d_x=d_vn_r)], use_lo=lo)
+        # ---- the four products, each stated once (ops.sim_backward derives the two d_x launches and the six weight sums; the sharded
+        # loss has no scalar-walk form).  A gradient that only a row range of the tokens receives (the rank's b texts / videos) is
+        # accumulated in a buffer of its own and added to the full one afterwards.
+        t, v, bt, bv = (ops.TokenSet(st[p], st[w]) for p, w in (("pt", "w_t"), ("pv", "w_v"), ("pbt", "w_bt"), ("pbv", "w_bv")))
+        t_r, v_r = ops.TokenSet(st["pt_r"], st["w_t_r"]), ops.TokenSet(st["pv_r"], st["w_v_r"])
+        Pc = ops.SimProduct(t, v_r, dS_cols, 0, 1.0, aux_c)
+        Pr = ops.SimProduct(t_r, v, dS_rows, 0, 1.0, aux_r)
+        P1 = ops.SimProduct(t_r, bv, d_c1, 1, 1.0 / M, aux1)
+        P2 = ops.SimProduct(bt, v_r, d_c0, 2, 1.0 / M, aux2)
+        (d_tn, d_wt), (d_tn_r, d_wt_r), (d_vn, d_wv), (d_vn_r, d_wv_r), g_bv, g_bt = ops.sim_backward(
+            [ops.SimTarget(t, [Pc]), ops.SimTarget(t_r, [Pr, P1]), ops.SimTarget(v, [Pr]), ops.SimTarget(v_r, [Pc, P2]),
+             ops.SimTarget(bv, [P1], False), ops.SimTarget(bt, [P2], False)], use_lo=st["exact"], fallback=False)
         d_tn[r0 * Nt:(r0 + b) * Nt] += d_tn_r
         d_vn[r0 * Nv:(r0 + b) * Nv] += d_vn_r
-        # ---- token-weight gradients, all six sums in one launch
-        d_wt, d_wv = torch.empty((B * Nt,), **f32), torch.empty((B * Nv,), **f32)
-        d_wt_r, d_wv_r = torch.empty((b * Nt,), **f32), torch.empty((b * Nv,), **f32)
-        d_wbt, d_wbv = torch.empty((M * Nt,), **f32), torch.empty((M * Nv,), **f32)
-        ops.pool_weight_bwd_group([
-            dict(side=0, N=Nt, d_w=d_wt, srcs=[(dS_cols, 0, 1.0, aux_c[2], B, b)]),
-            dict(side=0, N=Nt, d_w=d_wt_r, srcs=[(dS_rows, 0, 1.0, aux_r[2], b, B), (d_c1, 1, 1.0 / M, aux1[2], b, M)]),
-            dict(side=1, N=Nv, d_w=d_wv, srcs=[(dS_rows, 0, 1.0, aux_r[3], b, B)]),
-            dict(side=1, N=Nv, d_w=d_wv_r, srcs=[(dS_cols, 0, 1.0, aux_c[3], B, b), (d_c0, 2, 1.0 / M, aux2[3], M, b)]),
-            dict(side=1, N=Nv, d_w=d_wbv, srcs=[(d_c1, 1, 1.0 / M, aux1[3], b, M)]),
-            dict(side=0, N=Nt, d_w=d_wbt, srcs=[(d_c0, 2, 1.0 / M, aux2[2], M, b)])])
         d_wt[r0 * Nt:(r0 + b) * Nt] += d_wt_r
         d_wv[r0 * Nv:(r0 + b) * Nv] += d_wv_r
-        # ---- normalise / mask / centrality-mean backward, softmax backward, fused scorer backward
-        d_text = ops.normalize_bwd(text_feat, pt.norm, text_mask, d_tn, dmean_t)
-        d_video = ops.normalize_bwd(video_feat, pv.norm, video_mask, d_vn, dmean_v)
-        dl_t = ops.token_softmax_bwd(st["w_t"], d_wt.view(B, Nt))
-        dl_v = ops.token_softmax_bwd(st["w_v"], d_wv.view(B, Nv))
-        dl_bt = ops.token_softmax_bwd(st["w_bt"], d_wbt.view(M, Nt))
-        dl_bv = ops.token_softmax_bwd(st["w_bv"], d_wbv.view(M, Nv))
-        _, p_mlp, p_bank = st["plan"]
-        model = st["model"]
-        (dW1t, db1t, dW2t, db2t, d_text), (dW1v, db1v, dW2v, db2v, d_video) = _mlp_backward_hip([
-            dict(sw=model.scorer_weights("text_weight_fc"), add_to=d_text,
-                 sets=[(pt, text_feat, dl_t, p_mlp), (pbt, mb_feat_t, dl_bt, p_bank)]),
-            dict(sw=model.scorer_weights("video_weight_fc"), add_to=d_video,
-                 sets=[(pv, video_feat, dl_v, p_mlp), (pbv, mb_feat_v, dl_bv, p_bank)])])
+        d_text, d_video, scorer = token_tail((t, v, bt, bv), feats, (text_mask, video_mask), ((d_tn, d_wt), (d_vn, d_wv), g_bt, g_bv),
+                                             (dmean_t, dmean_v), st["plan"], st["model"])
         ctx.st = None
-        return (None, None, None, None, d_text.view(text_feat.shape), d_video.view(video_feat.shape), None, None,
-                dW1t, db1t, dW2t, db2t, dW1v, db1v, dW2v, db2v)
+        return (None, None, None, None, d_text, d_video, None, None, *scorer)
 
 
 class ShardedGlobalFn(torch.autograd.Function):
@@ -255,11 +215,11 @@ class ShardedGlobalFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .backward import _coef_rowloss
+        from .backward import coef_rowloss
         S_rows, S_cols, c0, c1, mean_t, mean_v, gt2, gv2, ls, G, tgt_r, tgt_c, wc_t, wc_v, gn_t, gn_v, wtok_t, wtok_v = ctx.saved_tensors
         hp, r0 = ctx.hp, ctx.r0
         b, B = S_rows.shape
-        coef = _coef_rowloss(g.float().contiguous(), hp, B)
+        coef = coef_rowloss(g.float().contiguous(), hp, B)
         dS, dG_dir, dC, dwc, dls = ops.row_losses_bwd_slab(S_rows, S_cols, r0, G, tgt_r, tgt_c, c0, c1, wc_t, wc_v, ls,
                                                            int(hp["num_neighbors"]), float(hp["temperature"]), coef)
         dG = torch.zeros_like(G)

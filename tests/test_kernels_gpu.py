@@ -631,6 +631,146 @@ def test_grouped_backward_equals_the_products_one_by_one(use_lo):
         assert maxdiff(got, ref) < 2e-6 * float(ref.abs().max())
 
 
+def _step_problem(B, M, Nt, Nv, d):
+    """The token sets of a loss step (batch text / video, bank text / video) as ops.TokenSets, a seeded generator, and a function
+    product(text, video) -> the stored indices of that fused product."""
+    pt, pv, w_t, w_v, _, g = _bwd_problem(B, B, Nt, Nv, d, 5)
+    _, pbv, _, w_bv, _, _ = _bwd_problem(2, M, Nt, Nv, d, 6)
+    pbt, _, w_bt, _, _, _ = _bwd_problem(M, 2, Nt, Nv, d, 7)
+    sets = [ops.TokenSet(p, w) for p, w in ((pt, w_t), (pv, w_v), (pbt, w_bt), (pbv, w_bv))]
+    aux = lambda a, b: ops.local_level(a.prep, b.prep, a.w, b.w, a.n, Nt, b.n, Nv, hip.PREC_BF16X3, hip.OUT_FULL, want_arg=True)[1]  # noqa: E731
+    return sets, g, aux
+
+
+def _nan_out(targets, d):
+    """Output buffers of ops.sim_backward pre-filled with NaN: a row the launches do not write shows."""
+    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)      # noqa: E731
+    return [(nan(tg.set.n * tg.set.N, d) if tg.want_dx else None, nan(tg.set.n * tg.set.N)) for tg in targets]
+
+
+def _replicated_table(sets, g, aux, B, M):
+    t, v, bt, bv = sets
+    dS, d_c1, d_c0 = torch.randn(B, B, generator=g).to(DEV), torch.randn(B, generator=g).to(DEV), torch.randn(B, generator=g).to(DEV)
+    P0 = ops.SimProduct(t, v, dS, 0, 1.0, aux(t, v))
+    P1 = ops.SimProduct(t, bv, d_c1, 1, 1.0 / M, aux(t, bv))
+    P2 = ops.SimProduct(bt, v, d_c0, 2, 1.0 / M, aux(bt, v))
+    return (P0, P1, P2), [ops.SimTarget(t, [P0, P1]), ops.SimTarget(v, [P0, P2]), ops.SimTarget(bv, [P1], False),
+                          ops.SimTarget(bt, [P2], False)]
+
+
+@pytest.mark.parametrize("d,use_lo", [(512, False), (256, True), (256, False)])
+def test_replicated_table_issues_the_hand_written_launches(d, use_lo):
+    """ops.sim_backward on the replicated step's table (three products, four targets) == the launches as they were written out
+    by hand, item by item and job by job (the lists of test_grouped_backward_equals_the_products_one_by_one), bit for bit: the
+    composition of a launch picks the kernel variant (512 dims per workgroup; 256 with / without the low halves) and the
+    chunking (M = 70: several slices), and with them the summation order."""
+    B, M, Nt, Nv = 20, 70, 24, 12
+    sets, g, aux = _step_problem(B, M, Nt, Nv, d)
+    (t, v, bt, bv), ((P0, P1, P2), table) = sets, _replicated_table(sets, g, aux, B, M)
+    (dS, aux0), (d_c1, aux1), (d_c0, aux2) = ((p.dS, p.aux) for p in (P0, P1, P2))
+    (d_tn, d_wt), (d_vn, d_wv), (_, d_wbv), (_, d_wbt) = ops.sim_backward(table, use_lo=use_lo, out=_nan_out(table, d))
+    (r_tn, r_wt), (r_vn, r_wv), (_, r_wbv), (_, r_wbt) = _nan_out(table, d)
+    T_pv, T_pt, T_pbv, T_pbt = ops.transpose_prepared([v.prep, t.prep, bv.prep, bt.prep], use_lo=use_lo)
+    ops.local_level_bwd_group([
+        dict(side=0, dS=dS, ds_mode=0, ds_scale=1.0, other_T=T_pv, w_self=t.w, w_other=v.w, aux=aux0, A=B, Nt=Nt, Bv=B, Nv=Nv, d_x=r_tn),
+        dict(side=0, dS=d_c1, ds_mode=1, ds_scale=1.0 / M, other_T=T_pbv, w_self=t.w, w_other=bv.w, aux=aux1, A=B, Nt=Nt, Bv=M, Nv=Nv,
+             d_x=r_tn),
+        dict(side=1, dS=dS, ds_mode=0, ds_scale=1.0, other_T=T_pt, w_self=v.w, w_other=t.w, aux=aux0, A=B, Nt=Nt, Bv=B, Nv=Nv, d_x=r_vn),
+        dict(side=1, dS=d_c0, ds_mode=2, ds_scale=1.0 / M, other_T=T_pbt, w_self=v.w, w_other=bt.w, aux=aux2, A=M, Nt=Nt, Bv=B, Nv=Nv,
+             d_x=r_vn)], use_lo=use_lo)
+    ops.pool_weight_bwd_group([
+        dict(side=0, N=Nt, d_w=r_wt, srcs=[(dS, 0, 1.0, aux0[2], B, B), (d_c1, 1, 1.0 / M, aux1[2], B, M)]),
+        dict(side=1, N=Nv, d_w=r_wv, srcs=[(dS, 0, 1.0, aux0[3], B, B), (d_c0, 2, 1.0 / M, aux2[3], M, B)]),
+        dict(side=1, N=Nv, d_w=r_wbv, srcs=[(d_c1, 1, 1.0 / M, aux1[3], B, M)]),
+        dict(side=0, N=Nt, d_w=r_wbt, srcs=[(d_c0, 2, 1.0 / M, aux2[2], M, B)])])
+    for got, ref in ((d_tn, r_tn), (d_vn, r_vn), (d_wt, r_wt), (d_wv, r_wv), (d_wbt, r_wbt), (d_wbv, r_wbv)):
+        assert torch.isfinite(ref).all() and torch.equal(got, ref)
+
+
+@pytest.mark.parametrize("use_lo", [False, True])
+def test_sharded_table_issues_the_hand_written_launches(use_lo):
+    """ops.sim_backward on a rank's table of the sharded loss (four products, six targets; rows [r0, r0 + b) of B) == the two
+    d_x launches of 4 + 2 items and the six weight-sum jobs as ShardedLocalFn.backward wrote them out by hand, with the adds of
+    the row-range buffers into the full ones, bit for bit."""
+    from neighborretr_amd.head import _rows
+    B, b, r0, M, Nt, Nv, d = 20, 5, 10, 70, 24, 12, 512
+    (t, v, bt, bv), g, aux = _step_problem(B, M, Nt, Nv, d)
+    t_r = ops.TokenSet(_rows(t.prep, r0 * Nt, b * Nt), t.w[r0:r0 + b].contiguous())
+    v_r = ops.TokenSet(_rows(v.prep, r0 * Nv, b * Nv), v.w[r0:r0 + b].contiguous())
+    r = lambda *shape: torch.randn(*shape, generator=g).to(DEV)      # noqa: E731
+    dS_rows, dS_cols, d_c1, d_c0 = r(b, B), r(B, b), r(b), r(b)
+    aux_r, aux_c, aux1, aux2 = aux(t_r, v), aux(t, v_r), aux(t_r, bv), aux(bt, v_r)
+    Pc = ops.SimProduct(t, v_r, dS_cols, 0, 1.0, aux_c)
+    Pr = ops.SimProduct(t_r, v, dS_rows, 0, 1.0, aux_r)
+    P1 = ops.SimProduct(t_r, bv, d_c1, 1, 1.0 / M, aux1)
+    P2 = ops.SimProduct(bt, v_r, d_c0, 2, 1.0 / M, aux2)
+    table = [ops.SimTarget(t, [Pc]), ops.SimTarget(t_r, [Pr, P1]), ops.SimTarget(v, [Pr]), ops.SimTarget(v_r, [Pc, P2]),
+             ops.SimTarget(bv, [P1], False), ops.SimTarget(bt, [P2], False)]
+    got = ops.sim_backward(table, use_lo=use_lo, out=_nan_out(table, d), fallback=False)
+    # by hand, as ShardedLocalFn.backward issued them before the table
+    (d_tn, d_wt), (d_tn_r, d_wt_r), (d_vn, d_wv), (d_vn_r, d_wv_r), (_, d_wbv), (_, d_wbt) = ref = _nan_out(table, d)
+    T_pv, T_pv_r, T_pbv, T_pt_r = ops.transpose_prepared([v.prep, v_r.prep, bv.prep, t_r.prep], use_lo=use_lo)
+    T_pt, T_pbt = ops.transpose_prepared([t.prep, bt.prep], use_lo=use_lo)
+    ops.local_level_bwd_group([
+        dict(side=0, dS=dS_cols, ds_mode=0, ds_scale=1.0, other_T=T_pv_r, w_self=t.w, w_other=v_r.w, aux=aux_c,
+             A=B, Nt=Nt, Bv=b, Nv=Nv, d_x=d_tn),
+        dict(side=0, dS=dS_rows, ds_mode=0, ds_scale=1.0, other_T=T_pv, w_self=t_r.w, w_other=v.w, aux=aux_r,
+             A=b, Nt=Nt, Bv=B, Nv=Nv, d_x=d_tn_r),
+        dict(side=0, dS=d_c1, ds_mode=1, ds_scale=1.0 / M, other_T=T_pbv, w_self=t_r.w, w_other=bv.w, aux=aux1,
+             A=b, Nt=Nt, Bv=M, Nv=Nv, d_x=d_tn_r),
+        dict(side=1, dS=dS_rows, ds_mode=0, ds_scale=1.0, other_T=T_pt_r, w_self=v.w, w_other=t_r.w, aux=aux_r,
+             A=b, Nt=Nt, Bv=B, Nv=Nv, d_x=d_vn)], use_lo=use_lo)
+    ops.local_level_bwd_group([
+        dict(side=1, dS=dS_cols, ds_mode=0, ds_scale=1.0, other_T=T_pt, w_self=v_r.w, w_other=t.w, aux=aux_c,
+             A=B, Nt=Nt, Bv=b, Nv=Nv, d_x=d_vn_r),
+        dict(side=1, dS=d_c0, ds_mode=2, ds_scale=1.0 / M, other_T=T_pbt, w_self=v_r.w, w_other=bt.w, aux=aux2,
+             A=M, Nt=Nt, Bv=b, Nv=Nv, d_x=d_vn_r)], use_lo=use_lo)
+    ops.pool_weight_bwd_group([
+        dict(side=0, N=Nt, d_w=d_wt, srcs=[(dS_cols, 0, 1.0, aux_c[2], B, b)]),
+        dict(side=0, N=Nt, d_w=d_wt_r, srcs=[(dS_rows, 0, 1.0, aux_r[2], b, B), (d_c1, 1, 1.0 / M, aux1[2], b, M)]),
+        dict(side=1, N=Nv, d_w=d_wv, srcs=[(dS_rows, 0, 1.0, aux_r[3], b, B)]),
+        dict(side=1, N=Nv, d_w=d_wv_r, srcs=[(dS_cols, 0, 1.0, aux_c[3], B, b), (d_c0, 2, 1.0 / M, aux2[3], M, b)]),
+        dict(side=1, N=Nv, d_w=d_wbv, srcs=[(d_c1, 1, 1.0 / M, aux1[3], b, M)]),
+        dict(side=0, N=Nt, d_w=d_wbt, srcs=[(d_c0, 2, 1.0 / M, aux2[2], M, b)])])
+    for res in (got, ref):                             # the row-range buffers into the full ones, as the caller does
+        (f_tn, f_wt), (p_tn, p_wt), (f_vn, f_wv), (p_vn, p_wv) = res[:4]
+        f_tn[r0 * Nt:(r0 + b) * Nt] += p_tn
+        f_vn[r0 * Nv:(r0 + b) * Nv] += p_vn
+        f_wt[r0 * Nt:(r0 + b) * Nt] += p_wt
+        f_wv[r0 * Nv:(r0 + b) * Nv] += p_wv
+    for (g_x, g_w), (r_x, r_w) in zip(got, ref):
+        assert torch.isfinite(r_w).all() and torch.equal(g_w, r_w)
+        assert (g_x is None and r_x is None) or (torch.isfinite(r_x).all() and torch.equal(g_x, r_x))
+
+
+@pytest.mark.parametrize("Nt,Nv,B,M,mfma_switch", [(12, 12, 6, 9, True), (24, 12, 6, 9, False)])
+def test_replicated_table_falls_back_to_the_products_one_by_one(Nt, Nv, B, M, mfma_switch):
+    """Where the matrix-core kernel refuses the token counts (12 x 12), and on a shape it takes with USE_MFMA_BACKWARD off,
+    ops.sim_backward on the replicated table == the six one-by-one ops.local_level_bwd calls the loss head fell back to when its
+    launches were written out by hand, bit for bit: the order of the contributions into one buffer is kept."""
+    d, use_lo = 512, True
+    assert bool(hip.lib().nr_local_level_bwd_mfma_supported(Nt, Nv, d)) == ((Nt, Nv) != (12, 12))
+    sets, g, aux = _step_problem(B, M, Nt, Nv, d)
+    (t, v, bt, bv), ((P0, P1, P2), table) = sets, _replicated_table(sets, g, aux, B, M)
+    (dS, aux0), (d_c1, aux1), (d_c0, aux2) = ((p.dS, p.aux) for p in (P0, P1, P2))
+    (r_tn, r_wt), (r_vn, r_wv), (_, r_wbv), (_, r_wbt) = _nan_out(table, d)
+    try:
+        ops.USE_MFMA_BACKWARD = mfma_switch
+        with pytest.raises(hip.NrHipError):
+            ops.sim_backward(table, use_lo=use_lo, fallback=False)           # (what the sharded loss asks for)
+        (d_tn, d_wt), (d_vn, d_wv), (_, d_wbv), (_, d_wbt) = ops.sim_backward(table, use_lo=use_lo, out=_nan_out(table, d))
+        ops.local_level_bwd(0, dS, 0, 1.0, v.prep, t.w, v.w, aux0, B, Nt, B, Nv, d_x=r_tn, d_w=r_wt, use_lo=use_lo)
+        ops.local_level_bwd(1, dS, 0, 1.0, t.prep, v.w, t.w, aux0, B, Nt, B, Nv, d_x=r_vn, d_w=r_wv, use_lo=use_lo)
+        ops.local_level_bwd(0, d_c1, 1, 1.0 / M, bv.prep, t.w, bv.w, aux1, B, Nt, M, Nv, d_x=r_tn, d_w=r_wt, accumulate=True, use_lo=use_lo)
+        ops.local_level_bwd(1, d_c1, 1, 1.0 / M, t.prep, bv.w, t.w, aux1, B, Nt, M, Nv, d_w=r_wbv, want_dx=False)
+        ops.local_level_bwd(1, d_c0, 2, 1.0 / M, bt.prep, v.w, bt.w, aux2, M, Nt, B, Nv, d_x=r_vn, d_w=r_wv, accumulate=True, use_lo=use_lo)
+        ops.local_level_bwd(0, d_c0, 2, 1.0 / M, v.prep, bt.w, v.w, aux2, M, Nt, B, Nv, d_w=r_wbt, want_dx=False)
+    finally:
+        ops.USE_MFMA_BACKWARD = True
+    for got, ref in ((d_tn, r_tn), (d_vn, r_vn), (d_wt, r_wt), (d_wv, r_wv), (d_wbt, r_wbt), (d_wbv, r_wbv)):
+        assert torch.isfinite(ref).all() and torch.equal(got, ref)
+
+
 @pytest.mark.parametrize("B,d", [(128, 512), (37, 96)])
 def test_the_three_launches_of_the_backward_head(B, d):
     """nr_rowloss_bwd_finish, nr_centrality_weights_bwd_pair and nr_global_logits_bwd against their plain torch forms (and the

@@ -27,7 +27,7 @@ with torch.no_grad():
         dh = torch.where(h > 0, dl.double()[:, None] * w2, torch.zeros_like(h))
         truth = (dh.T @ X, dh.sum(0), (dl.double()[:, None] * h.clamp(min=0)).sum(0).reshape(1, -1), dl.double().sum().reshape(1), dh @ W1)
         res = backward._mlp_backward_hip([dict(sw=sw, sets=[(pt, x, dl, hip.PREC_BF16X3)])])[0]
-        ref = backward._mlp_backward([x], [dl], mlp[0].weight, mlp[0].bias, mlp[2].weight, n, True)
+        ref = backward._mlp_backward([x], [dl], mlp[0].weight, mlp[0].bias, mlp[2].weight, n)
         e1 = [float((a.double() - t.reshape(a.shape)).abs().max() / t.abs().max()) for a, t in zip(res, truth)]
         e2 = [float((a.double().reshape(t.shape) - t).abs().max() / t.abs().max()) for a, t in zip(ref, truth)]
         print(n, "fused", ["%.1e" % e for e in e1], " torch-form", ["%.1e" % e for e in e2])
